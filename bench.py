@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — certified-smoothing throughput of the HIP path on N MI355X GPUs of one node.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One process per GPU over RCCL.  Under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
 (WORLD_SIZE set) this process is one rank.  Started plainly with --gpus N > 1 (WORLD_SIZE unset) the parent — before any
@@ -18,8 +18,20 @@ all-reduce (RCCL int64[10]) — weak scaling: every rank works on its own shard 
 `value` is measured in the engine's EXACT-VOTE mode (the drop-in default): f16-operand MFMA WaveNet, and every sample
 whose top-2 logit margin is below the recheck bound is re-evaluated on the split-f16 / exact-fp32 tiers from the same
 Philox key.  The bound is a measured one, so the equality of the counts with the fp32 path's is an
-empirical guarantee — and the line itself checks it: `exact_equals_fp32` re-runs the first timed steps' sample range in
-the exact-vote mode and on the exact-fp32 path and prints both vote vectors.  The line also carries
+empirical guarantee.
+
+A plain run sets up, warms up, times the --steps steps and prints the line: `value`, `ms_per_step`, the timed votes and the
+recheck fractions of the timed steps.  --dump-outputs DIR then also writes what the last timed step computed, as .npy files
+(float32 / float64, a few MB): votes.npy — the step's vote counts, summed over the ranks, as the caller of the vote loop
+receives them; logits.npy — the classifier logits of rank 0's samples of that step (a fixed, seeded 65 536 of them when
+there are more); purified_rows.npy and purified.npy — a fixed, seeded choice of at most 64 of those samples and their
+purified waveforms.  The logits and waveforms come from the same sample range evaluated once more after the timed region
+(the vote loop keeps them only on request), whose votes must equal the timed step's.  The inputs depend only on the
+arguments, so two builds can be compared file by file.
+
+--full adds everything else, outside the timed region unless said otherwise: the per-kernel roofline figures (HIP event pairs
+around the timed steps' launches, so the timed steps themselves carry them), and `exact_equals_fp32`, which re-runs the first
+timed steps' sample range in the exact-vote mode and on the exact-fp32 path and prints both vote vectors.  It also carries
   fast_mode / fp32_mode — the same step with the recheck off (16-bit path alone) and on the exact-fp32 path alone;
   sigma_grid     — the other sigmas of BASELINE C4's grid (0.25 and 1.0; README.md:12-14, scripts/certified_robust_eval.sh:3-6):
                    a few timed steps each in the exact-vote mode and on the 16-bit tier alone, their recheck fractions, and
@@ -161,7 +173,10 @@ def main():
     ap.add_argument('--side-steps', type=int, default=None, help='steps of the two side measurements (fast / exact, fp32); 0 = skip')
     ap.add_argument('--cpu-samples', type=int, default=6)
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--full', action='store_true', help='kept for older command lines: the default run already times certify(n_0=100, n=100000)')
+    ap.add_argument('--full', action='store_true', help='also measure and check everything beyond the headline figure: roofline, side modes, '
+                                                        'exact == fp32, sigma grid, certify(), C2 / C3 / C5, ResNeXt29, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (votes, logits, sampled purified waveforms) as DIR/<name>.npy')
     ap.add_argument('--full-n', type=int, default=100000, help='n of the certify() run through the host mirror (about 65 s / n_gpus at 100000)')
     ap.add_argument('--check-steps', type=int, default=2, help='steps of the timed sample range re-run in the exact-vote mode and on the '
                                                                'exact-fp32 path to print exact_equals_fp32 (0 = skip; fp32 costs ~2.8 s per step)')
@@ -248,10 +263,7 @@ def main():
 
     cur = {'eng': eng}                         # the engine the step / timed helpers drive (the ResNeXt29 leg swaps it)
 
-    def step(i, cfg=cfg0):
-        # global sample index range of this step: [i*S*world, (i+1)*S*world), rank r takes its slice
-        base = (i * world + rank) * S
-        counts, _, _ = cur['eng'].smooth_votes(clip, cfg[0], cfg[1], cfg[2], cfg[3], cfg[4], S, seed=2024, sample0=base)
+    def reduce_votes(counts):
         if dist is not None:
             if backend == 'gloo':
                 c = counts.cpu()
@@ -259,7 +271,15 @@ def main():
                 counts = c.cuda()
             else:
                 dist.all_reduce(counts)
+        return counts
+
+    def step(i, cfg=cfg0):
+        # global sample index range of this step: [i*S*world, (i+1)*S*world), rank r takes its slice
+        base = (i * world + rank) * S
+        counts, _, _ = cur['eng'].smooth_votes(clip, cfg[0], cfg[1], cfg[2], cfg[3], cfg[4], S, seed=2024, sample0=base)
+        counts = reduce_votes(counts)
         total.add_(counts)
+        return counts
 
     def fence():
         if dist is not None:
@@ -281,7 +301,7 @@ def main():
         fence()
         t0 = time.perf_counter()
         for i in range(steps):
-            step(first_step + warmup + i, cfg)
+            cur['last_counts'] = step(first_step + warmup + i, cfg)
         fence()
         dt = time.perf_counter() - t0
         prof = None
@@ -297,10 +317,36 @@ def main():
         voted, rechecked, rechecked32 = eng.recheck_stats(detail=True)
         return dt, votes, ((rechecked / voted, rechecked32 / voted) if voted else (0.0, 0.0)), prof
 
+    if not args.full:
+        # a plain run measures the headline figure alone: every leg below is switched off, and the timed steps carry no event pairs
+        args.side_steps, args.check_steps, args.sigma_grid, args.grid_steps = 0, 0, '', 0
+        args.no_certify, args.c2_iters, args.c5_n, args.resnext_steps, args.no_cpu_baseline = True, 0, 0, 0, True
+
     recheck_margin, recheck_margin2 = eng.recheck_margin, eng.recheck_margin2
     # ---- the measured region: exactly --steps steps after --warmup untimed ones, in --mode --------------------------
-    dt, votes, recheck_frac, prof = timed(args.mode, args.steps, args.warmup, 0, profile=(args.mode != 'fp32'))
+    dt, votes, recheck_frac, prof = timed(args.mode, args.steps, args.warmup, 0, profile=(args.full and args.mode != 'fp32'))
     clips = args.steps * S * world
+
+    # ---- --dump-outputs: what the last timed step computed, on the same engine before any other leg runs ------------
+    if args.dump_outputs:
+        import numpy as np
+        last_votes = cur['last_counts'].cpu()
+        i_last = args.warmup + args.steps - 1
+        re_counts, lg, x0 = eng.smooth_votes(clip, cfg0[0], cfg0[1], cfg0[2], cfg0[3], cfg0[4], S, seed=2024,
+                                             sample0=(i_last * world + rank) * S, want_logits=True, want_x0=True)
+        re_counts = reduce_votes(re_counts)
+        if re_counts.cpu().tolist() != last_votes.tolist():
+            raise SystemExit('bench.py: the last timed step voted %s, the same samples evaluated again %s'
+                             % (last_votes.tolist(), re_counts.cpu().tolist()))
+        if rank == 0:
+            rows = np.sort(np.random.default_rng(0).choice(S, size=min(S, 64), replace=False))
+            lrows = np.sort(np.random.default_rng(1).choice(S, size=65536, replace=False)) if S > 65536 else np.arange(S)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, 'votes.npy'), last_votes.numpy().astype(np.float64))
+            np.save(os.path.join(args.dump_outputs, 'logits.npy'), lg.cpu().numpy()[lrows].astype(np.float32))
+            np.save(os.path.join(args.dump_outputs, 'purified_rows.npy'), rows.astype(np.float64))
+            np.save(os.path.join(args.dump_outputs, 'purified.npy'), x0[torch.from_numpy(rows).cuda()].cpu().numpy().astype(np.float32))
+        del lg, x0
     # ---- side measurements on the same engine (outside the timed region) -----------------------------------------
     side = {}
     side_steps = args.side_steps if args.side_steps is not None else (4 if world == 1 else 0)
@@ -537,8 +583,8 @@ def main():
                                    "N=100000 clip" % (sigma, t + 1, 'VGG19_bn' if args.classifier == 'vgg19_bn' else 'ResNeXt29', S, -(-100000 // S)),
                        "samples_per_step_per_gpu": S, "engine_batch": args.max_batch, "sigma": sigma, "t_star": t + 1,
                        "mode": {"exact": "exact-vote: %s MFMA WaveNet + split-f16 / exact-fp32 re-evaluation of samples with top-2 logit margin < %.3g "
-                                         "(empirical bound: no vote differed from the fp32 path's on 236 864 samples (36 864 + 2 x 100 000); this "
-                                         "line's own check: exact_equals_fp32)" % (args.half, recheck_margin),
+                                         "(empirical bound: no vote differed from the fp32 path's on 236 864 samples (36 864 + 2 x 100 000); the "
+                                         "--full line's own check: exact_equals_fp32)" % (args.half, recheck_margin),
                                 "fast": "%s MFMA WaveNet alone (no recheck)" % args.half, "fp32": "exact-fp32 WaveNet alone"}[args.mode],
                        "noise": "device Philox4x32-10", "classifier": "VGG19_bn (synthetic seed 4321)" if args.classifier == 'vgg19_bn' else "ResNeXt29 8x64d (synthetic seed 2929)",
                        "parallelism": "mc-samples sharded x%d, one int64[10] all-reduce per step" % world},

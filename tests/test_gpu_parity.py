@@ -1255,13 +1255,13 @@ def test_other_wavenet_geometry(orc):
 
 
 def test_bench_contract():
-    """bench.py prints ONE JSON line with the driver's keys; `metric` is BASELINE.json's; roofline and (at N = 1) cpu_baseline
+    """bench.py --full prints ONE JSON line with the driver's keys; `metric` is BASELINE.json's; roofline and (at N = 1) cpu_baseline
     objects are present and consistent (tiny run: 1 step of 8 samples, 2-sample CPU leg)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '1', '--warmup', '1', '--samples-per-step', '8',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '1', '--warmup', '1', '--samples-per-step', '8',
                         '--max-batch', '8', '--cpu-samples', '2', '--full-n', '64', '--c5-n', '16', '--c5-batch', '16', '--c2-iters', '1', '--c2-batch', '8', '--c3-clips', '1',
                         '--check-steps', '1', '--grid-steps', '1', '--resnext-steps', '1'], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -1320,7 +1320,46 @@ def test_bench_contract():
     assert r.returncode != 0 and 'refusing' in r.stderr and not r.stdout.strip()
 
 
-def test_bench_two_ranks_rehearsal():
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run times exactly --steps steps and carries the headline figure alone (every other leg is --full's);
+    --dump-outputs writes what the last timed step computed: its votes, the logits they were taken from and a seeded sample of
+    the purified waveforms, the same from run to run."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--samples-per-step', '8',
+                            '--max-batch', '8', '--dump-outputs', str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        return json.loads(lines[0]), {n: np.load(d / (n + '.npy')) for n in ('votes', 'logits', 'purified_rows', 'purified')}
+
+    j, out = run(tmp_path / 'a')
+    base = json.load(open(os.path.join(root, 'BASELINE.json')))
+    assert j['metric'] == base['metric'] and j['unit'] == 'clips/s' and j['higher_is_better'] is True and j['dtype'] == 'f16'
+    assert j['steps'] == 3 and j['warmup'] == 1 and sum(j['votes']) == 3 * 8
+    assert abs(j['value'] - 3 * 8 / (j['ms_per_step'] * 3e-3)) < 1e-6 * j['value']
+    assert 0.0 <= j['recheck']['frac_fp32'] <= j['recheck']['frac'] <= 1.0
+    for k in ('roofline', 'roofline_final', 'exact_equals_fp32', 'fast_mode', 'fp32_mode', 'sigma_grid', 'certify_full', 'c2_ddpm_mode',
+              'c5_spec_mode', 'resnext29_mode', 'cpu_baseline'):
+        assert k not in j, k
+    votes, logits, rows, wave = out['votes'], out['logits'], out['purified_rows'], out['purified']
+    assert votes.dtype == np.float64 and votes.shape == (10,) and votes.sum() == 8
+    assert logits.dtype == np.float32 and logits.shape == (8, 10) and np.isfinite(logits).all()
+    assert np.bincount(logits.argmax(1), minlength=10).tolist() == votes.astype(np.int64).tolist()      # the votes are the logits' arg-max
+    assert rows.dtype == np.float64 and rows.tolist() == list(range(8))                                  # all 8 samples (at most 64)
+    assert wave.dtype == np.float32 and wave.shape == (8, 16000) and np.isfinite(wave).all() and np.abs(wave).max() > 0
+    assert sum(a.nbytes for a in out.values()) < 64 << 20
+    _, again = run(tmp_path / 'b')                                   # same arguments -> same inputs -> same outputs
+    for n, a in out.items():
+        assert again[n].dtype == a.dtype and again[n].shape == a.shape, n
+        assert np.allclose(again[n], a, rtol=0, atol=1e-6 * max(1.0, float(np.abs(a).max()))), n
+
+
+def test_bench_two_ranks_rehearsal(tmp_path):
     """The N > 1 form of bench.py, rehearsed as two ranks sharing this box's GPU (gloo for the collectives: DMAD_BENCH_BACKEND, a
     rehearsal switch; the measured configuration is one rank per GPU over RCCL): the line carries n_gpus = 2, the aggregate
     value of both ranks' steps, `certify_full` with one clip's samples SHARDED over the ranks (strong scaling), the C3 / C2 legs
@@ -1332,9 +1371,10 @@ def test_bench_two_ranks_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     env.update(DMAD_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', str(29700 + os.getpid() % 200), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2',
+                        '--master-port', str(29700 + os.getpid() % 200), os.path.join(root, 'bench.py'), '--full', '--gpus', '2', '--steps', '2',
                         '--warmup', '1', '--samples-per-step', '16', '--max-batch', '16', '--full-n', '200', '--c5-n', '16', '--c5-batch', '16', '--c2-iters', '1',
-                        '--c2-batch', '8', '--c3-clips', '1', '--check-steps', '1'], capture_output=True, text=True, timeout=900, cwd=root, env=env)
+                        '--c2-batch', '8', '--c3-clips', '1', '--check-steps', '1', '--dump-outputs', str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -1348,6 +1388,8 @@ def test_bench_two_ranks_rehearsal():
     c5 = j['c5_spec_mode']
     assert c5['n'] == 32 and c5['n_gpus'] == 2 and sum(c5['votes']) == 32 and c5['exact_equals_fp32'] is True
     assert 'cpu_baseline' not in j                                    # rank 0 at N = 1 only
+    assert np.load(tmp_path / 'votes.npy').sum() == 2 * 16            # the last timed step's votes, summed over both ranks
+    assert np.load(tmp_path / 'logits.npy').shape == (16, 10)         # rank 0's samples of that step
 
 
 # ------------------------------------------------------------------------------------------ exact-vote mode, C4's sigmas
