@@ -12,6 +12,7 @@
 
 #include "../../include/dmad.h"
 #include "dmad_common.h"
+#include "wn_vjp.h"
 #include "unet_ops.h"
 #include "elementwise.h"
 #include "gemm_f32.h"
@@ -208,6 +209,10 @@ struct dmad_engine {
     long long* rc_list2 = nullptr;         // samples the x3 tier leaves to the fp32 tier
     int64_t st_rechecked2 = 0;
     float *hA32 = nullptr, *hB32 = nullptr, *H32 = nullptr, *g32 = nullptr, *skip32 = nullptr;
+    // VJP workspace (dmad_reserve_vjp): saved residual streams [NL][vjpB][LP][256], gradient maps, transposed weight images
+    int vjpB = 0;
+    float *vjp_save = nullptr, *vjp_gH = nullptr, *vjp_G = nullptr, *vjp_gg = nullptr;
+    float *vjp_wdilT = nullptr, *vjp_wgT = nullptr, *vjp_wf0T = nullptr;
     // common work buffers
     float *xt = nullptr, *eps = nullptr, *x0 = nullptr, *znoise = nullptr;
     // classifier
@@ -291,6 +296,15 @@ struct dmad_engine {
         bytes += (int64_t)(n * sizeof(T));
         *p = (T*)d;
         return 0;
+    }
+    template <typename T>
+    void release(T** p, size_t n) {        // frees a buffer of alloc() (a reservation that is replaced)
+        if (!*p) return;
+        for (size_t i = 0; i < allocs.size(); ++i)
+            if (allocs[i] == (void*)*p) { allocs.erase(allocs.begin() + i); break; }
+        (void)hipFree(*p);
+        bytes -= (int64_t)(n * sizeof(T));
+        *p = nullptr;
     }
     template <typename T>
     int upload(T** p, const std::vector<T>& h) {
@@ -1214,7 +1228,9 @@ GemmF32Args plain_gemm(const float* A, const float* X, float* C, const float* sc
 
 // exact32: evaluate on the exact-fp32 path (the only one of a DMAD_FP32 engine; DMAD_MODE_FP32 and the recheck pass of a
 // DMAD_EXACT engine); batches larger than the fp32 workspace are walked in chunks of maxB32 clips
-int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipStream_t s, int path = PATH_DEFAULT) {
+// save != nullptr (the VJP's forward pass; B <= maxB32, fp32 path): layer n reads its residual stream from slot n of `save`
+// ([NL][vjpB][LP][256]) and writes the next one to slot n + 1 instead of the A / B ping-pong — the same launches, the same bits
+int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipStream_t s, int path = PATH_DEFAULT, float* save = nullptr) {
     if (!e->wn_final) return fail(DMAD_ERR_STATE, "WaveNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
     if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
     if (t < 0) return fail(DMAD_ERR_INVALID, "diffusion step %d < 0", t);
@@ -1256,11 +1272,12 @@ int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipS
         if (timed_f) (void)hipEventRecord(e->prof_ev_f[e->prof_used_f++], s);
     } else {
         const long N = (long)B * L;
-        launch_wn_init_f32(x_t, e->init_w, e->init_b, e->emb_table, e->hA32, B, L, LP, s, x3, x3 && e->diag[4]);
+        const size_t sslot = (size_t)e->vjpB * LP * kC;           // one saved stream (VJP)
+        launch_wn_init_f32(x_t, e->init_w, e->init_b, e->emb_table, save ? save : e->hA32, B, L, LP, s, x3, x3 && e->diag[4]);
         const size_t slab = (size_t)e->maxB32 * L * 256;          // one gate-output slab per layer
         for (int n = 0; n < NL; ++n) {
-            float* hin = (n & 1) ? e->hB32 : e->hA32;
-            float* hout = (n & 1) ? e->hA32 : e->hB32;
+            float* hin = save ? save + n * sslot : (n & 1) ? e->hB32 : e->hA32;
+            float* hout = save ? save + (n + 1) * sslot : (n & 1) ? e->hA32 : e->hB32;
             const int d = 1 << (n % e->cfg.dilation_cycle);
             const bool last = n == NL - 1;
             float* gout = e->gstore32 + (size_t)n * slab;
@@ -1294,6 +1311,66 @@ int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipS
         launch_dot256(e->H32, e->wz, e->bz, eps, N, s);
     }
     LASTCHK();
+    return 0;
+}
+
+// One pass of dmad_wavenet_eps_vjp (B <= vjpB): forward-save, then the backward layer by layer.
+//   G = three zero-padded [vjpB][LP][256] maps: region 0 g_s (the gradient of the skip sum, every layer's g_skip), regions 1 / 2 the
+//   gradient of the residual stream ping-pong.  The gate-gradient GEMM contracts K = 512 over two taps — tap 0 = region 0 through
+//   W_skip^T, tap 1 = region r through sqrt(1/2) W_res^T — by reading region r with a tap stride of r regions.
+int wavenet_vjp_pass(dmad_engine* e, const float* x_t, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s) {
+    const int L = e->L, LP = e->LP, NL = e->NL;
+    const long N = (long)B * L;
+    const size_t RS = (size_t)e->vjpB * LP * kC, sslot = RS;
+    CHK(wavenet_eps(e, x_t, t, B, eps, s, PATH_FP32, e->vjp_save));
+    // final block: g_y = [y > 0] wz g_eps (y = relu(f0), kept in H32), g_s = sqrt(1/NL) W_f0^T g_y (scale folded into the image)
+    launch_vjp_final(e->H32, e->wz, g_eps, e->vjp_gg, N, s);
+    GemmF32Args f = plain_gemm(e->vjp_wf0T, e->vjp_gg, nullptr, nullptr, nullptr, 256, 256, N, 256, 256, 0);
+    f.epi = 4; f.L = L; f.LP = LP; f.hin = nullptr; f.hout = e->vjp_G;
+    CHK(launch_gemm_f32(f, s) ? fail(DMAD_ERR_INVALID, "VJP: no kernel for the f0 backward") : 0);
+    for (int n = NL - 1; n >= 0; --n) {
+        const int d = 1 << (n % e->cfg.dilation_cycle);
+        const bool last = n == NL - 1;
+        const int r_out = 1 + ((NL - 2 - n) & 1), r_in = 1 + ((NL - 1 - n) & 1);   // regions of g_h(n+1) (input) and g_h(n) (output)
+        float* g_hout = e->vjp_G + (size_t)r_out * RS;
+        float* g_hin = e->vjp_G + (size_t)r_in * RS;
+        // g_gate = W_skip^T g_s + sqrt(1/2) W_res^T g_h(n+1)   (the last layer: the first term alone)
+        GemmF32Args gg{};
+        gg.A = e->vjp_wgT + (size_t)n * 2 * 256 * 256; gg.X = (last ? e->vjp_G : g_hout) + (size_t)kPad * kC; gg.C = e->vjp_gg;
+        gg.M = 256; gg.K = 256; gg.taps = last ? 1 : 2; gg.ldc = 256; gg.N = N; gg.mode = 0;
+        gg.rows_per_batch = L; gg.batch_stride = (long)LP * kC; gg.row_stride = kC; gg.tap_stride = last ? 0 : (long)r_out * (long)RS;
+        CHK(launch_gemm_f32(gg, s) ? fail(DMAD_ERR_INVALID, "VJP: no kernel for the gate gradient") : 0);
+        // g_H from the recomputed H (epi 3), into the zero-padded [B][LP][512] map
+        GemmF32Args g3{};
+        g3.A = e->wdil + (size_t)n * 3 * 512 * 256; g3.X = e->vjp_save + n * sslot + (size_t)kPad * kC; g3.shift = e->bdil + (size_t)n * 512;
+        g3.M = 512; g3.K = 256; g3.taps = 3; g3.ldc = 512; g3.N = N; g3.mode = 0;
+        g3.rows_per_batch = L; g3.batch_stride = (long)LP * kC; g3.row_stride = kC; g3.tap_stride = (long)d * kC;
+        g3.epi = 3; g3.L = L; g3.LP = LP; g3.hin = e->vjp_gg; g3.hout = e->vjp_gH;
+        CHK(launch_gemm_f32(g3, s) ? fail(DMAD_ERR_INVALID, "VJP: no kernel for the gate backward") : 0);
+        // g_h(n) = sqrt(1/2) g_h(n+1) + transposed dilated conv of g_H (taps flipped in the image), epi 4
+        GemmF32Args g4{};
+        g4.A = e->vjp_wdilT + (size_t)n * 3 * 256 * 512; g4.X = e->vjp_gH + (size_t)kPad * 512;
+        g4.M = 256; g4.K = 512; g4.taps = 3; g4.ldc = 256; g4.N = N; g4.mode = 0;
+        g4.rows_per_batch = L; g4.batch_stride = (long)LP * 512; g4.row_stride = 512; g4.tap_stride = (long)d * 512;
+        g4.epi = 4; g4.L = L; g4.LP = LP; g4.hin = last ? nullptr : g_hout; g4.hout = g_hin;
+        CHK(launch_gemm_f32(g4, s) ? fail(DMAD_ERR_INVALID, "VJP: no kernel for the transposed dilated conv") : 0);
+    }
+    launch_vjp_init(x_t, e->init_w, e->init_b, e->vjp_G + (size_t)(1 + ((NL - 1) & 1)) * RS, g_x, B, L, LP, s);
+    LASTCHK();
+    return 0;
+}
+
+int wavenet_vjp(dmad_engine* e, const float* x_t, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s) {
+    if (!e->f32) return fail(DMAD_ERR_STATE, "the WaveNet VJP runs on the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights");
+    if (!e->wn_final) return fail(DMAD_ERR_STATE, "WaveNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    if (!e->vjpB) return fail(DMAD_ERR_STATE, "no VJP workspace: call dmad_reserve_vjp first");
+    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    if (t < 0) return fail(DMAD_ERR_INVALID, "diffusion step %d < 0", t);
+    const size_t L = e->L;
+    for (int b0 = 0; b0 < B; b0 += e->vjpB) {
+        const int bb = B - b0 < e->vjpB ? B - b0 : e->vjpB;
+        CHK(wavenet_vjp_pass(e, x_t + b0 * L, t, bb, g_eps + b0 * L, g_x + b0 * L, (eps ? eps : e->eps) + b0 * L, s));
+    }
     return 0;
 }
 
@@ -1828,6 +1905,40 @@ int dmad_recheck_stats(dmad_engine* e, int64_t* samples, int64_t* rechecked, int
     if (rechecked_fp32) *rechecked_fp32 = e->st_rechecked2;
     if (reset) e->st_samples = e->st_rechecked = e->st_rechecked2 = 0;
     return 0;
+}
+
+int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
+    if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
+    if (!e->f32) return fail(DMAD_ERR_STATE, "the WaveNet VJP runs on the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights");
+    if (!e->wn_final) return fail(DMAD_ERR_STATE, "WaveNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    const int vB = max_batch < e->maxB32 ? max_batch : e->maxB32;
+    if (vB <= e->vjpB) return 0;
+    const size_t LP = e->LP, NL = e->NL;
+    if (e->vjpB) {                          // a larger reservation replaces the present one
+        const size_t ob = e->vjpB;
+        e->release(&e->vjp_save, NL * ob * LP * kC); e->release(&e->vjp_gH, ob * LP * 512);
+        e->release(&e->vjp_G, 3 * ob * LP * kC); e->release(&e->vjp_gg, ob * e->L * kC);
+        e->vjpB = 0;
+    }
+    if (!e->vjp_wdilT) {
+        CHK(e->alloc(&e->vjp_wdilT, NL * 3 * 256 * 512)); CHK(e->alloc(&e->vjp_wgT, NL * 2 * 256 * 256)); CHK(e->alloc(&e->vjp_wf0T, 256 * 256));
+        launch_vjp_pack(e->wdil, e->wrs, e->wf0, e->vjp_wdilT, e->vjp_wgT, e->vjp_wf0T, e->NL, nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    // zeroed: the padding rows of the saved streams and of the gradient maps are read as the convs' zero padding and never written
+    CHK(e->alloc(&e->vjp_save, NL * vB * LP * kC, true));
+    CHK(e->alloc(&e->vjp_gH, (size_t)vB * LP * 512, true));
+    CHK(e->alloc(&e->vjp_G, 3 * (size_t)vB * LP * kC, true));
+    CHK(e->alloc(&e->vjp_gg, (size_t)vB * e->L * kC));
+    HIPCHK(hipDeviceSynchronize());
+    e->vjpB = vB;
+    return 0;
+}
+
+int dmad_wavenet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps, dmad_stream s) {
+    if (!e || !x_t || !g_eps || !g_x) return fail(DMAD_ERR_INVALID, "null argument");
+    return wavenet_vjp(e, x_t, t, B, g_eps, g_x, eps, (hipStream_t)s);
 }
 
 int dmad_wavenet_eps_path(dmad_engine* e, const float* x_t, int32_t t, int32_t B, int32_t path, float* eps, dmad_stream s) {

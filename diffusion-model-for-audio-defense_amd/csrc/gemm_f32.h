@@ -33,6 +33,13 @@ struct GemmF32Args {
     //          (row(n) = position n inside the zero-padded residual stream; the last layer, whose residual output is never
     //          consumed, has no such launch; the skip convs run as one K = NL * 256 GEMM after the layer loop).
     //          `first` / `skip` are unused since then.
+    // Epilogues of the WaveNet's vector-Jacobian product (dmad_wavenet_eps_vjp), 128-row tiles, their own kernel instantiation:
+    //   epi 3  gate backward (M = 512, K = 256, A / shift = the permuted dilated-conv image of epi 1, X = the saved stream h_n):
+    //          the recomputed H never leaves the registers; with g = hin[n][ch] ([N][256], the gradient of the gate output)
+    //          hout[row(n)][ch] = g (1 - tanh^2) sigmoid,  hout[row(n)][256 + ch] = g tanh sigmoid (1 - sigmoid)
+    //          (hout: zero-padded [B][LP][512] map, row(n) as for epi 2; its padding rows are never written).
+    //   epi 4  M = 256, no bias: hout[row(n)][m] = sqrt(1/2) * hin[row(n)][m] + v  (hin == nullptr: v), both zero-padded
+    //          [B][LP][256] maps with the row mapping of epi 2 (the gradient of the residual stream).
     int epi, res_rows, first, L, LP;
     const float* hin;
     float* hout;

@@ -86,7 +86,9 @@ __device__ __forceinline__ void gf_wait_stages(int stages) {
 //      is bound by ONE workgroup's 64 x 128 tile — 64 x 32 tiles are four times as many workgroups; and alone on its CU a workgroup
 //      sees the staging latency over its prefetch distance, hence 7 stages in flight instead of 2.  Same k order, same MFMA
 //      sequence per output: the same bits.
-template <int BM, bool TWO, int NS = 3, int NT = 4>
+// BWD: the epilogues of the WaveNet's vector-Jacobian product (epi 3 / 4, gemm_f32.h); an instantiation of its own, so that the
+//      forward kernels' code is what it was.
+template <int BM, bool TWO, int NS = 3, int NT = 4, bool BWD = false>
 __global__ void __launch_bounds__(256) gemm_f32_kernel(GemmF32Args a) {
     constexpr int MT = BM / 32;            // 16-row accumulator tiles per wave along M (2 M-waves)
     constexpr int BNT = 32 * NT, XP = NT == 4 ? 2 : 1;      // tile width in pixels; 64-row activation pieces per stage
@@ -216,6 +218,81 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(GemmF32Args a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (m + r < a.M) dst[r] = acc[i][j][r];
+            }
+        }
+        return;
+    }
+    if constexpr (BWD) {
+        static_assert(BM == 128 && NT == 4, "the backward epilogues use the 128 x 128 tile");
+        // row of position n inside a zero-padded [B][LP][ld] map, once per accumulator column (N < 2^31 positions: launcher)
+        long prow[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            unsigned n32 = (unsigned)(n0 + wn * 64 + j * 16 + r16);
+            if ((long)n32 >= a.N) n32 = (unsigned)(a.N - 1);                 // (never stored)
+            const unsigned bb = n32 / (unsigned)a.L;
+            prow[j] = (long)bb * a.LP + kPad + (n32 - bb * (unsigned)a.L);
+        }
+        if (a.epi == 3) {                   // gate backward: H recomputed with the permuted image of epi 1, g_gate = hin [N][256]
+            float4 gv[2][4];                // (all loads ahead of the stores: hin and hout are distinct buffers)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    long n = n0 + wn * 64 + j * 16 + r16;
+                    if (n >= a.N) n = a.N - 1;
+                    gv[i][j] = *(const float4*)(a.hin + n * 256 + blockIdx.y * 64 + wm * 32 + i * 16 + q * 4);
+                }
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int mrow = m0 + wm * 64 + i * 16 + q * 4;          // permuted row of the tanh half (its partner: + 32)
+                const int ch = blockIdx.y * 64 + wm * 32 + i * 16 + q * 4;
+                const float4 bt = *(const float4*)(a.shift + mrow), bs = *(const float4*)(a.shift + mrow + 32);
+                const float bta[4] = {bt.x, bt.y, bt.z, bt.w}, bsa[4] = {bs.x, bs.y, bs.z, bs.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const long n = n0 + wn * 64 + j * 16 + r16;
+                    if (n >= a.N) continue;
+                    const float ga[4] = {gv[i][j].x, gv[i][j].y, gv[i][j].z, gv[i][j].w};
+                    float dt[4], ds[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float ht = acc[i][j][r] + bta[r], hs = acc[i + 2][j][r] + bsa[r];
+                        const float t = tanhf(ht), sg = 1.f / (1.f + expf(-hs)), g = ga[r];
+                        dt[r] = g * (1.f - t * t) * sg;                  // d g / d H[ch]        = (1 - tanh^2) sigmoid
+                        ds[r] = g * t * (sg * (1.f - sg));               // d g / d H[256 + ch]  = tanh sigmoid (1 - sigmoid)
+                    }
+                    float* dst = a.hout + prow[j] * 512 + ch;
+                    *(float4*)dst = float4{dt[0], dt[1], dt[2], dt[3]};
+                    *(float4*)(dst + 256) = float4{ds[0], ds[1], ds[2], ds[3]};
+                }
+            }
+            return;
+        }
+        // epi 4: hout[row(n)][m] = sqrt(1/2) * hin[row(n)][m] + acc   (hin == nullptr: acc alone); M = 256, no bias
+        float4 hv[MT][4];
+        if (a.hin) {
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) hv[i][j] = *(const float4*)(a.hin + prow[j] * kC + m0 + wm * 64 + i * 16 + q * 4);
+        } else {
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) hv[i][j] = float4{0.f, 0.f, 0.f, 0.f};
+        }
+        const float k = 0.70710678118654752440f;
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            const int m = m0 + wm * 64 + i * 16 + q * 4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long n = n0 + wn * 64 + j * 16 + r16;
+                if (n >= a.N) continue;
+                const float4 h = hv[i][j];
+                *(float4*)(a.hout + prow[j] * kC + m) = float4{__fadd_rn(__fmul_rn(h.x, k), acc[i][j][0]), __fadd_rn(__fmul_rn(h.y, k), acc[i][j][1]),
+                                                             __fadd_rn(__fmul_rn(h.z, k), acc[i][j][2]), __fadd_rn(__fmul_rn(h.w, k), acc[i][j][3])};
             }
         }
         return;
@@ -761,6 +838,14 @@ int launch_gemm_f32(const GemmF32Args& a0, hipStream_t s, float* slab, long slab
     GemmF32Args a = a0;
     // the update epilogue indexes positions in 32 bits and serves M = 256 residual rows (the skip convs are one GEMM of their own)
     if (a.epi == 2 && (a.N >= (1l << 31) || a.L < 1 || a.M != 256 || a.res_rows != a.M || !a.hin || !a.hout || !a.emb_next)) { ++g_bad_shapes; return kGemmBadShape; }
+    if (a.epi == 3 || a.epi == 4) {               // the VJP's epilogues (fp32 operands, 128 x 128 tile, no split-K)
+        if (a.x3 || a.X2 || a.groups > 1 || a.N < 1 || a.N >= (1l << 31) || a.L < 1 || a.LP < a.L + 2 * kPad || !a.hout || (a.K % BK) ||
+            (a.epi == 3 && (a.M != 512 || a.K != 256 || !a.hin || !a.shift)) || (a.epi == 4 && a.M != 256)) { ++g_bad_shapes; return kGemmBadShape; }
+        a.splits = 1; a.slab = nullptr;
+        const dim3 grid((unsigned)((a.N + BN - 1) / BN), (unsigned)(a.M / 128));
+        hipLaunchKernelGGL((gemm_f32_kernel<128, false, 3, 4, true>), grid, dim3(256), 3 * SLOT, s, a);
+        return 0;
+    }
     if (a.x3) {                                   // split-f16 operands (shapes checked here, not in the kernel)
         a.splits = 1; a.slab = nullptr;
         if ((a.K % 32) || (a.ldc & 3) || a.K < 32) { ++g_bad_shapes; return kGemmBadShape; }

@@ -11,9 +11,10 @@ engine (libdmad_hip.so).  Same names, argument meaning and error behaviour as th
 
 The eps-network runs in hand-written HIP kernels without autograd.  There is no CPU path; inputs must be
 CUDA tensors (the reference itself hard-codes .cuda()).  Callers that DIFFERENTIATE through the
-purifier (the white-box attack drivers: `x.requires_grad` with gradients enabled) get the torch
-restatement of dmad_hip/autograd.py on that branch — `DiffWave.forward`, `one_shot_denoise`, `compute_eps_t`
-and `model((x, t))`; every other call is the HIP engine's.
+purifier (the white-box attack drivers: `x.requires_grad` with gradients enabled) get, on that branch —
+`DiffWave.forward`, `one_shot_denoise`, `compute_eps_t` and `model((x, t))` —, the backend WaveNetHIP.grad_backend
+names: 'torch', the torch restatement of dmad_hip/autograd.py, or 'hip', the engine's exact-fp32 forward with its
+native vector-Jacobian product (dmad_wavenet_eps_vjp); every other call is the HIP engine's.
 
 Noise: the reference draws every Gaussian on the CPU default generator and copies it over
 (ref l.66,100).  `noise_source='torch_cpu'` reproduces exactly that stream (parity);
@@ -34,14 +35,30 @@ class WaveNetHIP(torch.nn.Module):
     callable on the tuple (audio [B,1,L], diffusion_steps [B,1]); all rows must carry the same step,
     which is what every inference caller of the reference passes (t * ones)."""
 
-    def __init__(self, engine: "_eng.Engine", state_dict=None):
+    GRAD_BACKENDS = ('auto', 'torch', 'hip')
+
+    def __init__(self, engine: "_eng.Engine", state_dict=None, grad_backend: str = 'auto'):
         super().__init__()
         self.engine = engine
-        # the differentiation branch (dmad_hip/autograd.py) evaluates the same folded weights with torch ops
+        # the torch differentiation branch (dmad_hip/autograd.py) evaluates the same folded weights with torch ops
         self._folded = None
         if state_dict is not None:
             cyc = dict(engine.wavenet_geometry)['dilation_cycle']
             self._folded = _ag.FoldedWaveNet(_eng.fold_wavenet_state_dict(state_dict, engine.num_res_layers), engine.num_res_layers, cyc)
+        self.grad_backend = grad_backend
+
+    @property
+    def grad_backend(self) -> str:
+        """Backend of the gradient branch: 'torch' (the torch restatement; needs the state dict), 'hip' (the engine's fp32 forward +
+        native VJP; FP32 / EXACT engines), 'auto' (the default) = 'torch' when the folded weights are held, otherwise no gradient
+        branch (NotImplementedError, as before 'hip' existed: opting in is the caller's choice)."""
+        return self._grad_backend
+
+    @grad_backend.setter
+    def grad_backend(self, value: str):
+        if value not in self.GRAD_BACKENDS:
+            raise ValueError('grad_backend must be one of %s, not %r' % (self.GRAD_BACKENDS, value))
+        self._grad_backend = value
 
     def forward(self, input_data):
         audio, diffusion_steps = input_data
@@ -50,9 +67,12 @@ class WaveNetHIP(torch.nn.Module):
         if not bool((steps == t).all()) or t != int(t):
             raise NotImplementedError('per-row / fractional diffusion steps are not supported by the HIP engine')
         if _ag.needs_grad(audio):
+            if self._grad_backend == 'hip':
+                return _ag.wavenet_eps_hip(self.engine, audio, int(t))
             if self._folded is None:
-                raise NotImplementedError('the HIP eps-network has no autograd; build the model with create_diffwave_model(...) or '
-                                          'WaveNetHIP(engine, state_dict=...) to get the torch restatement on the gradient branch')
+                raise NotImplementedError("this WaveNetHIP has no gradient branch: pass grad_backend='hip' for the engine's native VJP "
+                                          '(FP32 / EXACT engines), or build the model with create_diffwave_model(...) or '
+                                          'WaveNetHIP(engine, state_dict=...) to get the torch restatement')
             return _ag.wavenet_eps(self._folded, audio, int(t))
         return self.engine.wavenet_eps(audio, int(t)).unsqueeze(1)
 
@@ -327,11 +347,11 @@ class ReffWave(torch.nn.Module):
 
 
 def create_diffwave_model(model_path, config_path, reverse_timestep=25, state_dict=None, noise_source='device',
-                          precision=None, max_batch=None, engine=None):
+                          precision=None, max_batch=None, engine=None, grad_backend='auto'):
     """Reference signature (ref l.395-411) plus optional keyword-only extras.  Reads the JSON keys
     `wavenet_config` and `diffusion_config`, loads checkpoint['model_state_dict'] (weight_g/weight_v
     layout), folds and uploads the weights.  `state_dict` may be passed instead of
-    a checkpoint path (synthetic weights)."""
+    a checkpoint path (synthetic weights).  `grad_backend`: WaveNetHIP.grad_backend of the model."""
     with open(config_path) as f:
         cfg = json.loads(f.read())
     wavenet_config = cfg["wavenet_config"]
@@ -343,5 +363,5 @@ def create_diffwave_model(model_path, config_path, reverse_timestep=25, state_di
     if engine is None and eng.has_wavenet and eng.wavenet_owner != _eng.state_fingerprint(state_dict):
         eng = _eng.get_engine(wavenet_config, precision=precision, max_batch=max_batch, fresh=True)   # a second, different DiffWave
     eng.bind('wavenet', state_dict, eng.load_wavenet)
-    return DiffWave(model=WaveNetHIP(eng, state_dict=state_dict), diffusion_hyperparams=diffusion_hyperparams,
+    return DiffWave(model=WaveNetHIP(eng, state_dict=state_dict, grad_backend=grad_backend), diffusion_hyperparams=diffusion_hyperparams,
                     reverse_timestep=reverse_timestep, noise_source=noise_source)

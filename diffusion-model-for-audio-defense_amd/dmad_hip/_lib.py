@@ -67,6 +67,8 @@ _SIGNATURES = {
     'dmad_set_recheck_margin2': (C.c_int, [_P, C.c_float]),
     'dmad_recheck_stats': (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]),
     'dmad_wavenet_eps_path': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_reserve_vjp': (C.c_int, [_P, C.c_int32]),
+    'dmad_wavenet_eps_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     'dmad_eval_samples': (C.c_int, [_P, _P, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_uint64, _P, _P, C.c_int64,
                                     C.c_int32, _P, _P, _P]),
     'dmad_debug_rounding': (C.c_int, [_P, C.POINTER(C.c_int32)]),

@@ -14,6 +14,10 @@ Scope: gradients only.  Nothing here runs when no gradient is requested — infe
 without it — tensors must live on the GPU like everywhere else in this package, nothing here is timed by bench.py, and nothing
 here imports `oracle/` (test infrastructure).  tests/test_gpu_parity.py::test_autograd_branch checks the forward values of this
 branch against the HIP fp32 path and its gradients against finite differences taken WITH the HIP fp32 path.
+
+WaveNetEpsHIP is the native alternative for the eps-network (WaveNetHIP(..., grad_backend='hip')): its forward is the engine's
+exact-fp32 path and its backward the engine's vector-Jacobian product (dmad_wavenet_eps_vjp), which saves the residual streams
+only — no torch activations are kept between forward and backward.
 """
 import math
 
@@ -108,3 +112,40 @@ def mel_db(x: torch.Tensor) -> torch.Tensor:
     power = spec.real ** 2 + spec.imag ** 2                                        # [B, 1025, 32]
     mel = torch.matmul(fb, power)                                                  # [B, 32, 32]
     return (10.0 * torch.log10(torch.clamp(mel, min=1e-10))).unsqueeze(1)
+
+
+class WaveNetEpsHIP(torch.autograd.Function):
+    """eps = WaveNet((audio [B,1,L], t * ones)) on the engine's exact-fp32 path, differentiable in `audio` through the engine's VJP.
+    Saves only the input; the backward re-runs the forward with its residual streams saved (dmad_wavenet_eps_vjp).  The VJP
+    workspace is reserved on first use.  First-order only: create_graph=True raises."""
+
+    @staticmethod
+    def forward(ctx, audio, engine, t):
+        from . import engine as _eng
+        _require_cuda(audio)
+        if engine.precision == _eng.FP32:
+            eps = engine.wavenet_eps(audio, t)
+        elif engine.precision == _eng.EXACT:
+            eps = engine.wavenet_eps_path(audio, t, _eng.WAVE_FP32)
+        else:
+            raise DmadError('the HIP VJP runs on the exact-fp32 path: a BF16 engine holds no fp32 weights (use an FP32 or EXACT engine)')
+        ctx.engine, ctx.t = engine, int(t)
+        ctx.save_for_backward(audio)
+        return eps.view(audio.shape)
+
+    @staticmethod
+    def backward(ctx, g_eps):
+        if torch.is_grad_enabled():
+            raise DmadError('the HIP WaveNet VJP is first-order only: create_graph=True (double backward) is not supported; '
+                            "use grad_backend='torch' for higher derivatives")
+        audio, = ctx.saved_tensors
+        eng, B = ctx.engine, audio.shape[0]
+        if getattr(eng, 'vjp_batch', 0) < B:
+            eng.reserve_vjp(B)
+        g_x = eng.wavenet_eps_vjp(audio, ctx.t, g_eps.reshape(audio.shape).contiguous())
+        return g_x.view(audio.shape).to(audio.dtype), None, None
+
+
+def wavenet_eps_hip(engine, audio: torch.Tensor, t: int) -> torch.Tensor:
+    """eps = WaveNet((audio [B,1,L], t * ones)) on the engine, differentiable in `audio` (WaveNetEpsHIP)."""
+    return WaveNetEpsHIP.apply(audio, engine, int(t))

@@ -480,6 +480,25 @@ class Engine:
             check(self.lib.dmad_wavenet_eps_path(self._h, _ptr(x[s:e]), int(t), e - s, int(path), _ptr(out[s:e]), _stream()))
         return out
 
+    def reserve_vjp(self, max_batch: int):
+        """dmad_reserve_vjp: the workspace of wavenet_eps_vjp for up to max_batch clips per pass (capped at the engine's fp32 pass
+        size; a larger reservation replaces a smaller one).  FP32 / EXACT engines; DmadError otherwise."""
+        check(self.lib.dmad_reserve_vjp(self._h, int(max_batch)))
+        self.vjp_batch = max(getattr(self, 'vjp_batch', 0), int(max_batch))
+
+    def wavenet_eps_vjp(self, x_t: torch.Tensor, t: int, g_eps: torch.Tensor, want_eps: bool = False):
+        """g_x = (d eps / d x_t)^T g_eps for eps = WaveNet((x_t, t * ones)) on the exact-fp32 path ([B,L] or [B,1,L] -> [B,L]).
+        want_eps: also return eps, bit-identical to wavenet_eps_path(x_t, t, 1).  Needs reserve_vjp first (DmadError otherwise)."""
+        x, g = self._wave(x_t), self._wave(g_eps)
+        if g.shape != x.shape:
+            raise DmadError('g_eps has shape %s, x_t %s' % (tuple(g.shape), tuple(x.shape)))
+        gx = torch.empty_like(x)
+        eps = torch.empty_like(x) if want_eps else None
+        for s, e in self._chunks(x.shape[0]):
+            check(self.lib.dmad_wavenet_eps_vjp(self._h, _ptr(x[s:e]), int(t), e - s, _ptr(g[s:e]), _ptr(gx[s:e]),
+                                                _ptr(None if eps is None else eps[s:e]), _stream()))
+        return (gx, eps) if want_eps else gx
+
     def load_unet(self, state_dict):
         """improved_diffusion.unet.UNetModel state dict (synth.UNET_CONFIG geometry) -> engine, names prefixed 'un.'."""
         if self.has_unet:

@@ -227,6 +227,28 @@ int dmad_set_recheck_margin2(dmad_engine* e, float tau2);
 int dmad_recheck_stats(dmad_engine* e, int64_t* samples, int64_t* rechecked, int64_t* rechecked_fp32, int32_t reset);
 int dmad_wavenet_eps_path(dmad_engine* e, const float* x_t, int32_t t, int32_t B, int32_t path, float* eps, dmad_stream s);
 
+/* Vector-Jacobian product of the eps-network on the exact-fp32 path — the gradient the white-box attack drivers take THROUGH the
+ * DiffWave purifier (white_box_attack.py: loss.backward() through AcousticSystem; kws_adaptive_attack_eval.py:111).
+ *
+ * dmad_reserve_vjp reserves the VJP workspace for up to max_batch clips per pass: the saved residual streams h_n (step embedding
+ * included) of every layer, NL x (L + 2 kPad) x 256 fp32 per clip (0.74 GB at the reference geometry, kPad = 2048), the zero-padded
+ * gradient maps of the dilated conv input ((L + 2 kPad) x 512) and of the residual stream (3 x (L + 2 kPad) x 256), and the transposed
+ * weight images (NL x 2.0 MB + 256 KB), packed on the device from the resident forward images.  max_batch is capped at the engine's
+ * fp32 pass size (max_batch of a DMAD_FP32 engine, recheck_batch of a DMAD_EXACT one).  A larger reservation replaces a smaller one;
+ * a smaller one keeps the present.  Counted by dmad_device_bytes.  This is the only allocation of the VJP: the data path below
+ * allocates nothing.  DMAD_ERR_STATE for a DMAD_BF16 engine (it holds no fp32 weights) or before dmad_finalize_weights.
+ *
+ * dmad_wavenet_eps_vjp:  g_x = (d eps / d x_t)^T g_eps  for eps = WaveNet((x_t, t * ones)) on the exact-fp32 path.
+ * x_t, g_eps, g_x: device fp32 [B][clip_len].  eps: optional (NULL) device fp32 [B][clip_len], bit-identical to
+ * dmad_wavenet_eps_path(.., path = 1, ..) (to dmad_wavenet_eps on a DMAD_FP32 engine).  DMAD_FP32 and DMAD_EXACT engines only;
+ * B in [1, max_batch], processed in passes of the reservation's size.  Recompute scheme: a forward pass saves the residual streams
+ * only; the backward recomputes each layer's dilated-conv output H inside the GEMM that applies the gate's derivative, so the
+ * 512-channel H never reaches HBM.  Every reduction runs in a fixed order (no atomics, no split-K): g_x is bit-identical across
+ * calls and independent of the batch a clip is in.  DMAD_ERR_STATE without a reservation. */
+int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch);
+int dmad_wavenet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps,
+                         dmad_stream s);
+
 /* The forward of RobustCertificate.smooth_predict's loop body (certified_robust.py:46-56) for an explicit LIST of Monte Carlo
  * samples on an explicit WaveNet path — the audit of the exact-vote mode (RobustCertificate.certify(audit=k): k samples that
  * voted on the 16-bit tier are re-evaluated on a higher one) and the measurement tools' hook:  row i of logits_out [n][num_classes]
