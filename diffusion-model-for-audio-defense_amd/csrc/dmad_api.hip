@@ -28,6 +28,8 @@ thread_local std::string g_err, g_warn;
 // WaveNet paths of an engine (dmad_wavenet_eps_path / dmad_set_waveform_tier): the mode's default (16-bit where resident), exact fp32,
 // the fp32 pipeline on split-f16 operands
 enum { PATH_DEFAULT = 0, PATH_FP32 = 1, PATH_X3 = 2 };
+// Philox streams of the reverse VP-SDE chain (dmad_vpsde_purify, include/dmad.h): the initial diffusion draw, then one per Euler step
+constexpr uint32_t kVpsdeStreamDiffuse = 0x5DE00000u, kVpsdeStreamStep0 = 0x5DE00001u;
 
 int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -213,6 +215,7 @@ struct dmad_engine {
     int vjpB = 0;
     float *vjp_save = nullptr, *vjp_gH = nullptr, *vjp_G = nullptr, *vjp_gg = nullptr;
     float *vjp_wdilT = nullptr, *vjp_wgT = nullptr, *vjp_wf0T = nullptr;
+    float* vjp_g2 = nullptr;               // [2][vjpB][L]: the ping-pong adjoint of dmad_vpsde_purify_vjp
     // common work buffers
     float *xt = nullptr, *eps = nullptr, *x0 = nullptr, *znoise = nullptr;
     // classifier
@@ -1318,7 +1321,9 @@ int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipS
 //   G = three zero-padded [vjpB][LP][256] maps: region 0 g_s (the gradient of the skip sum, every layer's g_skip), regions 1 / 2 the
 //   gradient of the residual stream ping-pong.  The gate-gradient GEMM contracts K = 512 over two taps — tap 0 = region 0 through
 //   W_skip^T, tap 1 = region r through sqrt(1/2) W_res^T — by reading region r with a tap stride of r regions.
-int wavenet_vjp_pass(dmad_engine* e, const float* x_t, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s) {
+// affine (the reverse VP-SDE chain): g_x = alpha * g_eps - gamma * (d eps / d x_t)^T g_eps, in the init-conv backward's epilogue
+int wavenet_vjp_pass(dmad_engine* e, const float* x_t, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s,
+                     bool affine = false, float alpha = 1.f, float gamma = 0.f) {
     const int L = e->L, LP = e->LP, NL = e->NL;
     const long N = (long)B * L;
     const size_t RS = (size_t)e->vjpB * LP * kC, sslot = RS;
@@ -1355,7 +1360,7 @@ int wavenet_vjp_pass(dmad_engine* e, const float* x_t, int t, int B, const float
         g4.epi = 4; g4.L = L; g4.LP = LP; g4.hin = last ? nullptr : g_hout; g4.hout = g_hin;
         CHK(launch_gemm_f32(g4, s) ? fail(DMAD_ERR_INVALID, "VJP: no kernel for the transposed dilated conv") : 0);
     }
-    launch_vjp_init(x_t, e->init_w, e->init_b, e->vjp_G + (size_t)(1 + ((NL - 1) & 1)) * RS, g_x, B, L, LP, s);
+    launch_vjp_init(x_t, e->init_w, e->init_b, e->vjp_G + (size_t)(1 + ((NL - 1) & 1)) * RS, g_x, B, L, LP, s, affine ? g_eps : nullptr, alpha, gamma);
     LASTCHK();
     return 0;
 }
@@ -1746,6 +1751,64 @@ int dmad_ddpm_purify(dmad_engine* e, const float* x0, int32_t t_star, float c_a,
     return 0;
 }
 
+int dmad_vpsde_purify(dmad_engine* e, const float* x0, int32_t B, int32_t n_steps, float c_a, float c_b, const int32_t* k, const float* h,
+                      const float* hb, const float* q, const float* gs, const float* z, uint64_t seed, uint64_t sample0, int32_t path, float* out,
+                      float* traj, dmad_stream s) {
+    if (!e || !x0 || !out || !k || !h || !hb || !q || !gs) return fail(DMAD_ERR_INVALID, "null argument");
+    if (n_steps < 1) return fail(DMAD_ERR_INVALID, "n_steps %d < 1", n_steps);
+    if (B < 1) return fail(DMAD_ERR_INVALID, "batch %d < 1", B);
+    if (path != 0 && path != 1) return fail(DMAD_ERR_INVALID, "unknown path %d (0 the mode's default, 1 exact fp32)", path);
+    if (path == 1 && !e->f32) return fail(DMAD_ERR_STATE, "path 1 is the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights");
+    if (!e->wn_final) return fail(DMAD_ERR_STATE, "WaveNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    for (int n = 0; n < n_steps; ++n)
+        if (k[n] < 0) return fail(DMAD_ERR_INVALID, "step %d: k = %d < 0", n, k[n]);
+    const int wp = path == 1 ? PATH_FP32 : wave_path(e);
+    const size_t L = e->L, slot = (size_t)B * L;
+    const hipStream_t st = (hipStream_t)s;
+    for (int b0 = 0; b0 < B; b0 += e->maxB) {                  // a pass: the whole chain for up to max_batch clips
+        const int bb = B - b0 < e->maxB ? B - b0 : e->maxB;
+        float* x = out + b0 * L;
+        const uint64_t s0 = sample0 + (uint64_t)b0;
+        launch_vpsde_step(x0 + b0 * L, nullptr, z ? z + b0 * L : nullptr, c_a, c_b, 0.f, 0.f, seed, s0, kVpsdeStreamDiffuse, x,
+                          traj ? traj + b0 * L : nullptr, bb, e->L, st);
+        for (int n = 0; n < n_steps; ++n) {
+            CHK(wavenet_eps(e, x, k[n], bb, e->eps, st, wp));
+            launch_vpsde_step(x, e->eps, z ? z + (n + 1) * slot + b0 * L : nullptr, hb[n], q[n], h[n], gs[n], seed, s0,
+                              kVpsdeStreamStep0 + (uint32_t)n, x, traj ? traj + (n + 1) * slot + b0 * L : nullptr, bb, e->L, st);
+        }
+    }
+    LASTCHK();
+    return 0;
+}
+
+int dmad_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int32_t n_steps, float c_a, const int32_t* k, const float* h,
+                          const float* hb, const float* q, const float* g_out, float* g_x0, dmad_stream s) {
+    if (!e || !traj || !k || !h || !hb || !q || !g_out || !g_x0) return fail(DMAD_ERR_INVALID, "null argument");
+    if (g_out == g_x0) return fail(DMAD_ERR_INVALID, "g_out and g_x0 must not alias");
+    if (n_steps < 1) return fail(DMAD_ERR_INVALID, "n_steps %d < 1", n_steps);
+    if (!e->f32) return fail(DMAD_ERR_STATE, "the WaveNet VJP runs on the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights");
+    if (!e->wn_final) return fail(DMAD_ERR_STATE, "WaveNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    if (!e->vjpB) return fail(DMAD_ERR_STATE, "no VJP workspace: call dmad_reserve_vjp first");
+    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    for (int n = 0; n < n_steps; ++n)
+        if (k[n] < 0) return fail(DMAD_ERR_INVALID, "step %d: k = %d < 0", n, k[n]);
+    const size_t L = e->L, slot = (size_t)B * L;
+    const hipStream_t st = (hipStream_t)s;
+    for (int b0 = 0; b0 < B; b0 += e->vjpB) {                  // a pass of the reservation: the whole reverse walk
+        const int bb = B - b0 < e->vjpB ? B - b0 : e->vjpB;
+        const float* g = g_out + b0 * L;
+        for (int n = n_steps - 1; n >= 0; --n) {
+            // g <- (1 + h hb) g - (h q) J_n^T g, J_n = d eps / d x at traj[n]; the last step (n = 0) folds in d x_0 / d x0 = c_a
+            double alpha = 1.0 + (double)h[n] * (double)hb[n], gamma = (double)h[n] * (double)q[n];
+            if (n == 0) { alpha *= c_a; gamma *= c_a; }
+            float* dst = n == 0 ? g_x0 + b0 * L : e->vjp_g2 + (size_t)((n_steps - 1 - n) & 1) * e->vjpB * L;
+            CHK(wavenet_vjp_pass(e, traj + n * slot + b0 * L, k[n], bb, g, dst, e->eps, st, true, (float)alpha, (float)gamma));
+            g = dst;
+        }
+    }
+    return 0;
+}
+
 int dmad_mel_db(dmad_engine* e, const float* x, int32_t B, float* spec, dmad_stream s) {
     if (!e || !x || !spec) return fail(DMAD_ERR_INVALID, "null argument");
     return mel_db(e, x, B, spec, (hipStream_t)s);
@@ -1918,7 +1981,7 @@ int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch) {
     if (e->vjpB) {                          // a larger reservation replaces the present one
         const size_t ob = e->vjpB;
         e->release(&e->vjp_save, NL * ob * LP * kC); e->release(&e->vjp_gH, ob * LP * 512);
-        e->release(&e->vjp_G, 3 * ob * LP * kC); e->release(&e->vjp_gg, ob * e->L * kC);
+        e->release(&e->vjp_G, 3 * ob * LP * kC); e->release(&e->vjp_gg, ob * e->L * kC); e->release(&e->vjp_g2, 2 * ob * e->L);
         e->vjpB = 0;
     }
     if (!e->vjp_wdilT) {
@@ -1931,6 +1994,7 @@ int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch) {
     CHK(e->alloc(&e->vjp_gH, (size_t)vB * LP * 512, true));
     CHK(e->alloc(&e->vjp_G, 3 * (size_t)vB * LP * kC, true));
     CHK(e->alloc(&e->vjp_gg, (size_t)vB * e->L * kC));
+    CHK(e->alloc(&e->vjp_g2, 2 * (size_t)vB * e->L));
     HIPCHK(hipDeviceSynchronize());
     e->vjpB = vB;
     return 0;

@@ -19,6 +19,10 @@ void launch_embed_table(float t, const float* w1, const float* b1, const float* 
                         const float* bt, float* table, float* emb2_out, const float* b_res, float* epi_c, int NL, hipStream_t s);
 void launch_lincomb(int op, const float* x, const float* y, const float* z, float c0, float c1, float c2, float* out, long n,
                     hipStream_t s);
+// reverse VP-SDE (dmad_vpsde_purify): eps == nullptr -> y = c0 x + c1 z; else y = x + (c0 x - c1 eps) h + c2 z; z == nullptr: Philox
+// draw keyed (seed, sample0 + row, stream) in registers; y may alias x; traj (optional) gets a copy of y
+void launch_vpsde_step(const float* x, const float* eps, const float* z, float c0, float c1, float h, float c2, uint64_t seed,
+                       uint64_t sample0, uint32_t stream, float* y, float* traj, int B, int L, hipStream_t s);
 void launch_wn_init_f32(const float* x, const float* w, const float* bias, const float* emb0, float* h, int B, int L, int LP,
                         hipStream_t s, bool split = false, bool hi_only = false);
 void launch_scale(const float* x, float c, float* y, long n, hipStream_t s, bool split = false);

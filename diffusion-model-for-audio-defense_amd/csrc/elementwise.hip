@@ -194,6 +194,49 @@ __global__ void lincomb_kernel(int op, const float* __restrict__ x, const float*
     out[i] = r;
 }
 
+// Reverse VP-SDE chain (dmad_vpsde_purify), one thread per 4 samples of a row; the N(0,1) draw stays in registers (Philox keyed
+// (seed, sample0 + row, stream), the words of philox_normal_kernel) unless the caller passes z.
+//   eps == nullptr: the initial diffusion       y = c0 * x + c1 * z                        (the rounding of lincomb op 1)
+//   otherwise:      the Euler-Maruyama step     y = x + (c0 * x - c1 * eps) * h + c2 * z    (c2 == 0: no draw)
+// y may alias x (each thread reads its elements before it writes them), so neither carries __restrict__; traj (optional)
+// receives a second copy of y.
+__global__ void vpsde_step_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ z, float c0, float c1, float h,
+                                  float c2, uint64_t seed, uint64_t sample0, uint32_t stream, float* y, float* traj, int B, int L) {
+    const int per = L / 4;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * per) return;
+    const int b = (int)(i / per), blk = (int)(i - (long)b * per);
+    const long o = (long)b * L + blk * 4;
+    const float4 xv = *(const float4*)(x + o);
+    const float xa[4] = {xv.x, xv.y, xv.z, xv.w};
+    const bool draw = eps == nullptr || c2 != 0.f;
+    float za[4] = {0.f, 0.f, 0.f, 0.f};
+    if (draw) {
+        if (z) {
+            const float4 zv = *(const float4*)(z + o);
+            za[0] = zv.x; za[1] = zv.y; za[2] = zv.z; za[3] = zv.w;
+        } else {
+            philox_normal4(seed, sample0 + b, stream, blk, za);
+        }
+    }
+    float r[4];
+    if (!eps) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = __fadd_rn(__fmul_rn(c0, xa[j]), __fmul_rn(c1, za[j]));
+    } else {
+        const float4 ev = *(const float4*)(eps + o);
+        const float ea[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            r[j] = __fadd_rn(xa[j], __fmul_rn(__fsub_rn(__fmul_rn(c0, xa[j]), __fmul_rn(c1, ea[j])), h));
+            if (draw) r[j] = __fadd_rn(r[j], __fmul_rn(c2, za[j]));
+        }
+    }
+    const float4 out = float4{r[0], r[1], r[2], r[3]};
+    *(float4*)(y + o) = out;
+    if (traj) *(float4*)(traj + o) = out;
+}
+
 // ----------------------------------------------------------------------------------------------
 // fp32 (parity) WaveNet helpers
 // ----------------------------------------------------------------------------------------------
@@ -418,6 +461,11 @@ void launch_embed_table(float t, const float* w1, const float* b1, const float* 
 void launch_lincomb(int op, const float* x, const float* y, const float* z, float c0, float c1, float c2, float* out, long n,
                     hipStream_t s) {
     hipLaunchKernelGGL(lincomb_kernel, dim3(nblk(n, 256)), dim3(256), 0, s, op, x, y, z, c0, c1, c2, out, n);
+}
+void launch_vpsde_step(const float* x, const float* eps, const float* z, float c0, float c1, float h, float c2, uint64_t seed,
+                       uint64_t sample0, uint32_t stream, float* y, float* traj, int B, int L, hipStream_t s) {
+    hipLaunchKernelGGL(vpsde_step_kernel, dim3(nblk((long)B * (L / 4), 256)), dim3(256), 0, s, x, eps, z, c0, c1, h, c2, seed, sample0, stream,
+                       y, traj, B, L);
 }
 void launch_wn_init_f32(const float* x, const float* w, const float* bias, const float* emb0, float* h, int B, int L, int LP,
                         hipStream_t s, bool split, bool hi_only) {

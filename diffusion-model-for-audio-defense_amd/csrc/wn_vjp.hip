@@ -19,9 +19,13 @@ __global__ void vjp_final_kernel(const float* __restrict__ y, const float* __res
     ((float4*)g_y)[i] = float4{v.x > 0.f ? w.x * g : 0.f, v.y > 0.f ? w.y * g : 0.f, v.z > 0.f ? w.z * g : 0.f, v.w > 0.f ? w.w * g : 0.f};
 }
 
-// one wave per position (the layout of dot256_kernel): lane l holds channels 4l .. 4l+3, then a fixed butterfly
+// one wave per position (the layout of dot256_kernel): lane l holds channels 4l .. 4l+3, then a fixed butterfly.
+// AFFINE (the reverse VP-SDE chain, dmad_vpsde_purify_vjp): g_x[p] = alpha * g_in[p] - gamma * sum instead of the sum, so the adjoint
+// update of an Euler step costs no pass of its own.  g_in and g_x are two different buffers (the caller ping-pongs them).
+template <bool AFFINE>
 __global__ void __launch_bounds__(256) vjp_init_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                       const float* __restrict__ g_h0, float* __restrict__ g_x, int L, int LP, long N) {
+                                                       const float* __restrict__ g_h0, float* __restrict__ g_x, int L, int LP, long N,
+                                                       const float* __restrict__ g_in, float alpha, float gamma) {
     const long p = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (p >= N) return;
@@ -36,7 +40,10 @@ __global__ void __launch_bounds__(256) vjp_init_kernel(const float* __restrict__
         if (__fadd_rn(__fmul_rn(wa[j], xv), ba[j]) > 0.f) s = __fadd_rn(s, __fmul_rn(wa[j], ga[j]));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) g_x[p] = s;
+    if (lane == 0) {
+        if constexpr (AFFINE) g_x[p] = __fsub_rn(__fmul_rn(alpha, g_in[p]), __fmul_rn(gamma, s));
+        else g_x[p] = s;
+    }
 }
 
 // one thread per element of the forward image wdil[n][tap][R][ci]; R -> output channel as packed by finalize_wavenet (epi 1)
@@ -73,9 +80,11 @@ void launch_vjp_final(const float* y, const float* wz, const float* g_eps, float
     const long total4 = N * 64;
     hipLaunchKernelGGL(vjp_final_kernel, dim3(nblk(total4, 256)), dim3(256), 0, s, y, wz, g_eps, g_y, total4);
 }
-void launch_vjp_init(const float* x, const float* w, const float* bias, const float* g_h0, float* g_x, int B, int L, int LP, hipStream_t s) {
+void launch_vjp_init(const float* x, const float* w, const float* bias, const float* g_h0, float* g_x, int B, int L, int LP, hipStream_t s,
+                     const float* g_in, float alpha, float gamma) {
     const long N = (long)B * L;
-    hipLaunchKernelGGL(vjp_init_kernel, dim3(nblk(N, 4)), dim3(256), 0, s, x, w, bias, g_h0, g_x, L, LP, N);
+    if (g_in) hipLaunchKernelGGL(vjp_init_kernel<true>, dim3(nblk(N, 4)), dim3(256), 0, s, x, w, bias, g_h0, g_x, L, LP, N, g_in, alpha, gamma);
+    else hipLaunchKernelGGL(vjp_init_kernel<false>, dim3(nblk(N, 4)), dim3(256), 0, s, x, w, bias, g_h0, g_x, L, LP, N, nullptr, 0.f, 0.f);
 }
 void launch_vjp_pack(const float* wdil, const float* wrs, const float* wf0, float* wdilT, float* wgT, float* wf0T, int NL, hipStream_t s) {
     const long td = (long)NL * 3 * 512 * 256, tg = (long)NL * 2 * 256 * 256;

@@ -499,6 +499,51 @@ class Engine:
                                                 _ptr(None if eps is None else eps[s:e]), _stream()))
         return (gx, eps) if want_eps else gx
 
+    def vpsde_purify(self, x0: torch.Tensor, c_a: float, c_b: float, k, h, hb, q, gs, z: Optional[torch.Tensor] = None, seed: int = 0,
+                     sample0: int = 0, path: int = 0, want_traj: bool = False):
+        """dmad_vpsde_purify: the reverse VP-SDE chain (diffusion to the start, then one Euler-Maruyama step per entry of k / h / hb /
+        q / gs), one library call per chunk of max_batch clips.  path 0: the mode's default WaveNet path, 1: exact fp32.  z: optional
+        explicit noise [S + 1, B, L] (slot 0 the diffusion draw, slot n + 1 step n); None = Philox keyed (seed, sample0 + row).
+        want_traj: also return the trajectory for vpsde_purify_vjp, a [(S + 1) * B, L] tensor stored chunk by chunk: rows
+        [(S + 1) * s, (S + 1) * e) hold the [S + 1][e - s][L] slots of the chunk [s, e)."""
+        x = self._wave(x0)
+        B, S = x.shape[0], len(k)
+        out = torch.empty_like(x)
+        traj = torch.empty(((S + 1) * B, self.L), dtype=torch.float32, device=x.device) if want_traj else None
+        ka, ha, hba, qa, gsa = self._vpsde_arrays(k, h, hb, q, gs)
+        if z is not None:
+            z = z.detach()
+            if not z.is_cuda or tuple(z.shape) != (S + 1, B, self.L):
+                raise DmadError('z must be a CUDA tensor [%d, %d, %d], not %s' % (S + 1, B, self.L, tuple(z.shape)))
+            z = z.float()
+        for s, e in self._chunks(B):
+            zz = None if z is None else z[:, s:e].contiguous()
+            tr = None if traj is None else traj[(S + 1) * s:(S + 1) * e]
+            check(self.lib.dmad_vpsde_purify(self._h, _ptr(x[s:e]), e - s, S, float(c_a), float(c_b), ka, ha, hba, qa, gsa, _ptr(zz), int(seed),
+                                             int(sample0) + s, int(path), _ptr(out[s:e]), _ptr(tr), _stream()))
+        return (out, traj) if want_traj else out
+
+    def vpsde_purify_vjp(self, traj: torch.Tensor, c_a: float, k, h, hb, q, g_out: torch.Tensor) -> torch.Tensor:
+        """dmad_vpsde_purify_vjp: g_x0 = (d out / d x0)^T g_out of the chain vpsde_purify(.., path=1, want_traj=True) ran, the draws held
+        fixed ([B, L] or [B, 1, L] -> [B, L]).  traj: that call's trajectory.  Needs reserve_vjp first (DmadError otherwise)."""
+        g = self._wave(g_out)
+        B, S = g.shape[0], len(k)
+        if not traj.is_cuda or tuple(traj.shape) != ((S + 1) * B, self.L):
+            raise DmadError('traj must be the [(S + 1) * B, L] = [%d, %d] trajectory of vpsde_purify, not %s' % ((S + 1) * B, self.L, tuple(traj.shape)))
+        gx = torch.empty_like(g)
+        ka, ha, hba, qa, _ = self._vpsde_arrays(k, h, hb, q, h)
+        for s, e in self._chunks(B):
+            check(self.lib.dmad_vpsde_purify_vjp(self._h, _ptr(traj[(S + 1) * s:(S + 1) * e]), e - s, S, float(c_a), ka, ha, hba, qa,
+                                                 _ptr(g[s:e]), _ptr(gx[s:e]), _stream()))
+        return gx
+
+    @staticmethod
+    def _vpsde_arrays(k, h, hb, q, gs):
+        S = len(k)
+        if not (len(h) == len(hb) == len(q) == len(gs) == S) or S < 1:
+            raise DmadError('the schedule arrays k / h / hb / q / gs must have one entry per Euler step (%d)' % S)
+        return ((C.c_int32 * S)(*[int(v) for v in k]),) + tuple((C.c_float * S)(*[float(v) for v in a]) for a in (h, hb, q, gs))
+
     def load_unet(self, state_dict):
         """improved_diffusion.unet.UNetModel state dict (synth.UNET_CONFIG geometry) -> engine, names prefixed 'un.'."""
         if self.has_unet:

@@ -249,6 +249,33 @@ int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch);
 int dmad_wavenet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps,
                          dmad_stream s);
 
+/* The reverse VP-SDE purifier of the reference's adaptive-attack driver (adaptive_attack_eval.py --defense Diffusion ->
+ * diffusion_models/diffwave_sde.py RevDiffWave.audio_editing_sample: torchsde.sdeint_adjoint(RevVPSDE, method='euler', dt = 1/T)).
+ * The step schedule is built by the CALLER on the host, in float32 and in torchsde's order (diffusion_models/diffwave_sde.py
+ * vpsde_schedule): the float32 time grid repeats and skips step indices, so no index sequence is assumed here.
+ *
+ * dmad_vpsde_purify:  x <- c_a * x0 + c_b * z_0;  for n = 0 .. n_steps-1:  x <- x + (hb[n] * x - q[n] * eps(x, k[n])) * h[n] + gs[n] * z_{n+1}
+ * (gs[n] == 0: no draw).  k (step index of the eps-network), h (step length), hb (beta / 2), q (beta / sqrt(1 - alpha_bar[k])), gs (the
+ * noise scale of the step): HOST arrays of n_steps.  Noise: z (optional, device fp32 [n_steps + 1][B][clip_len], test hook), or, with
+ * z == NULL, Philox N(0,1) drawn in registers, keyed (seed, sample0 + b, stream 0x5DE00000 for the diffusion draw, 0x5DE00001 + n
+ * for Euler step n).  path: 0 = the mode's default WaveNet path (dmad_set_waveform_tier's tier on an exact-vote engine, like the other
+ * waveform-returning surfaces), 1 = exact fp32 (DMAD_FP32 / DMAD_EXACT engines).  x0, out: device fp32 [B][clip_len] (may alias).
+ * traj: optional device fp32 [n_steps + 1][B][clip_len]; slot n receives the state entering Euler step n, slot n_steps the output.  B is
+ * processed in passes of max_batch clips.  One fused kernel per step after the eps-network (read x and eps, draw z, write x and the
+ * trajectory slot).
+ *
+ * dmad_vpsde_purify_vjp:  g_x0 = (d out / d x0)^T g_out of that chain on the exact-fp32 path, the draws held fixed: walking the steps
+ * in reverse,  g <- (1 + h[n] hb[n]) g - (h[n] q[n]) J_n^T g  with J_n^T g the eps-network's VJP (dmad_wavenet_eps_vjp's recompute
+ * scheme) at traj slot n, and g_x0 = c_a * g.  The update is the epilogue of the VJP's init-conv backward (two ping-pong buffers of the
+ * reservation); the last step folds c_a in.  traj: as written by dmad_vpsde_purify(.., path = 1, ..) for the same B (slots 0 .. n_steps-1
+ * are read).  g_out, g_x0: device fp32 [B][clip_len], must not alias.  B <= max_batch, processed in passes of the dmad_reserve_vjp
+ * reservation; nothing is allocated.  Every reduction in a fixed order: g_x0 is bit-reproducible and independent of the batch. */
+int dmad_vpsde_purify(dmad_engine* e, const float* x0, int32_t B, int32_t n_steps, float c_a, float c_b, const int32_t* k, const float* h,
+                      const float* hb, const float* q, const float* gs, const float* z, uint64_t seed, uint64_t sample0, int32_t path, float* out,
+                      float* traj, dmad_stream s);
+int dmad_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int32_t n_steps, float c_a, const int32_t* k, const float* h,
+                          const float* hb, const float* q, const float* g_out, float* g_x0, dmad_stream s);
+
 /* The forward of RobustCertificate.smooth_predict's loop body (certified_robust.py:46-56) for an explicit LIST of Monte Carlo
  * samples on an explicit WaveNet path — the audit of the exact-vote mode (RobustCertificate.certify(audit=k): k samples that
  * voted on the 16-bit tier are re-evaluated on a higher one) and the measurement tools' hook:  row i of logits_out [n][num_classes]
