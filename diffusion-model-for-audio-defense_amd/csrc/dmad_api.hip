@@ -166,6 +166,13 @@ struct HostW {
     std::vector<int64_t> shape;
 };
 
+// The exact-vote state of one vote loop (dmad_smooth_votes / dmad_spec_smooth_votes): the bounds of its first pass and of its
+// split-f16 middle tier (< 0: no middle tier), and the statistics dmad_recheck_stats / dmad_spec_recheck_stats2 report
+struct RecheckTiers {
+    float tau1 = 0.f, tau2 = 0.f;
+    int64_t samples = 0, rechecked = 0, rechecked_fp32 = 0;
+};
+
 }  // namespace
 
 struct dmad_engine {
@@ -175,12 +182,11 @@ struct dmad_engine {
     int maxB32 = 0;                        // clips per exact-fp32 WaveNet pass (== maxB for DMAD_FP32, recheck_batch for DMAD_EXACT)
     int mode = DMAD_MODE_FAST;             // enum dmad_mode (DMAD_EXACT engines switch at run time)
     int wave_tier = 2;                     // dmad_set_waveform_tier: WaveNet path of the waveform-returning entry points in DMAD_MODE_EXACT_VOTES
-    float tau = 0.f;                       // recheck bound on the bf16 top-2 logit margin
-    long long* rc_list = nullptr;          // global indices of the samples queued for the fp32 re-evaluation
+    RecheckTiers wave_rt, spec_rt;         // exact-vote bounds and statistics of the waveform / spec-domain vote loop
+    long long* rc_list = nullptr;          // global indices of the samples queued for the re-evaluation
     unsigned long long* rc_n = nullptr;    // their number (device) ...
     unsigned long long* rc_n_host = nullptr;   // ... and its pinned host mirror
     long rc_cap = 0;
-    int64_t st_samples = 0, st_rechecked = 0;
     int diag[5] = {0, 0, 0, 0, 0};         // dmad_debug_rounding: GemmF32Args::diag of the x3 tier's dil / res / skip / f0 launches, init hi-only
     std::string warn;                      // dmad_last_warning
     std::map<std::string, HostW> hw;
@@ -207,9 +213,7 @@ struct dmad_engine {
     float *wdil_x3 = nullptr, *wrs_x3 = nullptr, *wf0_x3 = nullptr;      // the same weights in the split-f16 storage format (x3 tier)
     float *wskip32 = nullptr, *wskip_x3 = nullptr, *bskip32 = nullptr;   // [NL][256][256] skip weights (fp32 / split-f16), sum of the skip biases
     float* gstore32 = nullptr;                                           // gate outputs of all layers [NL][maxB32 * L][256] (fp32 and x3 tiers)
-    float tau2 = 0.f;                      // recheck bound of the x3 tier (its logit-difference error against the fp32 path)
     long long* rc_list2 = nullptr;         // samples the x3 tier leaves to the fp32 tier
-    int64_t st_rechecked2 = 0;
     float *hA32 = nullptr, *hB32 = nullptr, *H32 = nullptr, *g32 = nullptr, *skip32 = nullptr;
     // VJP workspace (dmad_reserve_vjp): saved residual streams [NL][vjpB][LP][256], gradient maps, transposed weight images
     int vjpB = 0;
@@ -282,9 +286,6 @@ struct dmad_engine {
     float* un_st_buf[3] = {nullptr};
     float* un_st_t2 = nullptr;
     std::vector<float*> un_st_hs;
-    float tau_spec = 0.f;                  // recheck bound of the spec-domain vote loop's 16-bit tier (dmad_set_spec_recheck_margin)
-    float tau_spec2 = 0.f;                 // ... and of its split-f16 tier (dmad_set_spec_recheck_margin2; < 0: no middle tier)
-    int64_t st_spec_samples = 0, st_spec_rechecked = 0, st_spec_rechecked2 = 0;
 
     template <typename T>
     int alloc(T** p, size_t n, bool zero = false) {
@@ -1458,6 +1459,27 @@ inline int cls_tier(const dmad_engine* e) {
 // WaveNet's), the exact-fp32 WaveNet tier with the fp32 classifier: what reaches tier 3 is the fp32 path bit for bit
 inline int cls_tier_of_path(const dmad_engine* e, int path) { return (path == PATH_X3 && e->rx_x3 && e->cls_kind == 1) ? 2 : 0; }
 
+// dmad_set_{,spec_}recheck_margin{,2}: the first pass's bound (tier 1) must be >= 0; the middle tier's (tier 2) must not be NaN,
+// < 0 turns that tier off (the queued samples go straight to the exact-fp32 tier)
+int set_recheck_bound(dmad_engine* e, bool spec, int tier, float tau) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
+    if (tier == 1 && !(tau >= 0.f)) return fail(DMAD_ERR_INVALID, "recheck margin must be >= 0");
+    if (tau != tau) return fail(DMAD_ERR_INVALID, "recheck margin is NaN");
+    RecheckTiers& rt = spec ? e->spec_rt : e->wave_rt;
+    (tier == 1 ? rt.tau1 : rt.tau2) = tau;
+    return 0;
+}
+
+int read_recheck_stats(dmad_engine* e, bool spec, int64_t* samples, int64_t* rechecked, int64_t* rechecked_fp32, int32_t reset) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
+    RecheckTiers& rt = spec ? e->spec_rt : e->wave_rt;
+    if (samples) *samples = rt.samples;
+    if (rechecked) *rechecked = rt.rechecked;
+    if (rechecked_fp32) *rechecked_fp32 = rt.rechecked_fp32;
+    if (reset) rt.samples = rt.rechecked = rt.rechecked_fp32 = 0;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1497,15 +1519,15 @@ int dmad_create(const dmad_config* cfg, dmad_engine** out) {
     e->maxB32 = cfg->precision == DMAD_FP32 ? cfg->max_batch : (cfg->recheck_batch > 0 ? cfg->recheck_batch : 32);
     if (e->maxB32 > cfg->max_batch) e->maxB32 = cfg->max_batch;
     e->mode = cfg->precision == DMAD_EXACT ? DMAD_MODE_EXACT_VOTES : (cfg->precision == DMAD_FP32 ? DMAD_MODE_FP32 : DMAD_MODE_FAST);
-    e->tau = cfg->half_type == DMAD_HALF_F16 ? 0.034f : 0.30f;  // measured logit-difference error (against the leader) of the 16-bit path x 1.4 (see dmad.h)
-    e->tau2 = 1e-3f;                        // the same for the split-f16 tier (dmad_set_recheck_margin2)
+    e->wave_rt.tau1 = cfg->half_type == DMAD_HALF_F16 ? 0.034f : 0.30f;  // measured logit-difference error (against the leader) of the 16-bit path x 1.4 (see dmad.h)
+    e->wave_rt.tau2 = 1e-3f;                // the same for the split-f16 tier (dmad_set_recheck_margin2)
     e->un_h16 = cfg->precision != DMAD_FP32;    // engines with a 16-bit side also get the UNet's f16 tier (once UNet weights are loaded)
     e->rx_h16 = cfg->precision != DMAD_FP32;    // ... and ResNeXt29's (once its weights are loaded)
     if (const char* v = getenv("DMAD_RX_H16")) if (v[0] == '0') e->rx_h16 = false;      // A/B switch: ResNeXt29 on the fp32 matrix cores in every tier
     e->rx_x3 = cfg->precision == DMAD_EXACT;    // ... and its split-f16 tier
     if (const char* v = getenv("DMAD_RX_X3")) if (v[0] == '0') e->rx_x3 = false;        // A/B switch
-    e->tau_spec = 0.13f;                    // spec-domain vote loop: measured logit-difference error of the f16 UNet chain x headroom (see dmad.h)
-    e->tau_spec2 = 5e-4f;                   // ... of the chain on the split-f16 tier (measured 2.3e-4)
+    e->spec_rt.tau1 = 0.13f;                // spec-domain vote loop: measured logit-difference error of the f16 UNet chain x headroom (see dmad.h)
+    e->spec_rt.tau2 = 5e-4f;                // ... of the chain on the split-f16 tier (measured 2.3e-4)
     e->un_x3 = cfg->precision == DMAD_EXACT;    // exact-vote engines also hold the UNet's split-f16 middle tier
     const bool wn = cfg->with_wavenet != 0;
     if (e->bf16 && !wn_final_p_supported(cfg->num_res_layers)) {
@@ -1947,27 +1969,19 @@ int dmad_set_waveform_tier(dmad_engine* e, int32_t tier) {
     return 0;
 }
 
-int dmad_set_recheck_margin(dmad_engine* e, float tau) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (!(tau >= 0.f)) return fail(DMAD_ERR_INVALID, "recheck margin must be >= 0");
-    e->tau = tau;
-    return 0;
-}
-
-int dmad_set_recheck_margin2(dmad_engine* e, float tau2) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (tau2 != tau2) return fail(DMAD_ERR_INVALID, "recheck margin is NaN");
-    e->tau2 = tau2;                          // < 0: no middle tier, the queued samples go straight to the fp32 path
-    return 0;
-}
+int dmad_set_recheck_margin(dmad_engine* e, float tau) { return set_recheck_bound(e, false, 1, tau); }
+int dmad_set_recheck_margin2(dmad_engine* e, float tau2) { return set_recheck_bound(e, false, 2, tau2); }
+int dmad_set_spec_recheck_margin(dmad_engine* e, float tau) { return set_recheck_bound(e, true, 1, tau); }
+int dmad_set_spec_recheck_margin2(dmad_engine* e, float tau2) { return set_recheck_bound(e, true, 2, tau2); }
 
 int dmad_recheck_stats(dmad_engine* e, int64_t* samples, int64_t* rechecked, int64_t* rechecked_fp32, int32_t reset) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (samples) *samples = e->st_samples;
-    if (rechecked) *rechecked = e->st_rechecked;
-    if (rechecked_fp32) *rechecked_fp32 = e->st_rechecked2;
-    if (reset) e->st_samples = e->st_rechecked = e->st_rechecked2 = 0;
-    return 0;
+    return read_recheck_stats(e, false, samples, rechecked, rechecked_fp32, reset);
+}
+int dmad_spec_recheck_stats(dmad_engine* e, int64_t* samples, int64_t* rechecked, int32_t reset) {
+    return read_recheck_stats(e, true, samples, rechecked, nullptr, reset);
+}
+int dmad_spec_recheck_stats2(dmad_engine* e, int64_t* samples, int64_t* rechecked, int64_t* rechecked_fp32, int32_t reset) {
+    return read_recheck_stats(e, true, samples, rechecked, rechecked_fp32, reset);
 }
 
 int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch) {
@@ -2022,62 +2036,9 @@ int dmad_debug_rounding(dmad_engine* e, const int32_t masks[5]) {
     return 0;
 }
 
-int dmad_eval_samples(dmad_engine* e, const float* clip, float sigma, float sqrt_alpha_bar_star, int32_t t, float c_a, float c_b,
-                      uint64_t seed, uint64_t sample0, const float* delta, const int64_t* idx, int64_t n, int32_t path, float* logits_out,
-                      float* x0_out, dmad_stream s) {
-    if (!e || !clip || !idx || (!logits_out && !x0_out)) return fail(DMAD_ERR_INVALID, "null argument");
-    if (n < 0) return fail(DMAD_ERR_INVALID, "n < 0");
-    if (path != PATH_DEFAULT && path != PATH_FP32 && path != PATH_X3) return fail(DMAD_ERR_INVALID, "unknown path %d", path);
-    if (path != PATH_DEFAULT && !(e->bf16 && e->f32)) return fail(DMAD_ERR_STATE, "explicit WaveNet paths need a DMAD_EXACT engine");
-    if (logits_out && !e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
-    hipStream_t st = (hipStream_t)s;
-    const int L = e->L, C = e->cfg.num_classes;
-    const int cap = path == PATH_DEFAULT ? e->maxB : e->maxB32;
-    for (int64_t done = 0; done < n; done += cap) {
-        const int B = (int)(n - done < cap ? n - done : cap);
-        launch_mc_noise_scale_idx(clip, delta, sigma, sqrt_alpha_bar_star, seed, sample0, (const long long*)idx + done, e->xt, B, L, st);
-        CHK(wavenet_eps(e, e->xt, t, B, e->eps, st, path));
-        float* x0 = x0_out ? x0_out + done * L : e->x0;
-        launch_lincomb(0, e->xt, e->eps, nullptr, c_a, c_b, 0.f, x0, (long)B * L, st);
-        if (logits_out) {
-            CHK(mel_db(e, x0, B, e->spec, st));
-            CHK(classify(e, e->spec, B, logits_out + done * C, st, path == PATH_DEFAULT ? cls_tier(e) : cls_tier_of_path(e, path)));
-        }
-    }
-    LASTCHK();
-    return 0;
-}
-
 }  // extern "C"
 
 namespace {
-
-// The queued samples of an exact-vote pass, re-evaluated on the exact-fp32 WaveNet from the same noise.  Waits for the
-// stream once (the queue length decides the launches).
-struct RecheckJob {
-    const float* clip; const float* delta; float sigma, scale; int t; float c_a, c_b; uint64_t seed, sample0;
-    int64_t* counts; float* logits_out; float* x0_out;
-};
-// one tier of the recheck: rows idx[0..n) re-evaluated on `path`; tau >= 0: rows whose margin is still below tau are queued in
-// `next` (they do not vote), tau < 0: every row votes
-int recheck_pass(dmad_engine* e, const RecheckJob& j, const long long* list, long n, int path, float tau, long long* next, hipStream_t st) {
-    const int L = e->L, C = e->cfg.num_classes;
-    for (long done = 0; done < n; done += e->maxB32) {
-        const int B = (int)(n - done < e->maxB32 ? n - done : e->maxB32);
-        const long long* idx = list + done;
-        launch_mc_noise_scale_idx(j.clip, j.delta, j.sigma, j.scale, j.seed, j.sample0, idx, e->xt, B, L, st);
-        CHK(wavenet_eps(e, e->xt, j.t, B, e->eps, st, path));
-        launch_lincomb(0, e->xt, e->eps, nullptr, j.c_a, j.c_b, 0.f, e->x0, (long)B * L, st);
-        if (j.x0_out) launch_scatter_rows(e->x0, idx, (long long)j.sample0, j.x0_out, B, L, st);
-        CHK(mel_db(e, e->x0, B, e->spec, st));
-        CHK(classify(e, e->spec, B, e->logits, st, cls_tier_of_path(e, path)));
-        if (j.logits_out) launch_scatter_rows(e->logits, idx, (long long)j.sample0, j.logits_out, B, C, st);
-        if (tau >= 0.f) launch_vote_margin(e->logits, B, C, (unsigned long long*)j.counts, tau, 0, idx, next, e->rc_n, e->rc_cap, nullptr, st);
-        else launch_vote(e->logits, B, C, (unsigned long long*)j.counts, nullptr, st);
-    }
-    LASTCHK();
-    return 0;
-}
 
 long read_queue_length(dmad_engine* e, hipStream_t st, int* rc) {
     *rc = 0;
@@ -2091,32 +2052,117 @@ long read_queue_length(dmad_engine* e, hipStream_t st, int* rc) {
     return n;
 }
 
-// The samples the 16-bit pass queued: tier 2 = the fp32 pipeline on split-f16 operands (three MFMAs per product, ~fp32
-// accuracy at several times the fp32 matrix rate) settles every sample whose margin exceeds ITS error bound tau2; what is
-// left (margins inside tau2) goes to tier 3, the exact-fp32 path.  Two stream synchronisations (the queue lengths decide
-// the launches).
-int run_recheck(dmad_engine* e, const RecheckJob& j, hipStream_t st) {
-    int rc = 0;
-    const long n1 = read_queue_length(e, st, &rc);
-    if (rc) return rc;
-    e->st_rechecked += n1;
-    if (n1 == 0) return 0;
-    if (e->tau2 >= 0.f && e->wdil_x3) {
-        CHK(recheck_pass(e, j, e->rc_list, n1, PATH_X3, e->tau2, e->rc_list2, st));
-        const long n2 = read_queue_length(e, st, &rc);
+enum { TIER_SPLIT = 2, TIER_FP32 = 3 };    // the recheck tiers of vote_loop
+
+// The vote loop of dmad_smooth_votes and dmad_spec_smooth_votes.  first(done, B, &lg) runs samples sample0 + done .. + B on the
+// loop's first pass and points lg at their logits; with an engine without classifier nothing votes.  Without `recheck` every
+// sample votes there.  With it (the exact-vote mode) a sample whose top-2 margin is below rt.tau1 is queued instead, and the queue
+// drains at the end, or mid-call when the next batch could overflow it: rows(idx, B, tier) re-runs listed samples from the same
+// Philox keys on TIER_SPLIT / TIER_FP32 into e->logits (and scatters the loop's outputs), in chunks of up to `chunk`.  The
+// split-f16 tier (`mid` and rt.tau2 >= 0) settles every sample whose margin there is at least rt.tau2; the rest, or every queued
+// sample without that tier, goes to the exact-fp32 tier.  A re-run row of the loop's outputs carries the last tier's result.
+template <class First, class Rows>
+int vote_loop(dmad_engine* e, RecheckTiers& rt, bool recheck, bool mid, int chunk, int64_t n, int batch, uint64_t sample0,
+              int64_t* counts, First first, Rows rows, hipStream_t st) {
+    const int C = e->cfg.num_classes;
+    unsigned long long* cnt = (unsigned long long*)counts;
+    // one recheck tier over list[0..nq): tau >= 0 queues the rows whose margin is still below tau in `next`, tau < 0 votes every row
+    auto pass = [&](const long long* list, long nq, int tier, float tau, long long* next) -> int {
+        for (long done = 0; done < nq; done += chunk) {
+            const int B = (int)(nq - done < chunk ? nq - done : chunk);
+            const long long* idx = list + done;
+            CHK(rows(idx, B, tier));
+            if (tau >= 0.f) launch_vote_margin(e->logits, B, C, cnt, tau, 0, idx, next, e->rc_n, e->rc_cap, nullptr, st);
+            else launch_vote(e->logits, B, C, cnt, nullptr, st);
+        }
+        return 0;
+    };
+    // two stream synchronisations at most: the queue lengths decide the launches
+    auto drain = [&]() -> int {
+        int rc = 0;
+        const long n1 = read_queue_length(e, st, &rc);
         if (rc) return rc;
-        e->st_rechecked2 += n2;
-        if (n2) CHK(recheck_pass(e, j, e->rc_list2, n2, PATH_FP32, -1.f, nullptr, st));
-    } else {
-        e->st_rechecked2 += n1;
-        CHK(recheck_pass(e, j, e->rc_list, n1, PATH_FP32, -1.f, nullptr, st));
+        rt.rechecked += n1;
+        if (n1 == 0) return 0;
+        if (mid && rt.tau2 >= 0.f) {
+            CHK(pass(e->rc_list, n1, TIER_SPLIT, rt.tau2, e->rc_list2));
+            const long n2 = read_queue_length(e, st, &rc);
+            if (rc) return rc;
+            rt.rechecked_fp32 += n2;
+            if (n2) CHK(pass(e->rc_list2, n2, TIER_FP32, -1.f, nullptr));
+        } else {
+            rt.rechecked_fp32 += n1;
+            CHK(pass(e->rc_list, n1, TIER_FP32, -1.f, nullptr));
+        }
+        return 0;
+    };
+    // an earlier call that failed between queueing and draining must not leave its indices to this one
+    if (recheck) HIPCHK(hipMemsetAsync(e->rc_n, 0, sizeof(unsigned long long), st));
+    int64_t queued_from = 0;               // first sample (relative) of the current recheck segment
+    for (int64_t done = 0; done < n; done += batch) {
+        const int B = (int)((n - done < batch) ? (n - done) : batch);
+        const float* lg = nullptr;
+        CHK(first(done, B, &lg));
+        if (!e->cfg.with_classifier) continue;
+        if (recheck) {
+            launch_vote_margin(lg, B, C, cnt, rt.tau1, (long long)(sample0 + (uint64_t)done), nullptr, e->rc_list, e->rc_n, e->rc_cap, nullptr, st);
+            // the queue holds at most rc_cap indices: drain it before the samples voted since the last drain could overflow it
+            if (done + B - queued_from + batch > e->rc_cap && done + B < n) {
+                CHK(drain());
+                queued_from = done + B;
+            }
+        } else {
+            launch_vote(lg, B, C, cnt, nullptr, st);
+        }
     }
+    if (recheck && n > 0) CHK(drain());
+    if (e->cfg.with_classifier) rt.samples += n;
+    LASTCHK();
     return 0;
+}
+
+struct WaveJob {
+    const float* clip; const float* delta; float sigma, scale; int t; float c_a, c_b; uint64_t seed, sample0;
+    float* x0_out;                         // listed rows' x0 is also scattered here (dmad_smooth_votes' recheck)
+};
+// One batch of the waveform chain: noise -> WaveNet on `path` -> x0 (into x0_dst) -> mel dB -> logits (into logits_dst; nullptr:
+// none).  Rows are samples s0 + b, or idx[b] when an index list is given.  The classifier tier: the mode's on the default path (a
+// vote loop's first pass), the one paired with the WaveNet tier on an explicit path.
+int wave_rows(dmad_engine* e, const WaveJob& j, uint64_t s0, const long long* idx, int B, int path, float* x0_dst, float* logits_dst,
+              hipStream_t st) {
+    const int L = e->L;
+    if (idx) launch_mc_noise_scale_idx(j.clip, j.delta, j.sigma, j.scale, j.seed, j.sample0, idx, e->xt, B, L, st);
+    else launch_mc_noise_scale(j.clip, j.delta ? j.delta + (s0 - j.sample0) * L : nullptr, j.sigma, j.scale, j.seed, s0, e->xt, B, L, st);
+    CHK(wavenet_eps(e, e->xt, j.t, B, e->eps, st, path));
+    launch_lincomb(0, e->xt, e->eps, nullptr, j.c_a, j.c_b, 0.f, x0_dst, (long)B * L, st);
+    if (idx && j.x0_out) launch_scatter_rows(x0_dst, idx, (long long)j.sample0, j.x0_out, B, L, st);
+    if (!logits_dst) return 0;
+    CHK(mel_db(e, x0_dst, B, e->spec, st));
+    return classify(e, e->spec, B, logits_dst, st, path == PATH_DEFAULT ? cls_tier(e) : cls_tier_of_path(e, path));
 }
 
 }  // namespace
 
 extern "C" {
+
+int dmad_eval_samples(dmad_engine* e, const float* clip, float sigma, float sqrt_alpha_bar_star, int32_t t, float c_a, float c_b,
+                      uint64_t seed, uint64_t sample0, const float* delta, const int64_t* idx, int64_t n, int32_t path, float* logits_out,
+                      float* x0_out, dmad_stream s) {
+    if (!e || !clip || !idx || (!logits_out && !x0_out)) return fail(DMAD_ERR_INVALID, "null argument");
+    if (n < 0) return fail(DMAD_ERR_INVALID, "n < 0");
+    if (path != PATH_DEFAULT && path != PATH_FP32 && path != PATH_X3) return fail(DMAD_ERR_INVALID, "unknown path %d", path);
+    if (path != PATH_DEFAULT && !(e->bf16 && e->f32)) return fail(DMAD_ERR_STATE, "explicit WaveNet paths need a DMAD_EXACT engine");
+    if (logits_out && !e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
+    const WaveJob job{clip, delta, sigma, sqrt_alpha_bar_star, t, c_a, c_b, seed, sample0, nullptr};
+    const int cap = path == PATH_DEFAULT ? e->maxB : e->maxB32;
+    for (int64_t done = 0; done < n; done += cap) {
+        const int B = (int)(n - done < cap ? n - done : cap);
+        CHK(wave_rows(e, job, 0, (const long long*)idx + done, B, path, x0_out ? x0_out + done * e->L : e->x0,
+                      logits_out ? logits_out + done * e->cfg.num_classes : nullptr, (hipStream_t)s));
+    }
+    LASTCHK();
+    return 0;
+}
 
 int dmad_smooth_votes(dmad_engine* e, const float* clip, float sigma, float sqrt_alpha_bar_star, int32_t t, float c_a,
                       float c_b, int64_t n, int32_t batch, uint64_t seed, uint64_t sample0, const float* delta, int64_t* counts,
@@ -2126,39 +2172,22 @@ int dmad_smooth_votes(dmad_engine* e, const float* clip, float sigma, float sqrt
     if (e->cfg.with_classifier && !counts) return fail(DMAD_ERR_INVALID, "counts must not be null");
     hipStream_t st = (hipStream_t)s;
     const int L = e->L, C = e->cfg.num_classes;
+    const WaveJob job{clip, delta, sigma, sqrt_alpha_bar_star, t, c_a, c_b, seed, sample0, x0_out};
+    // exact-vote mode: the queued samples re-run on the split-f16 WaveNet (~fp32 accuracy at several times the fp32 matrix rate),
+    // those still inside tau2 there on the exact-fp32 WaveNet
     const bool recheck = e->bf16 && e->f32 && e->mode == DMAD_MODE_EXACT_VOTES && e->cfg.with_classifier;
-    int64_t queued_from = 0;               // first sample (relative) of the current recheck segment
-    // an earlier call that failed between queueing and draining must not leave its indices to this one
-    if (recheck) HIPCHK(hipMemsetAsync(e->rc_n, 0, sizeof(unsigned long long), st));
-    for (int64_t done = 0; done < n; done += batch) {
-        const int B = (int)((n - done < batch) ? (n - done) : batch);
-        launch_mc_noise_scale(clip, delta ? delta + done * L : nullptr, sigma, sqrt_alpha_bar_star, seed, sample0 + (uint64_t)done,
-                              e->xt, B, L, st);
-        CHK(wavenet_eps(e, e->xt, t, B, e->eps, st));
-        float* x0 = x0_out ? x0_out + done * L : e->x0;
-        launch_lincomb(0, e->xt, e->eps, nullptr, c_a, c_b, 0.f, x0, (long)B * L, st);
-        if (e->cfg.with_classifier) {
-            CHK(mel_db(e, x0, B, e->spec, st));
-            float* lg = logits_out ? logits_out + done * C : e->logits;
-            CHK(classify(e, e->spec, B, lg, st, cls_tier(e)));
-            if (recheck) {
-                launch_vote_margin(lg, B, C, (unsigned long long*)counts, e->tau, (long long)(sample0 + (uint64_t)done), nullptr, e->rc_list,
-                                   e->rc_n, e->rc_cap, nullptr, st);
-                // the queue holds at most rc_cap indices: drain it before the samples voted since the last drain could overflow it
-                if (done + B - queued_from + batch > e->rc_cap && done + B < n) {
-                    CHK(run_recheck(e, RecheckJob{clip, delta, sigma, sqrt_alpha_bar_star, t, c_a, c_b, seed, sample0, counts, logits_out, x0_out}, st));
-                    queued_from = done + B;
-                }
-            } else {
-                launch_vote(lg, B, C, (unsigned long long*)counts, nullptr, st);
-            }
-        }
-    }
-    if (recheck && n > 0)
-        CHK(run_recheck(e, RecheckJob{clip, delta, sigma, sqrt_alpha_bar_star, t, c_a, c_b, seed, sample0, counts, logits_out, x0_out}, st));
-    if (e->cfg.with_classifier) e->st_samples += n;
-    LASTCHK();
-    return 0;
+    auto first = [&](int64_t done, int B, const float** lg) -> int {
+        float* out = logits_out ? logits_out + done * C : e->logits;
+        *lg = out;
+        return wave_rows(e, job, sample0 + (uint64_t)done, nullptr, B, PATH_DEFAULT, x0_out ? x0_out + done * L : e->x0,
+                         e->cfg.with_classifier ? out : nullptr, st);
+    };
+    auto rows = [&](const long long* idx, int B, int tier) -> int {
+        CHK(wave_rows(e, job, 0, idx, B, tier == TIER_SPLIT ? PATH_X3 : PATH_FP32, e->x0, e->logits, st));
+        if (logits_out) launch_scatter_rows(e->logits, idx, (long long)sample0, logits_out, B, C, st);
+        return 0;
+    };
+    return vote_loop(e, e->wave_rt, recheck, e->wdil_x3 != nullptr, e->maxB32, n, batch, sample0, counts, first, rows, st);
 }
 
 }  // extern "C"
@@ -2213,62 +2242,23 @@ int dmad_spec_smooth_votes(dmad_engine* e, const float* clip, float sigma, int32
     hipStream_t st = (hipStream_t)s;
     const int C = e->cfg.num_classes;
     const SpecJob job{clip, sigma, t_star, q_a, q_b, c_a, c_b, c_1, c_2, c_sig, mel_lo, mel_hi, seed};
-    // exact-vote mode of a DMAD_EXACT engine: the chain runs on the UNet's 16-bit tier, a sample whose top-2 margin is below
-    // tau_spec is queued and its WHOLE chain is re-run on the exact-fp32 UNet from the same Philox keys
+    // exact-vote mode of a DMAD_EXACT engine: the chain runs on the UNet's 16-bit tier; a queued sample re-runs its WHOLE chain from
+    // the same Philox keys on the UNet's split-f16 tier (fp32-grade at several times the fp32 matrix rate), and on the exact-fp32
+    // UNet if its margin there is still inside tau2
     const bool recheck = e->bf16 && e->f32 && e->un_h16 && e->mode == DMAD_MODE_EXACT_VOTES;
-    if (recheck) HIPCHK(hipMemsetAsync(e->rc_n, 0, sizeof(unsigned long long), st));
-    // The queued samples: tier 2 = the whole chain again on the UNet's split-f16 tier (fp32-grade at several times the fp32 matrix rate)
-    // settles every sample whose margin exceeds ITS bound tau_spec2; what is left goes to tier 3, the exact-fp32 UNet.  Every pass runs
-    // its samples in batches of up to max_batch from the same Philox keys; a re-evaluated row of logits_out / spec_out carries the last
-    // tier's result.
-    auto pass = [&](const long long* list, long nq, int tier, float tau, long long* next) -> int {
-        for (long done = 0; done < nq; done += e->maxB) {
-            const int B = (int)(nq - done < e->maxB ? nq - done : e->maxB);
-            const long long* idx = list + done;
-            CHK(spec_chain(e, job, 0, idx, B, tier, e->spec, e->logits, st));
-            if (spec_out) launch_scatter_rows(e->spec, idx, (long long)sample0, spec_out, B, 1024, st);
-            if (logits_out) launch_scatter_rows(e->logits, idx, (long long)sample0, logits_out, B, C, st);
-            if (tau >= 0.f) launch_vote_margin(e->logits, B, C, (unsigned long long*)counts, tau, 0, idx, next, e->rc_n, e->rc_cap, nullptr, st);
-            else launch_vote(e->logits, B, C, (unsigned long long*)counts, nullptr, st);
-        }
+    auto first = [&](int64_t done, int B, const float** lg) -> int {
+        float* out = logits_out ? logits_out + done * C : e->logits;
+        *lg = out;
+        return spec_chain(e, job, sample0 + (uint64_t)done, nullptr, B, (e->un_h16 && e->mode != DMAD_MODE_FP32) ? 1 : 0,
+                          spec_out ? spec_out + done * 1024 : e->spec, out, st);
+    };
+    auto rows = [&](const long long* idx, int B, int tier) -> int {
+        CHK(spec_chain(e, job, 0, idx, B, tier == TIER_SPLIT ? 2 : 0, e->spec, e->logits, st));
+        if (spec_out) launch_scatter_rows(e->spec, idx, (long long)sample0, spec_out, B, 1024, st);
+        if (logits_out) launch_scatter_rows(e->logits, idx, (long long)sample0, logits_out, B, C, st);
         return 0;
     };
-    auto drain = [&]() -> int {
-        int rc = 0;
-        const long nq = read_queue_length(e, st, &rc);
-        if (rc) return rc;
-        e->st_spec_rechecked += nq;
-        if (nq == 0) return 0;
-        if (e->un_x3 && e->tau_spec2 >= 0.f) {
-            CHK(pass(e->rc_list, nq, 2, e->tau_spec2, e->rc_list2));
-            const long n2 = read_queue_length(e, st, &rc);
-            if (rc) return rc;
-            e->st_spec_rechecked2 += n2;
-            if (n2) CHK(pass(e->rc_list2, n2, 0, -1.f, nullptr));
-        } else {
-            e->st_spec_rechecked2 += nq;
-            CHK(pass(e->rc_list, nq, 0, -1.f, nullptr));
-        }
-        return 0;
-    };
-    int64_t queued_from = 0;
-    for (int64_t done = 0; done < n; done += batch) {
-        const int B = (int)((n - done < batch) ? (n - done) : batch);
-        const uint64_t s0 = sample0 + (uint64_t)done;
-        float* sp = spec_out ? spec_out + done * 1024 : e->spec;
-        float* lg = logits_out ? logits_out + done * C : e->logits;
-        CHK(spec_chain(e, job, s0, nullptr, B, (e->un_h16 && e->mode != DMAD_MODE_FP32) ? 1 : 0, sp, lg, st));     // first pass: the 16-bit tier
-        if (recheck) {
-            launch_vote_margin(lg, B, C, (unsigned long long*)counts, e->tau_spec, (long long)s0, nullptr, e->rc_list, e->rc_n, e->rc_cap, nullptr, st);
-            if (done + B - queued_from + batch > e->rc_cap && done + B < n) { CHK(drain()); queued_from = done + B; }
-        } else {
-            launch_vote(lg, B, C, (unsigned long long*)counts, nullptr, st);
-        }
-    }
-    if (recheck && n > 0) CHK(drain());
-    e->st_spec_samples += n;
-    LASTCHK();
-    return 0;
+    return vote_loop(e, e->spec_rt, recheck, e->un_x3, e->maxB, n, batch, sample0, counts, first, rows, st);
 }
 
 int dmad_spec_eval_samples(dmad_engine* e, const float* clip, float sigma, int32_t t_star, float q_a, float q_b, const float* c_a,
@@ -2292,34 +2282,6 @@ int dmad_spec_eval_samples(dmad_engine* e, const float* clip, float sigma, int32
     }
     LASTCHK();
     return 0;
-}
-
-int dmad_set_spec_recheck_margin(dmad_engine* e, float tau) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (!(tau >= 0.f)) return fail(DMAD_ERR_INVALID, "recheck margin must be >= 0");
-    e->tau_spec = tau;
-    return 0;
-}
-
-int dmad_spec_recheck_stats(dmad_engine* e, int64_t* samples, int64_t* rechecked, int32_t reset) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (samples) *samples = e->st_spec_samples;
-    if (rechecked) *rechecked = e->st_spec_rechecked;
-    if (reset) e->st_spec_samples = e->st_spec_rechecked = e->st_spec_rechecked2 = 0;
-    return 0;
-}
-
-int dmad_set_spec_recheck_margin2(dmad_engine* e, float tau2) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (tau2 != tau2) return fail(DMAD_ERR_INVALID, "recheck margin is NaN");
-    e->tau_spec2 = tau2;                     // < 0: no middle tier, the queued samples go straight to the exact-fp32 UNet
-    return 0;
-}
-
-int dmad_spec_recheck_stats2(dmad_engine* e, int64_t* samples, int64_t* rechecked, int64_t* rechecked_fp32, int32_t reset) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (rechecked_fp32) *rechecked_fp32 = e->st_spec_rechecked2;
-    return dmad_spec_recheck_stats(e, samples, rechecked, reset);
 }
 
 int dmad_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, int32_t sampler, int32_t t_star, float c_a, float c_b,
@@ -2369,8 +2331,8 @@ int dmad_spec_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t re
     for (long r0 = 0; r0 < rows; r0 += e->maxB) {
         const int nb = (int)(rows - r0 < e->maxB ? rows - r0 : e->maxB);
         launch_repeat_rows(x, e->xt, B, r0, nb, L, st);
-        // the UNet tier of the map-returning surfaces (exact fp32 unless the engine is in its fast mode), the fp32 classifier: like
-        // dmad_query_logits, a query hands logits back and has no recheck
+        // the UNet tier of the map-returning surfaces (unet_eps, h16 = -1: on an exact-vote engine the dmad_set_waveform_tier tier, split-f16
+        // by default), the fp32 classifier: like dmad_query_logits, a query hands logits back and has no recheck
         CHK(spec_chain_from_xt(e, job, sample0 + (uint64_t)r0, nullptr, nb, -1, 0, e->spec, logits + r0 * C, st));
         if (decisions) launch_vote(logits + r0 * C, nb, C, nullptr, decisions + r0, st);
     }

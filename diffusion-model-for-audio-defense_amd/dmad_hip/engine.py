@@ -288,13 +288,17 @@ class Engine:
         check(self.lib.dmad_set_waveform_tier(self._h, int(tier)))
         self.waveform_tier = int(tier)
 
+    def _set_margin(self, setter, attr: str, floor_attr: str, committed: float, tau: float, calibrated: bool):
+        """the four margin setters (the floor rule: set_recheck_margin)"""
+        check(setter(self._h, float(tau)))
+        setattr(self, attr, float(tau))
+        if not calibrated:
+            setattr(self, floor_attr, max(committed, float(tau)))
+
     def set_recheck_margin(self, tau: float, calibrated: bool = False):
         """bound of the 16-bit tier.  A value the CALLER sets (calibrated = False) also becomes the floor of later calibrations when it
         is wider than the committed default: a calibration may only widen what is in force."""
-        check(self.lib.dmad_set_recheck_margin(self._h, float(tau)))
-        self.recheck_margin = float(tau)
-        if not calibrated:
-            self.floor1 = max(self._committed_margin1(), float(tau))
+        self._set_margin(self.lib.dmad_set_recheck_margin, 'recheck_margin', 'floor1', self._committed_margin1(), tau, calibrated)
 
     def _committed_margin1(self) -> float:
         """the committed tier-1 bound for this engine's operand format and resident classifier kind"""
@@ -303,24 +307,16 @@ class Engine:
 
     def set_recheck_margin2(self, tau2: float, calibrated: bool = False):
         """bound of the split-f16 middle tier (< 0: tier off, queued samples go straight to the fp32 path)."""
-        check(self.lib.dmad_set_recheck_margin2(self._h, float(tau2)))
-        self.recheck_margin2 = float(tau2)
-        if not calibrated:
-            self.floor2 = max(DEFAULT_RECHECK_MARGIN2, float(tau2))
+        self._set_margin(self.lib.dmad_set_recheck_margin2, 'recheck_margin2', 'floor2', DEFAULT_RECHECK_MARGIN2, tau2, calibrated)
 
     def set_spec_recheck_margin(self, tau: float, calibrated: bool = False):
         """bound of the spec-domain vote loop's 16-bit UNet tier (dmad_set_spec_recheck_margin)."""
-        check(self.lib.dmad_set_spec_recheck_margin(self._h, float(tau)))
-        self.spec_recheck_margin = float(tau)
-        if not calibrated:
-            self.floor_spec = max(DEFAULT_SPEC_RECHECK_MARGIN, float(tau))
+        self._set_margin(self.lib.dmad_set_spec_recheck_margin, 'spec_recheck_margin', 'floor_spec', DEFAULT_SPEC_RECHECK_MARGIN, tau, calibrated)
 
     def set_spec_recheck_margin2(self, tau2: float, calibrated: bool = False):
         """bound of the spec-domain loop's split-f16 UNet tier (dmad_set_spec_recheck_margin2); < 0: queued samples go straight to fp32."""
-        check(self.lib.dmad_set_spec_recheck_margin2(self._h, float(tau2)))
-        self.spec_recheck_margin2 = float(tau2)
-        if not calibrated:
-            self.floor_spec2 = max(DEFAULT_SPEC_RECHECK_MARGIN2, float(tau2))
+        self._set_margin(self.lib.dmad_set_spec_recheck_margin2, 'spec_recheck_margin2', 'floor_spec2', DEFAULT_SPEC_RECHECK_MARGIN2, tau2,
+                         calibrated)
 
     def spec_recheck_stats(self, reset: bool = False, detail: bool = False):
         """-> (samples voted by spec_smooth_votes, samples whose chain left the 16-bit tier) since the last reset; detail: + the samples
@@ -334,6 +330,38 @@ class Engine:
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(self.lib.dmad_recheck_stats(self._h, C.byref(a), C.byref(b), C.byref(c), 1 if reset else 0))
         return (int(a.value), int(b.value), int(c.value)) if detail else (int(a.value), int(b.value))
+
+    def _measure_tiers(self, what: str, clips: list, n: int, n_fp32: int, seed: int, tiers: list):
+        """The measurement behind both loops' calibrations.  tiers = evaluators (clip, idx, seed) -> logits of the loop's first pass, its
+        split-f16 tier and its exact-fp32 tier; per clip (seed + its position) n Philox samples run on the first two, the first n_fp32 of
+        them on the third, in the exact-vote mode (the first pass's classifier tier depends on the mode).  Returns (e1, s1, e2): the largest
+        leader-difference error of the first pass against the split-f16 tier, its Gaussian scale, and the largest error of the split-f16
+        tier against fp32, each the maximum over the clips."""
+        if self.precision != EXACT:
+            raise DmadError('%s needs an EXACT engine' % what)
+
+        def lead_err(a, ref):                # per-sample error of a logit difference against the reference's leader (see DEFAULT_RECHECK_MARGIN)
+            d = a - ref
+            return (d - d.gather(1, ref.argmax(1, keepdim=True))).abs().max(1).values
+
+        def gauss_scale(le):                 # P(max of 9 |normal differences| > x) ~= 18 Q(x / s): s from the q90 and q99 points
+            zs = {0.9: 2.5392, 0.99: 3.2608}            # 18 Q(z) = 1 - q
+            return max(float(torch.quantile(le, q)) / z for q, z in zs.items())
+        e1 = s1 = e2 = 0.0
+        mode = self.mode
+        self.set_mode(MODE_EXACT_VOTES)
+        try:
+            for ci, x in enumerate(clips):
+                idx = torch.arange(n, dtype=torch.int64, device=self.device)
+                lo, mid, ref = (f(x, i, seed + ci) for f, i in zip(tiers, (idx, idx, idx[:n_fp32])))
+                if not all(bool(torch.isfinite(v).all()) for v in (lo, mid, ref)):
+                    raise DmadError('%s: non-finite logits' % what)
+                le1 = lead_err(lo.double(), mid.double())
+                e1, s1 = max(e1, float(le1.max())), max(s1, gauss_scale(le1))
+                e2 = max(e2, float(lead_err(mid[:n_fp32].double(), ref.double()).max()))
+        finally:
+            self.set_mode(mode)
+        return e1, s1, e2
 
     def calibrate_recheck(self, clip, sigma: float, sqrt_abar_star: float, t: int, c_a: float, c_b: float,
                           n: int = 1024, n_fp32: int = 512, headroom: float = 1.5, seed: int = 0xCA11B):
@@ -351,38 +379,13 @@ class Engine:
         classifier — hence the error a given eps error turns into — is a property of its weights: call this once per
         (WaveNet, classifier, sigma) before certifying with checkpoints other than the ones the defaults were measured on.
         Returns (tau1, tau2, e1, e2); the observed errors are also kept in self.calibration."""
-        if self.precision != EXACT:
-            raise DmadError('calibrate_recheck needs an EXACT engine')
         clips = list(clip) if isinstance(clip, (list, tuple)) else [clip]
-        mode, tau1, tau2 = self.mode, self.recheck_margin, self.recheck_margin2
+        tau1, tau2 = self.recheck_margin, self.recheck_margin2
         n_fp32 = min(n_fp32, n)
 
-        def lead_err(a, b):                  # per-sample error of a logit difference against the reference's leader (see DEFAULT_RECHECK_MARGIN)
-            e = a - b
-            return (e - e.gather(1, b.argmax(1, keepdim=True))).abs().max(1).values
-
-        def pair_err(a, b):
-            return float(lead_err(a, b).max())
-
-        def gauss_scale(le):                 # P(max of 9 |normal differences| > x) ~= 18 Q(x / s): s from the q90 and q99 points
-            zs = {0.9: 2.5392, 0.99: 3.2608}            # 18 Q(z) = 1 - q
-            return max(float(torch.quantile(le, q)) / z for q, z in zs.items())
-        e1 = e2 = s1 = 0.0
-        try:
-            for ci, x in enumerate(clips):
-                args = (x, sigma, sqrt_abar_star, t, c_a, c_b)
-                idx = torch.arange(n, dtype=torch.int64, device=self.device)
-                self.set_mode(MODE_EXACT_VOTES)       # path 0 there = the loop's FIRST PASS: 16-bit WaveNet + the classifier tier it runs (ResNeXt29: split-f16)
-                fast = self.eval_samples(*args, idx, path=0, seed=seed + ci)
-                mid = self.eval_samples(*args, idx, path=2, seed=seed + ci)
-                ref = self.eval_samples(*args, idx[:n_fp32], path=1, seed=seed + ci)
-                if not (bool(torch.isfinite(fast).all()) and bool(torch.isfinite(mid).all()) and bool(torch.isfinite(ref).all())):
-                    raise DmadError('calibrate_recheck: non-finite logits')
-                le1 = lead_err(fast.double(), mid.double())
-                e1, s1 = max(e1, float(le1.max())), max(s1, gauss_scale(le1))
-                e2 = max(e2, pair_err(mid[:n_fp32].double(), ref.double()))
-        finally:
-            self.set_mode(mode)
+        def path(p):                         # path 0 in the exact-vote mode = the loop's FIRST PASS: 16-bit WaveNet + the classifier tier it runs
+            return lambda x, idx, sd: self.eval_samples(x, sigma, sqrt_abar_star, t, c_a, c_b, idx, path=p, seed=sd)
+        e1, s1, e2 = self._measure_tiers('calibrate_recheck', clips, n, n_fp32, seed, [path(0), path(2), path(1)])
         floor1, floor2 = self.floor1, self.floor2         # the committed defaults, or a wider bound the caller put in force
         new2 = max(floor2, headroom * e2)
         new1 = max(floor1, headroom * e1 + new2, TAIL_Z * s1 + new2)
@@ -418,27 +421,12 @@ class Engine:
         with e its largest value and s its Gaussian scale (q90 / q99 points), floors = the committed defaults (or wider bounds the
         caller put in force): widen-only.  chain_args = (t_star, q_a, q_b, c_a, c_b, c_1, c_2, c_sig, mel_lo, mel_hi) as for
         spec_smooth_votes.  Returns (tau_spec, e, s); the full record is kept in self.spec_calibration."""
-        if self.precision != EXACT:
-            raise DmadError('calibrate_spec_recheck needs an EXACT engine')
         clips = list(clip) if isinstance(clip, (list, tuple)) else [clip]
         n_fp32 = max(1, min(n, n // 2 if n_fp32 is None else n_fp32))
-        e = s = e2 = 0.0
-        zs = {0.9: 2.5392, 0.99: 3.2608}                  # 18 Q(z) = 1 - q (the maximum of 9 |normal differences|)
 
-        def lead_err(a, ref):
-            d = a - ref
-            return (d - d.gather(1, ref.argmax(1, keepdim=True))).abs().max(1).values
-        for ci, x in enumerate(clips):
-            idx = torch.arange(n, dtype=torch.int64, device=self.device)
-            lo = self.spec_eval_samples(x, sigma, *chain_args, idx, tier=1, seed=seed + ci).double()
-            mid = self.spec_eval_samples(x, sigma, *chain_args, idx, tier=2, seed=seed + ci).double()
-            ref = self.spec_eval_samples(x, sigma, *chain_args, idx[:n_fp32], tier=0, seed=seed + ci).double()
-            if not (bool(torch.isfinite(lo).all()) and bool(torch.isfinite(mid).all()) and bool(torch.isfinite(ref).all())):
-                raise DmadError('calibrate_spec_recheck: non-finite logits')
-            le = lead_err(lo, mid)
-            e = max(e, float(le.max()))
-            s = max(s, max(float(torch.quantile(le, q)) / z for q, z in zs.items()))
-            e2 = max(e2, float(lead_err(mid[:n_fp32], ref).max()))
+        def tier(k):
+            return lambda x, idx, sd: self.spec_eval_samples(x, sigma, *chain_args, idx, tier=k, seed=sd)
+        e, s, e2 = self._measure_tiers('calibrate_spec_recheck', clips, n, n_fp32, seed, [tier(1), tier(2), tier(0)])
         previous, floor, floor2 = (self.spec_recheck_margin, self.spec_recheck_margin2), self.floor_spec, self.floor_spec2
         new2 = max(floor2, headroom * e2)
         new = max(floor, headroom * e + new2, TAIL_Z * s + new2)

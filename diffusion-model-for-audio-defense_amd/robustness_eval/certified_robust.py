@@ -145,25 +145,14 @@ class RobustCertificate():
                       float(torch.tensor(alpha_bar_star ** 0.5, dtype=torch.float32)))
 
         fused = self._fused()
-        if fused and self.calibrate > 0:
-            eng = self.denoiser.engine
-            tk = coeffs[0]
-            seen = self._calibrated_clips.setdefault(tk, [])
-            fp = self._clip_fingerprint(x)
-            if getattr(eng, 'precision', None) == 2 and fp not in seen and len(seen) < self.calibrate_clips:    # EXACT engines, once per CLIP
-                new = eng.calibrate_recheck(x, sigma, coeffs[3], tk, coeffs[1], coeffs[2], n=self.calibrate, n_fp32=max(16, self.calibrate // 2))
-                old = self._calibrated.get(tk)
-                if old is not None:             # the bounds of a sigma only widen from clip to clip
-                    new = (max(new[0], old[0]), max(new[1], old[1]), max(new[2], old[2]), max(new[3], old[3]))
-                    eng.set_recheck_margin(new[0], calibrated=True); eng.set_recheck_margin2(new[1], calibrated=True)
-                self._calibrated[tk] = new
-                seen.append(fp)
-                if self.log is not None:
-                    self.log('recheck bounds at sigma=%g (t*=%d), clip %d of %d: observed 16-bit error %.4g, split-f16 error %.3g -> tau1 %.4g, tau2 %.3g'
-                             % (sigma, tk + 1, len(seen), self.calibrate_clips, new[2], new[3], new[0], new[1]))
-            elif getattr(eng, 'precision', None) == 2 and tk in self._calibrated:
-                eng.set_recheck_margin(self._calibrated[tk][0], calibrated=True)      # another sigma ran in between
-                eng.set_recheck_margin2(self._calibrated[tk][1], calibrated=True)
+        if fused and self.calibrate > 0 and getattr(self.denoiser.engine, 'precision', None) == 2:      # EXACT engines
+            eng, tk = self.denoiser.engine, coeffs[0]
+            self._calibrate_clip(
+                x, tk, lambda: eng.calibrate_recheck(x, sigma, coeffs[3], tk, coeffs[1], coeffs[2], n=self.calibrate,
+                                                     n_fp32=max(16, self.calibrate // 2)),
+                eng.set_recheck_margin, eng.set_recheck_margin2,
+                lambda c, r: 'recheck bounds at sigma=%g (t*=%d), clip %d of %d: observed 16-bit error %.4g, split-f16 error %.3g -> tau1 %.4g, '
+                             'tau2 %.3g' % (sigma, tk + 1, c, self.calibrate_clips, r[2], r[3], r[0], r[1]))
         self._last = (seed, sigma, coeffs, num_sampling) if (fused and self.noise_source == 'device') else None
         spec_eng = self._fused_spec() if not fused else None
         spec_args = None
@@ -171,23 +160,14 @@ class RobustCertificate():
             from diffusion_models.Improved_Diffusion_Unconditional.improved_diffusion.sc09_spectrogram_dataset import MEL_LOWER_BOUND, MEL_UPPER_BOUND
             spec_args = tuple(self.transform.purifier.purify_coefficients()) + (MEL_LOWER_BOUND, MEL_UPPER_BOUND)
             exact = getattr(spec_eng, 'precision', None) == 2 and spec_eng.mode == 1           # DMAD_EXACT engine in DMAD_MODE_EXACT_VOTES
-            if exact and self.calibrate > 0:        # the spec tier's bound for the resident weights at this (sigma, t*): widen-only, per clip
-                key = ('spec', spec_args[0], round(float(sigma), 6))
-                seen = self._calibrated_clips.setdefault(key, [])
-                fp = self._clip_fingerprint(x)
-                if fp not in seen and len(seen) < self.calibrate_clips:
+            if exact and self.calibrate > 0:        # the spec tiers' bounds for the resident weights at this (sigma, t*)
+                def measure():
                     tau, e_, s_ = spec_eng.calibrate_spec_recheck(x, sigma, spec_args, n=max(64, min(self.calibrate, 512)))
-                    old = self._calibrated.get(key)
-                    if old is not None and old[0] > tau:
-                        tau = old[0]
-                        spec_eng.set_spec_recheck_margin(tau, calibrated=True)
-                    self._calibrated[key] = (tau, max(e_, old[1]) if old else e_, max(s_, old[2]) if old else s_)
-                    seen.append(fp)
-                    if self.log is not None:
-                        self.log('spec-tier recheck bound at sigma=%g (t*=%d), clip %d of %d: observed 16-bit chain error %.4g (scale %.3g) -> tau_spec %.4g'
-                                 % (sigma, spec_args[0], len(seen), self.calibrate_clips, e_, s_, tau))
-                elif key in self._calibrated:
-                    spec_eng.set_spec_recheck_margin(self._calibrated[key][0], calibrated=True)
+                    return tau, spec_eng.spec_recheck_margin2, e_, s_
+                self._calibrate_clip(
+                    x, ('spec', spec_args[0], round(float(sigma), 6)), measure, spec_eng.set_spec_recheck_margin, spec_eng.set_spec_recheck_margin2,
+                    lambda c, r: 'spec-tier recheck bound at sigma=%g (t*=%d), clip %d of %d: observed 16-bit chain error %.4g (scale %.3g) -> '
+                                 'tau_spec %.4g, tau_spec2 %.3g' % (sigma, spec_args[0], c, self.calibrate_clips, r[2], r[3], r[0], r[1]))
             if exact and self.noise_source == 'device':
                 self._last = ('spec', seed, sigma, spec_args, num_sampling)
         if self.noise_source == 'torch_cpu':
@@ -223,6 +203,24 @@ class RobustCertificate():
                 counts = counts.cpu()
             dist.all_reduce(counts)                 # the single collective of the path: int64[num_classes]
         return counts.cpu()
+
+    def _calibrate_clip(self, x, key, measure, set_tau1, set_tau2, line):
+        """The per-clip recheck calibration of either vote loop at `key` (t for the waveform loop, ('spec', t*, sigma) for the spec
+        loop).  The first `calibrate_clips` distinct clips of a key are measured — certify() calls smooth_predict twice per clip —
+        by measure() -> (tau1, tau2, errors...), the engine's calibration (it can only WIDEN a bound); the key keeps the elementwise
+        maximum of what its clips gave, and both of its bounds are installed on every visit (another key may have run in between).
+        line(clip number, record) is the log line of a measurement."""
+        seen = self._calibrated_clips.setdefault(key, [])
+        fp = self._clip_fingerprint(x)
+        if fp not in seen and len(seen) < self.calibrate_clips:
+            new, old = measure(), self._calibrated.get(key)
+            self._calibrated[key] = new if old is None else tuple(max(a, b) for a, b in zip(new, old))
+            seen.append(fp)
+            if self.log is not None:
+                self.log(line(len(seen), self._calibrated[key]))
+        if key in self._calibrated:
+            set_tau1(self._calibrated[key][0], calibrated=True)
+            set_tau2(self._calibrated[key][1], calibrated=True)
 
     def _generic_votes(self, x, sigma, coeffs, lo, hi, seed, delta, batch_size):
         """Purify with the HIP one-shot, then call the caller's transform / classifier modules."""
@@ -263,67 +261,52 @@ class RobustCertificate():
         import hashlib
         return hashlib.sha1(x.detach().float().cpu().contiguous().numpy().tobytes()).hexdigest()
 
-    def _audit_spec(self, x: torch.Tensor, k: int):
-        """audit() for the spec-domain loop: k samples' chains on the UNet's 16-bit tier; those that VOTED there (margin >= tau_spec)
-        re-run on the UNet's split-f16 tier (fp32-grade: its own error against the exact-fp32 UNet is ~1e-4) from the same keys."""
-        _, seed, sigma, spec_args, n = self._last
-        eng = self._fused_spec()
-        k = min(int(k), n)
-        g = torch.Generator().manual_seed(seed & 0x7FFFFFFFFFFFFFFF)
-        idx = torch.randperm(n, generator=g)[:k].sort()[0].to(x.device)
-        fast = eng.spec_eval_samples(x, sigma, *spec_args, idx, tier=1, seed=seed)
-        top2 = fast.topk(2, dim=1)
-        margin = top2.values[:, 0] - top2.values[:, 1]
-        voted = (margin >= eng.spec_recheck_margin) & torch.isfinite(fast).all(1)
-        vidx = idx[voted]
-        rec = {'audited': int(k), 'voted_on_tier1': int(vidx.numel()), 'disagreements': [], 'max_leader_diff_error': 0.0,
-               'tau_spec': eng.spec_recheck_margin, 'sigma': sigma, 'loop': 'spec'}
-        if vidx.numel():
-            ref = eng.spec_eval_samples(x, sigma, *spec_args, vidx, tier=2, seed=seed)
-            f = fast[voted]
-            e = (f - ref).double()
-            rec['max_leader_diff_error'] = float((e - e.gather(1, ref.argmax(1, keepdim=True))).abs().max())
-            bad = (f.argmax(1) != ref.argmax(1)).nonzero().reshape(-1)
-            rec['disagreements'] = [(int(vidx[j]), int(f[j].argmax()), int(ref[j].argmax()), float(margin[voted][j])) for j in bad.tolist()]
-        self.audit_log.append(rec)
-        if self.log is not None:
-            self.log('audit (spec loop): %d samples, %d voted on the 16-bit UNet tier, %d disagree with the split-f16 UNet tier, largest leader-difference '
-                     'error %.4g (tau_spec %.4g)' % (rec['audited'], rec['voted_on_tier1'], len(rec['disagreements']), rec['max_leader_diff_error'], rec['tau_spec']))
-        return rec
-
     @torch.no_grad()
     def audit(self, x: torch.Tensor, k: int):
-        """Opt-in check of the exact-vote mode on the LAST fused smooth_predict(x, ...): k of its Monte Carlo samples (drawn
-        without replacement from the global index range, the same on every rank) are evaluated on the 16-bit tier; those that
-        VOTED there (margin >= the recheck bound) are re-evaluated on the split-f16 tier from the same Philox keys, and every
-        sample whose arg-max differs is reported.  Returns (and appends to self.audit_log) a dict: audited, voted_on_tier1,
-        disagreements [(sample index, tier-1 class, tier-2 class, tier-1 margin)], largest leader-difference error seen, tau1."""
+        """Opt-in check of the exact-vote mode on the LAST fused smooth_predict(x, ...) of either loop: k of its Monte Carlo samples
+        (drawn without replacement from the global index range, the same on every rank) are evaluated on the loop's first pass (the
+        16-bit tier, in the exact-vote mode whatever the engine's mode); those that VOTED there (margin >= the recheck bound) are
+        re-evaluated on the split-f16 tier (fp32-grade) from the same Philox keys, and every sample whose arg-max differs is
+        reported.  Returns (and appends to self.audit_log) a dict: audited, voted_on_tier1, disagreements [(sample index, tier-1
+        class, tier-2 class, tier-1 margin)], largest leader-difference error seen, the bound (tau1; spec loop: tau_spec, loop)."""
         if self._last is None:
             raise RuntimeError('audit() follows a fused smooth_predict with device noise on an exact-vote engine')
-        if self._last[0] == 'spec':
-            return self._audit_spec(x, k)
-        seed, sigma, coeffs, n = self._last
-        eng = self.denoiser.engine
+        spec = self._last[0] == 'spec'
+        if spec:
+            _, seed, sigma, spec_args, n = self._last
+            eng = self._fused_spec()
+            tau, tau_key, unet = eng.spec_recheck_margin, 'tau_spec', ' UNet'
+
+            def evaluate(idx, tier):            # the UNet's 16-bit (1) / split-f16 (2) tier
+                return eng.spec_eval_samples(x, sigma, *spec_args, idx, tier=tier, seed=seed)
+        else:
+            seed, sigma, coeffs, n = self._last
+            eng = self.denoiser.engine
+            tau, tau_key, unet = eng.recheck_margin, 'tau1', ''
+
+            def evaluate(idx, tier):            # path 0 = the loop's first pass (16-bit WaveNet + the classifier tier it runs), 2 = split-f16
+                return eng.eval_samples(x, sigma, coeffs[3], coeffs[0], coeffs[1], coeffs[2], idx, path=0 if tier == 1 else 2, seed=seed)
         if getattr(eng, 'precision', None) != 2:
             raise RuntimeError('audit() needs an exact-vote (DMAD_EXACT) engine')
         k = min(int(k), n)
         g = torch.Generator().manual_seed(seed & 0x7FFFFFFFFFFFFFFF)
         idx = torch.randperm(n, generator=g)[:k].sort()[0].to(x.device)
-        args = (x, sigma, coeffs[3], coeffs[0], coeffs[1], coeffs[2])
         mode = eng.mode
         try:
-            eng.set_mode(1)                         # exact-vote mode: path 0 = the loop's first pass (16-bit WaveNet + the classifier tier it runs)
-            fast = eng.eval_samples(*args, idx, path=0, seed=seed)
+            eng.set_mode(1)                         # the exact-vote mode: the first pass's classifier tier depends on the mode
+            fast = evaluate(idx, 1)
         finally:
             eng.set_mode(mode)
         top2 = fast.topk(2, dim=1)
         margin = top2.values[:, 0] - top2.values[:, 1]
-        voted = (margin >= eng.recheck_margin) & torch.isfinite(fast).all(1)
+        voted = (margin >= tau) & torch.isfinite(fast).all(1)
         vidx = idx[voted]
         rec = {'audited': int(k), 'voted_on_tier1': int(vidx.numel()), 'disagreements': [], 'max_leader_diff_error': 0.0,
-               'tau1': eng.recheck_margin, 'sigma': sigma}
+               tau_key: tau, 'sigma': sigma}
+        if spec:
+            rec['loop'] = 'spec'
         if vidx.numel():
-            mid = eng.eval_samples(*args, vidx, path=2, seed=seed)
+            mid = evaluate(vidx, 2)
             f = fast[voted]
             e = (f - mid).double()
             rec['max_leader_diff_error'] = float((e - e.gather(1, mid.argmax(1, keepdim=True))).abs().max())
@@ -331,8 +314,9 @@ class RobustCertificate():
             rec['disagreements'] = [(int(vidx[j]), int(f[j].argmax()), int(mid[j].argmax()), float(margin[voted][j])) for j in bad.tolist()]
         self.audit_log.append(rec)
         if self.log is not None:
-            self.log('audit: %d samples, %d voted on the 16-bit tier, %d disagree with the split-f16 tier, largest leader-difference error %.4g (tau1 %.4g)'
-                     % (rec['audited'], rec['voted_on_tier1'], len(rec['disagreements']), rec['max_leader_diff_error'], rec['tau1']))
+            self.log('audit%s: %d samples, %d voted on the 16-bit%s tier, %d disagree with the split-f16%s tier, largest leader-difference '
+                     'error %.4g (%s %.4g)' % (' (spec loop)' if spec else '', rec['audited'], rec['voted_on_tier1'], unet, len(rec['disagreements']),
+                                               unet, rec['max_leader_diff_error'], tau_key, tau))
         return rec
 
     @torch.no_grad()

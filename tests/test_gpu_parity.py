@@ -1915,6 +1915,36 @@ def test_exact_vote_queue_drains_mid_call(weights, sched, monkeypatch):
     assert out['8'][2][:2] == out[None][2][:2] == (30, 30) and sum(out[None][0]) == 30
 
 
+def test_spec_exact_vote_queue_drains_mid_call(monkeypatch):
+    """The spec-domain loop drains its bounded recheck queue between batches like the waveform loop: with an 8-entry queue
+    (DMAD_RECHECK_QUEUE) and every sample forced through both recheck tiers, the counts, logits and stats equal those of the
+    default-sized queue, and the logits are the fp32 mode's."""
+    from diffusion_models.improved_diffusion_ddpm import create_improved_diffusion
+    from dmad_hip import engine as E
+    clip = torch.from_numpy(synth.synthetic_clip(4)).cuda()
+    out = {}
+    for cap in ('8', None):
+        if cap:
+            monkeypatch.setenv('DMAD_RECHECK_QUEUE', cap)
+        else:
+            monkeypatch.delenv('DMAD_RECHECK_QUEUE', raising=False)
+        eng = E.Engine(max_batch=4, precision=E.EXACT, with_wavenet=False)
+        eng.load_vgg19_bn(synth.vgg19_bn_state_dict(4321, calibrated='c5'))
+        pur = create_improved_diffusion(None, reverse_timestep=2, state_dict=synth.unet_state_dict(31), engine=eng)
+        args = (clip, 0.5) + tuple(pur.purify_coefficients()) + (-100.0, 38.22)
+        eng.set_spec_recheck_margin(1e30)                   # nothing votes from the 16-bit tier ...
+        eng.set_spec_recheck_margin2(1e30)                  # ... nor from the split-f16 tier
+        c, lg, _ = eng.spec_smooth_votes(*args, 30, batch=4, seed=12, sample0=7, want_logits=True)
+        out[cap] = (c.cpu().tolist(), lg.cpu(), eng.spec_recheck_stats(detail=True))
+        if cap is None:
+            eng.set_mode(E.MODE_FP32)
+            c32, lg32, _ = eng.spec_smooth_votes(*args, 30, batch=4, seed=12, sample0=7, want_logits=True)
+            assert c32.cpu().tolist() == out[None][0] and torch.equal(lg32.cpu(), out[None][1])
+        eng.close()
+    assert out['8'][0] == out[None][0] and torch.equal(out['8'][1], out[None][1])
+    assert out['8'][2] == out[None][2] == (30, 30, 30) and sum(out[None][0]) == 30
+
+
 def test_recheck_bounds_are_calibrated_for_the_resident_weights(exact_engine, sched):
     """Engine.calibrate_recheck measures the two error statistics of the exact-vote mode for the weights that are loaded (the
     defaults were measured on the synthetic VGG19_bn over 36 864 samples; a checkpoint with another logit sensitivity needs its

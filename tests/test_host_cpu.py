@@ -629,3 +629,67 @@ def test_certificate_calibration_and_audit_host_logic():
     # certify(audit=k) audits every example
     y, r = rc.certify(x.reshape(1, 1, 16000), torch.tensor([3]), sigma=0.5, n_0=10, n=40, batch_size=8, audit=8)
     assert int(y[0]) == 3 and len(rc.audit_log) == 2 and rc.audit_log[-1]['audited'] == 8
+
+
+def test_spec_loop_calibration_and_audit_host_logic(monkeypatch):
+    """The same housekeeping for the spec-domain loop (BASELINE C5) on a scripted engine: one calibration per clip, BOTH tau_spec and
+    tau_spec2 keep the elementwise maximum over the clips of a (t*, sigma) and are both re-installed after another sigma ran in
+    between; the audit evaluates the first pass in the exact-vote mode, restores the engine's mode and keeps its record keys."""
+    from robustness_eval.certified_robust import RobustCertificate
+
+    class ScriptedSpecEngine:
+        precision, mode, num_classes = 2, 1, 10
+        spec_recheck_margin, spec_recheck_margin2 = 0.13, 5e-4
+
+        def __init__(self):
+            self.cal = [(0.15, 9e-4, 0.10, 0.020), (0.20, 6e-4, 0.12, 0.010), (0.90, 0.5, 0.50, 0.30)]
+            self.cal_calls, self.eval_calls, self.modes = [], [], []
+
+        def set_spec_recheck_margin(self, v, calibrated=False): self.spec_recheck_margin = v
+        def set_spec_recheck_margin2(self, v, calibrated=False): self.spec_recheck_margin2 = v
+        def set_mode(self, m): self.modes.append(m); self.mode = m
+
+        def calibrate_spec_recheck(self, x, sigma, chain_args, n):
+            self.cal_calls.append((sigma, chain_args[0], n))
+            tau, tau2, e, s = self.cal[len(self.cal_calls) - 1]
+            self.spec_recheck_margin, self.spec_recheck_margin2 = tau, tau2
+            return tau, e, s
+
+        def spec_smooth_votes(self, x, sigma, *args, batch=64, seed=0, sample0=0):
+            c = torch.zeros(10, dtype=torch.int64); c[2] = args[-1]
+            return c, None, None
+
+        def spec_eval_samples(self, x, sigma, *args, tier, seed=0):
+            idx = args[-1].tolist()
+            self.eval_calls.append((tier, self.mode, idx))
+            lg = torch.zeros(len(idx), 10)
+            for r, i in enumerate(idx):
+                lg[r, 2] = 1.0; lg[r, 4] = 1.0 - 0.15 * (i % 4)     # margin 0.15 * (i % 4): the voters (>= 0.2) are i % 4 >= 2
+            return lg
+
+    eng = ScriptedSpecEngine()
+    pur = type('Pur', (), {'purify_coefficients': lambda self: (4, 0.9, 0.1, [1.0] * 5, [0.0] * 5, [1.0] * 5, [0.0] * 5, [0.0] * 5)})()
+    tr = type('Tr', (), {})(); tr.purifier = pur
+    monkeypatch.setattr(RobustCertificate, '_fused_spec', lambda self: eng)
+    lines = []
+    rc = RobustCertificate(classifier=torch.nn.Identity(), transform=tr, seed=9, calibrate=128, calibrate_clips=2, log=lines.append)
+    x, x_b = torch.zeros(1, 16000), torch.full((1, 16000), 0.25)
+    assert rc.smooth_predict(x, num_sampling=20, sigma=0.5).tolist()[2] == 20
+    rc.smooth_predict(x, num_sampling=20, sigma=0.5)                                  # the same clip again: measured once
+    assert eng.cal_calls == [(0.5, 4, 128)] and len(lines) == 1 and lines[0].startswith('spec-tier recheck bound')
+    rc.smooth_predict(x_b, num_sampling=20, sigma=0.5)                                # wider tau_spec, narrower tau_spec2 -> elementwise max
+    assert len(eng.cal_calls) == 2 and (eng.spec_recheck_margin, eng.spec_recheck_margin2) == (0.20, 9e-4)
+    assert rc._calibrated[('spec', 4, 0.5)] == (0.20, 9e-4, 0.12, 0.020)
+    rc.smooth_predict(x, num_sampling=20, sigma=1.0)                                  # another sigma: its own calibration
+    assert eng.cal_calls[-1][0] == 1.0 and (eng.spec_recheck_margin, eng.spec_recheck_margin2) == (0.90, 0.5)
+    rc.smooth_predict(x, num_sampling=20, sigma=0.5)                                  # back: both bounds re-installed, nothing measured
+    assert len(eng.cal_calls) == 3 and (eng.spec_recheck_margin, eng.spec_recheck_margin2) == (0.20, 9e-4) and len(lines) == 3
+    # the audit of that call, with the engine left in another mode: the first pass runs in the exact-vote mode, the mode is restored
+    eng.mode = 2
+    rec = rc.audit(x, 12)
+    (t1, m1, audited), (t2, _, rechecked) = eng.eval_calls
+    assert (t1, m1, t2) == (1, 1, 2) and eng.modes == [1, 2] and eng.mode == 2
+    assert len(audited) == 12 and audited == sorted(audited) and rechecked == [i for i in audited if i % 4 >= 2]
+    assert list(rec) == ['audited', 'voted_on_tier1', 'disagreements', 'max_leader_diff_error', 'tau_spec', 'sigma', 'loop']
+    assert rec['loop'] == 'spec' and rec['tau_spec'] == 0.20 and rec['voted_on_tier1'] == len(rechecked) and rec['disagreements'] == []
+    assert rc.audit_log[-1] is rec and lines[-1].startswith('audit (spec loop)')
