@@ -13,6 +13,7 @@
 #include "../../include/dmad.h"
 #include "dmad_common.h"
 #include "wn_vjp.h"
+#include "unet_vjp.h"
 #include "unet_ops.h"
 #include "elementwise.h"
 #include "gemm_f32.h"
@@ -255,6 +256,7 @@ struct dmad_engine {
         float *skw = nullptr, *skb = nullptr;                                       // res: 1x1 skip_connection
         h16_t *w1h = nullptr, *w2h = nullptr, *skwh = nullptr;                      // f16 images of w1 / w2 / skw (16-bit tier)
         float *w1x = nullptr, *w2x = nullptr, *skwx = nullptr;                      // the same weights in the split-f16 storage format (middle tier)
+        float *w1T = nullptr, *w2T = nullptr, *skwT = nullptr;                      // transposed (3x3: tap-flipped) images of w1 / w2 / skw (UNet VJP)
         size_t ss_off = 0;                 // res: offset of its (scale, shift) row [2 * cout] inside a step's row of un_ss_table
     };
     std::vector<std::vector<UnOp>> un_in, un_out;
@@ -286,6 +288,16 @@ struct dmad_engine {
     float* un_st_buf[3] = {nullptr};
     float* un_st_t2 = nullptr;
     std::vector<float*> un_st_hs;
+    // UNet VJP workspace (dmad_reserve_unet_vjp): the tape of the exact-fp32 forward — per module (in forward order over
+    // un_in / un_mid / un_out) its output map, and a ResBlock's conv1 output / an AttentionBlock's qkv — [unvjpB] spectrograms per slot,
+    // the gradient maps of the saved skips (g_hs), six work maps and the transposed weight images
+    struct UnTape { std::vector<float*> out, t2, qkv; };
+    int unvjpB = 0;
+    size_t unvjp_tape_per = 0, unvjp_ghs_per = 0;          // floats per spectrogram
+    float *unvjp_tape = nullptr, *unvjp_ghs = nullptr, *unvjp_work = nullptr, *unvjp_zero = nullptr;
+    float *un_inT = nullptr, *un_outT = nullptr;            // conv_in [9][128] / out.2 [128][9] images, tap-flipped
+    UnTape un_tape;
+    std::vector<float*> unvjp_ghs_at;
 
     template <typename T>
     int alloc(T** p, size_t n, bool zero = false) {
@@ -1004,9 +1016,10 @@ const float* gn_fail(int HW, int C) { fail(DMAD_ERR_STATE, "GroupNorm: no kernel
 // (three f16 MFMAs per product, ~22 significant bits, gemm_x3_kernel): GroupNorm writes its output in the split format, the maps a GEMM
 // reads without a GroupNorm in between (the block input of a 1x1 skip conv, of a Downsample / Upsample conv, the attention output) are
 // converted by one elementwise pass.
+// t2dst / qkvdst (the VJP's tape, fp32 tier): where a ResBlock's conv1 output / an AttentionBlock's qkv land instead of the work buffers.
 const float* unet_apply(dmad_engine* e, const dmad_engine::UnOp& o, const float* in, int B, int& H, float* dst, int& rot, hipStream_t s,
-                        const float* in2 = nullptr, int c1 = 0, bool x3 = false) {
-    float *T1 = e->un_buf[3], *T2 = e->un_buf[4], *SK = e->un_buf[5], *QKV = e->un_buf[6], *ATT = e->un_buf[7];
+                        const float* in2 = nullptr, int c1 = 0, bool x3 = false, float* t2dst = nullptr, float* qkvdst = nullptr) {
+    float *T1 = e->un_buf[3], *T2 = t2dst ? t2dst : e->un_buf[4], *SK = e->un_buf[5], *QKV = qkvdst ? qkvdst : e->un_buf[6], *ATT = e->un_buf[7];
     auto next = [&]() { float* p = e->un_buf[rot]; rot = (rot + 1) % 3; if (p == in) { p = e->un_buf[rot]; rot = (rot + 1) % 3; } return p; };
     float* out = dst ? dst : next();
     const long nref = (long)e->maxB * H * H;
@@ -1151,7 +1164,9 @@ bool unet_apply_h16(dmad_engine* e, const dmad_engine::UnOp& o, UMap in, int B, 
 // tier dmad_set_waveform_tier selects — the split-f16 tier by default (fp32-grade, 2.2 x the fp32 rate), the exact-fp32 UNet on request
 // and in DMAD_MODE_FP32 — only the spec-domain vote loop has a recheck, so it alone runs the 16-bit tier by default (it passes h16 = 1);
 // 0 / 1 / 2: explicit
-int unet_eps(dmad_engine* e, const float* x, int t, int B, float* eps, hipStream_t s, int h16 = -1) {
+// tape (exact-fp32 tier only, B <= unvjpB): every module writes its output (and a ResBlock its conv1 output, an AttentionBlock its qkv) to
+// its tape slot instead of the work buffers — the same launches, the same bits (dmad_unet_eps_vjp's forward)
+int unet_eps(dmad_engine* e, const float* x, int t, int B, float* eps, hipStream_t s, int h16 = -1, const dmad_engine::UnTape* tape = nullptr) {
     if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
     if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
     if (t < 0) return fail(DMAD_ERR_INVALID, "diffusion step %d < 0", t);
@@ -1190,19 +1205,29 @@ int unet_eps(dmad_engine* e, const float* x, int t, int B, float* eps, hipStream
     }
     const bool x3 = h16 == 2;
     if (x3 && !e->un_x3) return fail(DMAD_ERR_STATE, "this engine has no split-f16 UNet tier (it needs DMAD_EXACT precision)");
+    if (tape && h16 != 0) return fail(DMAD_ERR_STATE, "the UNet tape belongs to the exact-fp32 tier");
     int H = 32, rot = 0;
+    size_t k = 0;                                               // module index in forward order (the tape's slot)
+    auto t2 = [&]() { return tape ? tape->t2[k] : nullptr; };
+    auto qkv = [&]() { return tape ? tape->qkv[k] : nullptr; };
+    std::vector<float*> hsp(e->un_hs);                          // where the saved maps land: un_hs, or their tape slots
     const float* h = x;
     for (size_t i = 0; i < e->un_in.size(); ++i)
-        for (size_t j = 0; j < e->un_in[i].size(); ++j)
-            if (!(h = unet_apply(e, e->un_in[i][j], h, B, H, j + 1 == e->un_in[i].size() ? e->un_hs[i] : nullptr, rot, s, nullptr, 0, x3))) return DMAD_ERR_STATE;
-    for (auto& o : e->un_mid) if (!(h = unet_apply(e, o, h, B, H, nullptr, rot, s, nullptr, 0, x3))) return DMAD_ERR_STATE;
+        for (size_t j = 0; j < e->un_in[i].size(); ++j, ++k) {
+            const bool last = j + 1 == e->un_in[i].size();
+            if (tape && last) hsp[i] = tape->out[k];
+            if (!(h = unet_apply(e, e->un_in[i][j], h, B, H, tape ? tape->out[k] : last ? e->un_hs[i] : nullptr, rot, s, nullptr, 0, x3, t2(), qkv()))) return DMAD_ERR_STATE;
+        }
+    for (size_t j = 0; j < e->un_mid.size(); ++j, ++k)
+        if (!(h = unet_apply(e, e->un_mid[j], h, B, H, tape ? tape->out[k] : nullptr, rot, s, nullptr, 0, x3, t2(), qkv()))) return DMAD_ERR_STATE;
     size_t top = e->un_hs.size();
     for (auto& blk : e->un_out) {
         --top;
         const int c1 = blk[0].cin - e->un_hs_ch[top];          // th.cat([h, hs.pop()], dim=1): h carries c1 channels, the saved map the rest
-        const float* hs = e->un_hs[top];
-        for (size_t j = 0; j < blk.size(); ++j) {
-            h = j == 0 ? unet_apply(e, blk[0], h, B, H, nullptr, rot, s, hs, c1, x3) : unet_apply(e, blk[j], h, B, H, nullptr, rot, s, nullptr, 0, x3);
+        const float* hs = hsp[top];
+        for (size_t j = 0; j < blk.size(); ++j, ++k) {
+            float* dst = tape ? tape->out[k] : nullptr;
+            h = j == 0 ? unet_apply(e, blk[0], h, B, H, dst, rot, s, hs, c1, x3, t2(), qkv()) : unet_apply(e, blk[j], h, B, H, dst, rot, s, nullptr, 0, x3, t2(), qkv());
             if (!h) return DMAD_ERR_STATE;
         }
     }
@@ -1210,6 +1235,109 @@ int unet_eps(dmad_engine* e, const float* x, int t, int B, float* eps, hipStream
     static_assert(kUnMC == 128, "launch_conv3x3_c128_to1 is the 128-channel output layer");
     launch_conv3x3_c128_to1(e->un_buf[3], e->un_outw, e->un_outb, eps, B, s);       // (the 128 -> 1 output conv: exact fp32 on every tier but the 16-bit one)
     LASTCHK();
+    return 0;
+}
+
+// ---- the UNet's vector-Jacobian product (dmad_unet_eps_vjp) ----------------------------------------------------------------
+// One module in forward order: its input resolution, its tape slot k, the saved map of its concatenated input (top, output blocks' first
+// modules) and the saved map whose gradient joins its input gradient (acc: the first module after each input block, which reads hs[acc]).
+struct UnRef { const dmad_engine::UnOp* o; int H, top, acc; };
+std::vector<UnRef> un_flat(const dmad_engine* e, std::vector<size_t>* hs_k = nullptr) {
+    std::vector<UnRef> r;
+    int H = 32;
+    for (size_t i = 0; i < e->un_in.size(); ++i) {
+        for (size_t j = 0; j < e->un_in[i].size(); ++j) {
+            const auto& o = e->un_in[i][j];
+            r.push_back({&o, H, -1, j == 0 && i > 0 ? (int)i - 1 : -1});
+            if (o.kind == 3) H /= 2;
+        }
+        if (hs_k) hs_k->push_back(r.size() - 1);
+    }
+    for (size_t j = 0; j < e->un_mid.size(); ++j) r.push_back({&e->un_mid[j], H, -1, j == 0 ? (int)e->un_in.size() - 1 : -1});
+    int top = (int)e->un_hs.size();
+    for (auto& blk : e->un_out) {
+        --top;
+        for (size_t j = 0; j < blk.size(); ++j) {
+            r.push_back({&blk[j], H, j == 0 ? top : -1, -1});
+            if (blk[j].kind == 4) H *= 2;
+        }
+    }
+    return r;
+}
+
+// One pass (B <= unvjpB): the forward with its tape, then the modules in reverse.  G[0] / G[1] carry the gradient of the current module's
+// output / input (ping-pong); G[2..5] are the per-module scratch maps (G[2] conv2^T / proj^T / the dilated map / the upsampled gradient,
+// G[3] GroupNorm2^T / the attention gradient, G[4] conv1^T / qkv^T, G[5] the skip conv^T).
+int unet_vjp_pass(dmad_engine* e, const float* x, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s) {
+    CHK(unet_eps(e, x, t, B, eps, s, 0, &e->un_tape));
+    std::vector<size_t> hs_k;
+    const std::vector<UnRef> ops = un_flat(e, &hs_k);
+    const size_t W = (size_t)e->unvjpB * 1024 * 384;
+    float* G[6];
+    for (int i = 0; i < 6; ++i) G[i] = e->unvjp_work + i * W;
+    const auto& tp = e->un_tape;
+    auto gemm = [&](const GemmF32Args& g) -> int {
+        if (launch_gemm_f32(g, s) != 0) return fail(DMAD_ERR_STATE, "UNet VJP: no GEMM for M = %d, K = %d, taps = %d", g.M, g.K, g.taps);
+        return 0;
+    };
+    auto gnb = [&](const float* xin, const float* xin2, int c1, const float* gw, const float* gb, const float* ss, int silu, const float* gy,
+                   const float* add, const float* add2, float* gx, float* gx2, int HW, int C) -> int {
+        if (launch_groupnorm_bwd(xin, xin2, c1, gw, gb, ss, silu, gy, add, add2, gx, gx2, B, HW, C, s)) return fail(DMAD_ERR_STATE, "UNet VJP: GroupNorm backward of a %d-channel map", C);
+        return 0;
+    };
+    // out.2 (128 -> 1) backward: a 1 -> 128 conv of g_eps with the flipped image; out.0 + SiLU backward into G[0]
+    if (launch_conv1ch_3x3(g_eps, e->un_outT, e->unvjp_zero, G[2], B, kUnMC, s)) return fail(DMAD_ERR_STATE, "UNet VJP: output conv backward");
+    CHK(gnb(tp.out.back(), nullptr, 0, e->un_outgw, e->un_outgb, nullptr, 1, G[2], nullptr, nullptr, G[0], nullptr, 1024, kUnMC));
+    float *cur = G[0], *nxt = G[1];
+    for (int k = (int)ops.size() - 1; k >= 0; --k) {
+        const auto& o = *ops[k].o;
+        const int H = ops[k].H, top = ops[k].top;
+        const float* in = k ? tp.out[k - 1] : x;
+        const float* in2 = top >= 0 ? tp.out[hs_k[top]] : nullptr;
+        const int c1 = top >= 0 ? o.cin - e->un_hs_ch[top] : 0;
+        float* gin2 = top >= 0 ? e->unvjp_ghs_at[top] : nullptr;
+        const float* acc = ops[k].acc >= 0 ? e->unvjp_ghs_at[ops[k].acc] : nullptr;
+        if (o.kind == 1) {                      // ResBlock: skip(in) + conv2(SiLU(GN2(conv1(SiLU(GN1(in)))) * (1 + scale) + shift))
+            CHK(gemm(un_conv_args(o.w2T, nullptr, cur, G[2], o.cout, o.cout, 9, B, H, 1, nullptr)));
+            CHK(gnb(tp.t2[k], nullptr, 0, o.gn2w, o.gn2b, e->un_ss_cur + o.ss_off, 1, G[2], nullptr, nullptr, G[3], nullptr, H * H, o.cout));
+            CHK(gemm(un_conv_args(o.w1T, nullptr, G[3], G[4], o.cin, o.cout, 9, B, H, 1, nullptr)));
+            const float *add = cur, *add2 = acc;
+            if (o.cin != o.cout) {              // the 1x1 skip conv's gradient, the consumer's saved-map gradient summed in its epilogue
+                CHK(gemm(un_conv_args(o.skwT, nullptr, cur, G[5], o.cin, o.cout, 1, B, H, 1, acc)));
+                add = G[5]; add2 = nullptr;
+            }
+            CHK(gnb(in, in2, c1, o.gn1w, o.gn1b, nullptr, 1, G[4], add, add2, nxt, gin2, H * H, o.cin));
+        } else if (o.kind == 2) {               // AttentionBlock: in + proj_out(attention(qkv(GN(in))))
+            const int T = H * H, C = o.cin;
+            CHK(gemm(un_conv_args(o.w2T, nullptr, cur, G[2], C, C, 1, B, H, 1, nullptr)));
+            if (int rc = launch_qkv_attention_bwd(tp.qkv[k], G[2], G[3], B, T, kUnHeads, s)) return fail(rc > 0 ? DMAD_ERR_HIP : DMAD_ERR_STATE, "UNet VJP: attention backward (T = %d)", T);
+            CHK(gemm(un_conv_args(o.w1T, nullptr, G[3], G[4], C, 3 * C, 1, B, H, 1, nullptr)));
+            CHK(gnb(in, nullptr, 0, o.gn1w, o.gn1b, nullptr, 0, G[4], cur, acc, nxt, nullptr, T, C));
+        } else if (o.kind == 3) {               // Downsample (3x3, stride 2): the stride-1 conv of the zero-dilated gradient
+            launch_dilate2x_nhwc(cur, G[2], B, H / 2, o.cout, s);
+            CHK(gemm(un_conv_args(o.w1T, nullptr, G[2], nxt, o.cin, o.cout, 9, B, H, 1, acc)));
+        } else if (o.kind == 4) {               // Upsample: the conv's gradient at 2H, then the 2x2 sums
+            CHK(gemm(un_conv_args(o.w1T, nullptr, cur, G[2], o.cin, o.cout, 9, B, 2 * H, 1, nullptr)));
+            launch_upsample2x_bwd_nhwc(G[2], acc, nxt, B, H, o.cin, s);
+        } else {                                // conv_in (1 -> 128): a 128 -> 1 conv of the gradient with the flipped image
+            launch_conv3x3_c128_to1(cur, o.w1T, e->unvjp_zero, g_x, B, s);
+        }
+        std::swap(cur, nxt);
+    }
+    LASTCHK();
+    return 0;
+}
+
+int unet_vjp(dmad_engine* e, const float* x, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s) {
+    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    if (!e->f32) return fail(DMAD_ERR_STATE, "the UNet VJP runs on the exact-fp32 UNet tier: it needs a DMAD_FP32 or DMAD_EXACT engine");
+    if (!e->unvjpB) return fail(DMAD_ERR_STATE, "no UNet VJP workspace: call dmad_reserve_unet_vjp first");
+    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    if (t < 0) return fail(DMAD_ERR_INVALID, "diffusion step %d < 0", t);
+    for (int b0 = 0; b0 < B; b0 += e->unvjpB) {
+        const int bb = B - b0 < e->unvjpB ? B - b0 : e->unvjpB;
+        CHK(unet_vjp_pass(e, x + (size_t)b0 * 1024, t, bb, g_eps + (size_t)b0 * 1024, g_x + (size_t)b0 * 1024, eps ? eps + (size_t)b0 * 1024 : e->un_eps, s));
+    }
     return 0;
 }
 
@@ -2017,6 +2145,74 @@ int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch) {
 int dmad_wavenet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps, dmad_stream s) {
     if (!e || !x_t || !g_eps || !g_x) return fail(DMAD_ERR_INVALID, "null argument");
     return wavenet_vjp(e, x_t, t, B, g_eps, g_x, eps, (hipStream_t)s);
+}
+
+int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
+    if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
+    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    if (!e->f32) return fail(DMAD_ERR_STATE, "the UNet VJP runs on the exact-fp32 UNet tier: it needs a DMAD_FP32 or DMAD_EXACT engine");
+    const int vB = max_batch < e->maxB32 ? max_batch : e->maxB32;
+    if (vB <= e->unvjpB) return 0;
+    // tape slots and saved-map gradients, in floats per spectrogram
+    std::vector<size_t> out_off, t2_off, qkv_off, ghs_off;
+    size_t tape = 0, ghs = 0;
+    for (const UnRef& r : un_flat(e)) {
+        const auto& o = *r.o;
+        const size_t px = (size_t)r.H * r.H, opx = o.kind == 3 ? px / 4 : o.kind == 4 ? px * 4 : px;
+        t2_off.push_back(o.kind == 1 ? tape : SIZE_MAX); if (o.kind == 1) tape += px * o.cout;
+        qkv_off.push_back(o.kind == 2 ? tape : SIZE_MAX); if (o.kind == 2) tape += px * 3 * o.cin;
+        out_off.push_back(tape); tape += opx * o.cout;
+    }
+    for (size_t i = 0; i < e->un_hs_ch.size(); ++i) { ghs_off.push_back(ghs); ghs += (size_t)e->un_hs_hw[i] * e->un_hs_ch[i]; }
+    const size_t W = (size_t)1024 * 384;
+    if (e->unvjpB) {                        // a larger reservation replaces the present one
+        const size_t ob = e->unvjpB;
+        e->release(&e->unvjp_tape, ob * e->unvjp_tape_per); e->release(&e->unvjp_ghs, ob * e->unvjp_ghs_per); e->release(&e->unvjp_work, 6 * ob * W);
+        e->unvjpB = 0;
+    }
+    if (!e->unvjp_zero) {                   // transposed weight images, packed on the device from the resident fp32 images
+        CHK(e->alloc(&e->unvjp_zero, kUnMC, true));
+        auto pack = [&](dmad_engine::UnOp& o) -> int {
+            const long ci = o.cin, co = o.cout;
+            if (o.kind == 0) {              // [co][9] -> [9][co], taps flipped (the 128 -> 1 conv's image)
+                CHK(e->alloc(&o.w1T, 9 * co)); launch_unvjp_pack(o.w1, o.w1T, 9, (int)co, 1, 1, 9, 0, 1, nullptr);
+            } else if (o.kind == 2) {       // qkv [3C][C] -> [C][3C], proj_out [C][C] -> transposed
+                CHK(e->alloc(&o.w1T, 3 * ci * ci)); launch_unvjp_pack(o.w1, o.w1T, 1, (int)ci, (int)(3 * ci), 0, 1, ci, 0, nullptr);
+                CHK(e->alloc(&o.w2T, ci * ci)); launch_unvjp_pack(o.w2, o.w2T, 1, (int)ci, (int)ci, 0, 1, ci, 0, nullptr);
+            } else {                        // 3x3 [tap][co][ci] -> [8 - tap][ci][co]
+                CHK(e->alloc(&o.w1T, 9 * ci * co)); launch_unvjp_pack(o.w1, o.w1T, 9, (int)ci, (int)co, co * ci, 1, ci, 1, nullptr);
+                if (o.kind == 1) {
+                    CHK(e->alloc(&o.w2T, 9 * co * co)); launch_unvjp_pack(o.w2, o.w2T, 9, (int)co, (int)co, co * co, 1, co, 1, nullptr);
+                    if (ci != co) { CHK(e->alloc(&o.skwT, ci * co)); launch_unvjp_pack(o.skw, o.skwT, 1, (int)ci, (int)co, 0, 1, ci, 0, nullptr); }
+                }
+            }
+            return 0;
+        };
+        for (auto& b : e->un_in) for (auto& o : b) CHK(pack(o));
+        for (auto& o : e->un_mid) CHK(pack(o));
+        for (auto& b : e->un_out) for (auto& o : b) CHK(pack(o));
+        CHK(e->alloc(&e->un_outT, 9 * kUnMC)); launch_unvjp_pack(e->un_outw, e->un_outT, kUnMC, 9, 1, 1, kUnMC, 0, 2, nullptr);   // [9][128] -> [128][9], flipped
+        HIPCHK(hipGetLastError());
+        if (int r = unvjp_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, attention backward) failed: %d", r);
+    }
+    CHK(e->alloc(&e->unvjp_tape, (size_t)vB * tape));
+    CHK(e->alloc(&e->unvjp_ghs, (size_t)vB * ghs));
+    CHK(e->alloc(&e->unvjp_work, 6 * (size_t)vB * W));
+    e->unvjp_tape_per = tape; e->unvjp_ghs_per = ghs;
+    auto at = [&](size_t off) { return off == SIZE_MAX ? nullptr : e->unvjp_tape + off * vB; };
+    e->un_tape = dmad_engine::UnTape{};
+    for (size_t k = 0; k < out_off.size(); ++k) { e->un_tape.out.push_back(at(out_off[k])); e->un_tape.t2.push_back(at(t2_off[k])); e->un_tape.qkv.push_back(at(qkv_off[k])); }
+    e->unvjp_ghs_at.clear();
+    for (size_t off : ghs_off) e->unvjp_ghs_at.push_back(e->unvjp_ghs + off * vB);
+    HIPCHK(hipDeviceSynchronize());
+    e->unvjpB = vB;
+    return 0;
+}
+
+int dmad_unet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps, dmad_stream s) {
+    if (!e || !x_t || !g_eps || !g_x) return fail(DMAD_ERR_INVALID, "null argument");
+    return unet_vjp(e, x_t, t, B, g_eps, g_x, eps, (hipStream_t)s);
 }
 
 int dmad_wavenet_eps_path(dmad_engine* e, const float* x_t, int32_t t, int32_t B, int32_t path, float* eps, dmad_stream s) {

@@ -61,6 +61,13 @@ class GaussianDiffusion:
         return (_extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
                 + _extract_into_tensor(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
 
+    def p_sample_coefficients(self, t0):
+        """(c_a, c_b, c_1, c_2, sig) of p_sample at step t0: the fp32 table entries its fused kernel takes (x0 = clamp(c_a x - c_b eps),
+        sample = c_1 x0 + c_2 x + sig z)."""
+        sig = 0.0 if t0 == 0 else float(torch.exp(torch.tensor(0.5 * self._f32(self.model_log_variance, t0))))
+        return (self._f32(self.sqrt_recip_alphas_cumprod, t0), self._f32(self.sqrt_recipm1_alphas_cumprod, t0),
+                self._f32(self.posterior_mean_coef1, t0), self._f32(self.posterior_mean_coef2, t0), sig)
+
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, noise=None, seed=0, sample0=0):
         """One reverse step (l.331-387) on the engine: returns {'sample', 'pred_xstart'}.  `noise`: the step's N(0, 1)
         draw ([B,1,32,32]); None = device Philox noise keyed (seed, sample0 + row, t)."""

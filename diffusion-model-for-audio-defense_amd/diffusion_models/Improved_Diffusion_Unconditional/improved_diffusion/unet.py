@@ -2,8 +2,12 @@
 keep the reference's names (time_embed, input_blocks.<i>.<j>.{in_layers,emb_layers,out_layers,skip_connection,norm,qkv,
 proj_out,op}, middle_block, output_blocks, out) so that checkpoints load unchanged; the forward pass runs in
 libdmad_hip.so (dmad_unet_eps): convs / linears on the fp32 matrix cores over NHWC maps, GroupNorm32 + SiLU +
-scale-shift, 4-head attention and nearest upsampling as small HIP kernels.  Inference only; all rows of a batch carry
-the same timestep (what p_sample_loop passes)."""
+scale-shift, 4-head attention and nearest upsampling as small HIP kernels.  All rows of a batch carry the same timestep
+(what p_sample_loop passes).  No weight gradients; the input gradient runs on the engine (grad_backend).
+
+grad_backend: 'auto' (default) differentiates through the engine's UNet VJP (dmad_hip.autograd.UNetEpsHIP, exact-fp32 tier) when
+the bound engine has the exact-fp32 UNet tier (FP32 / EXACT engines) and raises NotImplementedError otherwise; 'hip' always takes
+the engine's VJP (DmadError on an engine without that tier)."""
 import torch
 import torch.nn as nn
 
@@ -70,6 +74,19 @@ class UNetModel(nn.Module):
         self.middle_block = build(mid)
         self.output_blocks = nn.ModuleList([build(b) for b in outp])
         self.out = nn.Sequential(_gn(model_channels), nn.SiLU(), nn.Conv2d(model_channels, out_channels, 3, padding=1))
+        self.grad_backend = 'auto'
+
+    GRAD_BACKENDS = ('auto', 'hip')
+
+    @property
+    def grad_backend(self):
+        return self.__dict__['_grad_backend']
+
+    @grad_backend.setter
+    def grad_backend(self, value):
+        if value not in self.GRAD_BACKENDS:
+            raise ValueError('grad_backend must be one of %s, not %r' % (self.GRAD_BACKENDS, value))
+        self.__dict__['_grad_backend'] = value
 
     # -- HIP engine binding ---------------------------------------------------------------------
     def bind_engine(self, engine=None):
@@ -83,12 +100,18 @@ class UNetModel(nn.Module):
         assert y is None, 'must specify y if and only if the model is class-conditional'
         if self.training:
             raise NotImplementedError('the HIP UNet is inference-only: call .eval() first')
-        if torch.is_grad_enabled() and x.requires_grad:
-            raise NotImplementedError('the HIP UNet is inference-only (no autograd)')
+        grad = torch.is_grad_enabled() and x.requires_grad
         steps = torch.as_tensor(timesteps).detach().reshape(-1).float().cpu()
         t = float(steps[0])
         if not bool((steps == t).all()) or t != int(t):
             raise NotImplementedError('per-row / fractional timesteps are not supported by the HIP engine')
         if 'engine' not in self.__dict__:
             self.bind_engine()
-        return self.__dict__['engine'].unet_eps(x, int(t)).unsqueeze(1)
+        eng = self.__dict__['engine']
+        if grad:
+            from dmad_hip.autograd import has_unet_vjp, unet_eps_hip
+            if self.grad_backend == 'auto' and not has_unet_vjp(eng):
+                raise NotImplementedError('the HIP UNet is inference-only (no autograd) on this engine: its input gradient needs the '
+                                          'exact-fp32 UNet tier of an FP32 or EXACT engine')
+            return unet_eps_hip(eng, x if x.dim() == 4 else x.unsqueeze(1), int(t))
+        return eng.unet_eps(x, int(t)).unsqueeze(1)

@@ -7,6 +7,8 @@ from typing import Union
 import numpy as np
 import torch
 
+from dmad_hip.autograd import needs_grad
+
 from .Improved_Diffusion_Unconditional.improved_diffusion.script_util import create_model_and_diffusion, model_and_diffusion_defaults
 from .Improved_Diffusion_Unconditional.improved_diffusion.sc09_spectrogram_dataset import melspec_standardize, melspec_inv_standardize  # noqa: F401
 
@@ -71,7 +73,11 @@ class SpecPurifier(torch.nn.Module):
     mel-dB spectrograms [B,1,32,32] in, purified mel-dB spectrograms out — standardise, q_sample(t*), the t* + 1 p_sample steps, map
     back.  Every draw of row b is Philox-keyed (seed, draws so far + b) with the streams of dmad_spec_smooth_votes (include/dmad.h), so
     `AcousticSystem.query` can run the same rows as ONE engine call (dmad_spec_query_logits) and a row's result does not depend on how
-    the rows were batched."""
+    the rows were batched.
+
+    With a gradient requested (spec_db.requires_grad, e.g. an attack's loss.backward() through AcousticSystem(.., 'spec')) the same chain
+    runs as differentiable torch ops with the same Philox draws, the UNet on its exact-fp32 tier through the engine's VJP
+    (UNetModel.grad_backend); the clip_denoised clamp is part of it.  Without one, the engine's fused p_sample runs as before."""
     noise_source = 'device'
 
     def __init__(self, purifier: ImprovedDiffusion, seed: int = 0):
@@ -82,8 +88,31 @@ class SpecPurifier(torch.nn.Module):
     def engine(self):
         return getattr(self.purifier.model, 'engine', None)
 
-    @torch.no_grad()
     def forward(self, spec_db):
+        if needs_grad(spec_db):
+            return self._forward_grad(spec_db)
+        with torch.no_grad():
+            return self._forward_nograd(spec_db)
+
+    def _forward_grad(self, spec_db):
+        pur, eng = self.purifier, self.engine
+        if eng is None:
+            raise RuntimeError('SpecPurifier needs a UNet bound to a dmad engine (create_improved_diffusion(..., engine=...))')
+        B, ts, s0, gd = spec_db.shape[0], pur.reverse_timestep, self._draws, pur.diffusion
+        x0 = melspec_standardize(spec_db.float())
+        zq = eng.philox_normal(self.seed, s0, 0x5BEC, B)[:, :1024].reshape(B, 1, 32, 32)
+        x = gd.q_sample(x0, torch.full((B,), ts, dtype=torch.long, device=x0.device), noise=zq)
+        for t in range(ts, -1, -1):            # p_sample (gaussian_diffusion.py:331-387) with dmad_unet_p_sample's draws
+            ca, cb, c1, c2, sig = gd.p_sample_coefficients(t)
+            eps = pur.model(x, torch.full((B,), t))
+            xs = torch.clamp(ca * x - cb * eps, -1.0, 1.0)
+            x = c1 * xs + c2 * x
+            if sig != 0.0:
+                x = x + sig * eng.philox_normal(self.seed, s0, 0x0E70 + t, B)[:, :1024].reshape(B, 1, 32, 32)
+        self._draws += B
+        return melspec_inv_standardize(x)
+
+    def _forward_nograd(self, spec_db):
         pur, eng = self.purifier, self.engine
         if eng is None:
             raise RuntimeError('SpecPurifier needs a UNet bound to a dmad engine (create_improved_diffusion(..., engine=...))')
@@ -97,11 +126,12 @@ class SpecPurifier(torch.nn.Module):
         return melspec_inv_standardize(x)
 
 
-def create_improved_diffusion(model_path, reverse_timestep=25, state_dict=None, engine=None):
-    """reference l.64-93: image_size 32, 128 channels, 3 ResBlocks, fixed sigma, 1000 linear steps."""
+def create_improved_diffusion(model_path, reverse_timestep=25, state_dict=None, engine=None, grad_backend='auto'):
+    """reference l.64-93: image_size 32, 128 channels, 3 ResBlocks, fixed sigma, 1000 linear steps.  grad_backend: UNetModel.grad_backend."""
     args = model_and_diffusion_defaults()
     args.update(image_size=32, num_channels=128, num_res_blocks=3, learn_sigma=False, diffusion_steps=1000, noise_schedule='linear')
     model, diffusion = create_model_and_diffusion(**args)
+    model.grad_backend = grad_backend
     if state_dict is None:
         state_dict = torch.load(model_path, map_location='cpu')
     model.load_state_dict({k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v))) for k, v in state_dict.items()})

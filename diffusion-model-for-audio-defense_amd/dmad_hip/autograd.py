@@ -18,6 +18,10 @@ branch against the HIP fp32 path and its gradients against finite differences ta
 WaveNetEpsHIP is the native alternative for the eps-network (WaveNetHIP(..., grad_backend='hip')): its forward is the engine's
 exact-fp32 path and its backward the engine's vector-Jacobian product (dmad_wavenet_eps_vjp), which saves the residual streams
 only — no torch activations are kept between forward and backward.
+
+UNetEpsHIP does the same for the Improved-Diffusion UNet of the spectrogram-domain purifier (UNetModel(..., grad_backend='hip')): its
+forward is the engine's exact-fp32 UNet tier and its backward the engine's UNet VJP (dmad_unet_eps_vjp), which re-runs the forward
+with its tape stored on the device.  There is no torch restatement of the UNet in this package.
 """
 import math
 
@@ -149,3 +153,41 @@ class WaveNetEpsHIP(torch.autograd.Function):
 def wavenet_eps_hip(engine, audio: torch.Tensor, t: int) -> torch.Tensor:
     """eps = WaveNet((audio [B,1,L], t * ones)) on the engine, differentiable in `audio` (WaveNetEpsHIP)."""
     return WaveNetEpsHIP.apply(audio, engine, int(t))
+
+
+def has_unet_vjp(engine) -> bool:
+    """The engine holds the exact-fp32 UNet tier as a product path (FP32 and EXACT engines), the tier UNetEpsHIP runs on."""
+    from . import engine as _eng
+    return getattr(engine, 'precision', None) in (_eng.FP32, _eng.EXACT)
+
+
+class UNetEpsHIP(torch.autograd.Function):
+    """eps = UNetModel(x [B,1,32,32], t * ones) on the engine's exact-fp32 UNet tier, differentiable in `x` through the engine's VJP.
+    Saves only the input; the backward re-runs the forward with its tape saved (dmad_unet_eps_vjp).  The VJP workspace is reserved
+    on first use.  First-order only: create_graph=True raises."""
+
+    @staticmethod
+    def forward(ctx, x, engine, t):
+        _require_cuda(x)
+        if not has_unet_vjp(engine):
+            raise DmadError('the HIP UNet VJP runs on the exact-fp32 UNet tier: use an FP32 or EXACT engine')
+        eps = engine.unet_eps(x, t, tier=0)
+        ctx.engine, ctx.t = engine, int(t)
+        ctx.save_for_backward(x)
+        return eps.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, g_eps):
+        if torch.is_grad_enabled():
+            raise DmadError('the HIP UNet VJP is first-order only: create_graph=True (double backward) is not supported')
+        x, = ctx.saved_tensors
+        eng, B = ctx.engine, x.shape[0]
+        if getattr(eng, 'unet_vjp_batch', 0) < B:
+            eng.reserve_unet_vjp(B)
+        g_x = eng.unet_eps_vjp(x, ctx.t, g_eps.reshape(x.shape).contiguous())
+        return g_x.view(x.shape).to(x.dtype), None, None
+
+
+def unet_eps_hip(engine, x: torch.Tensor, t: int) -> torch.Tensor:
+    """eps = UNetModel(x [B,1,32,32], t * ones) on the engine, differentiable in `x` (UNetEpsHIP)."""
+    return UNetEpsHIP.apply(x, engine, int(t))

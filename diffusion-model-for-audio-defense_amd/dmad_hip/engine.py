@@ -633,6 +633,25 @@ class Engine:
                 check(self.lib.dmad_unet_eps_tier(self._h, _ptr(x[s:e]), int(t), e - s, int(tier), _ptr(out[s:e]), _stream()))
         return out
 
+    def reserve_unet_vjp(self, max_batch: int):
+        """dmad_reserve_unet_vjp: the workspace of unet_eps_vjp (the forward's tape) for up to max_batch spectrograms per pass (capped at
+        the engine's fp32 pass size; a larger reservation replaces a smaller one).  FP32 / EXACT engines; DmadError otherwise."""
+        check(self.lib.dmad_reserve_unet_vjp(self._h, int(max_batch)))
+        self.unet_vjp_batch = max(getattr(self, 'unet_vjp_batch', 0), int(max_batch))
+
+    def unet_eps_vjp(self, x_t: torch.Tensor, t: int, g_eps: torch.Tensor, want_eps: bool = False):
+        """g_x = (d eps / d x_t)^T g_eps for eps = UNetModel(x_t, t * ones) on the exact-fp32 tier ([B,1,32,32] or [B,32,32] -> [B,32,32]).
+        want_eps: also return eps, bit-identical to unet_eps(x_t, t, tier=0).  Needs reserve_unet_vjp first (DmadError otherwise)."""
+        x, g = self._spec(x_t), self._spec(g_eps)
+        if g.shape != x.shape:
+            raise DmadError('g_eps has shape %s, x_t %s' % (tuple(g.shape), tuple(x.shape)))
+        gx = torch.empty_like(x)
+        eps = torch.empty_like(x) if want_eps else None
+        for s, e in self._chunks(x.shape[0]):
+            check(self.lib.dmad_unet_eps_vjp(self._h, _ptr(x[s:e]), int(t), e - s, _ptr(g[s:e]), _ptr(gx[s:e]),
+                                             _ptr(None if eps is None else eps[s:e]), _stream()))
+        return (gx, eps) if want_eps else gx
+
     def unet_p_sample(self, x: torch.Tensor, t: int, c_a: float, c_b: float, c_1: float, c_2: float, c_sig: float,
                       z: Optional[torch.Tensor] = None, seed: int = 0, sample0: int = 0, want_x0: bool = False):
         """in place on x ([B,32,32] contiguous fp32 CUDA); returns pred_xstart when asked."""

@@ -249,6 +249,31 @@ int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch);
 int dmad_wavenet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps,
                          dmad_stream s);
 
+/* Vector-Jacobian product of the Improved-Diffusion UNet on its exact-fp32 tier — the gradient the white-box attack drivers take THROUGH
+ * the spectrogram-domain purifier (AcousticSystem(.., defense_type='spec'); adaptive_attack_eval.py --defense Diffusion-Spec calls the
+ * UNet outside no_grad, improved_diffusion_sde.py:90-118).
+ *
+ * dmad_reserve_unet_vjp reserves the workspace for up to max_batch spectrograms per pass: the TAPE of the forward — every module's output
+ * map (so every module's input, both parts of a concatenated one), each ResBlock's conv1 output and each AttentionBlock's qkv, 5.89 M
+ * floats (23.6 MB) per spectrogram, 1.51 GB at 64 —, the gradients of the 16 saved skip maps (3.3 MB), six work maps of 32 x 32 x 384
+ * floats (9.4 MB) and, on the first reservation, the transposed weight images (3x3 convs tap-flipped with ci / co swapped, 1x1 layers
+ * transposed; as large as the resident fp32 conv / 1x1 images), packed on the device from those.  max_batch is capped at the engine's fp32 pass size
+ * (max_batch of a DMAD_FP32 engine, recheck_batch of a DMAD_EXACT one).  A larger reservation replaces a smaller one; a smaller one keeps
+ * the present.  Counted by dmad_device_bytes.  This is the only allocation of the VJP: the data path below allocates nothing.
+ * DMAD_ERR_STATE before the UNet weights are finalised, or for a DMAD_BF16 engine (the exact-fp32 UNet tier is a product path of
+ * DMAD_FP32 and DMAD_EXACT engines only).
+ *
+ * dmad_unet_eps_vjp:  g_x = (d eps / d x_t)^T g_eps  for eps = UNetModel(x_t, t * ones) on the exact-fp32 tier.  x_t, g_eps, g_x:
+ * device fp32 [B][32][32].  eps: optional (NULL) device fp32 [B][32][32], bit-identical to dmad_unet_eps_tier(.., tier = 0, ..).  The input
+ * gradient only: no weight gradients; the scale-shift rows depend on t alone, so nothing flows into the step embedding.  B in
+ * [1, max_batch], processed in passes of the reservation's size.  Store scheme: the forward writes the tape, the backward walks the
+ * modules in reverse — convs and 1x1 layers as the fp32 GEMM on the transposed images, GroupNorm (+ scale-shift + SiLU), attention,
+ * stride-2 and upsampling backward as small kernels.  Every reduction runs in a fixed order (no atomics, no split-K): g_x is
+ * bit-identical across calls and independent of the batch a spectrogram is in.  DMAD_ERR_STATE without a reservation. */
+int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch);
+int dmad_unet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps,
+                      dmad_stream s);
+
 /* The reverse VP-SDE purifier of the reference's adaptive-attack driver (adaptive_attack_eval.py --defense Diffusion ->
  * diffusion_models/diffwave_sde.py RevDiffWave.audio_editing_sample: torchsde.sdeint_adjoint(RevVPSDE, method='euler', dt = 1/T)).
  * The step schedule is built by the CALLER on the host, in float32 and in torchsde's order (diffusion_models/diffwave_sde.py
