@@ -31,6 +31,8 @@ thread_local std::string g_err, g_warn;
 enum { PATH_DEFAULT = 0, PATH_FP32 = 1, PATH_X3 = 2 };
 // Philox streams of the reverse VP-SDE chain (dmad_vpsde_purify, include/dmad.h): the initial diffusion draw, then one per Euler step
 constexpr uint32_t kVpsdeStreamDiffuse = 0x5DE00000u, kVpsdeStreamStep0 = 0x5DE00001u;
+// ... and of the spectrogram-domain chain (dmad_spec_vpsde_purify)
+constexpr uint32_t kSpecVpsdeStreamDiffuse = 0x5DF00000u, kSpecVpsdeStreamStep0 = 0x5DF00001u;
 
 int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -295,6 +297,7 @@ struct dmad_engine {
     int unvjpB = 0;
     size_t unvjp_tape_per = 0, unvjp_ghs_per = 0;          // floats per spectrogram
     float *unvjp_tape = nullptr, *unvjp_ghs = nullptr, *unvjp_work = nullptr, *unvjp_zero = nullptr;
+    float* unvjp_g2 = nullptr;              // [2][unvjpB][1024]: the ping-pong adjoint of dmad_spec_vpsde_purify_vjp
     float *un_inT = nullptr, *un_outT = nullptr;            // conv_in [9][128] / out.2 [128][9] images, tap-flipped
     UnTape un_tape;
     std::vector<float*> unvjp_ghs_at;
@@ -1268,7 +1271,9 @@ std::vector<UnRef> un_flat(const dmad_engine* e, std::vector<size_t>* hs_k = nul
 // One pass (B <= unvjpB): the forward with its tape, then the modules in reverse.  G[0] / G[1] carry the gradient of the current module's
 // output / input (ping-pong); G[2..5] are the per-module scratch maps (G[2] conv2^T / proj^T / the dilated map / the upsampled gradient,
 // G[3] GroupNorm2^T / the attention gradient, G[4] conv1^T / qkv^T, G[5] the skip conv^T).
-int unet_vjp_pass(dmad_engine* e, const float* x, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s) {
+// affine (the reverse VP-SDE chain): g_x = alpha * g_eps - gamma * (d eps / d x)^T g_eps, in the input conv backward's epilogue
+int unet_vjp_pass(dmad_engine* e, const float* x, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s,
+                  bool affine = false, float alpha = 1.f, float gamma = 0.f) {
     CHK(unet_eps(e, x, t, B, eps, s, 0, &e->un_tape));
     std::vector<size_t> hs_k;
     const std::vector<UnRef> ops = un_flat(e, &hs_k);
@@ -1320,7 +1325,7 @@ int unet_vjp_pass(dmad_engine* e, const float* x, int t, int B, const float* g_e
             CHK(gemm(un_conv_args(o.w1T, nullptr, cur, G[2], o.cin, o.cout, 9, B, 2 * H, 1, nullptr)));
             launch_upsample2x_bwd_nhwc(G[2], acc, nxt, B, H, o.cin, s);
         } else {                                // conv_in (1 -> 128): a 128 -> 1 conv of the gradient with the flipped image
-            launch_conv3x3_c128_to1(cur, o.w1T, e->unvjp_zero, g_x, B, s);
+            launch_conv3x3_c128_to1(cur, o.w1T, e->unvjp_zero, g_x, B, s, affine ? g_eps : nullptr, alpha, gamma);
         }
         std::swap(cur, nxt);
     }
@@ -1959,6 +1964,64 @@ int dmad_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int32_t 
     return 0;
 }
 
+int dmad_spec_vpsde_purify(dmad_engine* e, const float* x0, int32_t B, int32_t n_steps, float c_a, float c_b, const int32_t* k, const float* h,
+                           const float* hb, const float* q, const float* gs, const float* z, uint64_t seed, uint64_t sample0, int32_t path,
+                           float* out, float* traj, dmad_stream s) {
+    if (!e || !x0 || !out || !k || !h || !hb || !q || !gs) return fail(DMAD_ERR_INVALID, "null argument");
+    if (n_steps < 1) return fail(DMAD_ERR_INVALID, "n_steps %d < 1", n_steps);
+    if (B < 1) return fail(DMAD_ERR_INVALID, "batch %d < 1", B);
+    if (path != 0 && path != 1) return fail(DMAD_ERR_INVALID, "unknown path %d (0 the mode's UNet map tier, 1 exact fp32)", path);
+    if (path == 1 && !e->f32) return fail(DMAD_ERR_STATE, "path 1 is the exact-fp32 UNet tier: a DMAD_BF16 engine holds no fp32 weights");
+    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    for (int n = 0; n < n_steps; ++n)
+        if (k[n] < 0 || k[n] > kUnSsSteps) return fail(DMAD_ERR_INVALID, "step %d: k = %d outside [0, %d]", n, k[n], kUnSsSteps);
+    const int tier = path == 1 ? 0 : -1;
+    const size_t L = 1024, slot = (size_t)B * L;
+    const hipStream_t st = (hipStream_t)s;
+    for (int b0 = 0; b0 < B; b0 += e->maxB) {                  // a pass: the whole chain for up to max_batch spectrograms
+        const int bb = B - b0 < e->maxB ? B - b0 : e->maxB;
+        float* x = out + b0 * L;
+        const uint64_t s0 = sample0 + (uint64_t)b0;
+        launch_vpsde_step(x0 + b0 * L, nullptr, z ? z + b0 * L : nullptr, c_a, c_b, 0.f, 0.f, seed, s0, kSpecVpsdeStreamDiffuse, x,
+                          traj ? traj + b0 * L : nullptr, bb, (int)L, st);
+        for (int n = 0; n < n_steps; ++n) {
+            CHK(unet_eps(e, x, k[n], bb, e->un_eps, st, tier));
+            launch_vpsde_step(x, e->un_eps, z ? z + (n + 1) * slot + b0 * L : nullptr, hb[n], q[n], h[n], gs[n], seed, s0,
+                              kSpecVpsdeStreamStep0 + (uint32_t)n, x, traj ? traj + (n + 1) * slot + b0 * L : nullptr, bb, (int)L, st);
+        }
+    }
+    LASTCHK();
+    return 0;
+}
+
+int dmad_spec_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int32_t n_steps, float c_a, const int32_t* k, const float* h,
+                               const float* hb, const float* q, const float* g_out, float* g_x0, dmad_stream s) {
+    if (!e || !traj || !k || !h || !hb || !q || !g_out || !g_x0) return fail(DMAD_ERR_INVALID, "null argument");
+    if (g_out == g_x0) return fail(DMAD_ERR_INVALID, "g_out and g_x0 must not alias");
+    if (n_steps < 1) return fail(DMAD_ERR_INVALID, "n_steps %d < 1", n_steps);
+    if (!e->f32) return fail(DMAD_ERR_STATE, "the UNet VJP runs on the exact-fp32 UNet tier: it needs a DMAD_FP32 or DMAD_EXACT engine");
+    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    if (!e->unvjpB) return fail(DMAD_ERR_STATE, "no UNet VJP workspace: call dmad_reserve_unet_vjp first");
+    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    for (int n = 0; n < n_steps; ++n)
+        if (k[n] < 0 || k[n] > kUnSsSteps) return fail(DMAD_ERR_INVALID, "step %d: k = %d outside [0, %d]", n, k[n], kUnSsSteps);
+    const size_t L = 1024, slot = (size_t)B * L;
+    const hipStream_t st = (hipStream_t)s;
+    for (int b0 = 0; b0 < B; b0 += e->unvjpB) {                // a pass of the reservation: the whole reverse walk
+        const int bb = B - b0 < e->unvjpB ? B - b0 : e->unvjpB;
+        const float* g = g_out + b0 * L;
+        for (int n = n_steps - 1; n >= 0; --n) {
+            // g <- (1 + h hb) g - (h q) J_n^T g, J_n = d eps / d x at traj[n]; the last step (n = 0) folds in d x_0 / d x0 = c_a
+            double alpha = 1.0 + (double)h[n] * (double)hb[n], gamma = (double)h[n] * (double)q[n];
+            if (n == 0) { alpha *= c_a; gamma *= c_a; }
+            float* dst = n == 0 ? g_x0 + b0 * L : e->unvjp_g2 + (size_t)((n_steps - 1 - n) & 1) * e->unvjpB * L;
+            CHK(unet_vjp_pass(e, traj + n * slot + b0 * L, k[n], bb, g, dst, e->un_eps, st, true, (float)alpha, (float)gamma));
+            g = dst;
+        }
+    }
+    return 0;
+}
+
 int dmad_mel_db(dmad_engine* e, const float* x, int32_t B, float* spec, dmad_stream s) {
     if (!e || !x || !spec) return fail(DMAD_ERR_INVALID, "null argument");
     return mel_db(e, x, B, spec, (hipStream_t)s);
@@ -2169,6 +2232,7 @@ int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch) {
     if (e->unvjpB) {                        // a larger reservation replaces the present one
         const size_t ob = e->unvjpB;
         e->release(&e->unvjp_tape, ob * e->unvjp_tape_per); e->release(&e->unvjp_ghs, ob * e->unvjp_ghs_per); e->release(&e->unvjp_work, 6 * ob * W);
+        e->release(&e->unvjp_g2, 2 * ob * 1024);
         e->unvjpB = 0;
     }
     if (!e->unvjp_zero) {                   // transposed weight images, packed on the device from the resident fp32 images
@@ -2199,6 +2263,7 @@ int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch) {
     CHK(e->alloc(&e->unvjp_tape, (size_t)vB * tape));
     CHK(e->alloc(&e->unvjp_ghs, (size_t)vB * ghs));
     CHK(e->alloc(&e->unvjp_work, 6 * (size_t)vB * W));
+    CHK(e->alloc(&e->unvjp_g2, 2 * (size_t)vB * 1024));
     e->unvjp_tape_per = tape; e->unvjp_ghs_per = ghs;
     auto at = [&](size_t off) { return off == SIZE_MAX ? nullptr : e->unvjp_tape + off * vB; };
     e->un_tape = dmad_engine::UnTape{};

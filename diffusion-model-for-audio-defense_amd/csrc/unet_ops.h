@@ -11,8 +11,10 @@ namespace dmad {
 // statistics of the f16 twin (GemmH16Args::stats layout, 64-pixel blocks).  Returns -1 for Cout > 128.
 int launch_conv1ch_3x3(const float* in, const float* w, const float* bias, float* out, int B, int Cout, hipStream_t s, h16_t* out16 = nullptr,
                        float* stats = nullptr);
-// conv 3x3, 128 -> 1 channel, padding 1, bias: in [B][1024][128] (NHWC), w [9][128] (tap-major), out [B][1024]   (out.2)
-void launch_conv3x3_c128_to1(const float* in, const float* w, const float* bias, float* out, int B, hipStream_t s);
+// conv 3x3, 128 -> 1 channel, padding 1, bias: in [B][1024][128] (NHWC), w [9][128] (tap-major), out [B][1024]   (out.2);
+// with g_in: out[p] = alpha * g_in[p] - gamma * (that conv)  (the adjoint update of a reverse VP-SDE step; g_in != out)
+void launch_conv3x3_c128_to1(const float* in, const float* w, const float* bias, float* out, int B, hipStream_t s, const float* g_in = nullptr,
+                             float alpha = 1.f, float gamma = 0.f);
 void launch_conv3x3_c128_to1_h16(const h16_t* in, const float* w, const float* bias, float* out, int B, hipStream_t s);   // the same on an f16 map
 // GroupNorm32(32, C) in fp32 (nn.py:15-17,92-100) over [B][HW][C], then optionally y * (1 + ss[c]) + ss[C + c]
 // (scale-shift norm, unet.py:190-194; ss = one row of 2C floats shared by the batch) and optionally SiLU.

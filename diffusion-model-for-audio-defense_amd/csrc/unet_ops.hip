@@ -52,8 +52,12 @@ __global__ void __launch_bounds__(128) conv1ch_3x3_kernel(const float* __restric
 // conv 3x3, 128 channels -> ONE output channel, padding 1, on 32x32 maps (the network's last layer, unet.py:421): a
 // 1152-term dot product per pixel, far too thin for a matrix tile (the 64-row GEMM tile spends 63/64 of its MFMAs on padding).
 // One lane per pixel; the weights are wave-uniform (scalar loads), each lane streams the 512-byte rows of its 9 neighbours.
+// AFFINE (the reverse VP-SDE chain's adjoint, dmad_spec_vpsde_purify_vjp): out[p] = alpha * g_in[p] - gamma * (the conv) instead of the
+// conv, so the adjoint update of an Euler step costs no pass of its own.  g_in and out are two different buffers (the caller ping-pongs).
+template <bool AFFINE>
 __global__ void __launch_bounds__(256) conv3x3_c128_to1_kernel(const float* __restrict__ in, const float* __restrict__ w,
-                                                               const float* __restrict__ bias, float* __restrict__ out, long total) {
+                                                               const float* __restrict__ bias, float* __restrict__ out, long total,
+                                                               const float* __restrict__ g_in, float alpha, float gamma) {
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= total) return;
     const int y = (int)((p >> 5) & 31), x = (int)(p & 31);
@@ -69,7 +73,9 @@ __global__ void __launch_bounds__(256) conv3x3_c128_to1_kernel(const float* __re
             acc[0] = fmaf(v.x, k.x, acc[0]); acc[1] = fmaf(v.y, k.y, acc[1]); acc[2] = fmaf(v.z, k.z, acc[2]); acc[3] = fmaf(v.w, k.w, acc[3]);
         }
     }
-    out[p] = (acc[0] + acc[1]) + (acc[2] + acc[3]) + bias[0];
+    const float r = (acc[0] + acc[1]) + (acc[2] + acc[3]) + bias[0];
+    if constexpr (AFFINE) out[p] = __fsub_rn(__fmul_rn(alpha, g_in[p]), __fmul_rn(gamma, r));
+    else out[p] = r;
 }
 
 // The same conv on an f16 map (the 16-bit tier's last layer), on the matrix cores: per pixel the nine taps' dot products with its OWN
@@ -624,9 +630,11 @@ int launch_conv1ch_3x3(const float* in, const float* w, const float* bias, float
     hipLaunchKernelGGL(conv1ch_3x3_kernel, dim3((unsigned)B * 16u), dim3(128), 0, s, in, w, bias, out, Cout, out16, stats);
     return 0;
 }
-void launch_conv3x3_c128_to1(const float* in, const float* w, const float* bias, float* out, int B, hipStream_t s) {
+void launch_conv3x3_c128_to1(const float* in, const float* w, const float* bias, float* out, int B, hipStream_t s, const float* g_in,
+                             float alpha, float gamma) {
     const long total = (long)B * 1024;
-    hipLaunchKernelGGL(conv3x3_c128_to1_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, in, w, bias, out, total);
+    if (g_in) hipLaunchKernelGGL(conv3x3_c128_to1_kernel<true>, dim3(nblk(total, 256)), dim3(256), 0, s, in, w, bias, out, total, g_in, alpha, gamma);
+    else hipLaunchKernelGGL(conv3x3_c128_to1_kernel<false>, dim3(nblk(total, 256)), dim3(256), 0, s, in, w, bias, out, total, nullptr, 0.f, 0.f);
 }
 void launch_conv3x3_c128_to1_h16(const h16_t* in, const float* w, const float* bias, float* out, int B, hipStream_t s) {
     hipLaunchKernelGGL(conv3x3_c128_to1_h16_kernel, dim3((unsigned)B), dim3(256), 0, s, in, w, bias, out);

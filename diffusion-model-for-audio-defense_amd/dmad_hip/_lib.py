@@ -74,6 +74,9 @@ _SIGNATURES = {
     'dmad_vpsde_purify': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64,
                                     C.c_int32, _P, _P, _P]),
     'dmad_vpsde_purify_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
+    'dmad_spec_vpsde_purify': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, C.c_uint64,
+                                         C.c_uint64, C.c_int32, _P, _P, _P]),
+    'dmad_spec_vpsde_purify_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
     'dmad_eval_samples': (C.c_int, [_P, _P, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_uint64, _P, _P, C.c_int64,
                                     C.c_int32, _P, _P, _P]),
     'dmad_debug_rounding': (C.c_int, [_P, C.POINTER(C.c_int32)]),

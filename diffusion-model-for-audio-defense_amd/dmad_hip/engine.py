@@ -652,6 +652,44 @@ class Engine:
                                              _ptr(None if eps is None else eps[s:e]), _stream()))
         return (gx, eps) if want_eps else gx
 
+    def spec_vpsde_purify(self, x0: torch.Tensor, c_a: float, c_b: float, k, h, hb, q, gs, z: Optional[torch.Tensor] = None, seed: int = 0,
+                          sample0: int = 0, path: int = 0, want_traj: bool = False):
+        """dmad_spec_vpsde_purify: vpsde_purify's chain on standardised spectrograms with the UNet as the eps-network ([B,1,32,32] or
+        [B,32,32] -> [B,32,32]), one library call per chunk of max_batch.  path 0: the mode's UNet map tier (unet_eps(tier=None)), 1: exact
+        fp32.  z: optional explicit noise [S + 1, B, 1024]; None = Philox keyed (seed, sample0 + row).  want_traj: also return the
+        trajectory for spec_vpsde_purify_vjp, [(S + 1) * B, 1024] stored chunk by chunk as in vpsde_purify."""
+        x = self._spec(x0)
+        B, S = x.shape[0], len(k)
+        out = torch.empty_like(x)
+        traj = torch.empty(((S + 1) * B, 1024), dtype=torch.float32, device=x.device) if want_traj else None
+        ka, ha, hba, qa, gsa = self._vpsde_arrays(k, h, hb, q, gs)
+        if z is not None:
+            z = z.detach()
+            if not z.is_cuda or tuple(z.shape) != (S + 1, B, 1024):
+                raise DmadError('z must be a CUDA tensor [%d, %d, 1024], not %s' % (S + 1, B, tuple(z.shape)))
+            z = z.float()
+        for s, e in self._chunks(B):
+            zz = None if z is None else z[:, s:e].contiguous()
+            tr = None if traj is None else traj[(S + 1) * s:(S + 1) * e]
+            check(self.lib.dmad_spec_vpsde_purify(self._h, _ptr(x[s:e]), e - s, S, float(c_a), float(c_b), ka, ha, hba, qa, gsa, _ptr(zz),
+                                                  int(seed), int(sample0) + s, int(path), _ptr(out[s:e]), _ptr(tr), _stream()))
+        return (out, traj) if want_traj else out
+
+    def spec_vpsde_purify_vjp(self, traj: torch.Tensor, c_a: float, k, h, hb, q, g_out: torch.Tensor) -> torch.Tensor:
+        """dmad_spec_vpsde_purify_vjp: g_x0 = (d out / d x0)^T g_out of the chain spec_vpsde_purify(.., path=1, want_traj=True) ran, the
+        draws held fixed ([B,1,32,32] or [B,32,32] -> [B,32,32]).  traj: that call's trajectory.  Needs reserve_unet_vjp first."""
+        g = self._spec(g_out)
+        B, S = g.shape[0], len(k)
+        if not traj.is_cuda or tuple(traj.shape) != ((S + 1) * B, 1024):
+            raise DmadError('traj must be the [(S + 1) * B, 1024] = [%d, 1024] trajectory of spec_vpsde_purify, not %s'
+                            % ((S + 1) * B, tuple(traj.shape)))
+        gx = torch.empty_like(g)
+        ka, ha, hba, qa, _ = self._vpsde_arrays(k, h, hb, q, h)
+        for s, e in self._chunks(B):
+            check(self.lib.dmad_spec_vpsde_purify_vjp(self._h, _ptr(traj[(S + 1) * s:(S + 1) * e]), e - s, S, float(c_a), ka, ha, hba, qa,
+                                                      _ptr(g[s:e]), _ptr(gx[s:e]), _stream()))
+        return gx
+
     def unet_p_sample(self, x: torch.Tensor, t: int, c_a: float, c_b: float, c_1: float, c_2: float, c_sig: float,
                       z: Optional[torch.Tensor] = None, seed: int = 0, sample0: int = 0, want_x0: bool = False):
         """in place on x ([B,32,32] contiguous fp32 CUDA); returns pred_xstart when asked."""

@@ -301,6 +301,33 @@ int dmad_vpsde_purify(dmad_engine* e, const float* x0, int32_t B, int32_t n_step
 int dmad_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int32_t n_steps, float c_a, const int32_t* k, const float* h,
                           const float* hb, const float* q, const float* g_out, float* g_x0, dmad_stream s);
 
+/* The reverse VP-SDE purifier on standardised mel spectrograms (adaptive_attack_eval.py --defense Diffusion-Spec ->
+ * diffusion_models/improved_diffusion_sde.py RevImprovedDiffusion.image_editing_sample: torchsde.sdeint_adjoint(RevVPSDE, method='euler')
+ * at torchsde's default dt = 1e-3).  The same chain as dmad_vpsde_purify with the Improved-Diffusion UNet as the eps-network; the
+ * schedule is again built by the CALLER on the host in float32 (diffusion_models/improved_diffusion_sde.py spec_vpsde_schedule; DESIGN
+ * §13): beta and the score are continuous in t, so k[n] (the UNet's step input) indexes no table and may be anything in [0, 1000].
+ *
+ * dmad_spec_vpsde_purify:  x <- c_a * x0 + c_b * z_0;  for n:  x <- x + (hb[n] * x - q[n] * eps(x, k[n])) * h[n] + gs[n] * z_{n+1}.
+ * x0, out: device fp32 [B][32][32] (standardised maps; may alias).  Host arrays k / h / hb / q / gs of n_steps.  Noise: z (optional,
+ * device fp32 [n_steps + 1][B][1024], test hook) or Philox N(0,1) keyed (seed, sample0 + b, stream 0x5DF00000 for the diffusion draw,
+ * 0x5DF00001 + n for Euler step n) — the first 1024 values of dmad_philox_normal's row.  path: 0 = the mode's UNet map tier (the tier
+ * dmad_unet_eps runs), 1 = the exact-fp32 tier (DMAD_FP32 / DMAD_EXACT engines).  traj: optional device fp32 [n_steps + 1][B][1024];
+ * slot n receives the state entering step n, slot n_steps the output.  B runs in passes of max_batch spectrograms.
+ *
+ * dmad_spec_vpsde_purify_vjp:  g_x0 = (d out / d x0)^T g_out of that chain on the exact-fp32 tier, the draws held fixed: walking the
+ * steps in reverse,  g <- (1 + h[n] hb[n]) g - (h[n] q[n]) J_n^T g  with J_n^T g the UNet VJP (dmad_unet_eps_vjp's recompute: forward
+ * with its tape at traj slot n, then the backward), and g_x0 = c_a * g.  The update is the epilogue of the input conv's transposed conv
+ * (two ping-pong buffers of the dmad_reserve_unet_vjp reservation); the last step folds c_a in.  No tape is kept across steps.  traj:
+ * as written by dmad_spec_vpsde_purify(.., path = 1, ..) for the same B.  g_out, g_x0: device fp32 [B][1024], must not alias.
+ * B <= max_batch, processed in passes of the reservation; nothing is allocated.  Every reduction in a fixed order: g_x0 is
+ * bit-reproducible and independent of the batch.  DMAD_ERR_STATE without a reservation or the fp32 tier; DMAD_ERR_INVALID for
+ * n_steps < 1 or a k outside [0, 1000]. */
+int dmad_spec_vpsde_purify(dmad_engine* e, const float* x0, int32_t B, int32_t n_steps, float c_a, float c_b, const int32_t* k, const float* h,
+                           const float* hb, const float* q, const float* gs, const float* z, uint64_t seed, uint64_t sample0, int32_t path,
+                           float* out, float* traj, dmad_stream s);
+int dmad_spec_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int32_t n_steps, float c_a, const int32_t* k, const float* h,
+                               const float* hb, const float* q, const float* g_out, float* g_x0, dmad_stream s);
+
 /* The forward of RobustCertificate.smooth_predict's loop body (certified_robust.py:46-56) for an explicit LIST of Monte Carlo
  * samples on an explicit WaveNet path — the audit of the exact-vote mode (RobustCertificate.certify(audit=k): k samples that
  * voted on the 16-bit tier are re-evaluated on a higher one) and the measurement tools' hook:  row i of logits_out [n][num_classes]
