@@ -78,6 +78,21 @@ class CifarResNeXt(nn.Module):
                                                           self.widen_factor))
         return block
 
+    GRAD_BACKENDS = ('auto', 'torch', 'hip')
+
+    @property
+    def grad_backend(self):
+        """Backend of the gradient branch (x.requires_grad under autograd): 'torch' = the module's own layers (reference l.133-142; MIOpen,
+        weight gradients included), 'hip' = the engine's fp32 tier and ResNeXt29 VJP (dmad_hip.autograd.ResNeXtHIP; input gradient
+        only), 'auto' (the default) = 'torch'."""
+        return self.__dict__.get('_grad_backend', 'auto')
+
+    @grad_backend.setter
+    def grad_backend(self, value):
+        if value not in self.GRAD_BACKENDS:
+            raise ValueError('grad_backend must be one of %s, not %r' % (self.GRAD_BACKENDS, value))
+        self.__dict__['_grad_backend'] = value
+
     # -- HIP engine binding ---------------------------------------------------------------------
     def bind_engine(self, engine=None):
         """Fold BatchNorm (eval statistics) and upload the weights into the engine (once).  An explicit `engine` that
@@ -93,6 +108,11 @@ class CifarResNeXt(nn.Module):
     def forward(self, x):
         if self.training:
             raise NotImplementedError('the HIP ResNeXt29 is inference-only: call .eval() first')
+        if torch.is_grad_enabled() and x.requires_grad and self.grad_backend == 'hip':
+            if 'engine' not in self.__dict__:
+                self.bind_engine()
+            from dmad_hip.autograd import resnext_hip
+            return resnext_hip(self.__dict__['engine'], x)
         if torch.is_grad_enabled() and x.requires_grad:
             # callers that differentiate through the system: the module's own layers, reference l.133-142; CUDA only
             if not x.is_cuda:

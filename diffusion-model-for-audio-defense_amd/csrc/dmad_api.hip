@@ -14,6 +14,7 @@
 #include "dmad_common.h"
 #include "wn_vjp.h"
 #include "unet_vjp.h"
+#include "classifier_vjp.h"
 #include "unet_ops.h"
 #include "elementwise.h"
 #include "gemm_f32.h"
@@ -237,7 +238,7 @@ struct dmad_engine {
     long slab_floats = 0;
     // ResNeXt29 8x64d (models/resnext.py): 9 bottlenecks, every conv with its folded eval-BatchNorm scale/shift
     int cls_kind = 0;                      // 0 = VGG19_bn, 1 = ResNeXt29
-    struct RxConv { float *w = nullptr, *scale = nullptr, *shift = nullptr; h16_t* wh = nullptr; float* wx = nullptr; };   // wh: f16 image with the BN scale folded in (16-bit tier); wx: split-f16 image (middle tier)
+    struct RxConv { float *w = nullptr, *scale = nullptr, *shift = nullptr; h16_t* wh = nullptr; float* wx = nullptr; float* wT = nullptr; };   // wh: f16 image with the BN scale folded in (16-bit tier); wx: split-f16 image (middle tier); wT: transposed (3x3: tap-flipped) image with the BN scale folded in (classifier VJP)
     struct RxBlock { RxConv reduce, conv, expand, shortc; bool has_short = false; int cin = 0, cout = 0, D = 0, stride = 1; };
     RxBlock rx[9];
     RxConv rxconv1;
@@ -249,6 +250,17 @@ struct dmad_engine {
     bool rx_h16 = false;
     bool rx_x3 = false;                    // exact-vote engines: ResNeXt29's split-f16 tier (every conv as three f16 MFMAs per product: fp32-grade), tier 1 of the exact-vote loop
     h16_t *rxX16 = nullptr, *rxY16 = nullptr, *rxT1h = nullptr, *rxT2h = nullptr, *rxS16 = nullptr;
+    // ResNeXt29 VJP workspace (dmad_reserve_classifier_vjp): the tape of the fp32 forward — conv1's output and per bottleneck
+    // its post-ReLU T1 / T2 and block output Y — [rxvjpB] spectrograms per slot, and six gradient work maps of 32 x 32 x 1024 floats
+    struct RxTape { float* c1 = nullptr; float* t1[9] = {}; float* t2[9] = {}; float* y[9] = {}; };
+    int rxvjpB = 0;
+    size_t rxvjp_tape_per = 0;             // floats per spectrogram
+    float *rxvjp_tape = nullptr, *rxvjp_work = nullptr;
+    RxTape rx_tape;
+    // mel front-end VJP (dmad_mel_db_vjp): transposed filterbank [kMelLd][32] and DFT [2048][kDftKT] images, gradient maps of
+    // melvjpB clips per pass (allocated on the first call)
+    int melvjpB = 0;
+    float *mel_fbT = nullptr, *mel_dftAT = nullptr, *melvjp_gM = nullptr, *melvjp_gP = nullptr, *melvjp_gD = nullptr, *melvjp_gF = nullptr;
     // Improved-Diffusion UNet purifier on 1x32x32 mel spectrograms (improved_diffusion/unet.py:278-477)
     struct UnOp {                          // one module of a TimestepEmbedSequential
         int kind = 0;                      // 0 conv_in, 1 res, 2 attn, 3 down, 4 up
@@ -765,21 +777,25 @@ int classify_resnext_h16(dmad_engine* e, const float* spec, int B, float* logits
     return 0;
 }
 
-// CifarResNeXt.forward (models/resnext.py:133-142) on NHWC fp32 maps
-int classify_resnext(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s) {
-    float *X = e->rxX, *Y = e->rxY;
+// CifarResNeXt.forward (models/resnext.py:133-142) on NHWC fp32 maps.  tape != nullptr (the classifier VJP; B <= rxvjpB): conv1's
+// output and every bottleneck's T1 / T2 / block output are written to the tape's slots instead of the work maps (same launches, same bits)
+int classify_resnext(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, const dmad_engine::RxTape* tape = nullptr) {
+    float *X = tape ? tape->c1 : e->rxX, *Y = e->rxY;
     launch_vgg_conv1(spec, e->rxconv1.w, e->rxconv1.scale, e->rxconv1.shift, X, B, s);      // 1 -> 64, 3x3, BN, ReLU
     int H = 32;
     for (int i = 0; i < 9; ++i) {
         const dmad_engine::RxBlock& b = e->rx[i];
+        float* T1 = tape ? tape->t1[i] : e->rxT1;
+        float* T2 = tape ? tape->t2[i] : e->rxT2;
+        if (tape) Y = tape->y[i];
         const int Ho = (H - 1) / b.stride + 1;
         const long Nin = (long)B * H * H, Nout = (long)B * Ho * Ho, nref_in = (long)e->maxB * H * H, nref_out = (long)e->maxB * Ho * Ho;
         // conv_reduce + bn_reduce + ReLU (1x1)
-        GemmF32Args g = plain_gemm(b.reduce.w, X, e->rxT1, b.reduce.scale, b.reduce.shift, b.D, b.cin, Nin, b.D, b.cin, 1);
+        GemmF32Args g = plain_gemm(b.reduce.w, X, T1, b.reduce.scale, b.reduce.shift, b.D, b.cin, Nin, b.D, b.cin, 1);
         launch_gemm_f32(g, s, e->slab, e->slab_floats, nref_in);
         // conv_conv (3x3, 8 groups, stride) + bn + ReLU
         GemmF32Args c{};
-        c.A = b.conv.w; c.X = e->rxT1; c.C = e->rxT2; c.scale = b.conv.scale; c.shift = b.conv.shift;
+        c.A = b.conv.w; c.X = T1; c.C = T2; c.scale = b.conv.scale; c.shift = b.conv.shift;
         c.M = b.D / 8; c.K = b.D / 8; c.taps = 9; c.ldc = b.D; c.relu = 1; c.N = Nout; c.mode = 2;
         c.H = H; c.W = H; c.Cin = b.D / 8; c.ldx = b.D; c.stride = b.stride; c.groups = 8;
         launch_gemm_f32(c, s);
@@ -794,9 +810,10 @@ int classify_resnext(dmad_engine* e, const float* spec, int B, float* logits, hi
             res = e->rxS;
         }
         // conv_expand + bn_expand, + shortcut, ReLU
-        GemmF32Args x = plain_gemm(b.expand.w, e->rxT2, Y, b.expand.scale, b.expand.shift, b.cout, b.D, Nout, b.cout, b.D, 1);
+        GemmF32Args x = plain_gemm(b.expand.w, T2, Y, b.expand.scale, b.expand.shift, b.cout, b.D, Nout, b.cout, b.D, 1);
         x.res = res;
         launch_gemm_f32(x, s, e->slab, e->slab_floats, nref_out);
+        if (tape) { X = Y; H = Ho; continue; }
         float* t = X; X = Y; Y = t;
         H = Ho;
     }
@@ -1530,6 +1547,126 @@ int mel_db(dmad_engine* e, const float* x, int B, float* spec, hipStream_t s, in
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Classifier-side vector-Jacobian products: the ResNeXt29 input VJP on its fp32 tier and the mel front-end VJP.
+// Both recompute their forward; every GEMM runs without split-K and every small kernel reduces in a fixed order, so the
+// gradients are bit-reproducible and do not depend on the batch.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kDftKT = 2064;             // K of the DFT^T GEMM: the 2050 re / im rows padded to a multiple of 16
+
+// floats per spectrogram of the six gradient work maps of rx_vjp_pass: block in / out gradients (32 x 32 x 256 at most), g_T2, its
+// zero-dilation and g_T1 (32 x 32 x 1024 at most: stage 2's first bottleneck), the shortcut gradient (64 K) and its dilation (256 K)
+const size_t kRxWork[6] = {262144, 262144, 1048576, 1048576, 1048576, 327680};
+
+// g_spec = (d logits / d spec)^T g_logits of classify_resnext; logits: the forward it recomputes (B <= rxvjpB)
+int rx_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
+    const dmad_engine::RxTape& tp = e->rx_tape;
+    CHK(classify_resnext(e, spec, B, logits, s, &tp));
+    float* G[6];
+    G[0] = e->rxvjp_work;
+    for (int k = 1; k < 6; ++k) G[k] = G[k - 1] + kRxWork[k - 1] * e->rxvjpB;
+    float *gT = G[2], *gD = G[3], *gU = G[4], *gS = G[5], *gSd = G[5] + 65536l * e->rxvjpB;
+    // NHWC conv on a transposed image, stride 1 (the stride-2 backward runs on the zero-dilated gradient), no split-K
+    auto conv = [&](const float* A, const float* X, float* C, int M, int K, int taps, int H, int groups, int ldx, int ldc,
+                    const float* res) -> int {
+        GemmF32Args g{};
+        g.A = A; g.X = X; g.C = C; g.M = M; g.K = K; g.taps = taps; g.ldc = ldc; g.N = (long)B * H * H; g.mode = 2;
+        g.H = H; g.W = H; g.Cin = K; g.ldx = ldx; g.stride = 1; g.groups = groups; g.res = res;
+        if (launch_gemm_f32(g, s) != 0) return fail(DMAD_ERR_STATE, "classifier VJP: no GEMM for M = %d, K = %d, taps = %d", M, K, taps);
+        return 0;
+    };
+    // head: FC, 8 x 8 average pool and the last block's ReLU in one kernel
+    launch_rx_head_bwd(g_logits, e->rxfcw, tp.y[8], G[0], B, e->cfg.num_classes, 64, 1024, s);
+    float *cur = G[0], *nxt = G[1];
+    int H = 8;
+    for (int i = 8; i >= 0; --i) {
+        const dmad_engine::RxBlock& b = e->rx[i];
+        const int Ho = H, Hin = Ho * b.stride, Gc = b.D / 8;
+        if (i < 8) launch_relu_mask(cur, tp.y[i], cur, (long)B * Ho * Ho * b.cout, s);     // the block output's ReLU
+        CHK(conv(b.expand.wT, cur, gT, b.D, b.cout, 1, Ho, 1, b.cout, b.D, nullptr));        // conv_expand (1x1) + bn_expand
+        launch_relu_mask(gT, tp.t2[i], gT, (long)B * Ho * Ho * b.D, s);
+        const float* gin = gT;
+        if (b.stride == 2) { launch_dilate2x_nhwc(gT, gD, B, Ho, b.D, s); gin = gD; }
+        CHK(conv(b.conv.wT, gin, gU, Gc, Gc, 9, Hin, 8, b.D, b.D, nullptr));                 // grouped 3x3 (stride) + bn
+        launch_relu_mask(gU, tp.t1[i], gU, (long)B * Hin * Hin * b.D, s);
+        const float* res = cur;                                                              // identity shortcut
+        if (b.has_short) {                                                                   // 1x1 (stride) + bn at the output resolution,
+            CHK(conv(b.shortc.wT, cur, gS, b.cin, b.cout, 1, Ho, 1, b.cout, b.cin, nullptr)); // scattered into the even pixels
+            res = gS;
+            if (b.stride == 2) { launch_dilate2x_nhwc(gS, gSd, B, Ho, b.cin, s); res = gSd; }
+        }
+        CHK(conv(b.reduce.wT, gU, nxt, b.cin, b.D, 1, Hin, 1, b.D, b.cin, res));            // conv_reduce (1x1) + bn, + shortcut
+        std::swap(cur, nxt);
+        H = Hin;
+    }
+    launch_rx_conv1_bwd(cur, tp.c1, e->rxconv1.w, e->rxconv1.scale, g_spec, B, s);            // conv1's ReLU, bn and 1 <- 64 3x3 conv
+    LASTCHK();
+    return 0;
+}
+
+int classify_vjp(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
+    if (!e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
+    if (!e->cls_final) return fail(DMAD_ERR_STATE, "classifier weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    if (e->cls_kind != 1) return fail(DMAD_ERR_STATE, "the classifier VJP serves ResNeXt29 only: this engine holds VGG19_bn");
+    if (!e->rxvjpB) return fail(DMAD_ERR_STATE, "no classifier VJP workspace: call dmad_reserve_classifier_vjp first");
+    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    const int nc = e->cfg.num_classes;
+    for (int b0 = 0; b0 < B; b0 += e->rxvjpB) {
+        const int bb = B - b0 < e->rxvjpB ? B - b0 : e->rxvjpB;
+        CHK(rx_vjp_pass(e, spec + (size_t)b0 * 1024, bb, g_logits + (size_t)b0 * nc, g_spec + (size_t)b0 * 1024,
+                        logits ? logits + (size_t)b0 * nc : e->logits, s));
+    }
+    return 0;
+}
+
+// first call: the transposed filterbank / DFT images and the gradient maps of up to 64 clips per pass
+int mel_vjp_prepare(dmad_engine* e) {
+    if (e->melvjpB) return 0;
+    const int vB = e->maxB < 64 ? e->maxB : 64;
+    const size_t rows = (size_t)vB * 32;
+    CHK(e->alloc(&e->mel_fbT, (size_t)kMelLd * 32));
+    CHK(e->alloc(&e->mel_dftAT, (size_t)2048 * kDftKT));
+    launch_cvjp_transpose(e->fbA, 32, kMelLd, kMelLd, nullptr, e->mel_fbT, 32, nullptr);
+    launch_cvjp_transpose(e->dftA, kDftM, 2048, 2048, nullptr, e->mel_dftAT, kDftKT, nullptr);
+    HIPCHK(hipGetLastError());
+    CHK(e->alloc(&e->melvjp_gM, rows * 32));
+    CHK(e->alloc(&e->melvjp_gP, rows * kMelLd));
+    CHK(e->alloc(&e->melvjp_gD, rows * kDftKT));
+    CHK(e->alloc(&e->melvjp_gF, rows * 2048));
+    HIPCHK(hipDeviceSynchronize());
+    e->melvjpB = vB;
+    return 0;
+}
+
+// g_x = (d melDB / d x)^T g_spec of mel_db (B <= melvjpB); spec: the forward it recomputes
+int mel_vjp_pass(dmad_engine* e, const float* x, int B, const float* g_spec, float* g_x, float* spec, hipStream_t s) {
+    CHK(mel_db(e, x, B, spec, s));                                          // leaves the DFT (dftD) and the mel power (melM) resident
+    const long rows = (long)B * 32;
+    auto gemm = [&](const GemmF32Args& g) -> int {
+        if (launch_gemm_f32(g, s) != 0) return fail(DMAD_ERR_STATE, "mel VJP: no GEMM for M = %d, K = %d", g.M, g.K);
+        return 0;
+    };
+    launch_mel_db_bwd(g_spec, e->melM, e->melvjp_gM, B, s);                                                        // dB
+    CHK(gemm(plain_gemm(e->mel_fbT, e->melvjp_gM, e->melvjp_gP, nullptr, nullptr, kMelLd, 32, rows, kMelLd, 32, 0)));   // filterbank
+    launch_mel_power_bwd(e->dftD, kDftLd, e->melvjp_gP, kMelLd, e->melvjp_gD, kDftKT, rows, s);                   // |.|^2
+    CHK(gemm(plain_gemm(e->mel_dftAT, e->melvjp_gD, e->melvjp_gF, nullptr, nullptr, 2048, kDftKT, rows, 2048, kDftKT, 0)));   // DFT
+    launch_mel_ola_bwd(e->melvjp_gF, g_x, B, e->L, s);                                                              // framing
+    LASTCHK();
+    return 0;
+}
+
+int mel_db_vjp(dmad_engine* e, const float* x, int B, const float* g_spec, float* g_x, float* spec, hipStream_t s) {
+    if (!e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
+    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(mel_vjp_prepare(e));
+    for (int b0 = 0; b0 < B; b0 += e->melvjpB) {
+        const int bb = B - b0 < e->melvjpB ? B - b0 : e->melvjpB;
+        CHK(mel_vjp_pass(e, x + (size_t)b0 * e->L, bb, g_spec + (size_t)b0 * 1024, g_x + (size_t)b0 * e->L,
+                         spec ? spec + (size_t)b0 * 1024 : e->spec, s));
+    }
+    return 0;
+}
+
 // h16 = 1: the classifier's 16-bit tier where one is resident (ResNeXt29 on engines with a 16-bit side) — the fast mode's; 2: its
 // split-f16 tier (exact-vote engines) — tier 1 of the exact-vote loops; every other caller (dmad_classify, the recheck tiers) gets the
 // fp32 matrix cores
@@ -1618,7 +1755,7 @@ int read_recheck_stats(dmad_engine* e, bool spec, int64_t* samples, int64_t* rec
 extern "C" {
 
 const char* dmad_last_error(void) { return g_err.c_str(); }
-const char* dmad_version(void) { return "dmad-hip 0.5 (gfx950)"; }
+const char* dmad_version(void) { return "dmad-hip 0.5.1 (gfx950)"; }
 const char* dmad_last_warning(void) { return g_warn.c_str(); }
 
 int dmad_create(const dmad_config* cfg, dmad_engine** out) {
@@ -2278,6 +2415,70 @@ int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch) {
 int dmad_unet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps, dmad_stream s) {
     if (!e || !x_t || !g_eps || !g_x) return fail(DMAD_ERR_INVALID, "null argument");
     return unet_vjp(e, x_t, t, B, g_eps, g_x, eps, (hipStream_t)s);
+}
+
+int dmad_reserve_classifier_vjp(dmad_engine* e, int32_t max_batch) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
+    if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
+    if (!e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
+    if (!e->cls_final) return fail(DMAD_ERR_STATE, "classifier weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    if (e->cls_kind != 1) return fail(DMAD_ERR_STATE, "the classifier VJP serves ResNeXt29 only: this engine holds VGG19_bn");
+    const int vB = max_batch < e->maxB ? max_batch : e->maxB;
+    if (vB <= e->rxvjpB) return 0;
+    // tape slots in floats per spectrogram: conv1's output, then per bottleneck T1 (input resolution), T2 and Y (output resolution)
+    size_t c1_off = 0, tape = (size_t)1024 * 64, t1_off[9], t2_off[9], y_off[9];
+    int H = 32;
+    for (int i = 0; i < 9; ++i) {
+        const dmad_engine::RxBlock& b = e->rx[i];
+        const size_t Ho = (size_t)(H - 1) / b.stride + 1;
+        t1_off[i] = tape; tape += (size_t)H * H * b.D;
+        t2_off[i] = tape; tape += Ho * Ho * b.D;
+        y_off[i] = tape; tape += Ho * Ho * b.cout;
+        H = (int)Ho;
+    }
+    size_t work = 0;
+    for (size_t w : kRxWork) work += w;
+    if (e->rxvjpB) {                        // a larger reservation replaces the present one
+        const size_t ob = e->rxvjpB;
+        e->release(&e->rxvjp_tape, ob * e->rxvjp_tape_per); e->release(&e->rxvjp_work, ob * work);
+        e->rxvjpB = 0;
+    }
+    if (!e->rx[0].reduce.wT) {              // transposed images with the BN scale folded in, packed on the device from the fp32 images
+        for (int i = 0; i < 9; ++i) {
+            dmad_engine::RxBlock& b = e->rx[i];
+            const int G = b.D / 8;
+            CHK(e->alloc(&b.reduce.wT, (size_t)b.cin * b.D));            // [D][cin] -> [cin][D]
+            launch_cvjp_transpose(b.reduce.w, b.D, b.cin, b.cin, b.reduce.scale, b.reduce.wT, b.D, nullptr);
+            CHK(e->alloc(&b.conv.wT, (size_t)8 * 9 * G * G));            // [g][tap][m][k] -> [g][8 - tap][k][m]
+            launch_cvjp_pack_grouped(b.conv.w, b.conv.scale, b.conv.wT, G, nullptr);
+            CHK(e->alloc(&b.expand.wT, (size_t)b.D * b.cout));           // [cout][D] -> [D][cout]
+            launch_cvjp_transpose(b.expand.w, b.cout, b.D, b.D, b.expand.scale, b.expand.wT, b.cout, nullptr);
+            if (b.has_short) {                                           // [cout][cin] -> [cin][cout]
+                CHK(e->alloc(&b.shortc.wT, (size_t)b.cin * b.cout));
+                launch_cvjp_transpose(b.shortc.w, b.cout, b.cin, b.cin, b.shortc.scale, b.shortc.wT, b.cout, nullptr);
+            }
+        }
+        HIPCHK(hipGetLastError());
+    }
+    CHK(e->alloc(&e->rxvjp_tape, (size_t)vB * tape));
+    CHK(e->alloc(&e->rxvjp_work, (size_t)vB * work));
+    e->rxvjp_tape_per = tape;
+    auto at = [&](size_t off) { return e->rxvjp_tape + off * vB; };
+    e->rx_tape.c1 = at(c1_off);
+    for (int i = 0; i < 9; ++i) { e->rx_tape.t1[i] = at(t1_off[i]); e->rx_tape.t2[i] = at(t2_off[i]); e->rx_tape.y[i] = at(y_off[i]); }
+    HIPCHK(hipDeviceSynchronize());
+    e->rxvjpB = vB;
+    return 0;
+}
+
+int dmad_classify_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s) {
+    if (!e || !spec || !g_logits || !g_spec) return fail(DMAD_ERR_INVALID, "null argument");
+    return classify_vjp(e, spec, B, g_logits, g_spec, logits, (hipStream_t)s);
+}
+
+int dmad_mel_db_vjp(dmad_engine* e, const float* x, int32_t B, const float* g_spec, float* g_x, float* spec, dmad_stream s) {
+    if (!e || !x || !g_spec || !g_x) return fail(DMAD_ERR_INVALID, "null argument");
+    return mel_db_vjp(e, x, B, g_spec, g_x, spec, (hipStream_t)s);
 }
 
 int dmad_wavenet_eps_path(dmad_engine* e, const float* x_t, int32_t t, int32_t B, int32_t path, float* eps, dmad_stream s) {

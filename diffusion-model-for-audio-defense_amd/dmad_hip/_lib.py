@@ -71,6 +71,9 @@ _SIGNATURES = {
     'dmad_wavenet_eps_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     'dmad_reserve_unet_vjp': (C.c_int, [_P, C.c_int32]),
     'dmad_unet_eps_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    'dmad_reserve_classifier_vjp': (C.c_int, [_P, C.c_int32]),
+    'dmad_classify_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    'dmad_mel_db_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     'dmad_vpsde_purify': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64,
                                     C.c_int32, _P, _P, _P]),
     'dmad_vpsde_purify_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P, _P, _P, _P]),

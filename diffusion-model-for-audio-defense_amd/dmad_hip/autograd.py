@@ -22,6 +22,11 @@ only — no torch activations are kept between forward and backward (DESIGN §10
 UNetEpsHIP does the same for the Improved-Diffusion UNet of the spectrogram-domain purifier (UNetModel(..., grad_backend='hip')): its
 forward is the engine's exact-fp32 UNet tier and its backward the engine's UNet VJP (dmad_unet_eps_vjp), which re-runs the forward
 with its tape stored on the device.  There is no torch restatement of the UNet in this package.
+
+ResNeXtHIP and MelDBHIP are the native alternatives for the last two stages of every attack gradient (CifarResNeXt.grad_backend =
+'hip', MelSpectrogramDB(..., grad_backend='hip')): the classifier's forward is the engine's fp32 ResNeXt29 tier and its backward the
+engine's ResNeXt29 VJP (dmad_classify_vjp, tape re-written on the device); the mel front-end's backward recomputes the forward and
+walks dB, filterbank, |.|^2, DFT and overlap-add in reverse (dmad_mel_db_vjp).  Neither computes weight gradients.
 """
 import math
 
@@ -191,3 +196,60 @@ class UNetEpsHIP(torch.autograd.Function):
 def unet_eps_hip(engine, x: torch.Tensor, t: int) -> torch.Tensor:
     """eps = UNetModel(x [B,1,32,32], t * ones) on the engine, differentiable in `x` (UNetEpsHIP)."""
     return UNetEpsHIP.apply(x, engine, int(t))
+
+
+class ResNeXtHIP(torch.autograd.Function):
+    """logits = CifarResNeXt(spec [B,1,32,32]) on the engine's fp32 ResNeXt29 tier (classify_tier(spec, 0)), differentiable in `spec`
+    through the engine's VJP.  Saves only the input; the backward re-runs the forward with its tape saved (dmad_classify_vjp).  The VJP
+    workspace is reserved on first use.  No weight gradients.  First-order only: create_graph=True raises."""
+
+    @staticmethod
+    def forward(ctx, spec, engine):
+        _require_cuda(spec)
+        logits = engine.classify_tier(spec, 0)
+        ctx.engine = engine
+        ctx.save_for_backward(spec)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g_logits):
+        if torch.is_grad_enabled():
+            raise DmadError('the HIP ResNeXt29 VJP is first-order only: create_graph=True (double backward) is not supported; '
+                            "use grad_backend='torch' for higher derivatives")
+        spec, = ctx.saved_tensors
+        eng, B = ctx.engine, spec.shape[0]
+        if getattr(eng, 'classifier_vjp_batch', 0) < B:
+            eng.reserve_classifier_vjp(B)
+        g = eng.classify_vjp(spec, g_logits.contiguous())
+        return g.view(spec.shape).to(spec.dtype), None
+
+
+def resnext_hip(engine, spec: torch.Tensor) -> torch.Tensor:
+    """logits = CifarResNeXt(spec [B,1,32,32]) on the engine's fp32 tier, differentiable in `spec` (ResNeXtHIP)."""
+    return ResNeXtHIP.apply(spec, engine)
+
+
+class MelDBHIP(torch.autograd.Function):
+    """[B,1,16000] -> [B,1,32,32] dB mel spectrogram on the engine (mel_db), differentiable in `x` through the engine's mel VJP
+    (dmad_mel_db_vjp, which recomputes the forward).  Saves only the input.  First-order only: create_graph=True raises."""
+
+    @staticmethod
+    def forward(ctx, x, engine):
+        _require_cuda(x)
+        ctx.engine = engine
+        ctx.save_for_backward(x)
+        return engine.mel_db(x)
+
+    @staticmethod
+    def backward(ctx, g_spec):
+        if torch.is_grad_enabled():
+            raise DmadError('the HIP mel VJP is first-order only: create_graph=True (double backward) is not supported; '
+                            "use grad_backend='torch' for higher derivatives")
+        x, = ctx.saved_tensors
+        g = ctx.engine.mel_db_vjp(x, g_spec.contiguous())
+        return g.view(x.shape).to(x.dtype), None
+
+
+def mel_db_hip(engine, x: torch.Tensor) -> torch.Tensor:
+    """[B,1,16000] -> [B,1,32,32] dB mel spectrogram on the engine, differentiable in x (MelDBHIP)."""
+    return MelDBHIP.apply(x, engine)

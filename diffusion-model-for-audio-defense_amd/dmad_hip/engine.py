@@ -742,6 +742,43 @@ class Engine:
             check(self.lib.dmad_classify_tier(self._h, _ptr(sp[s:e]), e - s, int(tier), _ptr(out[s:e]), _stream()))
         return out
 
+    def reserve_classifier_vjp(self, max_batch: int):
+        """dmad_reserve_classifier_vjp: the workspace of classify_vjp (the ResNeXt29 forward's tape) for up to max_batch spectrograms per
+        pass (capped at max_batch; a larger reservation replaces a smaller one).  ResNeXt29 engines of every precision; DmadError otherwise."""
+        check(self.lib.dmad_reserve_classifier_vjp(self._h, int(max_batch)))
+        self.classifier_vjp_batch = max(getattr(self, 'classifier_vjp_batch', 0), int(max_batch))
+
+    def classify_vjp(self, spec: torch.Tensor, g_logits: torch.Tensor, want_logits: bool = False):
+        """g_spec = (d logits / d spec)^T g_logits for logits = CifarResNeXt(spec) on the fp32 tier ([B,1,32,32] or [B,32,32] -> [B,32,32]).
+        want_logits: also return the logits, bit-identical to classify_tier(spec, 0).  Needs reserve_classifier_vjp first (DmadError
+        otherwise); ResNeXt29 engines only."""
+        sp = self._spec(spec)
+        B = sp.shape[0]
+        if not g_logits.is_cuda or tuple(g_logits.shape) != (B, self.num_classes):
+            raise DmadError('g_logits must be a CUDA tensor [%d, %d], not %s' % (B, self.num_classes, tuple(g_logits.shape)))
+        g = g_logits.detach().contiguous().float()
+        gs = torch.empty_like(sp)
+        lg = torch.empty((B, self.num_classes), device=sp.device, dtype=torch.float32) if want_logits else None
+        for s, e in self._chunks(B):
+            check(self.lib.dmad_classify_vjp(self._h, _ptr(sp[s:e]), e - s, _ptr(g[s:e]), _ptr(gs[s:e]),
+                                             _ptr(None if lg is None else lg[s:e]), _stream()))
+        return (gs, lg) if want_logits else gs
+
+    def mel_db_vjp(self, x: torch.Tensor, g_spec: torch.Tensor, want_spec: bool = False):
+        """g_x = (d melDB / d x)^T g_spec for the dB mel front-end of mel_db ([B,1,L] or [B,L] -> [B,L]; g_spec [B,1,32,32] or [B,32,32]).
+        want_spec: also return the spectrogram [B,1,32,32], bit-identical to mel_db(x).  The forward is recomputed; the first call
+        allocates the workspace."""
+        xw = self._wave(x)
+        g = self._spec(g_spec)
+        if g.shape[0] != xw.shape[0]:
+            raise DmadError('g_spec has %d rows, x %d' % (g.shape[0], xw.shape[0]))
+        gx = torch.empty_like(xw)
+        sp = torch.empty((xw.shape[0], 1, 32, 32), device=xw.device, dtype=torch.float32) if want_spec else None
+        for s, e in self._chunks(xw.shape[0]):
+            check(self.lib.dmad_mel_db_vjp(self._h, _ptr(xw[s:e]), e - s, _ptr(g[s:e]), _ptr(gx[s:e]),
+                                           _ptr(None if sp is None else sp[s:e]), _stream()))
+        return (gx, sp) if want_spec else gx
+
     def vote(self, logits: torch.Tensor, counts: torch.Tensor):
         lg = logits.detach().contiguous().float()
         assert lg.is_cuda and counts.is_cuda and counts.dtype == torch.int64 and lg.shape[1] == self.num_classes

@@ -9,11 +9,27 @@ from . import engine as _eng
 
 class MelSpectrogramDB(torch.nn.Module):
     """[B,1,16000] fp32 CUDA -> [B,1,32,32] dB mel spectrogram (windowed DFT on the fp32 matrix cores,
-    |.|^2, slaney filterbank, 10*log10(max(.,1e-10)))."""
+    |.|^2, slaney filterbank, 10*log10(max(.,1e-10))).
 
-    def __init__(self, engine=None):
+    grad_backend: the gradient branch (x.requires_grad under autograd): 'torch' = the torch restatement (autograd.mel_db), 'hip' = the
+    engine's forward and mel VJP (autograd.MelDBHIP), 'auto' (the default) = 'torch'."""
+
+    GRAD_BACKENDS = ('auto', 'torch', 'hip')
+
+    def __init__(self, engine=None, grad_backend='auto'):
         super().__init__()
         self._engine = engine
+        self.grad_backend = grad_backend
+
+    @property
+    def grad_backend(self):
+        return self.__dict__.get('_grad_backend', 'auto')
+
+    @grad_backend.setter
+    def grad_backend(self, value):
+        if value not in self.GRAD_BACKENDS:
+            raise ValueError('grad_backend must be one of %s, not %r' % (self.GRAD_BACKENDS, value))
+        self.__dict__['_grad_backend'] = value
 
     @property
     def engine(self):
@@ -22,7 +38,9 @@ class MelSpectrogramDB(torch.nn.Module):
         return self._engine
 
     def forward(self, x):
-        if _ag.needs_grad(x):                  # callers that differentiate through the system: torch restatement
+        if _ag.needs_grad(x):                  # callers that differentiate through the system
+            if self.grad_backend == 'hip':
+                return _ag.mel_db_hip(self.engine, x)
             return _ag.mel_db(x)
         with torch.no_grad():
             return self.engine.mel_db(x)

@@ -274,6 +274,38 @@ int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch);
 int dmad_unet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps,
                       dmad_stream s);
 
+/* Vector-Jacobian products of the classifier side — the last two stages of every gradient the white-box attack driver takes
+ * (adaptive_attack_eval.py: AudioAttack's loss.backward() through AcousticSystem -> MelSpectrogram + AmplitudeToDB -> the classifier,
+ * white_box_attack.py:356-376).  DESIGN §14.
+ *
+ * dmad_reserve_classifier_vjp reserves the ResNeXt29 VJP workspace for up to max_batch spectrograms per pass: the TAPE of the fp32
+ * forward — conv1's output and, per bottleneck, its post-ReLU T1 (reduce) and T2 (grouped 3x3) and its block output Y, 8.13 M floats
+ * (32.5 MB) per spectrogram —, six gradient work maps (4.0 M floats, 16.0 MB per spectrogram) and, on the first reservation, the
+ * transposed weight images (1x1 convs transposed, the grouped 3x3 conv tap-flipped with m / k swapped per group, every eval-BatchNorm
+ * scale folded in; as large as the resident fp32 images), packed on the device from those.  max_batch is capped at the engine's
+ * max_batch.  A larger reservation replaces a smaller one; a smaller one keeps the present.  Counted by dmad_device_bytes.
+ * DMAD_ERR_STATE before the classifier weights are finalised, or for an engine that holds VGG19_bn.
+ *
+ * dmad_classify_vjp:  g_spec = (d logits / d spec)^T g_logits  for logits = CifarResNeXt(spec) (models/resnext.py:133-142) on the fp32
+ * tier.  spec, g_spec: device fp32 [B][32][32]; g_logits: device fp32 [B][num_classes].  logits: optional (NULL) device fp32
+ * [B][num_classes], bit-identical to dmad_classify_tier(.., tier = 0, ..).  Every engine precision (the fp32 images are resident on all
+ * three).  The input gradient only: no weight gradients.  B in [1, max_batch], processed in passes of the reservation's size.  Store
+ * scheme: the forward writes the tape, the backward walks the bottlenecks in reverse — every conv as the fp32 GEMM on the transposed
+ * images (a stride-2 3x3 on the zero-dilated gradient; the stride-2 shortcut at the output resolution, scattered into the even
+ * pixels), every ReLU as g * [y > 0] on the saved map, the shortcut gradient summed in the reduce conv's epilogue; head and conv1 as
+ * small kernels.  No atomics, no split-K: g_spec is bit-identical across calls and independent of the batch.  DMAD_ERR_STATE without a
+ * reservation or for a VGG19_bn engine.
+ *
+ * dmad_mel_db_vjp:  g_x = (d melDB / d x)^T g_spec  for melDB = AmplitudeToDB(MelSpectrogram(x)) (certified_robustness_eval.py:85-87, the
+ * forward of dmad_mel_db).  x, g_x: device fp32 [B][clip_len]; g_spec: device fp32 [B][32][32].  spec: optional (NULL) device fp32
+ * [B][32][32], bit-identical to dmad_mel_db.  The forward is recomputed; nothing is kept across calls.  dB: g * 10 / (ln 10 M) where
+ * M >= 1e-10 (torch's clamp rule), filterbank and DFT as fp32 GEMMs on transposed images, |.|^2 and the overlap-add (center padding
+ * cropped) as small kernels in a fixed order.  The first call allocates the transposed images (17 MB) and the gradient maps of up to
+ * 64 clips per pass (42 MB); B in [1, max_batch].  Every engine with a classifier. */
+int dmad_reserve_classifier_vjp(dmad_engine* e, int32_t max_batch);
+int dmad_classify_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s);
+int dmad_mel_db_vjp(dmad_engine* e, const float* x, int32_t B, const float* g_spec, float* g_x, float* spec, dmad_stream s);
+
 /* The reverse VP-SDE purifier of the reference's adaptive-attack driver (adaptive_attack_eval.py --defense Diffusion ->
  * diffusion_models/diffwave_sde.py RevDiffWave.audio_editing_sample: torchsde.sdeint_adjoint(RevVPSDE, method='euler', dt = 1/T)).
  * The step schedule is built by the CALLER on the host, in float32 and in torchsde's order (diffusion_models/diffwave_sde.py
