@@ -1285,6 +1285,26 @@ std::vector<UnRef> un_flat(const dmad_engine* e, std::vector<size_t>* hs_k = nul
     return r;
 }
 
+// The weight image of a dense conv's data gradient, packed on the device: w [taps][co][ci] -> wT [taps - 1 - tap][ci][co] (the 3x3 taps
+// flipped; a 1x1 layer: the transpose)
+void un_pack_wT(const float* w, float* wT, int taps, long ci, long co, hipStream_t s) {
+    launch_unvjp_pack(w, wT, taps, (int)ci, (int)co, taps > 1 ? co * ci : 0, 1, ci, taps > 1 ? 1 : 0, s);
+}
+
+// The data gradient of one dense NHWC conv of the UNet (3x3 zero padding 1 / 1x1; H: the conv's input resolution) on its packed image
+// (un_pack_wT): g [B][Ho][Ho][co] -> gx [B][H][H][ci].  stride 2 (Downsample): the stride-1 conv of the zero-dilated gradient (work:
+// [B][H][H][co]).  up (Upsample = interpolate x2 + conv at 2H; g at 2H): the conv's gradient at 2H (work: [B][2H][2H][ci]), then the 2x2
+// sums.  acc (optional, [B][H][H][ci]) joins the result in the GEMM's epilogue, with `up` in the 2x2 sum's.
+int un_conv_dgrad(const float* wT, const float* g, float* gx, int ci, int co, int taps, int B, int H, int stride, bool up, const float* acc,
+                  float* work, hipStream_t s) {
+    const float* gin = g;
+    if (!up && stride == 2) { launch_dilate2x_nhwc(g, work, B, H / 2, co, s); gin = work; }
+    if (launch_gemm_f32(un_conv_args(wT, nullptr, gin, up ? work : gx, ci, co, taps, B, up ? 2 * H : H, 1, up ? nullptr : acc), s) != 0)
+        return fail(DMAD_ERR_STATE, "UNet VJP: no GEMM for M = %d, K = %d, taps = %d", ci, co, taps);
+    if (up) launch_upsample2x_bwd_nhwc(work, acc, gx, B, H, ci, s);
+    return 0;
+}
+
 // One pass (B <= unvjpB): the forward with its tape, then the modules in reverse.  G[0] / G[1] carry the gradient of the current module's
 // output / input (ping-pong); G[2..5] are the per-module scratch maps (G[2] conv2^T / proj^T / the dilated map / the upsampled gradient,
 // G[3] GroupNorm2^T / the attention gradient, G[4] conv1^T / qkv^T, G[5] the skip conv^T).
@@ -1298,10 +1318,6 @@ int unet_vjp_pass(dmad_engine* e, const float* x, int t, int B, const float* g_e
     float* G[6];
     for (int i = 0; i < 6; ++i) G[i] = e->unvjp_work + i * W;
     const auto& tp = e->un_tape;
-    auto gemm = [&](const GemmF32Args& g) -> int {
-        if (launch_gemm_f32(g, s) != 0) return fail(DMAD_ERR_STATE, "UNet VJP: no GEMM for M = %d, K = %d, taps = %d", g.M, g.K, g.taps);
-        return 0;
-    };
     auto gnb = [&](const float* xin, const float* xin2, int c1, const float* gw, const float* gb, const float* ss, int silu, const float* gy,
                    const float* add, const float* add2, float* gx, float* gx2, int HW, int C) -> int {
         if (launch_groupnorm_bwd(xin, xin2, c1, gw, gb, ss, silu, gy, add, add2, gx, gx2, B, HW, C, s)) return fail(DMAD_ERR_STATE, "UNet VJP: GroupNorm backward of a %d-channel map", C);
@@ -1320,27 +1336,25 @@ int unet_vjp_pass(dmad_engine* e, const float* x, int t, int B, const float* g_e
         float* gin2 = top >= 0 ? e->unvjp_ghs_at[top] : nullptr;
         const float* acc = ops[k].acc >= 0 ? e->unvjp_ghs_at[ops[k].acc] : nullptr;
         if (o.kind == 1) {                      // ResBlock: skip(in) + conv2(SiLU(GN2(conv1(SiLU(GN1(in)))) * (1 + scale) + shift))
-            CHK(gemm(un_conv_args(o.w2T, nullptr, cur, G[2], o.cout, o.cout, 9, B, H, 1, nullptr)));
+            CHK(un_conv_dgrad(o.w2T, cur, G[2], o.cout, o.cout, 9, B, H, 1, false, nullptr, nullptr, s));
             CHK(gnb(tp.t2[k], nullptr, 0, o.gn2w, o.gn2b, e->un_ss_cur + o.ss_off, 1, G[2], nullptr, nullptr, G[3], nullptr, H * H, o.cout));
-            CHK(gemm(un_conv_args(o.w1T, nullptr, G[3], G[4], o.cin, o.cout, 9, B, H, 1, nullptr)));
+            CHK(un_conv_dgrad(o.w1T, G[3], G[4], o.cin, o.cout, 9, B, H, 1, false, nullptr, nullptr, s));
             const float *add = cur, *add2 = acc;
             if (o.cin != o.cout) {              // the 1x1 skip conv's gradient, the consumer's saved-map gradient summed in its epilogue
-                CHK(gemm(un_conv_args(o.skwT, nullptr, cur, G[5], o.cin, o.cout, 1, B, H, 1, acc)));
+                CHK(un_conv_dgrad(o.skwT, cur, G[5], o.cin, o.cout, 1, B, H, 1, false, acc, nullptr, s));
                 add = G[5]; add2 = nullptr;
             }
             CHK(gnb(in, in2, c1, o.gn1w, o.gn1b, nullptr, 1, G[4], add, add2, nxt, gin2, H * H, o.cin));
         } else if (o.kind == 2) {               // AttentionBlock: in + proj_out(attention(qkv(GN(in))))
             const int T = H * H, C = o.cin;
-            CHK(gemm(un_conv_args(o.w2T, nullptr, cur, G[2], C, C, 1, B, H, 1, nullptr)));
+            CHK(un_conv_dgrad(o.w2T, cur, G[2], C, C, 1, B, H, 1, false, nullptr, nullptr, s));
             if (int rc = launch_qkv_attention_bwd(tp.qkv[k], G[2], G[3], B, T, kUnHeads, s)) return fail(rc > 0 ? DMAD_ERR_HIP : DMAD_ERR_STATE, "UNet VJP: attention backward (T = %d)", T);
-            CHK(gemm(un_conv_args(o.w1T, nullptr, G[3], G[4], C, 3 * C, 1, B, H, 1, nullptr)));
+            CHK(un_conv_dgrad(o.w1T, G[3], G[4], C, 3 * C, 1, B, H, 1, false, nullptr, nullptr, s));
             CHK(gnb(in, nullptr, 0, o.gn1w, o.gn1b, nullptr, 0, G[4], cur, acc, nxt, nullptr, T, C));
         } else if (o.kind == 3) {               // Downsample (3x3, stride 2): the stride-1 conv of the zero-dilated gradient
-            launch_dilate2x_nhwc(cur, G[2], B, H / 2, o.cout, s);
-            CHK(gemm(un_conv_args(o.w1T, nullptr, G[2], nxt, o.cin, o.cout, 9, B, H, 1, acc)));
+            CHK(un_conv_dgrad(o.w1T, cur, nxt, o.cin, o.cout, 9, B, H, 2, false, acc, G[2], s));
         } else if (o.kind == 4) {               // Upsample: the conv's gradient at 2H, then the 2x2 sums
-            CHK(gemm(un_conv_args(o.w1T, nullptr, cur, G[2], o.cin, o.cout, 9, B, 2 * H, 1, nullptr)));
-            launch_upsample2x_bwd_nhwc(G[2], acc, nxt, B, H, o.cin, s);
+            CHK(un_conv_dgrad(o.w1T, cur, nxt, o.cin, o.cout, 9, B, H, 1, true, acc, G[2], s));
         } else {                                // conv_in (1 -> 128): a 128 -> 1 conv of the gradient with the flipped image
             launch_conv3x3_c128_to1(cur, o.w1T, e->unvjp_zero, g_x, B, s, affine ? g_eps : nullptr, alpha, gamma);
         }
@@ -1558,6 +1572,31 @@ constexpr int kDftKT = 2064;             // K of the DFT^T GEMM: the 2050 re / i
 // zero-dilation and g_T1 (32 x 32 x 1024 at most: stage 2's first bottleneck), the shortcut gradient (64 K) and its dilation (256 K)
 const size_t kRxWork[6] = {262144, 262144, 1048576, 1048576, 1048576, 327680};
 
+// The weight image of a ResNeXt29 conv's data gradient with the eval-mode BN scale folded in: a 1x1 layer w [M][K] -> wT [K][ldt] (ldt >= M,
+// the rows beyond M zero: the K padding of the gradient GEMM); the grouped 3x3 (8 groups of G = M = K) [g][tap][m][k] -> [g][8 - tap][k][m]
+void rx_pack_wT(const float* w, const float* scale, float* wT, int M, int K, int taps, int ldt, hipStream_t s) {
+    if (taps == 9) launch_cvjp_pack_grouped(w, scale, wT, M, s);
+    else launch_cvjp_transpose(w, M, K, K, scale, wT, ldt, s);
+}
+
+// The data gradient of one ResNeXt29 conv on its packed image (rx_pack_wT): g [B][Ho][Ho][groups * K] -> gx [B][Hin][Hin][groups * M] (M: the
+// gradient's channels per group = the conv's input channels, K: the conv's output channels per group, padded for a 1x1 image with ldt > M),
+// no split-K.  Stride 2: the grouped 3x3 runs at Hin = 2 Ho on the zero-dilated gradient (work: [B][Hin][Hin][groups * K]); the 1x1
+// shortcut runs at Ho (work: [B][Ho][Ho][M]) and is scattered into the even pixels of gx.  res (optional, gx's shape; not with the
+// stride-2 1x1) is added in the GEMM's epilogue.
+int rx_conv_dgrad(const float* wT, const float* g, float* gx, int M, int K, int taps, int groups, int B, int Ho, int stride, float* work,
+                  const float* res, hipStream_t s) {
+    const bool dil_in = stride == 2 && taps == 9, dil_out = stride == 2 && taps == 1;
+    if (dil_in) launch_dilate2x_nhwc(g, work, B, Ho, groups * K, s);
+    const int H = dil_in ? 2 * Ho : Ho;
+    GemmF32Args a{};
+    a.A = wT; a.X = dil_in ? work : g; a.C = dil_out ? work : gx; a.M = M; a.K = K; a.taps = taps; a.ldc = groups * M; a.N = (long)B * H * H; a.mode = 2;
+    a.H = H; a.W = H; a.Cin = K; a.ldx = groups * K; a.stride = 1; a.groups = groups; a.res = dil_out ? nullptr : res;
+    if (launch_gemm_f32(a, s) != 0) return fail(DMAD_ERR_STATE, "classifier VJP: no GEMM for M = %d, K = %d, taps = %d", M, K, taps);
+    if (dil_out) launch_dilate2x_nhwc(work, gx, B, Ho, M, s);
+    return 0;
+}
+
 // g_spec = (d logits / d spec)^T g_logits of classify_resnext; logits: the forward it recomputes (B <= rxvjpB)
 int rx_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
     const dmad_engine::RxTape& tp = e->rx_tape;
@@ -1566,15 +1605,6 @@ int rx_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits,
     G[0] = e->rxvjp_work;
     for (int k = 1; k < 6; ++k) G[k] = G[k - 1] + kRxWork[k - 1] * e->rxvjpB;
     float *gT = G[2], *gD = G[3], *gU = G[4], *gS = G[5], *gSd = G[5] + 65536l * e->rxvjpB;
-    // NHWC conv on a transposed image, stride 1 (the stride-2 backward runs on the zero-dilated gradient), no split-K
-    auto conv = [&](const float* A, const float* X, float* C, int M, int K, int taps, int H, int groups, int ldx, int ldc,
-                    const float* res) -> int {
-        GemmF32Args g{};
-        g.A = A; g.X = X; g.C = C; g.M = M; g.K = K; g.taps = taps; g.ldc = ldc; g.N = (long)B * H * H; g.mode = 2;
-        g.H = H; g.W = H; g.Cin = K; g.ldx = ldx; g.stride = 1; g.groups = groups; g.res = res;
-        if (launch_gemm_f32(g, s) != 0) return fail(DMAD_ERR_STATE, "classifier VJP: no GEMM for M = %d, K = %d, taps = %d", M, K, taps);
-        return 0;
-    };
     // head: FC, 8 x 8 average pool and the last block's ReLU in one kernel
     launch_rx_head_bwd(g_logits, e->rxfcw, tp.y[8], G[0], B, e->cfg.num_classes, 64, 1024, s);
     float *cur = G[0], *nxt = G[1];
@@ -1583,19 +1613,17 @@ int rx_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits,
         const dmad_engine::RxBlock& b = e->rx[i];
         const int Ho = H, Hin = Ho * b.stride, Gc = b.D / 8;
         if (i < 8) launch_relu_mask(cur, tp.y[i], cur, (long)B * Ho * Ho * b.cout, s);     // the block output's ReLU
-        CHK(conv(b.expand.wT, cur, gT, b.D, b.cout, 1, Ho, 1, b.cout, b.D, nullptr));        // conv_expand (1x1) + bn_expand
+        CHK(rx_conv_dgrad(b.expand.wT, cur, gT, b.D, b.cout, 1, 1, B, Ho, 1, nullptr, nullptr, s));     // conv_expand (1x1) + bn_expand
         launch_relu_mask(gT, tp.t2[i], gT, (long)B * Ho * Ho * b.D, s);
-        const float* gin = gT;
-        if (b.stride == 2) { launch_dilate2x_nhwc(gT, gD, B, Ho, b.D, s); gin = gD; }
-        CHK(conv(b.conv.wT, gin, gU, Gc, Gc, 9, Hin, 8, b.D, b.D, nullptr));                 // grouped 3x3 (stride) + bn
+        CHK(rx_conv_dgrad(b.conv.wT, gT, gU, Gc, Gc, 9, 8, B, Ho, b.stride, gD, nullptr, s));          // grouped 3x3 (stride) + bn
         launch_relu_mask(gU, tp.t1[i], gU, (long)B * Hin * Hin * b.D, s);
         const float* res = cur;                                                              // identity shortcut
         if (b.has_short) {                                                                   // 1x1 (stride) + bn at the output resolution,
-            CHK(conv(b.shortc.wT, cur, gS, b.cin, b.cout, 1, Ho, 1, b.cout, b.cin, nullptr)); // scattered into the even pixels
-            res = gS;
-            if (b.stride == 2) { launch_dilate2x_nhwc(gS, gSd, B, Ho, b.cin, s); res = gSd; }
+            float* gsc = b.stride == 2 ? gSd : gS;                                           // scattered into the even pixels
+            CHK(rx_conv_dgrad(b.shortc.wT, cur, gsc, b.cin, b.cout, 1, 1, B, Ho, b.stride, gS, nullptr, s));
+            res = gsc;
         }
-        CHK(conv(b.reduce.wT, gU, nxt, b.cin, b.D, 1, Hin, 1, b.D, b.cin, res));            // conv_reduce (1x1) + bn, + shortcut
+        CHK(rx_conv_dgrad(b.reduce.wT, gU, nxt, b.cin, b.D, 1, 1, B, Hin, 1, nullptr, res, s));       // conv_reduce (1x1) + bn, + shortcut
         std::swap(cur, nxt);
         H = Hin;
     }
@@ -2267,6 +2295,123 @@ int dmad_groupnorm16_apply(const uint16_t* x, const float* st, const uint16_t* x
     return 0;
 }
 
+int dmad_conv_f32(const float* x, const float* x2, int32_t ksplit, const float* w, const float* scale, const float* shift, const float* res,
+                  int32_t B, int32_t H, int32_t M, int32_t K, int32_t taps, int32_t stride, int32_t groups, int32_t relu, float* slab,
+                  int64_t slab_floats, int64_t n_ref, float* out, int32_t* choice, dmad_stream s) {
+    if (!x || !w || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || H < 0 || M < 1 || K < 16 || (K % 16) || groups < 1 || groups > 65535 || (stride != 1 && stride != 2) || (taps != 1 && taps != 9))
+        return fail(DMAD_ERR_INVALID, "bad geometry (K a multiple of 16, taps 1 or 9, stride 1 or 2)");
+    if (H == 0 && (taps != 1 || stride != 1 || groups != 1 || x2)) return fail(DMAD_ERR_INVALID, "the row form (H = 0) is a plain GEMM: one tap, one group, one input");
+    if (x2 && groups > 1) return fail(DMAD_ERR_INVALID, "two-part input serves dense convs only");
+    if (slab_floats < 0 || n_ref < 0 || (slab && slab_floats < 1)) return fail(DMAD_ERR_INVALID, "bad split-K workspace");
+    if (int r = gemm_f32_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, fp32 narrow tile) failed: %d", r);
+    GemmF32Args g{};
+    if (H == 0) {
+        g = plain_gemm(w, x, out, scale, shift, M, K, B, M, K, relu);
+        g.res = res;
+    } else {
+        const int Ho = (H - 1) / stride + 1;
+        g.A = w; g.X = x; g.C = out; g.scale = scale; g.shift = shift; g.res = res; g.M = M; g.K = K; g.taps = taps; g.ldc = groups * M; g.relu = relu;
+        g.N = (long)B * Ho * Ho; g.mode = 2; g.H = H; g.W = H; g.Cin = K; g.ldx = x2 ? ksplit : groups * K; g.stride = stride; g.groups = groups;
+        if (x2) { g.X2 = x2; g.ksplit = ksplit; g.ldx2 = K - ksplit; }
+    }
+    if (launch_gemm_f32(g, (hipStream_t)s, slab, (long)slab_floats, (long)n_ref) != 0) {
+        gemm_take_bad_shapes();
+        return fail(DMAD_ERR_INVALID, "no fp32 GEMM serves this shape");
+    }
+    if (choice) { const GemmF32Choice c = gemm_f32_last_choice(); choice[0] = c.bm; choice[1] = c.narrow; choice[2] = c.two; choice[3] = c.splits; }
+    LASTCHK();
+    return 0;
+}
+
+int dmad_conv_f32_vjp(const float* g_y, const float* w, const float* scale, const float* mask_y, const float* acc, int32_t B, int32_t H,
+                      int32_t M, int32_t K, int32_t taps, int32_t stride, int32_t groups, int32_t form, int32_t ldt, float* wT, float* gm,
+                      float* work, float* g_x, dmad_stream s) {
+    if (!g_y || !w || !wT || !g_x) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || H < 1 || M < 16 || K < 4 || (M % 16) || (K % 4) || (stride != 1 && stride != 2) || (taps != 1 && taps != 9) || form < 0 || form > 2)
+        return fail(DMAD_ERR_INVALID, "bad geometry (M a multiple of 16, K of 4, taps 1 or 9, stride 1 or 2, form 0 - 2)");
+    if (stride == 2 && (H & 1)) return fail(DMAD_ERR_INVALID, "a stride-2 gradient is dilated to an even map: H = %d", H);
+    if ((stride == 2 || form == 1) && !work) return fail(DMAD_ERR_INVALID, "this form needs the work map");
+    if (int r = gemm_f32_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, fp32 narrow tile) failed: %d", r);
+    const hipStream_t st = (hipStream_t)s;
+    const int Ho = form == 1 ? 2 * H : (H - 1) / stride + 1;
+    if (form < 2) {                              // the UNet's forms
+        if (groups != 1 || scale || mask_y || gm || ldt || (form == 1 && (taps != 9 || stride != 1)))
+            return fail(DMAD_ERR_INVALID, "the UNet's forms are dense, unscaled and unmasked (Upsample: 3x3, stride 1)");
+        un_pack_wT(w, wT, taps, K, M, st);
+        CHK(un_conv_dgrad(wT, g_y, g_x, K, M, taps, B, H, stride, form == 1, acc, work, st));
+    } else {                                     // ResNeXt29's forms
+        if (taps == 1 ? (groups != 1 || (ldt && (ldt < M || (ldt % 16))) || (stride == 2 && acc)) : (groups != 8 || M != K || ldt || !scale))
+            return fail(DMAD_ERR_INVALID, "ResNeXt29's forms: a dense 1x1 (ldt 0 or a multiple of 16 >= M; no acc with stride 2) or the 8-group 3x3 with M = K and a scale");
+        const int kp = taps == 1 && ldt ? ldt : M;                       // the gradient's channel pitch (padded with the image's rows)
+        const float* g = g_y;
+        if (mask_y) {
+            const long n = (long)B * Ho * Ho * groups * kp;
+            if (!gm || kp != M || (n & 3)) return fail(DMAD_ERR_INVALID, "the ReLU mask needs its output map, an unpadded gradient and a multiple of 4 values");
+            launch_relu_mask(g_y, mask_y, gm, n, st);
+            g = gm;
+        }
+        rx_pack_wT(w, scale, wT, M, K, taps, kp, st);
+        CHK(rx_conv_dgrad(wT, g, g_x, K, kp, taps, groups, B, Ho, stride, work, acc, st));
+    }
+    LASTCHK();
+    return 0;
+}
+
+int dmad_groupnorm_f32(const float* x, const float* x2, int32_t c1, const float* gamma, const float* beta, const float* ss, int32_t silu,
+                       int32_t B, int32_t HW, int32_t C, float* y, dmad_stream s) {
+    if (!x || !gamma || !beta || !y) return fail(DMAD_ERR_INVALID, "null argument");
+    if (launch_groupnorm_nhwc(x, gamma, beta, ss, silu, y, B, HW, C, (hipStream_t)s, x2, x2 ? c1 : 0))
+        return fail(DMAD_ERR_INVALID, "no fp32 GroupNorm for a %d-pixel x %d-channel map (c1 = %d)", HW, C, c1);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_groupnorm_bwd(const float* x, const float* x2, int32_t c1, const float* gamma, const float* beta, const float* ss, int32_t silu,
+                       const float* gy, const float* add, const float* add2, int32_t B, int32_t HW, int32_t C, float* gx, float* gx2,
+                       dmad_stream s) {
+    if (!x || !gamma || !beta || !gy || !gx) return fail(DMAD_ERR_INVALID, "null argument");
+    if (launch_groupnorm_bwd(x, x2, x2 ? c1 : 0, gamma, beta, ss, silu, gy, add, add2, gx, gx2, B, HW, C, (hipStream_t)s))
+        return fail(DMAD_ERR_INVALID, "no GroupNorm backward for a %d-pixel x %d-channel map (c1 = %d)", HW, C, c1);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_qkv_attention_f32(const float* qkv, int32_t B, int32_t T, int32_t heads, float* out, dmad_stream s) {
+    if (!qkv || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || heads < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
+    if (int rc = launch_qkv_attention(qkv, out, B, T, heads, (hipStream_t)s))
+        return fail(rc > 0 ? DMAD_ERR_HIP : DMAD_ERR_INVALID, "attention (T = %d): %s", T, rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported map size");
+    LASTCHK();
+    return 0;
+}
+
+int dmad_qkv_attention_bwd(const float* qkv, const float* go, int32_t B, int32_t T, int32_t heads, float* gqkv, dmad_stream s) {
+    if (!qkv || !go || !gqkv) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || heads < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
+    if (int r = unvjp_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, attention backward) failed: %d", r);
+    if (int rc = launch_qkv_attention_bwd(qkv, go, gqkv, B, T, heads, (hipStream_t)s))
+        return fail(rc > 0 ? DMAD_ERR_HIP : DMAD_ERR_INVALID, "attention backward (T = %d): unsupported map size", T);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_rx_head_bwd(const float* g_logits, const float* W, const float* y, int32_t B, int32_t ncls, int32_t HW, int32_t C, float* gz, dmad_stream s) {
+    if (!g_logits || !W || !y || !gz) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || ncls < 1 || HW < 1 || C < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
+    launch_rx_head_bwd(g_logits, W, y, gz, B, ncls, HW, C, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_rx_conv1_bwd(const float* g, const float* a, const float* w, const float* scale, int32_t B, float* gspec, dmad_stream s) {
+    if (!g || !a || !w || !scale || !gspec) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
+    launch_rx_conv1_bwd(g, a, w, scale, gspec, B, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
 int dmad_vote(dmad_engine* e, const float* logits, int32_t B, int64_t* counts, dmad_stream s) {
     if (!e || !logits || !counts || B < 1) return fail(DMAD_ERR_INVALID, "bad argument to dmad_vote");
     launch_vote(logits, B, e->cfg.num_classes, (unsigned long long*)counts, nullptr, (hipStream_t)s);
@@ -2379,13 +2524,13 @@ int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch) {
             if (o.kind == 0) {              // [co][9] -> [9][co], taps flipped (the 128 -> 1 conv's image)
                 CHK(e->alloc(&o.w1T, 9 * co)); launch_unvjp_pack(o.w1, o.w1T, 9, (int)co, 1, 1, 9, 0, 1, nullptr);
             } else if (o.kind == 2) {       // qkv [3C][C] -> [C][3C], proj_out [C][C] -> transposed
-                CHK(e->alloc(&o.w1T, 3 * ci * ci)); launch_unvjp_pack(o.w1, o.w1T, 1, (int)ci, (int)(3 * ci), 0, 1, ci, 0, nullptr);
-                CHK(e->alloc(&o.w2T, ci * ci)); launch_unvjp_pack(o.w2, o.w2T, 1, (int)ci, (int)ci, 0, 1, ci, 0, nullptr);
+                CHK(e->alloc(&o.w1T, 3 * ci * ci)); un_pack_wT(o.w1, o.w1T, 1, ci, 3 * ci, nullptr);
+                CHK(e->alloc(&o.w2T, ci * ci)); un_pack_wT(o.w2, o.w2T, 1, ci, ci, nullptr);
             } else {                        // 3x3 [tap][co][ci] -> [8 - tap][ci][co]
-                CHK(e->alloc(&o.w1T, 9 * ci * co)); launch_unvjp_pack(o.w1, o.w1T, 9, (int)ci, (int)co, co * ci, 1, ci, 1, nullptr);
+                CHK(e->alloc(&o.w1T, 9 * ci * co)); un_pack_wT(o.w1, o.w1T, 9, ci, co, nullptr);
                 if (o.kind == 1) {
-                    CHK(e->alloc(&o.w2T, 9 * co * co)); launch_unvjp_pack(o.w2, o.w2T, 9, (int)co, (int)co, co * co, 1, co, 1, nullptr);
-                    if (ci != co) { CHK(e->alloc(&o.skwT, ci * co)); launch_unvjp_pack(o.skw, o.skwT, 1, (int)ci, (int)co, 0, 1, ci, 0, nullptr); }
+                    CHK(e->alloc(&o.w2T, 9 * co * co)); un_pack_wT(o.w2, o.w2T, 9, co, co, nullptr);
+                    if (ci != co) { CHK(e->alloc(&o.skwT, ci * co)); un_pack_wT(o.skw, o.skwT, 1, ci, co, nullptr); }
                 }
             }
             return 0;
@@ -2448,14 +2593,14 @@ int dmad_reserve_classifier_vjp(dmad_engine* e, int32_t max_batch) {
             dmad_engine::RxBlock& b = e->rx[i];
             const int G = b.D / 8;
             CHK(e->alloc(&b.reduce.wT, (size_t)b.cin * b.D));            // [D][cin] -> [cin][D]
-            launch_cvjp_transpose(b.reduce.w, b.D, b.cin, b.cin, b.reduce.scale, b.reduce.wT, b.D, nullptr);
+            rx_pack_wT(b.reduce.w, b.reduce.scale, b.reduce.wT, b.D, b.cin, 1, b.D, nullptr);
             CHK(e->alloc(&b.conv.wT, (size_t)8 * 9 * G * G));            // [g][tap][m][k] -> [g][8 - tap][k][m]
-            launch_cvjp_pack_grouped(b.conv.w, b.conv.scale, b.conv.wT, G, nullptr);
+            rx_pack_wT(b.conv.w, b.conv.scale, b.conv.wT, G, G, 9, 0, nullptr);
             CHK(e->alloc(&b.expand.wT, (size_t)b.D * b.cout));           // [cout][D] -> [D][cout]
-            launch_cvjp_transpose(b.expand.w, b.cout, b.D, b.D, b.expand.scale, b.expand.wT, b.cout, nullptr);
+            rx_pack_wT(b.expand.w, b.expand.scale, b.expand.wT, b.cout, b.D, 1, b.cout, nullptr);
             if (b.has_short) {                                           // [cout][cin] -> [cin][cout]
                 CHK(e->alloc(&b.shortc.wT, (size_t)b.cin * b.cout));
-                launch_cvjp_transpose(b.shortc.w, b.cout, b.cin, b.cin, b.shortc.scale, b.shortc.wT, b.cout, nullptr);
+                rx_pack_wT(b.shortc.w, b.shortc.scale, b.shortc.wT, b.cout, b.cin, 1, b.cout, nullptr);
             }
         }
         HIPCHK(hipGetLastError());

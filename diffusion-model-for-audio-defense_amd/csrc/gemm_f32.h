@@ -64,6 +64,10 @@ struct GemmF32Args {
 // Returns 0, or kGemmBadShape for an argument block no kernel serves (nothing is launched; the caller reports it).
 constexpr int kGemmBadShape = -1;
 int launch_gemm_f32(const GemmF32Args& a, hipStream_t s, float* slab = nullptr, long slab_floats = 0, long n_ref = 0);
+// what the plain fp32 path (no x3, epi 0 - 2) of this thread's last launch_gemm_f32 chose: tile height (64 / 128), the 64 x 32 narrow tile
+// with the 8-slot ring, the two-part instantiation, the split count (1: no split-K, no reduce kernel).  For the test hooks.
+struct GemmF32Choice { int bm, narrow, two, splits; };
+GemmF32Choice gemm_f32_last_choice();
 int gemm_take_bad_shapes();   // number of launches refused on this thread since the last call (reset to 0)
 int gemm_f32_configure();     // per device, from dmad_create: dynamic-LDS attribute of the 8-slot narrow-tile kernel (0 or a hipError_t)
 int gemm_x3_configure();      // per device, from dmad_create: dynamic-LDS attribute of the split-f16 kernel (0 or a hipError_t)

@@ -813,7 +813,8 @@ __global__ void gemm_f32_reduce_kernel(GemmF32Args a) {
     a.C[n * a.ldc + m] = a.relu ? relu_nan(t) : t;
 }
 
-namespace { thread_local int g_bad_shapes = 0; }
+namespace { thread_local int g_bad_shapes = 0; thread_local GemmF32Choice g_choice = {0, 0, 0, 0}; }
+GemmF32Choice gemm_f32_last_choice() { return g_choice; }
 // launches refused since the last call (and reset): the C ABI turns a non-zero count into DMAD_ERR_INVALID at the end of the entry point
 int gemm_take_bad_shapes() { const int n = g_bad_shapes; g_bad_shapes = 0; return n; }
 
@@ -883,8 +884,10 @@ int launch_gemm_f32(const GemmF32Args& a0, hipStream_t s, float* slab, long slab
     int S = 1;
     static const bool narrow_on = []() { const char* v = getenv("DMAD_F32_NARROW"); return !(v && v[0] == '0'); }();      // A/B switch
     auto launch = [&](dim3 grid) {
+        const bool narrow = !a.X2 && BM == 64 && narrow_on && (long)grid.x * grid.y * grid.z < 256 && nks >= 8;
+        g_choice = GemmF32Choice{a.X2 ? 128 : BM, narrow ? 1 : 0, a.X2 ? 1 : 0, a.splits > 1 ? a.splits : 1};
         if (a.X2) hipLaunchKernelGGL((gemm_f32_kernel<128, true>), grid, dim3(256), 3 * SLOT, s, a);
-        else if (BM == 64 && narrow_on && (long)grid.x * grid.y * grid.z < 256 && nks >= 8)       // fewer workgroups than CUs:
+        else if (narrow)                                                                           // fewer workgroups than CUs:
             hipLaunchKernelGGL((gemm_f32_kernel<64, false, 8, 1>), dim3((unsigned)((a.N + 31) / 32), grid.y, grid.z), dim3(256), 8 * SLOT, s, a);   // 64 x 32 tiles, 8-slot ring
         else if (BM == 64) hipLaunchKernelGGL((gemm_f32_kernel<64, false>), grid, dim3(256), 3 * SLOT, s, a);
         else hipLaunchKernelGGL((gemm_f32_kernel<128, false>), grid, dim3(256), 3 * SLOT, s, a);

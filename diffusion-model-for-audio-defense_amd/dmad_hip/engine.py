@@ -1022,6 +1022,166 @@ def groupnorm16_apply(x: torch.Tensor, st: torch.Tensor, gamma: torch.Tensor, be
     return y
 
 
+def _f32(t):
+    return None if t is None else t.detach().contiguous().float()
+
+
+def conv_f32(x: torch.Tensor, w: torch.Tensor, shift: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None, stride: int = 1,
+             groups: int = 1, relu: bool = False, res: Optional[torch.Tensor] = None, x2: Optional[torch.Tensor] = None,
+             slab: Optional[torch.Tensor] = None, n_ref: int = 0):
+    """dmad_conv_f32 — the exact-fp32 conv GEMM as a standalone op (test hook).  x: fp32 NHWC [B,H,H,Cx] (x2: optional second map whose
+    channels follow x's), or [B,K] rows (the plain GEMM of the Linear layers); w fp32 [groups, taps, M, K] (or [taps, M, K]); scale /
+    shift [groups*M]; res like the output; slab: optional fp32 split-K workspace, n_ref the row count the split count is derived from.
+    Returns (out, choice) with choice = dict(bm, narrow, two, splits): what the launcher chose."""
+    lib = _lib.load()
+    assert x.is_cuda and x.dtype == torch.float32 and w.is_cuda and w.dtype == torch.float32 and x.dim() in (2, 4) and w.dim() in (3, 4)
+    if w.dim() == 3:
+        w = w[None]
+    x, w = x.contiguous(), w.contiguous()
+    _, taps, M, K = w.shape
+    assert w.shape[0] == groups
+    x2c, ksplit = None, 0
+    if x.dim() == 2:
+        B, H = x.shape[0], 0
+        assert x.shape[1] == K and x2 is None
+        oshape = (B, M)
+    else:
+        B, H, W_, cx = x.shape
+        assert H == W_
+        if x2 is not None:
+            assert x2.shape[:3] == x.shape[:3] and cx + x2.shape[3] == K
+            x2c, ksplit = x2.contiguous(), cx
+        else:
+            assert cx == groups * K
+        Ho = (H - 1) // stride + 1
+        oshape = (B, Ho, Ho, groups * M)
+    out = torch.empty(oshape, device=x.device, dtype=torch.float32)
+    scale, shift, res = _f32(scale), _f32(shift), _f32(res)
+    if res is not None:
+        assert tuple(res.shape) == oshape
+    choice = (C.c_int32 * 4)()
+    check(lib.dmad_conv_f32(_ptr(x), _ptr(x2c), int(ksplit), _ptr(w), _ptr(scale), _ptr(shift), _ptr(res), B, H, M, K, taps, int(stride),
+                            int(groups), 1 if relu else 0, _ptr(slab), slab.numel() if slab is not None else 0, int(n_ref), _ptr(out), choice,
+                            _stream()))
+    return out, dict(bm=choice[0], narrow=choice[1], two=choice[2], splits=choice[3])
+
+
+def conv_f32_vjp(g_y: torch.Tensor, w: torch.Tensor, H: int, form: int = 0, stride: int = 1, groups: int = 1,
+                 scale: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None, acc: Optional[torch.Tensor] = None, ldt: int = 0):
+    """dmad_conv_f32_vjp — the data gradient of an NHWC conv (test hook; forms of include/dmad.h: 0 UNet conv, 1 UNet Upsample, 2
+    ResNeXt29).  g_y fp32 [B,Ho,Ho,groups*M] (ldt channels with a padded 1x1 image), w [groups, taps, M, K] in the forward layout, H the
+    forward conv's input resolution.  Returns (g_x, wT, gm | None, work | None): the gradient, the packed weight image as the pack kernel
+    wrote it, the masked gradient, and the dilated / pre-sum work map."""
+    lib = _lib.load()
+    assert g_y.is_cuda and g_y.dtype == torch.float32 and w.dtype == torch.float32 and g_y.dim() == 4 and w.dim() == 4
+    g_y, w = g_y.contiguous(), w.contiguous()
+    _, taps, M, K = w.shape
+    assert w.shape[0] == groups
+    B, dev = g_y.shape[0], g_y.device
+    Ho = 2 * H if form == 1 else (H - 1) // stride + 1
+    kp = ldt if (form == 2 and taps == 1 and ldt) else M
+    assert tuple(g_y.shape) == (B, Ho, Ho, groups * kp), (tuple(g_y.shape), (B, Ho, Ho, groups * kp))
+    if form == 2 and taps == 9:
+        wT = torch.full((groups, 9, K, M), float('nan'), device=dev)
+    elif form == 2:
+        wT = torch.full((K, kp), float('nan'), device=dev)
+    else:
+        wT = torch.full((taps, K, M), float('nan'), device=dev)
+    g_x = torch.empty((B, H, H, groups * K), device=dev, dtype=torch.float32)
+    gm = torch.empty_like(g_y) if mask_y is not None else None
+    work = None
+    if form == 1:
+        work = torch.empty((B, 2 * H, 2 * H, K), device=dev, dtype=torch.float32)
+    elif stride == 2:
+        work = torch.empty((B, H, H, groups * M) if taps == 9 else (B, Ho, Ho, K), device=dev, dtype=torch.float32)
+    scale, mask_y, acc = _f32(scale), _f32(mask_y), _f32(acc)
+    if acc is not None:
+        assert tuple(acc.shape) == tuple(g_x.shape)
+    if mask_y is not None:
+        assert tuple(mask_y.shape) == tuple(g_y.shape)
+    check(lib.dmad_conv_f32_vjp(_ptr(g_y), _ptr(w), _ptr(scale), _ptr(mask_y), _ptr(acc), B, int(H), M, K, taps, int(stride), int(groups),
+                                int(form), int(ldt), _ptr(wT), _ptr(gm), _ptr(work), _ptr(g_x), _stream()))
+    return g_x, wT, gm, work
+
+
+def groupnorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, silu: bool = False, ss: Optional[torch.Tensor] = None,
+                  x2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dmad_groupnorm_f32: GroupNorm32 (+ scale-shift, + SiLU) of the fp32 map x [B,HW,c1] (| x2 [B,HW,C-c1]) -> y [B,HW,C] (test hook)."""
+    lib = _lib.load()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
+    x, x2 = x.contiguous(), (None if x2 is None else x2.contiguous())
+    B, HW, c1 = x.shape
+    Cn = c1 + (x2.shape[2] if x2 is not None else 0)
+    y = torch.empty((B, HW, Cn), device=x.device, dtype=torch.float32)
+    check(lib.dmad_groupnorm_f32(_ptr(x), _ptr(x2), int(c1), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(_f32(ss)), 1 if silu else 0, B, HW, Cn,
+                                 _ptr(y), _stream()))
+    return y
+
+
+def groupnorm_bwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, gy: torch.Tensor, silu: bool = False,
+                  ss: Optional[torch.Tensor] = None, x2: Optional[torch.Tensor] = None, add: Optional[torch.Tensor] = None,
+                  add2: Optional[torch.Tensor] = None):
+    """dmad_groupnorm_bwd: the gradient of groupnorm_f32 with respect to its input -> (gx [B,HW,c1], gx2 [B,HW,C-c1] | None), add / add2
+    ([B,HW,C]) summed in (test hook)."""
+    lib = _lib.load()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
+    x, x2, gy = x.contiguous(), (None if x2 is None else x2.contiguous()), gy.contiguous()
+    B, HW, c1 = x.shape
+    Cn = c1 + (x2.shape[2] if x2 is not None else 0)
+    assert tuple(gy.shape) == (B, HW, Cn)
+    gx = torch.empty_like(x)
+    gx2 = torch.empty_like(x2) if x2 is not None else None
+    gamma, beta, ss, add, add2 = _f32(gamma), _f32(beta), _f32(ss), _f32(add), _f32(add2)
+    check(lib.dmad_groupnorm_bwd(_ptr(x), _ptr(x2), int(c1), _ptr(gamma), _ptr(beta), _ptr(ss), 1 if silu else 0, _ptr(gy), _ptr(add),
+                                 _ptr(add2), B, HW, Cn, _ptr(gx), _ptr(gx2), _stream()))
+    return gx, gx2
+
+
+def qkv_attention_f32(qkv: torch.Tensor, heads: int) -> torch.Tensor:
+    """dmad_qkv_attention_f32: qkv fp32 [B,T,heads*192] (head-major q | k | v) -> out [B,T,heads*64] (test hook)."""
+    lib = _lib.load()
+    assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3 and qkv.shape[2] == heads * 192
+    qkv = qkv.contiguous()
+    B, T, _ = qkv.shape
+    out = torch.empty((B, T, heads * 64), device=qkv.device, dtype=torch.float32)
+    check(lib.dmad_qkv_attention_f32(_ptr(qkv), B, T, int(heads), _ptr(out), _stream()))
+    return out
+
+
+def qkv_attention_bwd(qkv: torch.Tensor, go: torch.Tensor, heads: int) -> torch.Tensor:
+    """dmad_qkv_attention_bwd: the gradient of qkv_attention_f32 -> gqkv [B,T,heads*192] (dq | dk | dv per head) (test hook)."""
+    lib = _lib.load()
+    assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3 and qkv.shape[2] == heads * 192
+    qkv, go = qkv.contiguous(), go.contiguous()
+    B, T, _ = qkv.shape
+    assert tuple(go.shape) == (B, T, heads * 64) and go.dtype == torch.float32
+    gqkv = torch.empty_like(qkv)
+    check(lib.dmad_qkv_attention_bwd(_ptr(qkv), _ptr(go), B, T, int(heads), _ptr(gqkv), _stream()))
+    return gqkv
+
+
+def rx_head_bwd(g_logits: torch.Tensor, W: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """dmad_rx_head_bwd: g_logits [B,ncls], W [ncls,C], y [B,HW,C] -> gz [B,HW,C] (FC, average pool and the last ReLU backward) (test hook)."""
+    lib = _lib.load()
+    g_logits, W, y = _f32(g_logits), _f32(W), _f32(y)
+    B, HW, Cn = y.shape
+    assert tuple(g_logits.shape) == (B, W.shape[0]) and W.shape[1] == Cn and y.is_cuda
+    gz = torch.empty_like(y)
+    check(lib.dmad_rx_head_bwd(_ptr(g_logits), _ptr(W), _ptr(y), B, int(W.shape[0]), HW, Cn, _ptr(gz), _stream()))
+    return gz
+
+
+def rx_conv1_bwd(g: torch.Tensor, a: torch.Tensor, w: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """dmad_rx_conv1_bwd: g, a [B,32,32,64], w [64,9], scale [64] -> gspec [B,32,32] (conv1's ReLU, BN and 1 <- 64 conv backward) (test hook)."""
+    lib = _lib.load()
+    g, a, w, scale = _f32(g), _f32(a), _f32(w), _f32(scale)
+    B = g.shape[0]
+    assert tuple(g.shape) == (B, 32, 32, 64) and tuple(a.shape) == (B, 32, 32, 64) and tuple(w.shape) == (64, 9) and tuple(scale.shape) == (64,)
+    gspec = torch.empty((B, 32, 32), device=g.device, dtype=torch.float32)
+    check(lib.dmad_rx_conv1_bwd(_ptr(g), _ptr(a), _ptr(w), _ptr(scale), B, _ptr(gspec), _stream()))
+    return gspec
+
+
 def bind_classifier(state_dict, loader_name: str, engine: Optional[Engine] = None) -> Engine:
     """Engine that holds exactly `state_dict` as its classifier: `engine` (refused if it holds another one), else the
     shared engine, else — when the shared engine already serves a different classifier — an engine of this module's own

@@ -511,6 +511,54 @@ int dmad_conv_x3(const float* x, const float* x2, int32_t ksplit, const float* w
                  int32_t M, int32_t K, int32_t taps, int32_t stride, int32_t groups, int32_t relu, int32_t out_split, int32_t res_split, float* out,
                  dmad_stream s);
 
+/* Test hooks of the exact-fp32 tier, standalone (no engine state is read): the ops every vector-Jacobian product is built from, one at a
+ * time.  Each calls the launcher and the argument builders the engine paths call; a shape no kernel serves is DMAD_ERR_INVALID.
+ *
+ * dmad_conv_f32: NHWC convolution or plain GEMM on the fp32 matrix-core path of csrc/gemm_f32.hip (not the split-f16 one):
+ *   out[n][g*M + m] = relu?( scale[g*M + m] * sum_tap sum_k w[g][tap][m][k] x[pixel(n, tap)][g*K + k] + shift[g*M + m] + res[n][g*M + m] )
+ * x [B][H][H][groups * K] (or, dense only, x | x2 with ksplit channels in x; M > 64), w [groups][taps][M][K] (taps 9 = 3x3 with zero padding 1,
+ * or 1), scale / shift [groups * M] or NULL, res [N][groups * M] or NULL, N = B * Ho * Ho, Ho = (H - 1) / stride + 1; M and K per group,
+ * K % 16 == 0 (ksplit % 16 == 0).  H = 0: the row form the Linear layers and the mel DFT use — x [B][K], one tap, out [B][M].  slab /
+ * slab_floats / n_ref: optional split-K workspace and the reference row count the split count is derived from (0: N), as the engine
+ * passes them.  choice (optional, 4 ints): what the launcher chose — tile height (64 / 128), 1 for the 64 x 32 narrow tile with the
+ * 8-slot ring, 1 for the two-part instantiation, the split count (> 1: partial sums through the slab and the reduce kernel).
+ *
+ * dmad_conv_f32_vjp: the data gradient g_y -> g_x of such a conv (w in the forward layout above, M / K / H / stride the FORWARD conv's)
+ * through the engine's own sequence: the weight image packed into wT, the optional zero-dilation, the GEMM.
+ *   form 0  the UNet's convs: wT [taps][K][M] with flipped taps; stride 2 dilates g_y into work [B][H][H][M]; acc (optional, g_x's shape)
+ *           is added in the GEMM's epilogue.
+ *   form 1  the UNet's Upsample (interpolate x2 + 3x3 conv at 2H; H: the half resolution): g_y [B][2H][2H][M], the conv's gradient at 2H
+ *           in work [B][2H][2H][K], then g_x [B][H][H][K] = its 2x2 sums (+ acc).
+ *   form 2  ResNeXt29's convs with the eval-mode BN scale [groups * M] folded into the image: a dense 1x1 (wT [K][ldt], ldt = 0 -> M, or a
+ *           multiple of 16 >= M whose extra rows are zero; g_y then has ldt channels per pixel) or the 8-group 3x3 with M = K (wT
+ *           [g][8 - tap][k][m]).  mask_y (optional, g_y's shape): g_y is first masked by mask_y > 0 into gm (the ReLU backward).  Stride 2:
+ *           the 3x3 runs on the zero-dilated gradient (work [B][H][H][8 * M]); the 1x1 shortcut runs at Ho (work [B][Ho][Ho][K]) and is
+ *           scattered into the even pixels of g_x.  acc: the GEMM's residual (not with the stride-2 1x1).
+ * M % 16 == 0, K % 4 == 0; H even with stride 2.  wT, gm and work are left as the kernels wrote them (the tests read them). */
+int dmad_conv_f32(const float* x, const float* x2, int32_t ksplit, const float* w, const float* scale, const float* shift, const float* res,
+                  int32_t B, int32_t H, int32_t M, int32_t K, int32_t taps, int32_t stride, int32_t groups, int32_t relu, float* slab,
+                  int64_t slab_floats, int64_t n_ref, float* out, int32_t* choice, dmad_stream s);
+int dmad_conv_f32_vjp(const float* g_y, const float* w, const float* scale, const float* mask_y, const float* acc, int32_t B, int32_t H,
+                      int32_t M, int32_t K, int32_t taps, int32_t stride, int32_t groups, int32_t form, int32_t ldt, float* wT, float* gm,
+                      float* work, float* g_x, dmad_stream s);
+/* GroupNorm32 in fp32 and its backward (csrc/unet_ops.hip, csrc/unet_vjp.hip):  y = SiLU?(GN(cat(x, x2)) * gamma + beta [* (1 + ss[c]) +
+ * ss[C + c]]) over [B][HW][C], x holding c1 channels and x2 the rest (x2 NULL: one map).  Forward: C % 128 == 0, C <= 512, c1 % 4 == 0, maps
+ * up to 32 x 32 x 384 (16 float4s per thread).  Backward: C % 32 == 0, any 0 < c1 < C; gx / gx2 = the gradient's two parts (+ add + add2, [B][HW][C]). */
+int dmad_groupnorm_f32(const float* x, const float* x2, int32_t c1, const float* gamma, const float* beta, const float* ss, int32_t silu,
+                       int32_t B, int32_t HW, int32_t C, float* y, dmad_stream s);
+int dmad_groupnorm_bwd(const float* x, const float* x2, int32_t c1, const float* gamma, const float* beta, const float* ss, int32_t silu,
+                       const float* gy, const float* add, const float* add2, int32_t B, int32_t HW, int32_t C, float* gx, float* gx2,
+                       dmad_stream s);
+/* QKVAttention in fp32 and its backward: qkv [B][T][heads * 192] with the head-major split (head h: q, k, v = 64 channels each from h * 192),
+ * out / go [B][T][heads * 64], gqkv like qkv.  T = 16, 64 or 256; any other T is DMAD_ERR_INVALID. */
+int dmad_qkv_attention_f32(const float* qkv, int32_t B, int32_t T, int32_t heads, float* out, dmad_stream s);
+int dmad_qkv_attention_bwd(const float* qkv, const float* go, int32_t B, int32_t T, int32_t heads, float* gqkv, dmad_stream s);
+/* The two ends of ResNeXt29's backward walk.  dmad_rx_head_bwd: gz [B][HW][C] = (y > 0) * (W^T g_logits)[c] / HW — FC [ncls][C], average
+ * pool and the last ReLU.  dmad_rx_conv1_bwd: gspec [B][32][32] = the 1 <- 64 3x3 conv (w [64][9], BN scale [64]) of (a > 0) * g, both
+ * [B][32][32][64]. */
+int dmad_rx_head_bwd(const float* g_logits, const float* W, const float* y, int32_t B, int32_t ncls, int32_t HW, int32_t C, float* gz, dmad_stream s);
+int dmad_rx_conv1_bwd(const float* g, const float* a, const float* w, const float* scale, int32_t B, float* gspec, dmad_stream s);
+
 /* Bytes of device memory held by the engine. */
 int64_t dmad_device_bytes(const dmad_engine* e);
 

@@ -155,6 +155,31 @@ def test_mel_vjp_against_f64(eng, orc):
     got = eng.mel_db_vjp(x.cuda(), g.cuda())
     err = relmax(got.cpu(), ref[:, 0])
     assert err <= MEL_TOL, err
+    # clips as fix_length leaves them: the second half exactly zero, and an all-zero clip.  Frame fr reads samples [512 fr - 1024,
+    # 512 fr + 1024) (reflect padding mirrors zeros into zeros), so frames >= 18 are silent, their mel power is exactly 0 and the
+    # clamp(min=1e-10) branch of the dB stage decides the gradient: no gradient, not 10 / (ln 10 * 0).  Samples from 10240 on are read
+    # by silent frames only.  The cotangent covers the bins above -40 dB (as the finite-difference test) plus the silent ones, so that
+    # max |g_x| is not set by a near-silent bin of the two frames that straddle the edge.
+    # A third clip keeps a tail of 1e-9 instead of zeros: mel powers of ~1e-15, above 0 and below the clamp, where the rule is
+    # "M >= 1e-10 passes the gradient" and not "M > 0" (which would hand back g * 10 / (ln 10 * 1e-15)).
+    z = clips([0, 1, 2]).unsqueeze(1)
+    z[0, :, 8000:] = 0.0
+    z[1] = 0.0
+    z[2, :, 8000:] = 1e-9 * torch.randn(1, 8000, generator=torch.Generator().manual_seed(15))
+    spec = eng.mel_db(z.cuda()).cpu()
+    assert bool((spec[0, :, :, 18:] < -99.9).all()) and bool((spec[1] < -99.9).all())            # clamp(min=1e-10): -100 dB
+    assert bool((spec[2, :, :, 18:] < -99.9).all()) and bool((eng.mel_power(z[2:].cuda()) > 0).all())
+    gz = torch.randn(3, 1, 32, 32, generator=torch.Generator().manual_seed(14)) * ((spec > -40.0) | (spec < -99.9)).float()
+    assert float(gz[:, :, :, 18:].abs().min()) > 0                       # the silent bins do carry a cotangent
+    z64 = z.double().requires_grad_(True)
+    (refz,) = torch.autograd.grad((mel_f64(orc, z64) * gz.double()).sum(), z64)
+    gotz = eng.mel_db_vjp(z.cuda(), gz.cuda()).cpu()
+    assert bool(torch.isfinite(gotz).all())
+    assert bool((gotz[0].reshape(-1)[10240:] == 0).all()) and bool((gotz[1] == 0).all()) and bool((gotz[2].reshape(-1)[10240:] == 0).all())
+    assert bool((refz[0].reshape(-1)[10240:] == 0).all()) and bool((refz[1] == 0).all()) and bool((refz[2].reshape(-1)[10240:] == 0).all())
+    for j in (0, 2):
+        errz = relmax(gotz[j].reshape(-1), refz[j].reshape(-1))
+        assert errz <= MEL_TOL, (j, errz)
 
 
 def test_forward_outputs_bitwise(eng):
