@@ -2071,6 +2071,59 @@ int dmad_ddpm_purify(dmad_engine* e, const float* x0, int32_t t_star, float c_a,
     return 0;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The reverse VP-SDE chain of dmad_vpsde_purify and dmad_spec_vpsde_purify on rows of `width` floats, in passes of up to max_batch
+// rows: the diffusion draw (Philox stream stream_diffuse), then per Euler step n eps_fn(x, k, bb) -- the domain's eps-network into
+// `eps` -- and the update (stream stream_step0 + n).  z / traj hold n_steps + 1 slots of B rows: slot 0 the diffusion, n + 1 step n.
+template <class Eps>
+int vpsde_chain(dmad_engine* e, int width, uint32_t stream_diffuse, uint32_t stream_step0, const float* eps, Eps eps_fn, const float* x0,
+                int B, int n_steps, float c_a, float c_b, const int32_t* k, const float* h, const float* hb, const float* q, const float* gs,
+                const float* z, uint64_t seed, uint64_t sample0, float* out, float* traj, hipStream_t st) {
+    const size_t L = width, slot = (size_t)B * L;
+    for (int b0 = 0; b0 < B; b0 += e->maxB) {                  // a pass: the whole chain for up to max_batch rows
+        const int bb = B - b0 < e->maxB ? B - b0 : e->maxB;
+        float* x = out + b0 * L;
+        const uint64_t s0 = sample0 + (uint64_t)b0;
+        launch_vpsde_step(x0 + b0 * L, nullptr, z ? z + b0 * L : nullptr, c_a, c_b, 0.f, 0.f, seed, s0, stream_diffuse, x,
+                          traj ? traj + b0 * L : nullptr, bb, width, st);
+        for (int n = 0; n < n_steps; ++n) {
+            CHK(eps_fn(x, k[n], bb));
+            launch_vpsde_step(x, eps, z ? z + (n + 1) * slot + b0 * L : nullptr, hb[n], q[n], h[n], gs[n], seed, s0,
+                              stream_step0 + (uint32_t)n, x, traj ? traj + (n + 1) * slot + b0 * L : nullptr, bb, width, st);
+        }
+    }
+    LASTCHK();
+    return 0;
+}
+
+// The reverse walk over the trajectory of vpsde_chain, in passes of the domain's VJP reservation (per_pass rows; g2 is its two
+// gradient buffers): vjp_fn(x, k, bb, g, dst, alpha, gamma) is one affine VJP pass of the eps-network, dst = alpha g - gamma J^T g.
+template <class Vjp>
+int vpsde_chain_vjp(int width, int per_pass, float* g2, Vjp vjp_fn, const float* traj, int B, int n_steps, float c_a, const int32_t* k,
+                    const float* h, const float* hb, const float* q, const float* g_out, float* g_x0) {
+    const size_t L = width, slot = (size_t)B * L;
+    for (int b0 = 0; b0 < B; b0 += per_pass) {                 // a pass of the reservation: the whole reverse walk
+        const int bb = B - b0 < per_pass ? B - b0 : per_pass;
+        const float* g = g_out + b0 * L;
+        for (int n = n_steps - 1; n >= 0; --n) {
+            // g <- (1 + h hb) g - (h q) J_n^T g, J_n = d eps / d x at traj[n]; the last step (n = 0) folds in d x_0 / d x0 = c_a
+            double alpha = 1.0 + (double)h[n] * (double)hb[n], gamma = (double)h[n] * (double)q[n];
+            if (n == 0) { alpha *= c_a; gamma *= c_a; }
+            float* dst = n == 0 ? g_x0 + b0 * L : g2 + (size_t)((n_steps - 1 - n) & 1) * per_pass * L;
+            CHK(vjp_fn(traj + n * slot + b0 * L, k[n], bb, g, dst, (float)alpha, (float)gamma));
+            g = dst;
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
 int dmad_vpsde_purify(dmad_engine* e, const float* x0, int32_t B, int32_t n_steps, float c_a, float c_b, const int32_t* k, const float* h,
                       const float* hb, const float* q, const float* gs, const float* z, uint64_t seed, uint64_t sample0, int32_t path, float* out,
                       float* traj, dmad_stream s) {
@@ -2083,22 +2136,10 @@ int dmad_vpsde_purify(dmad_engine* e, const float* x0, int32_t B, int32_t n_step
     for (int n = 0; n < n_steps; ++n)
         if (k[n] < 0) return fail(DMAD_ERR_INVALID, "step %d: k = %d < 0", n, k[n]);
     const int wp = path == 1 ? PATH_FP32 : wave_path(e);
-    const size_t L = e->L, slot = (size_t)B * L;
     const hipStream_t st = (hipStream_t)s;
-    for (int b0 = 0; b0 < B; b0 += e->maxB) {                  // a pass: the whole chain for up to max_batch clips
-        const int bb = B - b0 < e->maxB ? B - b0 : e->maxB;
-        float* x = out + b0 * L;
-        const uint64_t s0 = sample0 + (uint64_t)b0;
-        launch_vpsde_step(x0 + b0 * L, nullptr, z ? z + b0 * L : nullptr, c_a, c_b, 0.f, 0.f, seed, s0, kVpsdeStreamDiffuse, x,
-                          traj ? traj + b0 * L : nullptr, bb, e->L, st);
-        for (int n = 0; n < n_steps; ++n) {
-            CHK(wavenet_eps(e, x, k[n], bb, e->eps, st, wp));
-            launch_vpsde_step(x, e->eps, z ? z + (n + 1) * slot + b0 * L : nullptr, hb[n], q[n], h[n], gs[n], seed, s0,
-                              kVpsdeStreamStep0 + (uint32_t)n, x, traj ? traj + (n + 1) * slot + b0 * L : nullptr, bb, e->L, st);
-        }
-    }
-    LASTCHK();
-    return 0;
+    auto eps = [=](const float* x, int kn, int bb) { return wavenet_eps(e, x, kn, bb, e->eps, st, wp); };
+    return vpsde_chain(e, e->L, kVpsdeStreamDiffuse, kVpsdeStreamStep0, e->eps, eps, x0, B, n_steps, c_a, c_b, k, h, hb, q, gs, z, seed,
+                       sample0, out, traj, st);
 }
 
 int dmad_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int32_t n_steps, float c_a, const int32_t* k, const float* h,
@@ -2112,21 +2153,10 @@ int dmad_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int32_t 
     if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
     for (int n = 0; n < n_steps; ++n)
         if (k[n] < 0) return fail(DMAD_ERR_INVALID, "step %d: k = %d < 0", n, k[n]);
-    const size_t L = e->L, slot = (size_t)B * L;
-    const hipStream_t st = (hipStream_t)s;
-    for (int b0 = 0; b0 < B; b0 += e->vjpB) {                  // a pass of the reservation: the whole reverse walk
-        const int bb = B - b0 < e->vjpB ? B - b0 : e->vjpB;
-        const float* g = g_out + b0 * L;
-        for (int n = n_steps - 1; n >= 0; --n) {
-            // g <- (1 + h hb) g - (h q) J_n^T g, J_n = d eps / d x at traj[n]; the last step (n = 0) folds in d x_0 / d x0 = c_a
-            double alpha = 1.0 + (double)h[n] * (double)hb[n], gamma = (double)h[n] * (double)q[n];
-            if (n == 0) { alpha *= c_a; gamma *= c_a; }
-            float* dst = n == 0 ? g_x0 + b0 * L : e->vjp_g2 + (size_t)((n_steps - 1 - n) & 1) * e->vjpB * L;
-            CHK(wavenet_vjp_pass(e, traj + n * slot + b0 * L, k[n], bb, g, dst, e->eps, st, true, (float)alpha, (float)gamma));
-            g = dst;
-        }
-    }
-    return 0;
+    auto vjp = [=](const float* x, int kn, int bb, const float* g, float* dst, float alpha, float gamma) {
+        return wavenet_vjp_pass(e, x, kn, bb, g, dst, e->eps, (hipStream_t)s, true, alpha, gamma);
+    };
+    return vpsde_chain_vjp(e->L, e->vjpB, e->vjp_g2, vjp, traj, B, n_steps, c_a, k, h, hb, q, g_out, g_x0);
 }
 
 int dmad_spec_vpsde_purify(dmad_engine* e, const float* x0, int32_t B, int32_t n_steps, float c_a, float c_b, const int32_t* k, const float* h,
@@ -2141,22 +2171,10 @@ int dmad_spec_vpsde_purify(dmad_engine* e, const float* x0, int32_t B, int32_t n
     for (int n = 0; n < n_steps; ++n)
         if (k[n] < 0 || k[n] > kUnSsSteps) return fail(DMAD_ERR_INVALID, "step %d: k = %d outside [0, %d]", n, k[n], kUnSsSteps);
     const int tier = path == 1 ? 0 : -1;
-    const size_t L = 1024, slot = (size_t)B * L;
     const hipStream_t st = (hipStream_t)s;
-    for (int b0 = 0; b0 < B; b0 += e->maxB) {                  // a pass: the whole chain for up to max_batch spectrograms
-        const int bb = B - b0 < e->maxB ? B - b0 : e->maxB;
-        float* x = out + b0 * L;
-        const uint64_t s0 = sample0 + (uint64_t)b0;
-        launch_vpsde_step(x0 + b0 * L, nullptr, z ? z + b0 * L : nullptr, c_a, c_b, 0.f, 0.f, seed, s0, kSpecVpsdeStreamDiffuse, x,
-                          traj ? traj + b0 * L : nullptr, bb, (int)L, st);
-        for (int n = 0; n < n_steps; ++n) {
-            CHK(unet_eps(e, x, k[n], bb, e->un_eps, st, tier));
-            launch_vpsde_step(x, e->un_eps, z ? z + (n + 1) * slot + b0 * L : nullptr, hb[n], q[n], h[n], gs[n], seed, s0,
-                              kSpecVpsdeStreamStep0 + (uint32_t)n, x, traj ? traj + (n + 1) * slot + b0 * L : nullptr, bb, (int)L, st);
-        }
-    }
-    LASTCHK();
-    return 0;
+    auto eps = [=](const float* x, int kn, int bb) { return unet_eps(e, x, kn, bb, e->un_eps, st, tier); };
+    return vpsde_chain(e, 1024, kSpecVpsdeStreamDiffuse, kSpecVpsdeStreamStep0, e->un_eps, eps, x0, B, n_steps, c_a, c_b, k, h, hb, q, gs, z,
+                       seed, sample0, out, traj, st);
 }
 
 int dmad_spec_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int32_t n_steps, float c_a, const int32_t* k, const float* h,
@@ -2170,21 +2188,10 @@ int dmad_spec_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int
     if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
     for (int n = 0; n < n_steps; ++n)
         if (k[n] < 0 || k[n] > kUnSsSteps) return fail(DMAD_ERR_INVALID, "step %d: k = %d outside [0, %d]", n, k[n], kUnSsSteps);
-    const size_t L = 1024, slot = (size_t)B * L;
-    const hipStream_t st = (hipStream_t)s;
-    for (int b0 = 0; b0 < B; b0 += e->unvjpB) {                // a pass of the reservation: the whole reverse walk
-        const int bb = B - b0 < e->unvjpB ? B - b0 : e->unvjpB;
-        const float* g = g_out + b0 * L;
-        for (int n = n_steps - 1; n >= 0; --n) {
-            // g <- (1 + h hb) g - (h q) J_n^T g, J_n = d eps / d x at traj[n]; the last step (n = 0) folds in d x_0 / d x0 = c_a
-            double alpha = 1.0 + (double)h[n] * (double)hb[n], gamma = (double)h[n] * (double)q[n];
-            if (n == 0) { alpha *= c_a; gamma *= c_a; }
-            float* dst = n == 0 ? g_x0 + b0 * L : e->unvjp_g2 + (size_t)((n_steps - 1 - n) & 1) * e->unvjpB * L;
-            CHK(unet_vjp_pass(e, traj + n * slot + b0 * L, k[n], bb, g, dst, e->un_eps, st, true, (float)alpha, (float)gamma));
-            g = dst;
-        }
-    }
-    return 0;
+    auto vjp = [=](const float* x, int kn, int bb, const float* g, float* dst, float alpha, float gamma) {
+        return unet_vjp_pass(e, x, kn, bb, g, dst, e->un_eps, (hipStream_t)s, true, alpha, gamma);
+    };
+    return vpsde_chain_vjp(1024, e->unvjpB, e->unvjp_g2, vjp, traj, B, n_steps, c_a, k, h, hb, q, g_out, g_x0);
 }
 
 int dmad_mel_db(dmad_engine* e, const float* x, int32_t B, float* spec, dmad_stream s) {

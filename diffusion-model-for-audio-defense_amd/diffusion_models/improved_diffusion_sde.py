@@ -36,8 +36,8 @@ import torch
 
 from dmad_hip import engine as _eng
 from dmad_hip._lib import DmadError
-from dmad_hip.autograd import has_unet_vjp, needs_grad
-from .diffwave_sde import VPSDESchedule, _ChainNone, _extract_into_tensor  # noqa: F401  (_extract_into_tensor: the reference's export)
+from dmad_hip.autograd import has_unet_vjp
+from ._rev_vpsde import ChainPurifier, RevVPSDEBase, VPSDESchedule, _extract_into_tensor, euler_schedule
 from .improved_diffusion_ddpm import create_improved_diffusion
 from .Improved_Diffusion_Unconditional.improved_diffusion.sc09_spectrogram_dataset import melspec_inv_standardize, melspec_standardize
 
@@ -59,56 +59,25 @@ def spec_vpsde_schedule(t: int, t_diffuse=None, beta_min=0.1, beta_max=20, N=100
             raise ValueError('%s = %d outside [1, %d]' % (name, v, N))
     a = (1 - betas).cumprod(dim=0)
     c_a, c_b = float(a[td - 1].sqrt()), float((1.0 - a[td - 1]).sqrt())
-    ts = torch.linspace(1 - t * 1. / 1000, 1 - 1e-5, 2)
-    curr, end = ts[0], ts[-1]
-    k, h, hb, q, gs = [], [], [], [], []
-    while curr < end:                                   # torchsde's fixed-step loop
-        nxt = min(curr + dt, end)
-        tt = 1 - curr.reshape(1)                        # RevVPSDE.f / g evaluate at 1 - t, the start of the step
-        kk = int((tt.float() * N).long()[0])            # _scale_timesteps
+
+    def coeffs(tt, kk, step):
         if not 0 <= kk <= N:
             raise ValueError('step index %d outside [0, %d] at t = %d' % (kk, N, t))
         beta_t = beta_min + tt * (beta_max - beta_min)                                      # vpsde_fn
         diffusion = torch.sqrt(beta_t)
         # 1 - alphas_cumprod_cont(tt) as -expm1: 1 - exp(..) loses up to 4 digits in float32 at small tt (1.2e-4 of q at t = 1)
         one_m_abar = -torch.expm1(-0.5 * (beta_max - beta_min) * tt ** 2 - beta_min * tt)
-        step = nxt - curr
-        k.append(kk)
-        h.append(float(step))
-        hb.append(float((0.5 * beta_t)[0]))
-        q.append(float((diffusion ** 2 / torch.sqrt(one_m_abar))[0]))
-        gs.append(float((diffusion * torch.sqrt(step))[0]))
-        curr = nxt
-    f32 = lambda v: np.asarray(v, dtype=np.float32)     # noqa: E731
-    return VPSDESchedule(np.asarray(k, dtype=np.int32), f32(h), f32(hb), f32(q), f32(gs), c_a, c_b)
+        return 0.5 * beta_t, diffusion ** 2 / torch.sqrt(one_m_abar), diffusion * torch.sqrt(step)
+    return VPSDESchedule(*euler_schedule(1 - t * 1. / 1000, 1 - 1e-5, dt, N, coeffs), c_a, c_b)
 
 
-class RevVPSDE(torch.nn.Module):
+class RevVPSDE(RevVPSDEBase):
     """The reverse VP-SDE of the reference (drift -f(x, 1 - t), diffusion g(1 - t)) on [B, 1024] tensors, the score from the UNet.
     RevImprovedDiffusion does not integrate it op by op: its chain runs on the engine (spec_vpsde_schedule)."""
 
     def __init__(self, model, score_type='guided_diffusion', beta_min=0.1, beta_max=20, N=1000, img_shape=(1, 32, 32), model_kwargs=None):
-        super().__init__()
-        self.model = model
-        self.score_type = score_type
-        self.model_kwargs = model_kwargs
+        super().__init__(model, score_type, beta_min, beta_max, N, model_kwargs)
         self.img_shape = img_shape
-        self.beta_0 = beta_min
-        self.beta_1 = beta_max
-        self.N = N
-        self.discrete_betas = torch.linspace(beta_min / N, beta_max / N, N)
-        self.alphas = 1. - self.discrete_betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        self.sqrt_alphas_cumprod = torch.sqrt(self.alphas_cumprod)
-        self.sqrt_1m_alphas_cumprod = torch.sqrt(1. - self.alphas_cumprod)
-        self.alphas_cumprod_cont = lambda t: torch.exp(-0.5 * (self.beta_1 - self.beta_0) * t ** 2 - self.beta_0 * t)
-        self.sqrt_1m_alphas_cumprod_neg_recip_cont = lambda t: -1. / torch.sqrt(1. - self.alphas_cumprod_cont(t))
-        self.noise_type = "diagonal"
-        self.sde_type = "ito"
-
-    def _scale_timesteps(self, t):
-        assert torch.all(t <= 1) and torch.all(t >= 0), f't has to be in [0, 1], but get {t} with shape {t.shape}'
-        return (t.float() * self.N).long()
 
     def vpsde_fn(self, t, x):
         beta_t = self.beta_0 + t * (self.beta_1 - self.beta_0)
@@ -127,47 +96,12 @@ class RevVPSDE(torch.nn.Module):
         score = _extract_into_tensor(self.sqrt_1m_alphas_cumprod_neg_recip_cont, t, x.shape) * eps.view(x.shape[0], -1)
         return drift - diffusion[:, None] ** 2 * score
 
-    def f(self, t, x):
-        """The drift -f(x, 1 - t) of the time-reversed SDE (t' = 1 - t), on [B, 1024]."""
-        drift = self.rvpsde_fn(1 - t.expand(x.shape[0]), x, return_type='drift')
-        assert drift.shape == x.shape
-        return -drift
 
-    def g(self, t, x):
-        """The diffusion g(1 - t) = sqrt(beta(1 - t)), broadcast to [B, 1024]."""
-        diffusion = self.rvpsde_fn(1 - t.expand(x.shape[0]), x, return_type='diffusion')
-        assert diffusion.shape == (x.shape[0],)
-        return diffusion[:, None].expand(x.shape)
-
-
-class _ChainHIP(torch.autograd.Function):
-    """score_grad='hip' with a gradient: the exact-fp32 chain, its trajectory kept; backward = dmad_spec_vpsde_purify_vjp."""
-
-    @staticmethod
-    def forward(ctx, x0, den, sch, sample0):
-        out, traj = den._run(x0, sch, sample0, path=1, want_traj=True)
-        ctx.engine, ctx.sch = den.engine, sch
-        ctx.save_for_backward(traj)
-        return out.view(x0.shape)
-
-    @staticmethod
-    def backward(ctx, g_out):
-        if torch.is_grad_enabled():
-            raise DmadError("the HIP VP-SDE gradient is first-order only: create_graph=True (double backward) is not supported; "
-                            "use score_grad='torch' for higher derivatives")
-        traj, = ctx.saved_tensors
-        eng, sch = ctx.engine, ctx.sch
-        B = g_out.shape[0]
-        if getattr(eng, 'unet_vjp_batch', 0) < min(B, eng.max_batch):
-            eng.reserve_unet_vjp(min(B, eng.max_batch))
-        g = eng.spec_vpsde_purify_vjp(traj, sch.c_a, sch.k, sch.h, sch.hb, sch.q, g_out.reshape(B, 32, 32).contiguous())
-        return g.view(g_out.shape).to(g_out.dtype), None, None, None
-
-
-class RevImprovedDiffusion(torch.nn.Module):
+class RevImprovedDiffusion(ChainPurifier, torch.nn.Module):
     """The reference's RevImprovedDiffusion.  Reads args.ddpm_path, t, score_type, sample_step, rand_t, t_delta and use_bm.  Keywords
     beyond the reference's: state_dict / engine (passed to create_improved_diffusion; synthetic weights, an explicit engine),
     score_grad ('hip' | 'torch' | 'none', see the module docstring), seed (Philox key)."""
+    SCORE_GRADS = SCORE_GRADS
 
     def __init__(self, args, config=None, device=None, score_grad='hip', seed=0, state_dict=None, engine=None):
         super().__init__()
@@ -190,20 +124,6 @@ class RevImprovedDiffusion(torch.nn.Module):
             raise DmadError("score_grad='hip' runs the chain on the exact-fp32 UNet tier, which this engine (precision %s) does not hold: "
                             "use an FP32 or EXACT engine, or score_grad='none'" % (self.engine.precision,))
 
-    @property
-    def score_grad(self) -> str:
-        return self._score_grad
-
-    @score_grad.setter
-    def score_grad(self, value: str):
-        if value not in SCORE_GRADS:
-            raise ValueError('score_grad must be one of %s, not %r' % (SCORE_GRADS, value))
-        self._score_grad = value
-
-    @property
-    def engine(self) -> "_eng.Engine":
-        return self.model.engine
-
     def schedule(self, t_diffuse=None) -> VPSDESchedule:
         """The Euler steps of one round at args.t (the initial diffusion at t_diffuse, default args.t)."""
         v = self.rev_vpsde
@@ -213,6 +133,13 @@ class RevImprovedDiffusion(torch.nn.Module):
         """One chain on the engine, no gradient: [B, 1, 32, 32] standardised -> [B, 32, 32] (and the trajectory)."""
         return self.engine.spec_vpsde_purify(x0, sch.c_a, sch.c_b, sch.k, sch.h, sch.hb, sch.q, sch.gs, seed=self.seed, sample0=sample0,
                                              path=path, want_traj=want_traj)
+
+    def _run_vjp(self, traj, sch, g_out):
+        """dmad_spec_vpsde_purify_vjp over the trajectory of _run(.., path=1, want_traj=True); the workspace is reserved on first use."""
+        eng, B = self.engine, g_out.shape[0]
+        if eng.unet_vjp_batch < min(B, eng.max_batch):
+            eng.reserve_unet_vjp(min(B, eng.max_batch))
+        return eng.spec_vpsde_purify_vjp(traj, sch.c_a, sch.k, sch.h, sch.hb, sch.q, g_out.reshape(B, 32, 32).contiguous())
 
     def _noise(self, sample0, stream, B):
         return self.engine.philox_normal(self.seed, sample0, stream, B)[:, :1024].reshape(B, 1, 32, 32)
@@ -227,22 +154,6 @@ class RevImprovedDiffusion(torch.nn.Module):
             x = x + float(sch.gs[n]) * self._noise(sample0, SPEC_VPSDE_STREAM_STEP0 + n, B)
         return x
 
-    def _chain(self, x0, sch):
-        sample0 = self._draws
-        self._draws += x0.shape[0]
-        grad = needs_grad(x0)
-        if self._score_grad == 'torch' and grad:
-            return self._run_torch(x0, sch, sample0)
-        if self._score_grad == 'hip':
-            if grad:
-                return _ChainHIP.apply(x0, self, sch, sample0)
-            with torch.no_grad():                       # the launches of _ChainHIP's forward: the same bits, no trajectory kept
-                return self._run(x0, sch, sample0, path=1).view(x0.shape)
-        if grad:
-            return _ChainNone.apply(x0, self, sch, sample0)
-        with torch.no_grad():
-            return self._run(x0, sch, sample0, path=0).view(x0.shape)
-
     def image_editing_sample(self, img):
         """Mel-dB spectrograms [B, 1, 32, 32]: standardise, then sample_step rounds of (diffuse to t, reverse VP-SDE chain, map back),
         each round's output the next one's input, the rounds concatenated on dim 0."""
@@ -251,14 +162,7 @@ class RevImprovedDiffusion(torch.nn.Module):
         if self.rev_vpsde.score_type != 'guided_diffusion':     # the reference raises when sdeint first evaluates the drift
             raise NotImplementedError(f'Unknown score type in RevVPSDE: {self.rev_vpsde.score_type}!')
         x0 = melspec_standardize(img.to(self.device).float())
-        xs = []
-        for _ in range(self.args.sample_step):
-            total_noise_levels = self.args.t
-            if self.args.rand_t:
-                total_noise_levels = self.args.t + np.random.randint(-self.args.t_delta, self.args.t_delta)
-            x0 = melspec_inv_standardize(self._chain(x0, self.schedule(total_noise_levels)))
-            xs.append(x0)
-        return torch.cat(xs, dim=0)
+        return self._rounds(x0, post=melspec_inv_standardize)
 
     def forward(self, x):
         return self.image_editing_sample(x)

@@ -149,7 +149,7 @@ class WaveNetEpsHIP(torch.autograd.Function):
                             "use grad_backend='torch' for higher derivatives")
         audio, = ctx.saved_tensors
         eng, B = ctx.engine, audio.shape[0]
-        if getattr(eng, 'vjp_batch', 0) < B:
+        if eng.vjp_batch < B:
             eng.reserve_vjp(B)
         g_x = eng.wavenet_eps_vjp(audio, ctx.t, g_eps.reshape(audio.shape).contiguous())
         return g_x.view(audio.shape).to(audio.dtype), None, None
@@ -187,7 +187,7 @@ class UNetEpsHIP(torch.autograd.Function):
             raise DmadError('the HIP UNet VJP is first-order only: create_graph=True (double backward) is not supported')
         x, = ctx.saved_tensors
         eng, B = ctx.engine, x.shape[0]
-        if getattr(eng, 'unet_vjp_batch', 0) < B:
+        if eng.unet_vjp_batch < B:
             eng.reserve_unet_vjp(B)
         g_x = eng.unet_eps_vjp(x, ctx.t, g_eps.reshape(x.shape).contiguous())
         return g_x.view(x.shape).to(x.dtype), None, None
@@ -218,7 +218,7 @@ class ResNeXtHIP(torch.autograd.Function):
                             "use grad_backend='torch' for higher derivatives")
         spec, = ctx.saved_tensors
         eng, B = ctx.engine, spec.shape[0]
-        if getattr(eng, 'classifier_vjp_batch', 0) < B:
+        if eng.classifier_vjp_batch < B:
             eng.reserve_classifier_vjp(B)
         g = eng.classify_vjp(spec, g_logits.contiguous())
         return g.view(spec.shape).to(spec.dtype), None

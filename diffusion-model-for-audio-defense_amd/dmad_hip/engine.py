@@ -204,6 +204,7 @@ class Engine:
         self.has_wavenet = False
         self.has_classifier = False
         self.has_unet = False
+        self.vjp_batch = self.unet_vjp_batch = self.classifier_vjp_batch = 0     # rows per pass the VJP workspaces are reserved for
         # which weights are resident (state_fingerprint): a module that binds to an engine holding OTHER weights must
         # not silently run them
         self.wavenet_owner = self.classifier_owner = self.unet_owner = None
@@ -472,7 +473,7 @@ class Engine:
         """dmad_reserve_vjp: the workspace of wavenet_eps_vjp for up to max_batch clips per pass (capped at the engine's fp32 pass
         size; a larger reservation replaces a smaller one).  FP32 / EXACT engines; DmadError otherwise."""
         check(self.lib.dmad_reserve_vjp(self._h, int(max_batch)))
-        self.vjp_batch = max(getattr(self, 'vjp_batch', 0), int(max_batch))
+        self.vjp_batch = max(self.vjp_batch, int(max_batch))
 
     def wavenet_eps_vjp(self, x_t: torch.Tensor, t: int, g_eps: torch.Tensor, want_eps: bool = False):
         """g_x = (d eps / d x_t)^T g_eps for eps = WaveNet((x_t, t * ones)) on the exact-fp32 path ([B,L] or [B,1,L] -> [B,L]).
@@ -494,35 +495,43 @@ class Engine:
         explicit noise [S + 1, B, L] (slot 0 the diffusion draw, slot n + 1 step n); None = Philox keyed (seed, sample0 + row).
         want_traj: also return the trajectory for vpsde_purify_vjp, a [(S + 1) * B, L] tensor stored chunk by chunk: rows
         [(S + 1) * s, (S + 1) * e) hold the [S + 1][e - s][L] slots of the chunk [s, e)."""
-        x = self._wave(x0)
-        B, S = x.shape[0], len(k)
-        out = torch.empty_like(x)
-        traj = torch.empty(((S + 1) * B, self.L), dtype=torch.float32, device=x.device) if want_traj else None
-        ka, ha, hba, qa, gsa = self._vpsde_arrays(k, h, hb, q, gs)
-        if z is not None:
-            z = z.detach()
-            if not z.is_cuda or tuple(z.shape) != (S + 1, B, self.L):
-                raise DmadError('z must be a CUDA tensor [%d, %d, %d], not %s' % (S + 1, B, self.L, tuple(z.shape)))
-            z = z.float()
-        for s, e in self._chunks(B):
-            zz = None if z is None else z[:, s:e].contiguous()
-            tr = None if traj is None else traj[(S + 1) * s:(S + 1) * e]
-            check(self.lib.dmad_vpsde_purify(self._h, _ptr(x[s:e]), e - s, S, float(c_a), float(c_b), ka, ha, hba, qa, gsa, _ptr(zz), int(seed),
-                                             int(sample0) + s, int(path), _ptr(out[s:e]), _ptr(tr), _stream()))
-        return (out, traj) if want_traj else out
+        return self._vpsde_chain(self.lib.dmad_vpsde_purify, self._wave, self.L, x0, c_a, c_b, k, h, hb, q, gs, z, seed, sample0, path, want_traj)
 
     def vpsde_purify_vjp(self, traj: torch.Tensor, c_a: float, k, h, hb, q, g_out: torch.Tensor) -> torch.Tensor:
         """dmad_vpsde_purify_vjp: g_x0 = (d out / d x0)^T g_out of the chain vpsde_purify(.., path=1, want_traj=True) ran, the draws held
         fixed ([B, L] or [B, 1, L] -> [B, L]).  traj: that call's trajectory.  Needs reserve_vjp first (DmadError otherwise)."""
-        g = self._wave(g_out)
+        return self._vpsde_chain_vjp(self.lib.dmad_vpsde_purify_vjp, self._wave, self.L, 'L', 'vpsde_purify', traj, c_a, k, h, hb, q, g_out)
+
+    def _vpsde_chain(self, fn, shaper, width, x0, c_a, c_b, k, h, hb, q, gs, z, seed, sample0, path, want_traj):
+        """vpsde_purify / spec_vpsde_purify: the library's chain `fn` on rows of `width` floats that `shaper` (_wave / _spec) checks."""
+        x = shaper(x0)
+        B, S = x.shape[0], len(k)
+        out = torch.empty_like(x)
+        traj = torch.empty(((S + 1) * B, width), dtype=torch.float32, device=x.device) if want_traj else None
+        ka, ha, hba, qa, gsa = self._vpsde_arrays(k, h, hb, q, gs)
+        if z is not None:
+            z = z.detach()
+            if not z.is_cuda or tuple(z.shape) != (S + 1, B, width):
+                raise DmadError('z must be a CUDA tensor [%d, %d, %d], not %s' % (S + 1, B, width, tuple(z.shape)))
+            z = z.float()
+        for s, e in self._chunks(B):
+            zz = None if z is None else z[:, s:e].contiguous()
+            tr = None if traj is None else traj[(S + 1) * s:(S + 1) * e]
+            check(fn(self._h, _ptr(x[s:e]), e - s, S, float(c_a), float(c_b), ka, ha, hba, qa, gsa, _ptr(zz), int(seed), int(sample0) + s,
+                     int(path), _ptr(out[s:e]), _ptr(tr), _stream()))
+        return (out, traj) if want_traj else out
+
+    def _vpsde_chain_vjp(self, fn, shaper, width, width_name, forward_name, traj, c_a, k, h, hb, q, g_out):
+        """vpsde_purify_vjp / spec_vpsde_purify_vjp: the library's reverse walk `fn` over the chunk-by-chunk trajectory of `forward_name`."""
+        g = shaper(g_out)
         B, S = g.shape[0], len(k)
-        if not traj.is_cuda or tuple(traj.shape) != ((S + 1) * B, self.L):
-            raise DmadError('traj must be the [(S + 1) * B, L] = [%d, %d] trajectory of vpsde_purify, not %s' % ((S + 1) * B, self.L, tuple(traj.shape)))
+        if not traj.is_cuda or tuple(traj.shape) != ((S + 1) * B, width):
+            raise DmadError('traj must be the [(S + 1) * B, %s] = [%d, %d] trajectory of %s, not %s'
+                            % (width_name, (S + 1) * B, width, forward_name, tuple(traj.shape)))
         gx = torch.empty_like(g)
         ka, ha, hba, qa, _ = self._vpsde_arrays(k, h, hb, q, h)
         for s, e in self._chunks(B):
-            check(self.lib.dmad_vpsde_purify_vjp(self._h, _ptr(traj[(S + 1) * s:(S + 1) * e]), e - s, S, float(c_a), ka, ha, hba, qa,
-                                                 _ptr(g[s:e]), _ptr(gx[s:e]), _stream()))
+            check(fn(self._h, _ptr(traj[(S + 1) * s:(S + 1) * e]), e - s, S, float(c_a), ka, ha, hba, qa, _ptr(g[s:e]), _ptr(gx[s:e]), _stream()))
         return gx
 
     @staticmethod
@@ -637,7 +646,7 @@ class Engine:
         """dmad_reserve_unet_vjp: the workspace of unet_eps_vjp (the forward's tape) for up to max_batch spectrograms per pass (capped at
         the engine's fp32 pass size; a larger reservation replaces a smaller one).  FP32 / EXACT engines; DmadError otherwise."""
         check(self.lib.dmad_reserve_unet_vjp(self._h, int(max_batch)))
-        self.unet_vjp_batch = max(getattr(self, 'unet_vjp_batch', 0), int(max_batch))
+        self.unet_vjp_batch = max(self.unet_vjp_batch, int(max_batch))
 
     def unet_eps_vjp(self, x_t: torch.Tensor, t: int, g_eps: torch.Tensor, want_eps: bool = False):
         """g_x = (d eps / d x_t)^T g_eps for eps = UNetModel(x_t, t * ones) on the exact-fp32 tier ([B,1,32,32] or [B,32,32] -> [B,32,32]).
@@ -658,37 +667,12 @@ class Engine:
         [B,32,32] -> [B,32,32]), one library call per chunk of max_batch.  path 0: the mode's UNet map tier (unet_eps(tier=None)), 1: exact
         fp32.  z: optional explicit noise [S + 1, B, 1024]; None = Philox keyed (seed, sample0 + row).  want_traj: also return the
         trajectory for spec_vpsde_purify_vjp, [(S + 1) * B, 1024] stored chunk by chunk as in vpsde_purify."""
-        x = self._spec(x0)
-        B, S = x.shape[0], len(k)
-        out = torch.empty_like(x)
-        traj = torch.empty(((S + 1) * B, 1024), dtype=torch.float32, device=x.device) if want_traj else None
-        ka, ha, hba, qa, gsa = self._vpsde_arrays(k, h, hb, q, gs)
-        if z is not None:
-            z = z.detach()
-            if not z.is_cuda or tuple(z.shape) != (S + 1, B, 1024):
-                raise DmadError('z must be a CUDA tensor [%d, %d, 1024], not %s' % (S + 1, B, tuple(z.shape)))
-            z = z.float()
-        for s, e in self._chunks(B):
-            zz = None if z is None else z[:, s:e].contiguous()
-            tr = None if traj is None else traj[(S + 1) * s:(S + 1) * e]
-            check(self.lib.dmad_spec_vpsde_purify(self._h, _ptr(x[s:e]), e - s, S, float(c_a), float(c_b), ka, ha, hba, qa, gsa, _ptr(zz),
-                                                  int(seed), int(sample0) + s, int(path), _ptr(out[s:e]), _ptr(tr), _stream()))
-        return (out, traj) if want_traj else out
+        return self._vpsde_chain(self.lib.dmad_spec_vpsde_purify, self._spec, 1024, x0, c_a, c_b, k, h, hb, q, gs, z, seed, sample0, path, want_traj)
 
     def spec_vpsde_purify_vjp(self, traj: torch.Tensor, c_a: float, k, h, hb, q, g_out: torch.Tensor) -> torch.Tensor:
         """dmad_spec_vpsde_purify_vjp: g_x0 = (d out / d x0)^T g_out of the chain spec_vpsde_purify(.., path=1, want_traj=True) ran, the
         draws held fixed ([B,1,32,32] or [B,32,32] -> [B,32,32]).  traj: that call's trajectory.  Needs reserve_unet_vjp first."""
-        g = self._spec(g_out)
-        B, S = g.shape[0], len(k)
-        if not traj.is_cuda or tuple(traj.shape) != ((S + 1) * B, 1024):
-            raise DmadError('traj must be the [(S + 1) * B, 1024] = [%d, 1024] trajectory of spec_vpsde_purify, not %s'
-                            % ((S + 1) * B, tuple(traj.shape)))
-        gx = torch.empty_like(g)
-        ka, ha, hba, qa, _ = self._vpsde_arrays(k, h, hb, q, h)
-        for s, e in self._chunks(B):
-            check(self.lib.dmad_spec_vpsde_purify_vjp(self._h, _ptr(traj[(S + 1) * s:(S + 1) * e]), e - s, S, float(c_a), ka, ha, hba, qa,
-                                                      _ptr(g[s:e]), _ptr(gx[s:e]), _stream()))
-        return gx
+        return self._vpsde_chain_vjp(self.lib.dmad_spec_vpsde_purify_vjp, self._spec, 1024, '1024', 'spec_vpsde_purify', traj, c_a, k, h, hb, q, g_out)
 
     def unet_p_sample(self, x: torch.Tensor, t: int, c_a: float, c_b: float, c_1: float, c_2: float, c_sig: float,
                       z: Optional[torch.Tensor] = None, seed: int = 0, sample0: int = 0, want_x0: bool = False):
@@ -746,7 +730,7 @@ class Engine:
         """dmad_reserve_classifier_vjp: the workspace of classify_vjp (the ResNeXt29 forward's tape) for up to max_batch spectrograms per
         pass (capped at max_batch; a larger reservation replaces a smaller one).  ResNeXt29 engines of every precision; DmadError otherwise."""
         check(self.lib.dmad_reserve_classifier_vjp(self._h, int(max_batch)))
-        self.classifier_vjp_batch = max(getattr(self, 'classifier_vjp_batch', 0), int(max_batch))
+        self.classifier_vjp_batch = max(self.classifier_vjp_batch, int(max_batch))
 
     def classify_vjp(self, spec: torch.Tensor, g_logits: torch.Tensor, want_logits: bool = False):
         """g_spec = (d logits / d spec)^T g_logits for logits = CifarResNeXt(spec) on the fp32 tier ([B,1,32,32] or [B,32,32] -> [B,32,32]).

@@ -102,8 +102,8 @@ def test_schedule_refusals(sde):
 
 def test_module_surface_without_torchsde(sde):
     assert 'torchsde' not in sys.modules
-    src = open(sde.__file__).read()
-    assert not re.search(r'^\s*(import|from)\s+torchsde', src, flags=re.M)
+    for path in (sde.__file__, os.path.join(os.path.dirname(sde.__file__), '_rev_vpsde.py')):     # the module and the shared host module
+        assert not re.search(r'^\s*(import|from)\s+torchsde', open(path).read(), flags=re.M), path
     p = inspect.signature(sde.RevVPSDE.__init__).parameters
     assert [(n, p[n].default) for n in list(p)[1:]] == [
         ('model', inspect.Parameter.empty), ('score_type', 'guided_diffusion'), ('beta_min', 0.1), ('beta_max', 20), ('N', 1000),
