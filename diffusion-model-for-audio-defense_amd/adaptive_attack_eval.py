@@ -9,7 +9,7 @@ AcousticSystem(classifier, MelSpectrogramDB, defender) with the defenses
   * Diffusion       RevDiffWave (the reverse VP-SDE on the waveform, diffusion_models/diffwave_sde.py);
   * Diffusion-Spec  RevImprovedDiffusion (the reverse VP-SDE on the spectrogram, diffusion_models/improved_diffusion_sde.py).
 Every other attack (Qin-I, Kenansville, FAKEBOB, SirenAttack) and defense (AS, MS, DS, LPF, BPF, FeCo, DefenseGAN) raises
-NotImplementedError naming the piece this package does not have.
+NotImplementedError naming the piece this package does not have (FAKEBOB: the driver that runs it, black_box_attack_eval.py).
 
 Additions to the reference's flags:
   * `--classifier_path`: the classifier checkpoint; its default is the path the reference hard-codes (it overrides
@@ -36,9 +36,9 @@ DEFENSES = ['Diffusion', 'Diffusion-Spec', 'AS', 'MS', 'DS', 'LPF', 'BPF', 'FeCo
 _MISSING_ATTACK = {
     'Qin-I': 'AudioAttack stage 2 (the psychoacoustic masker of white_box_attack.py)',
     'Kenansville': 'the black-box attacks (robustness_eval/black_box_attack.py)',
-    'FAKEBOB': 'the black-box attacks (robustness_eval/black_box_attack.py)',
     'SirenAttack': 'the black-box attacks (robustness_eval/black_box_attack.py)',
 }
+_OTHER_DRIVER = {'FAKEBOB': 'black_box_attack_eval.py'}          # attacks this package has, run by a driver of their own
 _MISSING_DEFENSE = {
     'AS': 'the time-domain defenses (transforms/time_defense.py)',
     'MS': 'the time-domain defenses (transforms/time_defense.py)',
@@ -106,18 +106,26 @@ def build_parser():
 
 def check_supported(args):
     """NotImplementedError for an attack / defense / option this package does not provide."""
+    if args.attack in _OTHER_DRIVER:
+        raise NotImplementedError('--attack %s is a query-only attack: %s runs it, this white-box driver does not'
+                                  % (args.attack, _OTHER_DRIVER[args.attack]))
     if args.attack in _MISSING_ATTACK:
         raise NotImplementedError('--attack %s needs %s, which this package does not provide (supported: CW)'
                                   % (args.attack, _MISSING_ATTACK[args.attack]))
     if args.attack != 'CW':
         raise NotImplementedError('unknown attack: %s' % args.attack)
+    check_defense(args)
+    if args.max_iter_2 > 0:
+        raise NotImplementedError('--max_iter_2 > 0 runs AudioAttack stage 2 (Qin-I), which this package does not provide')
+
+
+def check_defense(args):
+    """The part of check_supported that does not depend on the attack (shared with black_box_attack_eval.py): the defense and --save_path."""
     if args.defense in _MISSING_DEFENSE:
         raise NotImplementedError('--defense %s needs %s, which this package does not provide (supported: None, Diffusion, Diffusion-Spec)'
                                   % (args.defense, _MISSING_DEFENSE[args.defense]))
     if args.defense not in ('None', 'Diffusion', 'Diffusion-Spec'):
         raise NotImplementedError('unknown defense: %s' % args.defense)
-    if args.max_iter_2 > 0:
-        raise NotImplementedError('--max_iter_2 > 0 runs AudioAttack stage 2 (Qin-I), which this package does not provide')
     if args.save_path is not None and args.defense == 'Diffusion-Spec':
         raise NotImplementedError('--save_path with --defense Diffusion-Spec writes spectrogram images, which needs a plotting library '
                                   'this package does not use')
@@ -137,7 +145,7 @@ def build_system(args, classifier=None, defender=None):
     from acoustic_system import AcousticSystem
     from audio_models.ConvNets_SpeechCommands.create_model import create_model
     from dmad_hip.transforms import MelSpectrogramDB
-    check_supported(args)
+    check_defense(args)
     if classifier is None:
         classifier = create_model(args.classifier_path)
     classifier.cuda()
@@ -168,23 +176,34 @@ def build_system(args, classifier=None, defender=None):
 
 def run(args, classifier=None, defender=None, log=print):
     """The reference's evaluation loop.  Returns {'total', 'clean_acc', 'denoised_acc', 'robust_acc'} (accuracies in percent)."""
-    from datasets.sc_dataset import SC09Dataset
     from robustness_eval.white_box_attack import AudioAttack
-    from transforms import FixAudioLength, LoadAudio
     check_supported(args)
     torch.cuda.set_device(args.gpu)
     AS_MODEL, classifier = build_system(args, classifier, defender)
+
+    def make_attacker():
+        Attacker = AudioAttack(model=AS_MODEL, eps=args.eps, norm=args.bound_norm, max_iter_1=args.max_iter_1, max_iter_2=0,
+                               learning_rate_1=args.eps / 5 if args.bound_norm == 'linf' else args.eps / 50,
+                               eot_attack_size=args.eot_attack_size, eot_defense_size=args.eot_defense_size, verbose=args.verbose)
+        log('attack: {} with {}_eps={} & iter={} & eot={}-{}'.format(args.attack, args.bound_norm, args.eps, args.max_iter_1,
+                                                                    args.eot_attack_size, args.eot_defense_size))
+        return Attacker
+    return evaluate(args, AS_MODEL, classifier, make_attacker, log)
+
+
+def evaluate(args, AS_MODEL, classifier, make_attacker, log=print):
+    """The evaluation loop both attack drivers share (reference l.234-370): clean, purified-clean and attacked accuracy over the test folder.
+    `make_attacker()` is called after the model lines are logged and returns an object with generate(x=, y=, targeted=) -> (x_adv, success),
+    success a list per clip or the (stage 1, stage 2) pair of AudioAttack."""
+    from datasets.sc_dataset import SC09Dataset
+    from transforms import FixAudioLength, LoadAudio
     AS_MODEL.eval()
     test_dataset = SC09Dataset(folder=args.data_path, transform=_Compose([LoadAudio(), FixAudioLength()]), num_per_class=args.num_per_class)
     test_dataloader = DataLoader(test_dataset, batch_size=args.batch_size, sampler=None, shuffle=False, pin_memory=True,
                                  num_workers=args.dataload_workers_nums)
     log('classifier model: {}'.format(classifier._get_name()))
     log('defense: {}'.format(args.defense if AS_MODEL.defender is None else '{} with t={}'.format(AS_MODEL.defender._get_name(), args.t)))
-    Attacker = AudioAttack(model=AS_MODEL, eps=args.eps, norm=args.bound_norm, max_iter_1=args.max_iter_1, max_iter_2=0,
-                           learning_rate_1=args.eps / 5 if args.bound_norm == 'linf' else args.eps / 50,
-                           eot_attack_size=args.eot_attack_size, eot_defense_size=args.eot_defense_size, verbose=args.verbose)
-    log('attack: {} with {}_eps={} & iter={} & eot={}-{}'.format(args.attack, args.bound_norm, args.eps, args.max_iter_1,
-                                                                args.eot_attack_size, args.eot_defense_size))
+    Attacker = make_attacker()
     correct_orig = correct_orig_denoised = correct_adv_1 = total = 0
     acc_orig = acc_orig_denoised = acc_adv_1 = 0.0
     for batch in test_dataloader:
@@ -212,10 +231,11 @@ def run(args, classifier=None, defender=None, log=print):
                 _save_wav(waveforms_defended[i], clean_path, '{}_{}_clean_purified.wav'.format(audio_id, y))
                 _save_wav(waveforms_adv[i], adv_path, '{}_{}_adv.wav'.format(audio_id, y))
                 _save_wav(adv_defended[i], adv_path, '{}_{}_adv_purified.wav'.format(audio_id, y))
+        first_stage = attack_success[0] if isinstance(attack_success, tuple) else attack_success
         total += waveforms.shape[0]
         correct_orig += (pred_clean == targets).sum().item()
         correct_orig_denoised += (pred_defended == targets).sum().item()
-        correct_adv_1 += waveforms.shape[0] - int(torch.tensor(attack_success[0]).sum().item())
+        correct_adv_1 += waveforms.shape[0] - int(torch.tensor(first_stage).sum().item())
         acc_orig = correct_orig / total * 100
         acc_orig_denoised = correct_orig_denoised / total * 100
         acc_adv_1 = correct_adv_1 / total * 100
@@ -224,7 +244,7 @@ def run(args, classifier=None, defender=None, log=print):
     log('on {} test examples: '.format(total))
     log('original clean test accuracy: {:.4f}%'.format(acc_orig))
     log('denoised clean test accuracy: {:.4f}%'.format(acc_orig_denoised))
-    log('CW robust test accuracy: {:.4f}%'.format(acc_adv_1))
+    log('CW robust test accuracy: {:.4f}%'.format(acc_adv_1))           # the reference prints this label for every attack
     return {'total': total, 'clean_acc': acc_orig, 'denoised_acc': acc_orig_denoised, 'robust_acc': acc_adv_1}
 
 

@@ -2954,6 +2954,31 @@ int dmad_spec_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t re
     return 0;
 }
 
+// _NES.py:19-25 (noise = cat(noise, -noise), the zero probe in front, eval_input = noise * sigma + x), a chunk of rows at a time
+int dmad_nes_probes(dmad_engine* e, const float* x, int32_t B, int32_t P, float sigma, int32_t with_origin, uint64_t seed, uint64_t draw0,
+                    int64_t row0, int32_t rows, float* out, dmad_stream s) {
+    if (!e || !x || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || P < 2 || (P & 1)) return fail(DMAD_ERR_INVALID, "dmad_nes_probes: B %d must be >= 1 and P %d even and >= 2", B, P);
+    if (with_origin != 0 && with_origin != 1) return fail(DMAD_ERR_INVALID, "dmad_nes_probes: with_origin must be 0 or 1");
+    const int64_t total = (int64_t)B * (P + with_origin);
+    if (row0 < 0 || rows < 1 || row0 + rows > total)
+        return fail(DMAD_ERR_INVALID, "dmad_nes_probes: rows [%lld, %lld) are not inside the %lld query rows of %d clips", (long long)row0,
+                    (long long)row0 + rows, (long long)total, B);
+    launch_nes_probes(x, sigma, P / 2, with_origin, seed, draw0, DMAD_PHILOX_STREAM_NES, (long)row0, rows, out, e->L, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+// _NES.py:47,52,54 (grad = sum over draw batches of torch.mean(loss * noise, 1), / sigma / num_batches) without the noise tensor
+int dmad_nes_grad(dmad_engine* e, const float* w, int32_t B, int32_t P, float scale, uint64_t seed, uint64_t draw0, int32_t accumulate,
+                  float* grad, dmad_stream s) {
+    if (!e || !w || !grad) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || P < 2 || (P & 1)) return fail(DMAD_ERR_INVALID, "dmad_nes_grad: B %d must be >= 1 and P %d even and >= 2", B, P);
+    launch_nes_grad(w, P / 2, scale, seed, draw0, DMAD_PHILOX_STREAM_NES, accumulate != 0, grad, B, e->L, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
 int dmad_philox_raw(dmad_engine* e, uint64_t seed, uint64_t sample, uint32_t stream, uint32_t nblocks, uint32_t* out, dmad_stream s) {
     if (!e || !out) return fail(DMAD_ERR_INVALID, "null argument");
     launch_philox_raw(seed, sample, stream, nblocks, out, (hipStream_t)s);

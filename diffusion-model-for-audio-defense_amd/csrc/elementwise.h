@@ -23,6 +23,13 @@ void launch_lincomb(int op, const float* x, const float* y, const float* z, floa
 // draw keyed (seed, sample0 + row, stream) in registers; y may alias x; traj (optional) gets a copy of y
 void launch_vpsde_step(const float* x, const float* eps, const float* z, float c0, float c1, float h, float c2, uint64_t seed,
                        uint64_t sample0, uint32_t stream, float* y, float* traj, int B, int L, hipStream_t s);
+// NES probes and estimate (dmad_nes_probes / dmad_nes_grad): direction j of clip b is the Philox row keyed (seed, draw0 + b * H + j, stream),
+// regenerated in registers by both kernels.  probes: query rows [row0, row0 + rows) of the clip-major layout (2H + with_origin per clip);
+// grad[b] = (accumulate ? grad[b] : 0) + scale * sum_j (w[b][j] - w[b][H + j]) u_{b,j}, w device fp32 [B][2H]
+void launch_nes_probes(const float* x, float sigma, int H, int with_origin, uint64_t seed, uint64_t draw0, uint32_t stream, long row0,
+                       int rows, float* out, int L, hipStream_t s);
+void launch_nes_grad(const float* w, int H, float scale, uint64_t seed, uint64_t draw0, uint32_t stream, int accumulate, float* grad,
+                     int B, int L, hipStream_t s);
 void launch_wn_init_f32(const float* x, const float* w, const float* bias, const float* emb0, float* h, int B, int L, int LP,
                         hipStream_t s, bool split = false, bool hi_only = false);
 void launch_scale(const float* x, float c, float* y, long n, hipStream_t s, bool split = false);

@@ -237,6 +237,59 @@ __global__ void vpsde_step_kernel(const float* x, const float* __restrict__ eps,
     if (traj) *(float4*)(traj + o) = out;
 }
 
+// NES probes (dmad_nes_probes; robustness_eval/_NES.py:19-25), one thread per 4 samples of a query row.  Global row g = row0 + r is slot
+// g % per_clip of clip g / per_clip (per_clip = 2H + with_origin): the optional slot 0 is x[b] itself, then H rows x[b] + sigma * u_j and
+// H rows x[b] - sigma * u_j, with u_j the Philox row keyed (seed, draw0 + b * H + j, stream) — the words of philox_normal_kernel.  The
+// product is rounded before the sum, as torch's `noise * sigma + x` rounds it, so the two probes of a pair are mirror images.
+__global__ void nes_probes_kernel(const float* __restrict__ x, float sigma, int H, int with_origin, uint64_t seed, uint64_t draw0,
+                                  uint32_t stream, long row0, int rows, float* __restrict__ out, int L) {
+    const int per = L / 4;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)rows * per) return;
+    const int r = (int)(i / per), blk = (int)(i - (long)r * per);
+    const long g = row0 + r;
+    const int per_clip = 2 * H + with_origin;
+    const long b = g / per_clip;
+    const int slot = (int)(g - b * per_clip) - with_origin;        // -1: the unperturbed clip
+    float4 v = *(const float4*)(x + b * L + blk * 4);
+    if (slot >= 0) {
+        const int j = slot < H ? slot : slot - H;
+        const float sg = slot < H ? sigma : -sigma;
+        float z[4];
+        philox_normal4(seed, draw0 + (uint64_t)b * (uint64_t)H + (uint64_t)j, stream, blk, z);
+        v.x = __fadd_rn(v.x, __fmul_rn(sg, z[0])); v.y = __fadd_rn(v.y, __fmul_rn(sg, z[1]));
+        v.z = __fadd_rn(v.z, __fmul_rn(sg, z[2])); v.w = __fadd_rn(v.w, __fmul_rn(sg, z[3]));
+    }
+    *(float4*)(out + (long)r * L + blk * 4) = v;
+}
+
+// NES estimate (dmad_nes_grad; _NES.py:47,52,54): grad[b][l] = (accumulate ? grad[b][l] : 0) + scale * sum_j (w[b][j] - w[b][H + j]) u_{b,j}[l].
+// One thread per 4 output samples regenerates the H directions of its clip in registers, in the keying of nes_probes_kernel, and sums
+// them j ascending (product rounded, then added): no atomics, one store per output, the same bits for every batch size.
+__global__ void nes_grad_kernel(const float* __restrict__ w, int H, float scale, uint64_t seed, uint64_t draw0, uint32_t stream,
+                                int accumulate, float* __restrict__ grad, int B, int L) {
+    const int per = L / 4;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * per) return;
+    const int b = (int)(i / per), blk = (int)(i - (long)b * per);
+    const float* wb = w + (long)b * 2 * H;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < H; ++j) {
+        const float d = __fsub_rn(wb[j], wb[H + j]);
+        float z[4];
+        philox_normal4(seed, draw0 + (uint64_t)b * (uint64_t)H + (uint64_t)j, stream, blk, z);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = __fadd_rn(acc[k], __fmul_rn(d, z[k]));
+    }
+    float* o = grad + (long)b * L + blk * 4;
+    float4 r = float4{__fmul_rn(scale, acc[0]), __fmul_rn(scale, acc[1]), __fmul_rn(scale, acc[2]), __fmul_rn(scale, acc[3])};
+    if (accumulate) {
+        const float4 g = *(const float4*)o;
+        r.x = __fadd_rn(g.x, r.x); r.y = __fadd_rn(g.y, r.y); r.z = __fadd_rn(g.z, r.z); r.w = __fadd_rn(g.w, r.w);
+    }
+    *(float4*)o = r;
+}
+
 // ----------------------------------------------------------------------------------------------
 // fp32 (parity) WaveNet helpers
 // ----------------------------------------------------------------------------------------------
@@ -466,6 +519,16 @@ void launch_vpsde_step(const float* x, const float* eps, const float* z, float c
                        uint64_t sample0, uint32_t stream, float* y, float* traj, int B, int L, hipStream_t s) {
     hipLaunchKernelGGL(vpsde_step_kernel, dim3(nblk((long)B * (L / 4), 256)), dim3(256), 0, s, x, eps, z, c0, c1, h, c2, seed, sample0, stream,
                        y, traj, B, L);
+}
+void launch_nes_probes(const float* x, float sigma, int H, int with_origin, uint64_t seed, uint64_t draw0, uint32_t stream, long row0,
+                       int rows, float* out, int L, hipStream_t s) {
+    hipLaunchKernelGGL(nes_probes_kernel, dim3(nblk((long)rows * (L / 4), 256)), dim3(256), 0, s, x, sigma, H, with_origin, seed, draw0,
+                       stream, row0, rows, out, L);
+}
+void launch_nes_grad(const float* w, int H, float scale, uint64_t seed, uint64_t draw0, uint32_t stream, int accumulate, float* grad,
+                     int B, int L, hipStream_t s) {
+    hipLaunchKernelGGL(nes_grad_kernel, dim3(nblk((long)B * (L / 4), 256)), dim3(256), 0, s, w, H, scale, seed, draw0, stream, accumulate,
+                       grad, B, L);
 }
 void launch_wn_init_f32(const float* x, const float* w, const float* bias, const float* emb0, float* h, int B, int L, int LP,
                         hipStream_t s, bool split, bool hi_only) {

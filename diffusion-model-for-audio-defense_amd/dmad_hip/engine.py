@@ -20,6 +20,7 @@ BF16, FP32, EXACT = 0, 1, 2                       # enum dmad_precision
 MODE_FAST, MODE_EXACT_VOTES, MODE_FP32 = 0, 1, 2  # enum dmad_mode (EXACT engines)
 HALF_BF16, HALF_F16 = 0, 1                        # enum dmad_half_type: operand format of the 16-bit MFMA path
 WAVE_16BIT, WAVE_FP32, WAVE_SPLIT = 0, 1, 2       # dmad_set_waveform_tier: WaveNet tier of the waveform-returning surfaces (EXACT engines)
+NES_STREAM = 0x4E450000                           # DMAD_PHILOX_STREAM_NES: the Philox stream of the NES probe directions
 # Recheck bound of the exact-vote mode: a Monte Carlo sample whose 16-bit-path top-2 logit margin is below it is
 # re-evaluated on the higher tiers.  Let i be the exact path's arg-max and e = (16-bit logits) - (exact logits).  If the 16-bit
 # margin is >= tau and the 16-bit leader were some j != i, then l~_j - l~_i >= tau with l_j - l_i <= 0, i.e. e_j - e_i >= tau:
@@ -833,6 +834,36 @@ class Engine:
                                               arrs[3], arrs[4], float(mel_lo), float(mel_hi), int(seed), int(sample0), _ptr(logits), _ptr(dec),
                                               _stream()))
         return logits, dec
+
+    def nes_probes(self, x: torch.Tensor, P: int, sigma: float, with_origin: bool, seed: int = 0, draw0: int = 0, row0: int = 0,
+                   rows: Optional[int] = None) -> torch.Tensor:
+        """dmad_nes_probes: x [B,1,L] -> query rows [row0, row0 + rows) of the NES layout, [rows, L] (clip-major, P + with_origin rows per
+        clip: x[b], then x[b] + sigma * u_j, then x[b] - sigma * u_j; u_j = philox_normal(seed, draw0 + b * P/2 + j, NES_STREAM, 1)).
+        rows defaults to all that follow row0."""
+        xw = self._wave(x)
+        B = xw.shape[0]
+        if rows is None:
+            rows = B * (int(P) + int(bool(with_origin))) - int(row0)
+        out = torch.empty((max(int(rows), 0), self.L), device=xw.device, dtype=torch.float32)
+        check(self.lib.dmad_nes_probes(self._h, _ptr(xw), B, int(P), float(sigma), int(bool(with_origin)), int(seed), int(draw0), int(row0),
+                                       int(rows), _ptr(out), _stream()))
+        return out
+
+    def nes_grad(self, w: torch.Tensor, P: int, scale: float, seed: int = 0, draw0: int = 0, grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dmad_nes_grad: w [B, P] probe losses (+ probes first) -> scale * sum_j (w[b][j] - w[b][P/2 + j]) u_{b,j}, [B, L], the directions
+        regenerated on the device.  With `grad` ([B, L] contiguous fp32 CUDA) the estimate is added to it in place."""
+        if not w.is_cuda:
+            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
+        w = w.detach().contiguous().float()
+        assert w.dim() == 2 and w.shape[1] == int(P), 'expected w [B,%d], got %s' % (int(P), tuple(w.shape))
+        B = w.shape[0]
+        accumulate = grad is not None
+        if accumulate:
+            assert grad.is_cuda and grad.is_contiguous() and grad.dtype == torch.float32 and tuple(grad.shape) == (B, self.L)
+        else:
+            grad = torch.empty((B, self.L), device=w.device, dtype=torch.float32)
+        check(self.lib.dmad_nes_grad(self._h, _ptr(w), B, int(P), float(scale), int(seed), int(draw0), int(accumulate), _ptr(grad), _stream()))
+        return grad
 
     def philox_raw(self, seed: int, sample: int, stream: int, nblocks: int) -> torch.Tensor:
         out = torch.empty(nblocks * 4, dtype=torch.int32, device=self.device)

@@ -450,6 +450,32 @@ int dmad_spec_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t re
                            const float* c_b, const float* c_1, const float* c_2, const float* c_sig, float mel_lo, float mel_hi, uint64_t seed,
                            uint64_t sample0, float* logits, int32_t* decisions, dmad_stream s);
 
+/* NES gradient estimate of the query-only attacks (robustness_eval/_NES.py:15-55; caller black_box_attack.py:180-184) without its
+ * [n_audios, samples, 1, N] tensors: the probe directions are a pure function of a Philox key and are regenerated where they are used.
+ * Direction j (0 <= j < H, H = P / 2) of clip b is the row that dmad_philox_normal(seed, sample = draw0 + b * H + j, stream =
+ * DMAD_PHILOX_STREAM_NES) returns; both calls below produce exactly those bits.
+ * Philox stream ids in use, which a new draw must not collide with: 0 (smoothing noise of the vote loops), 1 + t for t < T (DDPM reverse
+ * step t), 0x0E70 + t (spec-domain p_sample at t), 0x5BEC (spec-domain q_sample), 0xD1FF (DiffWave diffusion draw), 0x5DE00000 + n
+ * (reverse VP-SDE: diffusion draw and Euler steps), 0x5DF00000 + n (the same on the spectrogram), 0x4E450000 (NES directions). */
+#define DMAD_PHILOX_STREAM_NES 0x4E450000u
+
+/* Query rows [row0, row0 + rows) of the reference's layout (_NES.py:19-25: noise = cat(noise, -noise), the zero probe in front on the
+ * first draw batch, eval_input = noise * sigma + x).  The layout is clip-major with per_clip = P + with_origin rows per clip: the optional
+ * slot 0 is x[b] unchanged, the next H slots are x[b] + sigma * u_j, the last H slots x[b] - sigma * u_j (product rounded, then the sum; no
+ * clamping, as in the reference).  A row's content depends only on its global index, never on row0 or rows, so the queries can be made
+ * a chunk at a time.  x: device fp32 [B][clip_len]; out: device fp32 [rows][clip_len].  P must be even and >= 2, and
+ * 0 <= row0, row0 + rows <= B * per_clip (DMAD_ERR_INVALID otherwise). */
+int dmad_nes_probes(dmad_engine* e, const float* x, int32_t B, int32_t P, float sigma, int32_t with_origin, uint64_t seed, uint64_t draw0,
+                    int64_t row0, int32_t rows, float* out, dmad_stream s);
+
+/* grad[b][l] = (accumulate ? grad[b][l] : 0) + scale * sum_{j < H} (w[b][j] - w[b][H + j]) * u_{b,j}[l]   (_NES.py:47,52,54:
+ * torch.mean(loss * noise, 1) over the antithetic pairs, / sigma / num_batches folded into scale).  w: device fp32 [B][P], the losses of
+ * the + probes in the first H entries of a clip and those of the - probes in the last H; grad: device fp32 [B][clip_len].  u is
+ * regenerated in registers.  Each output element is summed by one thread, j ascending, every product and sum rounded to fp32, without
+ * atomics: the result is bit-reproducible and a clip's row does not depend on B.  P even and >= 2. */
+int dmad_nes_grad(dmad_engine* e, const float* w, int32_t B, int32_t P, float scale, uint64_t seed, uint64_t draw0, int32_t accumulate,
+                  float* grad, dmad_stream s);
+
 /* counts[argmax_c logits[b][c]] += 1 (first maximum wins) — certified_robust.py:59-65. */
 int dmad_vote(dmad_engine* e, const float* logits, int32_t B, int64_t* counts, dmad_stream s);
 
