@@ -9,7 +9,8 @@ AcousticSystem(classifier, MelSpectrogramDB, defender) with the defenses
   * Diffusion       RevDiffWave (the reverse VP-SDE on the waveform, diffusion_models/diffwave_sde.py);
   * Diffusion-Spec  RevImprovedDiffusion (the reverse VP-SDE on the spectrogram, diffusion_models/improved_diffusion_sde.py).
 Every other attack (Qin-I, Kenansville, FAKEBOB, SirenAttack) and defense (AS, MS, DS, LPF, BPF, FeCo, DefenseGAN) raises
-NotImplementedError naming the piece this package does not have (FAKEBOB: the driver that runs it, black_box_attack_eval.py).
+NotImplementedError naming the piece this package does not have (FAKEBOB and SirenAttack: the driver that runs it,
+black_box_attack_eval.py and siren_attack_eval.py).
 
 Additions to the reference's flags:
   * `--classifier_path`: the classifier checkpoint; its default is the path the reference hard-codes (it overrides
@@ -36,9 +37,8 @@ DEFENSES = ['Diffusion', 'Diffusion-Spec', 'AS', 'MS', 'DS', 'LPF', 'BPF', 'FeCo
 _MISSING_ATTACK = {
     'Qin-I': 'AudioAttack stage 2 (the psychoacoustic masker of white_box_attack.py)',
     'Kenansville': 'the black-box attacks (robustness_eval/black_box_attack.py)',
-    'SirenAttack': 'the black-box attacks (robustness_eval/black_box_attack.py)',
 }
-_OTHER_DRIVER = {'FAKEBOB': 'black_box_attack_eval.py'}          # attacks this package has, run by a driver of their own
+_OTHER_DRIVER = {'FAKEBOB': 'black_box_attack_eval.py', 'SirenAttack': 'siren_attack_eval.py'}    # attacks run by a driver of their own
 _MISSING_DEFENSE = {
     'AS': 'the time-domain defenses (transforms/time_defense.py)',
     'MS': 'the time-domain defenses (transforms/time_defense.py)',

@@ -2979,6 +2979,48 @@ int dmad_nes_grad(dmad_engine* e, const float* w, int32_t B, int32_t P, float sc
     return 0;
 }
 
+// the uniform twin of dmad_philox_normal: the draws of the swarm kernels below, for tests
+int dmad_philox_uniform(dmad_engine* e, uint64_t seed, uint64_t sample0, uint32_t stream, int32_t B, float* out, dmad_stream s) {
+    if (!e || !out || B < 1) return fail(DMAD_ERR_INVALID, "bad argument");
+    launch_philox_uniform(seed, sample0, stream, out, B, e->L, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+// black_box_attack.py:371-391 (np.random.uniform positions and velocities, the carried best in front) and l.404 (the query rows)
+int dmad_pso_init(dmad_engine* e, const float* x, const float* lower, const float* upper, int32_t B, int32_t P, const float* keep,
+                  uint64_t seed, uint64_t draw0, float* pbest_loc, float* loc, float* vel, float* queries, dmad_stream s) {
+    if (!e || !x || !lower || !upper || !pbest_loc || !loc || !vel || !queries) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || P < 1) return fail(DMAD_ERR_INVALID, "dmad_pso_init: B %d and P %d must be >= 1", B, P);
+    launch_pso_init(x, lower, upper, keep, B, P, seed, draw0, DMAD_PHILOX_STREAM_PSO, pbest_loc, loc, vel, queries, e->L, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+// black_box_attack.py:474-484 (r1, r2, the velocity and position update, the clamp) and l.404 in one pass over the swarm
+int dmad_pso_step(dmad_engine* e, const float* x, const float* lower, const float* upper, const float* pbest_loc, const float* gbest_loc,
+                  int32_t B, int32_t P, float w, float c1, float c2, uint64_t seed, uint64_t draw0, float* loc, float* vel, float* queries,
+                  dmad_stream s) {
+    if (!e || !x || !lower || !upper || !pbest_loc || !gbest_loc || !loc || !vel || !queries) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || P < 1) return fail(DMAD_ERR_INVALID, "dmad_pso_step: B %d and P %d must be >= 1", B, P);
+    launch_pso_step(x, lower, upper, pbest_loc, gbest_loc, B, P, w, c1, c2, seed, draw0, DMAD_PHILOX_STREAM_PSO, loc, vel, queries, e->L,
+                    (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+// black_box_attack.py:420-437 (the personal and global bests) without the host loops
+int dmad_pso_update_best(dmad_engine* e, const float* loss, const int64_t* predict, const float* loc, const int64_t* index, int32_t B,
+                         int32_t P, float* pbests, float* pbest_loc, float* gbests, float* gbest_loc, int64_t* gbest_predict, dmad_stream s) {
+    if (!e || !loss || !predict || !loc || !pbests || !pbest_loc || !gbests || !gbest_loc || !gbest_predict)
+        return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || P < 1) return fail(DMAD_ERR_INVALID, "dmad_pso_update_best: B %d and P %d must be >= 1", B, P);
+    launch_pso_update_best(loss, (const long long*)predict, loc, (const long long*)index, B, P, pbests, pbest_loc, gbests, gbest_loc,
+                           (long long*)gbest_predict, e->L, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
 int dmad_philox_raw(dmad_engine* e, uint64_t seed, uint64_t sample, uint32_t stream, uint32_t nblocks, uint32_t* out, dmad_stream s) {
     if (!e || !out) return fail(DMAD_ERR_INVALID, "null argument");
     launch_philox_raw(seed, sample, stream, nblocks, out, (hipStream_t)s);

@@ -30,6 +30,18 @@ void launch_nes_probes(const float* x, float sigma, int H, int with_origin, uint
                        int rows, float* out, int L, hipStream_t s);
 void launch_nes_grad(const float* w, int H, float scale, uint64_t seed, uint64_t draw0, uint32_t stream, int accumulate, float* grad,
                      int B, int L, hipStream_t s);
+// Particle swarm of SirenAttack (dmad_pso_init / dmad_pso_step / dmad_pso_update_best): row r = b * P + p of the [B * P][L] state arrays,
+// its draws of one event keyed (seed, draw0 + r, stream + {0 position, 1 velocity, 2 r1, 3 r2}); out[b] of launch_philox_uniform is the
+// uniform row of key (seed, sample0 + b, stream).  update_best decides everything from the scalars as they are before the call.
+void launch_philox_uniform(uint64_t seed, uint64_t sample0, uint32_t stream, float* out, int B, int L, hipStream_t s);
+void launch_pso_init(const float* x, const float* lower, const float* upper, const float* keep, int B, int P, uint64_t seed, uint64_t draw0,
+                     uint32_t stream, float* pbest_loc, float* loc, float* vel, float* queries, int L, hipStream_t s);
+void launch_pso_step(const float* x, const float* lower, const float* upper, const float* pbest_loc, const float* gbest_loc, int B, int P,
+                     float w, float c1, float c2, uint64_t seed, uint64_t draw0, uint32_t stream, float* loc, float* vel, float* queries,
+                     int L, hipStream_t s);
+void launch_pso_update_best(const float* loss, const long long* predict, const float* loc, const long long* index, int B, int P,
+                            float* pbests, float* pbest_loc, float* gbests, float* gbest_loc, long long* gbest_predict, int L,
+                            hipStream_t s);
 void launch_wn_init_f32(const float* x, const float* w, const float* bias, const float* emb0, float* h, int B, int L, int LP,
                         hipStream_t s, bool split = false, bool hi_only = false);
 void launch_scale(const float* x, float c, float* y, long n, hipStream_t s, bool split = false);

@@ -291,6 +291,158 @@ __global__ void nes_grad_kernel(const float* __restrict__ w, int H, float scale,
 }
 
 // ----------------------------------------------------------------------------------------------
+// Particle swarm of SirenAttack (dmad_pso_*; robustness_eval/black_box_attack.py:344-498).  Row r = b * P + p of the [B * P][L] state
+// arrays is particle p of clip b; its draws of one swarm event are the Philox rows keyed (seed, draw0 + r, DMAD_PHILOX_STREAM_PSO + k).
+// One thread per 4 samples; every product, sum and difference is rounded on its own, so a row depends on its key and inputs only.
+// ----------------------------------------------------------------------------------------------
+// four uniforms in (0, 1) with 24 random bits each: the uniforms philox_normal4 feeds to Box-Muller
+__device__ inline void philox_uniform4(uint64_t seed, uint64_t sample, uint32_t stream, uint32_t block, float u[4]) {
+    uint32_t c[4] = {block, (uint32_t)sample, (uint32_t)(sample >> 32), stream};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u[k] = __fmul_rn(__fadd_rn((float)(c[k] >> 8), 0.5f), 5.9604644775390625e-8f);
+}
+
+__global__ void philox_uniform_kernel(uint64_t seed, uint64_t sample0, uint32_t stream, float* __restrict__ out, int B, int L) {
+    const int per = L / 4;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * per) return;
+    const int b = (int)(i / per), blk = (int)(i - (long)b * per);
+    float u[4];
+    philox_uniform4(seed, sample0 + b, stream, blk, u);
+    *(float4*)(out + (long)b * L + blk * 4) = float4{u[0], u[1], u[2], u[3]};
+}
+
+__device__ inline float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+
+// black_box_attack.py:371-391,404: positions uniform in [lower, upper] (particle 0 of a clip = keep[b] when keep is given), velocities
+// uniform in [-d, d] with d = |lower - upper|, loc = pbest_loc, queries = loc + x[b]
+__global__ void pso_init_kernel(const float* __restrict__ x, const float* __restrict__ lower, const float* __restrict__ upper,
+                                const float* __restrict__ keep, int P, uint64_t seed, uint64_t draw0, uint32_t stream,
+                                float* __restrict__ pbest_loc, float* __restrict__ loc, float* __restrict__ vel,
+                                float* __restrict__ queries, long rows, int L) {
+    const int per = L / 4;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * per) return;
+    const long r = i / per, b = r / P;
+    const int blk = (int)(i - r * per), p = (int)(r - b * P);
+    const long ob = b * L + blk * 4, o = r * L + blk * 4;
+    const float4 lo4 = *(const float4*)(lower + ob), up4 = *(const float4*)(upper + ob), x4 = *(const float4*)(x + ob);
+    const float lo[4] = {lo4.x, lo4.y, lo4.z, lo4.w}, up[4] = {up4.x, up4.y, up4.z, up4.w}, xs[4] = {x4.x, x4.y, x4.z, x4.w};
+    float pos[4], v[4], q[4], u[4];
+    if (keep && p == 0) {
+        const float4 k4 = *(const float4*)(keep + ob);
+        pos[0] = k4.x; pos[1] = k4.y; pos[2] = k4.z; pos[3] = k4.w;
+    } else {
+        philox_uniform4(seed, draw0 + (uint64_t)r, stream + 0u, blk, u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pos[k] = clampf(__fadd_rn(lo[k], __fmul_rn(__fsub_rn(up[k], lo[k]), u[k])), lo[k], up[k]);
+    }
+    philox_uniform4(seed, draw0 + (uint64_t)r, stream + 1u, blk, u);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float d = fabsf(__fsub_rn(lo[k], up[k]));
+        v[k] = __fadd_rn(-d, __fmul_rn(__fmul_rn(2.f, d), u[k]));
+        q[k] = __fadd_rn(pos[k], xs[k]);
+    }
+    const float4 pos4 = float4{pos[0], pos[1], pos[2], pos[3]};
+    *(float4*)(pbest_loc + o) = pos4;
+    *(float4*)(loc + o) = pos4;
+    *(float4*)(vel + o) = float4{v[0], v[1], v[2], v[3]};
+    *(float4*)(queries + o) = float4{q[0], q[1], q[2], q[3]};
+}
+
+// black_box_attack.py:474-484,404: vel <- w vel + c1 r1 (pbest - loc) + c2 r2 (gbest[b] - loc), left to right; loc <- clamp(loc + vel);
+// queries <- loc + x[b].  loc and vel are updated in place, each element by the thread that read it.
+__global__ void pso_step_kernel(const float* __restrict__ x, const float* __restrict__ lower, const float* __restrict__ upper,
+                                const float* __restrict__ pbest_loc, const float* __restrict__ gbest_loc, int P, float w, float c1, float c2,
+                                uint64_t seed, uint64_t draw0, uint32_t stream, float* __restrict__ loc, float* __restrict__ vel,
+                                float* __restrict__ queries, long rows, int L) {
+    const int per = L / 4;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * per) return;
+    const long r = i / per, b = r / P;
+    const int blk = (int)(i - r * per);
+    const long ob = b * L + blk * 4, o = r * L + blk * 4;
+    const float4 lo4 = *(const float4*)(lower + ob), up4 = *(const float4*)(upper + ob), x4 = *(const float4*)(x + ob);
+    const float4 g4 = *(const float4*)(gbest_loc + ob), pb4 = *(const float4*)(pbest_loc + o);
+    const float4 l4 = *(const float4*)(loc + o), v4 = *(const float4*)(vel + o);
+    const float lo[4] = {lo4.x, lo4.y, lo4.z, lo4.w}, up[4] = {up4.x, up4.y, up4.z, up4.w}, xs[4] = {x4.x, x4.y, x4.z, x4.w};
+    const float gb[4] = {g4.x, g4.y, g4.z, g4.w}, pb[4] = {pb4.x, pb4.y, pb4.z, pb4.w};
+    float l[4] = {l4.x, l4.y, l4.z, l4.w}, v[4] = {v4.x, v4.y, v4.z, v4.w}, q[4], u1[4], u2[4];
+    philox_uniform4(seed, draw0 + (uint64_t)r, stream + 2u, blk, u1);
+    philox_uniform4(seed, draw0 + (uint64_t)r, stream + 3u, blk, u2);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float r1 = __fadd_rn(u1[k], 1e-5f), r2 = __fadd_rn(u2[k], 1e-5f);
+        const float t1 = __fmul_rn(__fmul_rn(c1, r1), __fsub_rn(pb[k], l[k]));
+        const float t2 = __fmul_rn(__fmul_rn(c2, r2), __fsub_rn(gb[k], l[k]));
+        v[k] = __fadd_rn(__fadd_rn(__fmul_rn(w, v[k]), t1), t2);
+        l[k] = clampf(__fadd_rn(l[k], v[k]), lo[k], up[k]);
+        q[k] = __fadd_rn(l[k], xs[k]);
+    }
+    *(float4*)(vel + o) = float4{v[0], v[1], v[2], v[3]};
+    *(float4*)(loc + o) = float4{l[0], l[1], l[2], l[3]};
+    *(float4*)(queries + o) = float4{q[0], q[1], q[2], q[3]};
+}
+
+// black_box_attack.py:420-437 in three passes that all decide from the scalars as they were before the call: (1) the personal-best
+// rows, (2) the global-best rows, (3) the scalars.  A block serves one row, so its decision is one scalar read by thread 0.
+__global__ void pso_pbest_rows_kernel(const float* __restrict__ loss, const float* __restrict__ pbests, const float* __restrict__ loc,
+                                      float* __restrict__ pbest_loc, int bpr, int L) {
+    const long r = blockIdx.x / bpr;
+    const int t = (int)(blockIdx.x - r * bpr) * blockDim.x + threadIdx.x;
+    if (t >= L / 4 || !(loss[r] < pbests[r])) return;
+    *(float4*)(pbest_loc + r * L + t * 4) = *(const float4*)(loc + r * L + t * 4);
+}
+
+// first arg-min of the personal bests of clip b as they will be after the update, and its value
+__device__ inline int pso_best_particle(const float* __restrict__ loss, const float* __restrict__ pbests, long b, int P, float* best) {
+    int k = 0;
+    float m = 0.f;
+    for (int p = 0; p < P; ++p) {
+        const float l = loss[b * P + p], pb = pbests[b * P + p];
+        const float v = l < pb ? l : pb;
+        if (p == 0 || v < m) { k = p; m = v; }
+    }
+    *best = m;
+    return k;
+}
+
+__global__ void pso_gbest_rows_kernel(const float* __restrict__ loss, const float* __restrict__ pbests, const float* __restrict__ gbests,
+                                      const long long* __restrict__ index, const float* __restrict__ pbest_loc,
+                                      float* __restrict__ gbest_loc, int P, int bpr, int L) {
+    __shared__ int sel;
+    const long b = blockIdx.x / bpr;
+    const long i = index ? (long)index[b] : b;
+    if (threadIdx.x == 0) {
+        float m;
+        const int k = pso_best_particle(loss, pbests, b, P, &m);
+        sel = m < gbests[i] ? k : -1;
+    }
+    __syncthreads();
+    const int t = (int)(blockIdx.x - b * bpr) * blockDim.x + threadIdx.x;
+    if (sel < 0 || t >= L / 4) return;
+    *(float4*)(gbest_loc + i * L + t * 4) = *(const float4*)(pbest_loc + (b * P + sel) * L + t * 4);
+}
+
+__global__ void pso_best_scalars_kernel(const float* __restrict__ loss, const long long* __restrict__ predict,
+                                        const long long* __restrict__ index, float* __restrict__ pbests, float* __restrict__ gbests,
+                                        long long* __restrict__ gbest_predict, int B, int P) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const long i = index ? (long)index[b] : b;
+    float m;
+    const int k = pso_best_particle(loss, pbests, b, P, &m);
+    for (int p = 0; p < P; ++p)
+        if (loss[b * P + p] < pbests[b * P + p]) pbests[b * P + p] = loss[b * P + p];
+    if (m < gbests[i]) {
+        gbests[i] = m;
+        gbest_predict[i] = predict[b * P + k];
+    }
+}
+
+// ----------------------------------------------------------------------------------------------
 // fp32 (parity) WaveNet helpers
 // ----------------------------------------------------------------------------------------------
 template <bool SPLIT>      // SPLIT: write the split-f16 storage format (dmad_common.h) for the x3 GEMM tier
@@ -589,6 +741,31 @@ void launch_store_vec128(const float* host128, float* out, hipStream_t s) {
     hipLaunchKernelGGL(store_vec128_kernel, dim3(1), dim3(128), 0, s, a, out);
 }
 
+void launch_philox_uniform(uint64_t seed, uint64_t sample0, uint32_t stream, float* out, int B, int L, hipStream_t s) {
+    hipLaunchKernelGGL(philox_uniform_kernel, dim3(nblk((long)B * (L / 4), 256)), dim3(256), 0, s, seed, sample0, stream, out, B, L);
+}
+void launch_pso_init(const float* x, const float* lower, const float* upper, const float* keep, int B, int P, uint64_t seed, uint64_t draw0,
+                     uint32_t stream, float* pbest_loc, float* loc, float* vel, float* queries, int L, hipStream_t s) {
+    const long rows = (long)B * P;
+    hipLaunchKernelGGL(pso_init_kernel, dim3(nblk(rows * (L / 4), 256)), dim3(256), 0, s, x, lower, upper, keep, P, seed, draw0, stream,
+                       pbest_loc, loc, vel, queries, rows, L);
+}
+void launch_pso_step(const float* x, const float* lower, const float* upper, const float* pbest_loc, const float* gbest_loc, int B, int P,
+                     float w, float c1, float c2, uint64_t seed, uint64_t draw0, uint32_t stream, float* loc, float* vel, float* queries,
+                     int L, hipStream_t s) {
+    const long rows = (long)B * P;
+    hipLaunchKernelGGL(pso_step_kernel, dim3(nblk(rows * (L / 4), 256)), dim3(256), 0, s, x, lower, upper, pbest_loc, gbest_loc, P, w, c1, c2,
+                       seed, draw0, stream, loc, vel, queries, rows, L);
+}
+void launch_pso_update_best(const float* loss, const long long* predict, const float* loc, const long long* index, int B, int P,
+                            float* pbests, float* pbest_loc, float* gbests, float* gbest_loc, long long* gbest_predict, int L,
+                            hipStream_t s) {
+    const int bpr = (int)nblk(L / 4, 256);            // blocks per row
+    hipLaunchKernelGGL(pso_pbest_rows_kernel, dim3((unsigned)((long)B * P * bpr)), dim3(256), 0, s, loss, pbests, loc, pbest_loc, bpr, L);
+    hipLaunchKernelGGL(pso_gbest_rows_kernel, dim3((unsigned)((long)B * bpr)), dim3(256), 0, s, loss, pbests, gbests, index, pbest_loc,
+                       gbest_loc, P, bpr, L);
+    hipLaunchKernelGGL(pso_best_scalars_kernel, dim3(nblk(B, 64)), dim3(64), 0, s, loss, predict, index, pbests, gbests, gbest_predict, B, P);
+}
 void philox4x32_10_host(uint32_t c[4], uint32_t k0, uint32_t k1) { philox4x32_10(c, k0, k1); }
 
 }  // namespace dmad

@@ -107,6 +107,11 @@ _SIGNATURES = {
     'dmad_spec_recheck_stats2': (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]),
     'dmad_nes_probes': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, _P, _P]),
     'dmad_nes_grad': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint64, C.c_int32, _P, _P]),
+    'dmad_philox_uniform': (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, _P, _P]),
+    'dmad_pso_init': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P]),
+    'dmad_pso_step': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_uint64,
+                                _P, _P, _P, _P]),
+    'dmad_pso_update_best': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     'dmad_vote': (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     'dmad_philox_raw': (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     'dmad_philox_normal': (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, _P, _P]),

@@ -21,6 +21,7 @@ MODE_FAST, MODE_EXACT_VOTES, MODE_FP32 = 0, 1, 2  # enum dmad_mode (EXACT engine
 HALF_BF16, HALF_F16 = 0, 1                        # enum dmad_half_type: operand format of the 16-bit MFMA path
 WAVE_16BIT, WAVE_FP32, WAVE_SPLIT = 0, 1, 2       # dmad_set_waveform_tier: WaveNet tier of the waveform-returning surfaces (EXACT engines)
 NES_STREAM = 0x4E450000                           # DMAD_PHILOX_STREAM_NES: the Philox stream of the NES probe directions
+PSO_STREAM = 0x50530000                           # DMAD_PHILOX_STREAM_PSO: + 0 positions, 1 velocities, 2 r1, 3 r2 of the particle swarm
 # Recheck bound of the exact-vote mode: a Monte Carlo sample whose 16-bit-path top-2 logit margin is below it is
 # re-evaluated on the higher tiers.  Let i be the exact path's arg-max and e = (16-bit logits) - (exact logits).  If the 16-bit
 # margin is >= tau and the 16-bit leader were some j != i, then l~_j - l~_i >= tau with l_j - l_i <= 0, i.e. e_j - e_i >= tau:
@@ -864,6 +865,83 @@ class Engine:
             grad = torch.empty((B, self.L), device=w.device, dtype=torch.float32)
         check(self.lib.dmad_nes_grad(self._h, _ptr(w), B, int(P), float(scale), int(seed), int(draw0), int(accumulate), _ptr(grad), _stream()))
         return grad
+
+    def _owned(self, t: Optional[torch.Tensor], shape, dtype=torch.float32, name='state') -> torch.Tensor:
+        """A caller-owned tensor a swarm call updates in place: checked, never copied; None -> a new one."""
+        if t is None:
+            return torch.empty(shape, device=self.device, dtype=dtype)
+        if not t.is_cuda:
+            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
+        assert t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == tuple(shape), \
+            '%s: expected contiguous %s %s, got %s %s' % (name, dtype, tuple(shape), t.dtype, tuple(t.shape))
+        return t
+
+    def pso_init(self, x: torch.Tensor, lower: torch.Tensor, upper: torch.Tensor, P: int, seed: int = 0, draw0: int = 0,
+                 keep: Optional[torch.Tensor] = None, pbest_loc: Optional[torch.Tensor] = None, loc: Optional[torch.Tensor] = None,
+                 vel: Optional[torch.Tensor] = None, queries: Optional[torch.Tensor] = None):
+        """dmad_pso_init: x, lower, upper (and keep) [B,1,L] or [B,L] -> (pbest_loc, loc, vel, queries), each [B*P, L], row b*P+p particle p
+        of clip b: positions uniform in [lower, upper] (particle 0 = keep[b] when given), velocities uniform in +-|lower - upper|,
+        loc = pbest_loc, queries = loc + x[b]; draws keyed (seed, draw0 + b*P + p, PSO_STREAM + {0, 1}).  State tensors passed in are
+        written in place."""
+        xw, lo, up = self._wave(x), self._wave(lower), self._wave(upper)
+        B, P = xw.shape[0], int(P)
+        assert lo.shape == up.shape == xw.shape, 'x, lower and upper must have one shape'
+        kp = None if keep is None else self._wave(keep)
+        assert kp is None or kp.shape == xw.shape, 'keep must have the shape of x'
+        pbest_loc, loc, vel, queries = (self._owned(t, (B * P, self.L), name=n) for t, n in
+                                        ((pbest_loc, 'pbest_loc'), (loc, 'loc'), (vel, 'vel'), (queries, 'queries')))
+        check(self.lib.dmad_pso_init(self._h, _ptr(xw), _ptr(lo), _ptr(up), B, P, _ptr(kp), int(seed), int(draw0), _ptr(pbest_loc), _ptr(loc),
+                                     _ptr(vel), _ptr(queries), _stream()))
+        return pbest_loc, loc, vel, queries
+
+    def pso_step(self, x: torch.Tensor, lower: torch.Tensor, upper: torch.Tensor, pbest_loc: torch.Tensor, gbest_loc: torch.Tensor, P: int,
+                 w: float, c1: float, c2: float, seed: int, draw0: int, loc: torch.Tensor, vel: torch.Tensor,
+                 queries: Optional[torch.Tensor] = None):
+        """dmad_pso_step: vel <- w vel + c1 r1 (pbest_loc - loc) + c2 r2 (gbest_loc[b] - loc), loc <- clamp(loc + vel, lower, upper),
+        queries <- loc + x[b], with r = uniform + 1e-5 keyed (seed, draw0 + b*P + p, PSO_STREAM + {2, 3}).  loc, vel (and queries) are
+        updated in place and returned; gbest_loc is [B,1,L] or [B,L] in the order of x."""
+        xw, lo, up, gb = self._wave(x), self._wave(lower), self._wave(upper), self._wave(gbest_loc)
+        B, P = xw.shape[0], int(P)
+        assert lo.shape == up.shape == gb.shape == xw.shape, 'x, lower, upper and gbest_loc must have one shape'
+        rows = (B * P, self.L)
+        pbest_loc, loc, vel = self._owned(pbest_loc, rows, name='pbest_loc'), self._owned(loc, rows, name='loc'), self._owned(vel, rows, name='vel')
+        queries = self._owned(queries, rows, name='queries')
+        check(self.lib.dmad_pso_step(self._h, _ptr(xw), _ptr(lo), _ptr(up), _ptr(pbest_loc), _ptr(gb), B, P, float(w), float(c1), float(c2),
+                                     int(seed), int(draw0), _ptr(loc), _ptr(vel), _ptr(queries), _stream()))
+        return loc, vel, queries
+
+    def pso_update_best(self, loss: torch.Tensor, predict: torch.Tensor, loc: torch.Tensor, pbests: torch.Tensor, pbest_loc: torch.Tensor,
+                        gbests: torch.Tensor, gbest_loc: torch.Tensor, gbest_predict: torch.Tensor, index: Optional[torch.Tensor] = None):
+        """dmad_pso_update_best: loss fp32 [B,P], predict int64 [B,P], loc [B*P,L]; where loss < pbests the personal bests take loss and
+        loc; then the first arg-min k of pbests[b] replaces the global best of row i = index[b] (b without index) of gbests [N],
+        gbest_loc [N,L] / [N,1,L], gbest_predict int64 [N] where pbests[b][k] < gbests[i].  The five best tensors are updated in place and
+        returned."""
+        if not loss.is_cuda:
+            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
+        assert loss.dim() == 2, 'expected loss [B,P], got %s' % (tuple(loss.shape),)
+        B, P = loss.shape
+        loss = self._owned(loss.detach().contiguous().float(), (B, P), name='loss')
+        predict = self._owned(predict.contiguous(), (B, P), torch.int64, 'predict')
+        loc, pbest_loc = self._owned(loc, (B * P, self.L), name='loc'), self._owned(pbest_loc, (B * P, self.L), name='pbest_loc')
+        pbests = self._owned(pbests, (B, P), name='pbests')
+        assert gbests.dim() == 1, 'expected gbests [N]'
+        N = gbests.shape[0]
+        gbests, gbest_predict = self._owned(gbests, (N,), name='gbests'), self._owned(gbest_predict, (N,), torch.int64, 'gbest_predict')
+        assert gbest_loc.is_cuda and gbest_loc.is_contiguous() and gbest_loc.dtype == torch.float32 and gbest_loc.numel() == N * self.L, \
+            'gbest_loc: expected contiguous fp32 [%d,%d]' % (N, self.L)
+        if index is None:
+            assert N == B, 'without index, gbests must have one row per clip'
+        else:
+            index = self._owned(index, (B,), torch.int64, 'index')
+        check(self.lib.dmad_pso_update_best(self._h, _ptr(loss), _ptr(predict), _ptr(loc), _ptr(index), B, P, _ptr(pbests), _ptr(pbest_loc),
+                                            _ptr(gbests), _ptr(gbest_loc), _ptr(gbest_predict), _stream()))
+        return pbests, pbest_loc, gbests, gbest_loc, gbest_predict
+
+    def philox_uniform(self, seed: int, sample0: int, stream: int, B: int) -> torch.Tensor:
+        """dmad_philox_uniform: [B, L], row b the uniforms ((word >> 8) + 0.5) * 2^-24 of key (seed, sample0 + b, stream)."""
+        out = torch.empty((B, self.L), dtype=torch.float32, device=self.device)
+        check(self.lib.dmad_philox_uniform(self._h, int(seed), int(sample0), int(stream), int(B), _ptr(out), _stream()))
+        return out
 
     def philox_raw(self, seed: int, sample: int, stream: int, nblocks: int) -> torch.Tensor:
         out = torch.empty(nblocks * 4, dtype=torch.int32, device=self.device)

@@ -456,8 +456,10 @@ int dmad_spec_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t re
  * DMAD_PHILOX_STREAM_NES) returns; both calls below produce exactly those bits.
  * Philox stream ids in use, which a new draw must not collide with: 0 (smoothing noise of the vote loops), 1 + t for t < T (DDPM reverse
  * step t), 0x0E70 + t (spec-domain p_sample at t), 0x5BEC (spec-domain q_sample), 0xD1FF (DiffWave diffusion draw), 0x5DE00000 + n
- * (reverse VP-SDE: diffusion draw and Euler steps), 0x5DF00000 + n (the same on the spectrogram), 0x4E450000 (NES directions). */
+ * (reverse VP-SDE: diffusion draw and Euler steps), 0x5DF00000 + n (the same on the spectrogram), 0x4E450000 (NES directions),
+ * 0x50530000 + k for k < 4 (particle swarm: 0 positions, 1 velocities, 2 r1, 3 r2). */
 #define DMAD_PHILOX_STREAM_NES 0x4E450000u
+#define DMAD_PHILOX_STREAM_PSO 0x50530000u
 
 /* Query rows [row0, row0 + rows) of the reference's layout (_NES.py:19-25: noise = cat(noise, -noise), the zero probe in front on the
  * first draw batch, eval_input = noise * sigma + x).  The layout is clip-major with per_clip = P + with_origin rows per clip: the optional
@@ -475,6 +477,49 @@ int dmad_nes_probes(dmad_engine* e, const float* x, int32_t B, int32_t P, float 
  * atomics: the result is bit-reproducible and a clip's row does not depend on B.  P even and >= 2. */
 int dmad_nes_grad(dmad_engine* e, const float* w, int32_t B, int32_t P, float scale, uint64_t seed, uint64_t draw0, int32_t accumulate,
                   float* grad, dmad_stream s);
+
+/* Particle swarm of SirenAttack (robustness_eval/black_box_attack.py:344-498) without its host-side draws and loops.  The state is
+ * caller-owned device fp32; nothing is allocated.  Row r = b * P + p (clip-major, P = n_particles) of the [B * P][clip_len] arrays loc,
+ * vel, pbest_loc and queries is particle p of clip b; x, lower, upper (and keep, gbest_loc of dmad_pso_step) are [B][clip_len]; pbests is
+ * [B][P].  A uniform draw is u = ((float)(word >> 8) + 0.5f) * 2^-24 in fp32 — the uniforms dmad_philox_normal feeds to Box-Muller — of
+ * the Philox words at counter (block = l / 4, sample, stream) under key seed, with sample = draw0 + b * P + p and stream =
+ * DMAD_PHILOX_STREAM_PSO + {0 position, 1 velocity, 2 r1, 3 r2}.  One swarm event (an init or a step) consumes B * P sample keys: the
+ * caller advances draw0 by that much.  Every product, sum and difference is rounded to fp32 on its own (no contraction), there are no
+ * atomics, and a row is a function of its key and its inputs only, never of B.  B < 1, P < 1 or a required pointer that is null:
+ * DMAD_ERR_INVALID.
+ *
+ * dmad_philox_uniform (test hook, the uniform twin of dmad_philox_normal): out[b] = the clip_len uniforms of key (seed, sample0 + b,
+ * stream); out: device fp32 [B][clip_len]. */
+int dmad_philox_uniform(dmad_engine* e, uint64_t seed, uint64_t sample0, uint32_t stream, int32_t B, float* out, dmad_stream s);
+
+/* A new swarm (black_box_attack.py:371-391: the np.random.uniform positions and velocities of an epoch; l.404: the query rows).
+ *   pbest_loc[r] = clamp(lower + (upper - lower) * u_pos, lower, upper);   vel[r] = -d + (2 d) * u_vel,  d = |lower - upper|;
+ *   loc = pbest_loc;   queries[r] = loc[r] + x[b].
+ * keep (optional, [B][clip_len]): particle 0 of clip b is keep[b] bit for bit — the best personal best an epoch carries into the next,
+ * l.377-382; its position key is unused and every other particle is what the call without keep gives it. */
+int dmad_pso_init(dmad_engine* e, const float* x, const float* lower, const float* upper, int32_t B, int32_t P, const float* keep,
+                  uint64_t seed, uint64_t draw0, float* pbest_loc, float* loc, float* vel, float* queries, dmad_stream s);
+
+/* One swarm move (black_box_attack.py:474-484: np.random.rand r1 and r2, the velocity and position update, the clamp; l.404), in place:
+ *   r1 = fl(u_r1 + 1e-5f), r2 likewise;
+ *   vel <- fl(fl(fl(w vel) + fl(fl(c1 r1) fl(pbest_loc - loc))) + fl(fl(c2 r2) fl(gbest_loc[b] - loc)))   (the reference's expression,
+ *   left to right);   loc <- min(max(fl(loc + vel), lower), upper);   queries <- fl(loc + x[b]).
+ * gbest_loc: [B][clip_len], the global best of every working clip, in working-set order. */
+int dmad_pso_step(dmad_engine* e, const float* x, const float* lower, const float* upper, const float* pbest_loc, const float* gbest_loc,
+                  int32_t B, int32_t P, float w, float c1, float c2, uint64_t seed, uint64_t draw0, float* loc, float* vel, float* queries,
+                  dmad_stream s);
+
+/* The bests after an evaluation (black_box_attack.py:420-437: torch.where(loss < pbests) with its loop of row copies, the arg-min and
+ * the per-clip loop on gbests), without a host round trip.  loss: device fp32 [B][P]; predict: device int64 [B][P]; index: optional
+ * device int64 [B] of distinct rows, the row of gbests / gbest_loc / gbest_predict a working clip owns (null: row b).
+ *   where loss[b][p] < pbests[b][p]:  pbests[b][p] <- loss[b][p], pbest_loc[b * P + p] <- loc[b * P + p];
+ *   then, k = the first arg-min of the updated pbests[b], i = index ? index[b] : b:  if pbests[b][k] < gbests[i]:
+ *   gbests[i] <- pbests[b][k], gbest_loc[i] <- pbest_loc[b * P + k], gbest_predict[i] <- predict[b][k].
+ * A comparison that is false, with a NaN too, changes nothing (pbests itself must be free of NaN, as it is when it starts at +inf).
+ * Three launches in stream order — the personal-best rows, the global-best rows, then the scalars — so that every block that copies a
+ * row decides from the scalars as they were before the call. */
+int dmad_pso_update_best(dmad_engine* e, const float* loss, const int64_t* predict, const float* loc, const int64_t* index, int32_t B,
+                         int32_t P, float* pbests, float* pbest_loc, float* gbests, float* gbest_loc, int64_t* gbest_predict, dmad_stream s);
 
 /* counts[argmax_c logits[b][c]] += 1 (first maximum wins) — certified_robust.py:59-65. */
 int dmad_vote(dmad_engine* e, const float* logits, int32_t B, int64_t* counts, dmad_stream s);
