@@ -6,6 +6,7 @@ package (DiffWave, MelSpectrogramDB, VGG) or any callables the caller passes.
 `query(x, repeats)` is the batched entry of the gradient-free attack drivers (EOT / NES): every clip evaluated
 `repeats` times with fresh purification noise.  When the three stages are this package's HIP stages on one engine it is
 ONE C-ABI call — dmad_query_logits for defense_type 'wave' (repeat -> DDPM purify -> mel dB -> classifier -> arg-max),
+dmad_defense_query_logits for a baseline waveform defense (TimeDomainDefense / FreqDomainDefense on backend 'hip'),
 dmad_spec_query_logits for 'spec' (repeat -> mel dB -> spec-domain purifier -> classifier -> arg-max); otherwise it loops over
 forward()."""
 import torch
@@ -60,6 +61,11 @@ class AcousticSystem(torch.nn.Module):
             return (eng, 3) if (type(den) is SpecPurifier and den.engine is eng) else (None, 0)
         if type(den) is DiffWave and den.noise_source == 'device' and den.engine is eng and eng.has_wavenet:
             return eng, 1
+        from transforms.time_defense import TimeDomainDefense
+        from transforms.frequency_defense import FreqDomainDefense
+        if ((type(den) is TimeDomainDefense and den.defense_type in ('AS', 'MS')) or
+                (type(den) is FreqDomainDefense and den.defense_type in ('DS', 'LPF', 'BPF'))) and den.backend == 'hip' and den.engine is eng:
+            return eng, 4                                             # sampler 4: a baseline waveform defense (dmad_defense_query_logits)
         return None, 0
 
     @torch.no_grad()
@@ -84,6 +90,9 @@ class AcousticSystem(torch.nn.Module):
                 logits, dec = eng.spec_query_logits(x, repeats, *den.purifier.purify_coefficients(), MEL_LOWER_BOUND, MEL_UPPER_BOUND,
                                                     seed=den.seed, sample0=den._draws)
                 den._draws += repeats * B
+            elif sampler == 4:
+                den = self.defender
+                logits, dec = eng.defense_query_logits(x, repeats, den.engine_defense(x))
             else:
                 logits, dec = eng.query_logits(x, repeats, 0)
             return logits.view(repeats, B, -1), dec.view(repeats, B).long()

@@ -9,8 +9,8 @@ AcousticSystem(classifier, MelSpectrogramDB, defender) with the defenses
   * Diffusion       RevDiffWave (the reverse VP-SDE on the waveform, diffusion_models/diffwave_sde.py);
   * Diffusion-Spec  RevImprovedDiffusion (the reverse VP-SDE on the spectrogram, diffusion_models/improved_diffusion_sde.py).
 Every other attack (Qin-I, Kenansville, FAKEBOB, SirenAttack) and defense (AS, MS, DS, LPF, BPF, FeCo, DefenseGAN) raises
-NotImplementedError naming the piece this package does not have (FAKEBOB and SirenAttack: the driver that runs it,
-black_box_attack_eval.py and siren_attack_eval.py).
+NotImplementedError naming the piece this package does not have, or the driver that runs it (FAKEBOB and SirenAttack:
+black_box_attack_eval.py and siren_attack_eval.py; the baseline defenses AS, MS, DS, LPF, BPF: baseline_defense_eval.py).
 
 Additions to the reference's flags:
   * `--classifier_path`: the classifier checkpoint; its default is the path the reference hard-codes (it overrides
@@ -39,12 +39,8 @@ _MISSING_ATTACK = {
     'Kenansville': 'the black-box attacks (robustness_eval/black_box_attack.py)',
 }
 _OTHER_DRIVER = {'FAKEBOB': 'black_box_attack_eval.py', 'SirenAttack': 'siren_attack_eval.py'}    # attacks run by a driver of their own
+BASELINE_DEFENSES = ['AS', 'MS', 'DS', 'LPF', 'BPF']                # transforms/time_defense.py, transforms/frequency_defense.py
 _MISSING_DEFENSE = {
-    'AS': 'the time-domain defenses (transforms/time_defense.py)',
-    'MS': 'the time-domain defenses (transforms/time_defense.py)',
-    'DS': 'the frequency-domain defenses (transforms/frequency_defense.py)',
-    'LPF': 'the frequency-domain defenses (transforms/frequency_defense.py)',
-    'BPF': 'the frequency-domain defenses (transforms/frequency_defense.py)',
     'FeCo': 'the feature-compression defense (transforms/feature_defense.py)',
     'DefenseGAN': 'the DefenseGAN purifier (gan_models/DefenseGAN.py)',
 }
@@ -121,6 +117,9 @@ def check_supported(args):
 
 def check_defense(args):
     """The part of check_supported that does not depend on the attack (shared with black_box_attack_eval.py): the defense and --save_path."""
+    if args.defense in BASELINE_DEFENSES:
+        raise NotImplementedError('--defense %s is a baseline waveform defense: baseline_defense_eval.py runs it (with --attack CW, FAKEBOB '
+                                  'or SirenAttack), this driver does not (supported: None, Diffusion, Diffusion-Spec)' % args.defense)
     if args.defense in _MISSING_DEFENSE:
         raise NotImplementedError('--defense %s needs %s, which this package does not provide (supported: None, Diffusion, Diffusion-Spec)'
                                   % (args.defense, _MISSING_DEFENSE[args.defense]))
@@ -143,17 +142,8 @@ def _save_wav(x, path, name):
 def build_system(args, classifier=None, defender=None):
     """AcousticSystem of the driver's flags.  `classifier` / `defender` may be passed ready-made (tests, synthetic weights)."""
     from acoustic_system import AcousticSystem
-    from audio_models.ConvNets_SpeechCommands.create_model import create_model
-    from dmad_hip.transforms import MelSpectrogramDB
     check_defense(args)
-    if classifier is None:
-        classifier = create_model(args.classifier_path)
-    classifier.cuda()
-    if hasattr(classifier, 'bind_engine') and 'engine' not in classifier.__dict__:
-        classifier.bind_engine()
-    if 'torch' in getattr(classifier, 'GRAD_BACKENDS', ()) and 'hip' in classifier.GRAD_BACKENDS:    # ResNeXt29 (VGG19_bn: torch layers)
-        classifier.grad_backend = args.grad_backend
-    wave2spect = MelSpectrogramDB(classifier.__dict__.get('engine'), grad_backend=args.grad_backend)
+    classifier, wave2spect = build_front(args, classifier)
     kw = {} if args.score_grad is None else {'score_grad': args.score_grad}
     if args.defense == 'None':
         return AcousticSystem(classifier=classifier, transform=wave2spect, defender=None), classifier
@@ -174,12 +164,32 @@ def build_system(args, classifier=None, defender=None):
     return system, classifier
 
 
+def build_front(args, classifier=None):
+    """The classifier of the driver's flags on its engine, and the mel front-end on the same engine (shared with baseline_defense_eval.py)."""
+    from audio_models.ConvNets_SpeechCommands.create_model import create_model
+    from dmad_hip.transforms import MelSpectrogramDB
+    if classifier is None:
+        classifier = create_model(args.classifier_path)
+    classifier.cuda()
+    if hasattr(classifier, 'bind_engine') and 'engine' not in classifier.__dict__:
+        classifier.bind_engine()
+    if 'torch' in getattr(classifier, 'GRAD_BACKENDS', ()) and 'hip' in classifier.GRAD_BACKENDS:    # ResNeXt29 (VGG19_bn: torch layers)
+        classifier.grad_backend = args.grad_backend
+    return classifier, MelSpectrogramDB(classifier.__dict__.get('engine'), grad_backend=args.grad_backend)
+
+
 def run(args, classifier=None, defender=None, log=print):
     """The reference's evaluation loop.  Returns {'total', 'clean_acc', 'denoised_acc', 'robust_acc'} (accuracies in percent)."""
     from robustness_eval.white_box_attack import AudioAttack
     check_supported(args)
     torch.cuda.set_device(args.gpu)
     AS_MODEL, classifier = build_system(args, classifier, defender)
+    return evaluate(args, AS_MODEL, classifier, attacker_factory(args, AS_MODEL, log), log)
+
+
+def attacker_factory(args, AS_MODEL, log=print):
+    """make_attacker() of evaluate(): the CW attacker of the driver's flags (shared with baseline_defense_eval.py)."""
+    from robustness_eval.white_box_attack import AudioAttack
 
     def make_attacker():
         Attacker = AudioAttack(model=AS_MODEL, eps=args.eps, norm=args.bound_norm, max_iter_1=args.max_iter_1, max_iter_2=0,
@@ -188,7 +198,7 @@ def run(args, classifier=None, defender=None, log=print):
         log('attack: {} with {}_eps={} & iter={} & eot={}-{}'.format(args.attack, args.bound_norm, args.eps, args.max_iter_1,
                                                                     args.eot_attack_size, args.eot_defense_size))
         return Attacker
-    return evaluate(args, AS_MODEL, classifier, make_attacker, log)
+    return make_attacker
 
 
 def evaluate(args, AS_MODEL, classifier, make_attacker, log=print):

@@ -43,9 +43,14 @@ def check_supported(args):
 def run(args, classifier=None, defender=None, log=print, **attack_overrides):
     """The reference's evaluation loop.  Returns {'total', 'clean_acc', 'denoised_acc', 'robust_acc'} (accuracies in percent)."""
     check_supported(args)
-    from robustness_eval.black_box_attack import FAKEBOB
     torch.cuda.set_device(args.gpu)
     AS_MODEL, classifier = white_box.build_system(args, classifier, defender)
+    return white_box.evaluate(args, AS_MODEL, classifier, attacker_factory(args, AS_MODEL, log, **attack_overrides), log)
+
+
+def attacker_factory(args, AS_MODEL, log=print, **attack_overrides):
+    """make_attacker() of evaluate(): the FAKEBOB attacker of the driver's flags and constants (shared with baseline_defense_eval.py)."""
+    from robustness_eval.black_box_attack import FAKEBOB
 
     def make_attacker():
         k = dict(ATTACKER_CONSTANTS, **attack_overrides)
@@ -55,7 +60,7 @@ def run(args, classifier=None, defender=None, log=print, **attack_overrides):
         log('attack: {} with eps={} & confidence={} & iter={} & samples_per_draw={}\n'.format(args.attack, k['epsilon'], k['confidence'],
                                                                                             k['max_iter'], k['samples_per_draw']))
         return Attacker
-    return white_box.evaluate(args, AS_MODEL, classifier, make_attacker, log)
+    return make_attacker
 
 
 if __name__ == '__main__':

@@ -17,6 +17,7 @@
 #include "classifier_vjp.h"
 #include "unet_ops.h"
 #include "elementwise.h"
+#include "wave_defense.h"
 #include "gemm_f32.h"
 #include "gemm_h16.h"
 #include "wn_bf16.h"
@@ -3017,6 +3018,107 @@ int dmad_pso_update_best(dmad_engine* e, const float* loss, const int64_t* predi
     if (B < 1 || P < 1) return fail(DMAD_ERR_INVALID, "dmad_pso_update_best: B %d and P %d must be >= 1", B, P);
     launch_pso_update_best(loss, (const long long*)predict, loc, (const long long*)index, B, P, pbests, pbest_loc, gbests, gbest_loc,
                            (long long*)gbest_predict, e->L, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+// time_defense.py:102-127 (AS: F.conv1d with a 1 / w kernel, zero padding) and l.130-157 (MS: F.pad zeros, unfold, torch.median)
+int dmad_wave_smooth(dmad_engine* e, const float* x, int32_t B, int32_t kind, int32_t window, float* y, dmad_stream s) {
+    if (!e || !x || !y) return fail(DMAD_ERR_INVALID, "dmad_wave_smooth: null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "dmad_wave_smooth: B %d must be >= 1", B);
+    if (const char* m = wave_smooth_check(kind, window)) return fail(DMAD_ERR_INVALID, "dmad_wave_smooth: %s (kind %d, window %d)", m, kind, window);
+    launch_wave_smooth(x, B, e->L, kind, window, y, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+// the mean is symmetric under zero padding: its VJP is the forward kernel on g_y; the median routes g_y[t] to the window position it came from
+int dmad_wave_smooth_vjp(dmad_engine* e, const float* x, const float* g_y, int32_t B, int32_t kind, int32_t window, float* g_x, dmad_stream s) {
+    if (!e || !g_y || !g_x || (kind == 1 && !x)) return fail(DMAD_ERR_INVALID, "dmad_wave_smooth_vjp: null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "dmad_wave_smooth_vjp: B %d must be >= 1", B);
+    if (const char* m = wave_smooth_check(kind, window)) return fail(DMAD_ERR_INVALID, "dmad_wave_smooth_vjp: %s (kind %d, window %d)", m, kind, window);
+    if (kind == 0) launch_wave_smooth(g_y, B, e->L, 0, window, g_x, (hipStream_t)s);
+    else launch_wave_median_vjp(x, g_y, B, e->L, window, g_x, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+// frequency_defense.py:53-56 (torchaudio Resample down and up: F.conv1d of the padded clip with the sinc kernel, stride orig)
+int dmad_wave_resample(dmad_engine* e, const float* x, int32_t B, int32_t L_in, const float* ker, int32_t phases, int32_t taps, int32_t stride,
+                       int32_t width, int32_t L_out, float* y, dmad_stream s) {
+    if (!e || !x || !y || !ker) return fail(DMAD_ERR_INVALID, "dmad_wave_resample: null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "dmad_wave_resample: B %d must be >= 1", B);
+    if (const char* m = wave_resample_check(ker, L_in, phases, taps, stride, width, L_out)) return fail(DMAD_ERR_INVALID, "dmad_wave_resample: %s", m);
+    launch_wave_resample(x, B, L_in, ker, phases, taps, stride, width, L_out, y, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_wave_resample_vjp(dmad_engine* e, const float* g_y, int32_t B, int32_t L_in, const float* ker, int32_t phases, int32_t taps,
+                           int32_t stride, int32_t width, int32_t L_out, float* g_x, dmad_stream s) {
+    if (!e || !g_y || !g_x || !ker) return fail(DMAD_ERR_INVALID, "dmad_wave_resample_vjp: null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "dmad_wave_resample_vjp: B %d must be >= 1", B);
+    if (const char* m = wave_resample_check(ker, L_in, phases, taps, stride, width, L_out)) return fail(DMAD_ERR_INVALID, "dmad_wave_resample_vjp: %s", m);
+    launch_wave_resample_vjp(g_y, B, L_in, ker, phases, taps, stride, width, L_out, g_x, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+// frequency_defense.py:85-98 / 125-139 (lfilter one clip at a time on the CPU, then clamp) as one launch, parallel along time
+int dmad_wave_iir(dmad_engine* e, const float* x, int32_t B, const float* b, const float* a, int32_t order, float lo, float hi, float* y,
+                  dmad_stream s) {
+    if (!e || !x || !y || !b || !a) return fail(DMAD_ERR_INVALID, "dmad_wave_iir: null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "dmad_wave_iir: B %d must be >= 1", B);
+    if (!(hi >= lo)) return fail(DMAD_ERR_INVALID, "dmad_wave_iir: empty clamp range");
+    IirPlan plan;
+    if (const char* m = iir_plan(b, a, order, e->L, &plan)) return fail(DMAD_ERR_INVALID, "dmad_wave_iir: %s (order %d)", m, order);
+    HIPCHK((hipError_t)launch_wave_iir(plan, x, nullptr, B, e->L, lo, hi, 0, y, nullptr, (hipStream_t)s));
+    LASTCHK();
+    return 0;
+}
+
+// the adjoint of the clamped filter: the same kernel, backwards in time, on g_y masked by the recomputed unclamped forward
+int dmad_wave_iir_vjp(dmad_engine* e, const float* x, const float* g_y, int32_t B, const float* b, const float* a, int32_t order, float lo,
+                      float hi, float* g_x, float* y_or_null, dmad_stream s) {
+    if (!e || !x || !g_y || !g_x || !b || !a) return fail(DMAD_ERR_INVALID, "dmad_wave_iir_vjp: null argument");
+    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_INVALID, "dmad_wave_iir_vjp: B %d outside [1, max_batch = %d]", B, e->maxB);
+    if (!(hi >= lo)) return fail(DMAD_ERR_INVALID, "dmad_wave_iir_vjp: empty clamp range");
+    IirPlan plan;
+    if (const char* m = iir_plan(b, a, order, e->L, &plan)) return fail(DMAD_ERR_INVALID, "dmad_wave_iir_vjp: %s (order %d)", m, order);
+    HIPCHK((hipError_t)launch_wave_iir(plan, x, nullptr, B, e->L, lo, hi, 0, y_or_null, e->eps, (hipStream_t)s));
+    HIPCHK((hipError_t)launch_wave_iir(plan, g_y, e->eps, B, e->L, lo, hi, 1, g_x, nullptr, (hipStream_t)s));
+    LASTCHK();
+    return 0;
+}
+
+// adaptive_attack_eval.py:190-201 (AcousticSystem with a Time / FreqDomainDefense as its defender) behind the query layout of
+// dmad_query_logits
+int dmad_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, const dmad_wave_defense* d, float* logits,
+                              int32_t* decisions, dmad_stream s) {
+    if (!e || !x || !logits || !d) return fail(DMAD_ERR_INVALID, "dmad_defense_query_logits: null argument");
+    if (B < 1 || repeats < 1) return fail(DMAD_ERR_INVALID, "dmad_defense_query_logits: B and repeats must be >= 1");
+    IirPlan plan;
+    if (const char* m = wave_defense_check(d, e->L, &plan)) return fail(DMAD_ERR_INVALID, "dmad_defense_query_logits: %s", m);
+    if (!e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
+    hipStream_t st = (hipStream_t)s;
+    const int L = e->L, C = e->cfg.num_classes;
+    const long rows = (long)B * repeats;
+    for (long r0 = 0; r0 < rows; r0 += e->maxB) {
+        const int nb = (int)(rows - r0 < e->maxB ? rows - r0 : e->maxB);
+        launch_repeat_rows(x, e->xt, B, r0, nb, L, st);
+        switch (d->kind) {
+        case DMAD_WAVE_AS: launch_wave_smooth(e->xt, nb, L, 0, d->window, e->x0, st); break;
+        case DMAD_WAVE_MS: launch_wave_smooth(e->xt, nb, L, 1, d->window, e->x0, st); break;
+        case DMAD_WAVE_DS:
+            launch_wave_resample(e->xt, nb, L, d->down_ker, d->down_phases, d->down_taps, d->down_stride, d->down_width, d->down_len, e->eps, st);
+            launch_wave_resample(e->eps, nb, d->down_len, d->up_ker, d->up_phases, d->up_taps, d->up_stride, d->up_width, L, e->x0, st);
+            break;
+        default: HIPCHK((hipError_t)launch_wave_iir(plan, e->xt, nullptr, nb, L, d->lo, d->hi, 0, e->x0, nullptr, st)); break;
+        }
+        CHK(mel_db(e, e->x0, nb, e->spec, st));
+        CHK(classify(e, e->spec, nb, logits + r0 * C, st));       // the fp32 classifier, like dmad_query_logits
+        if (decisions) launch_vote(logits + r0 * C, nb, C, nullptr, decisions + r0, st);
+    }
     LASTCHK();
     return 0;
 }

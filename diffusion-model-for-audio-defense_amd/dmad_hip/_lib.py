@@ -28,7 +28,21 @@ class DmadConfig(C.Structure):
         super().__init__(C.sizeof(type(self)), *fields, **named)
 
 
+class DmadWaveDefense(C.Structure):
+    """dmad_wave_defense of include/dmad.h (host pointers); struct_size is filled in here."""
+    _PF = C.POINTER(C.c_float)
+    _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'kind', 'window', 'order')] + [('down_ker', _PF)] +
+                [(n, C.c_int32) for n in ('down_phases', 'down_taps', 'down_stride', 'down_width', 'down_len', 'up_phases', 'up_taps',
+                                          'up_stride', 'up_width')] +
+                [('up_ker', _PF), ('b', _PF), ('a', _PF), ('lo', C.c_float), ('hi', C.c_float)])
+
+    def __init__(self, **named):
+        super().__init__(**named)
+        self.struct_size = C.sizeof(type(self))
+
+
 _P = C.c_void_p
+_PF = C.POINTER(C.c_float)
 _SIGNATURES = {
     'dmad_create': (C.c_int, [C.POINTER(DmadConfig), C.POINTER(_P)]),
     'dmad_destroy': (None, [_P]),
@@ -112,6 +126,13 @@ _SIGNATURES = {
     'dmad_pso_step': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_uint64,
                                 _P, _P, _P, _P]),
     'dmad_pso_update_best': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    'dmad_wave_smooth': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_wave_smooth_vjp': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_wave_resample': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_wave_resample_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_wave_iir': (C.c_int, [_P, _P, C.c_int32, _PF, _PF, C.c_int32, C.c_float, C.c_float, _P, _P]),
+    'dmad_wave_iir_vjp': (C.c_int, [_P, _P, _P, C.c_int32, _PF, _PF, C.c_int32, C.c_float, C.c_float, _P, _P, _P]),
+    'dmad_defense_query_logits': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(DmadWaveDefense), _P, _P, _P]),
     'dmad_vote': (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     'dmad_philox_raw': (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     'dmad_philox_normal': (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, _P, _P]),

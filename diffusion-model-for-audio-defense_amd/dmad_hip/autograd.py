@@ -253,3 +253,55 @@ class MelDBHIP(torch.autograd.Function):
 def mel_db_hip(engine, x: torch.Tensor) -> torch.Tensor:
     """[B,1,16000] -> [B,1,32,32] dB mel spectrogram on the engine, differentiable in x (MelDBHIP)."""
     return MelDBHIP.apply(x, engine)
+
+
+class WaveSmoothHIP(torch.autograd.Function):
+    """[B,L] -> [B,L] zero-padded windowed mean (kind 0, AS) or median (kind 1, MS) on the engine (wave_smooth); the backward is the
+    engine's VJP (dmad_wave_smooth_vjp: the mean is its own transpose, the median routes by the lowest-position rule)."""
+
+    @staticmethod
+    def forward(ctx, x, engine, kind, window):
+        _require_cuda(x)
+        ctx.engine, ctx.kind, ctx.window = engine, int(kind), int(window)
+        ctx.save_for_backward(x)
+        return engine.wave_smooth(x, kind, window)
+
+    @staticmethod
+    def backward(ctx, g_y):
+        x, = ctx.saved_tensors
+        g = ctx.engine.wave_smooth_vjp(x, g_y.contiguous(), ctx.kind, ctx.window)
+        return g.view(x.shape).to(x.dtype), None, None, None
+
+
+class WaveResampleHIP(torch.autograd.Function):
+    """[B,L_in] -> [B,L_out] polyphase FIR resampling on the engine (wave_resample); the backward is the transposed operator
+    (dmad_wave_resample_vjp)."""
+
+    @staticmethod
+    def forward(ctx, x, engine, ker, stride, width, L_out):
+        _require_cuda(x)
+        ctx.engine, ctx.ker, ctx.stride, ctx.width, ctx.L_in = engine, ker, int(stride), int(width), x.shape[-1]
+        return engine.wave_resample(x, ker, stride, width, L_out)
+
+    @staticmethod
+    def backward(ctx, g_y):
+        g = ctx.engine.wave_resample_vjp(g_y.contiguous(), ctx.L_in, ctx.ker, ctx.stride, ctx.width)
+        return g.to(g_y.dtype), None, None, None, None, None
+
+
+class WaveIIRHIP(torch.autograd.Function):
+    """[B,L] -> clamp(lfilter(b, a, x), lo, hi) on the engine (wave_iir); the backward is the flipped filter on the masked gradient
+    (dmad_wave_iir_vjp, which recomputes the forward for the mask)."""
+
+    @staticmethod
+    def forward(ctx, x, engine, b, a, lo, hi):
+        _require_cuda(x)
+        ctx.engine, ctx.b, ctx.a, ctx.lo, ctx.hi = engine, b, a, float(lo), float(hi)
+        ctx.save_for_backward(x)
+        return engine.wave_iir(x, b, a, lo, hi)
+
+    @staticmethod
+    def backward(ctx, g_y):
+        x, = ctx.saved_tensors
+        g = ctx.engine.wave_iir_vjp(x, g_y.contiguous(), ctx.b, ctx.a, ctx.lo, ctx.hi)
+        return g.view(x.shape).to(x.dtype), None, None, None, None, None

@@ -866,6 +866,121 @@ class Engine:
         check(self.lib.dmad_nes_grad(self._h, _ptr(w), B, int(P), float(scale), int(seed), int(draw0), int(accumulate), _ptr(grad), _stream()))
         return grad
 
+    # ------------------------------------------------------------------ baseline waveform defenses (dmad_wave_*)
+    @staticmethod
+    def _rows(x: torch.Tensor, width: int, name: str = 'x') -> torch.Tensor:
+        if not x.is_cuda:
+            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
+        x = x.detach()
+        if x.dim() != 2 or x.shape[1] != width:
+            raise DmadError('%s must be [B, %d], not %s' % (name, width, tuple(x.shape)))
+        return x.contiguous().float()
+
+    @staticmethod
+    def _host_f32(a, n: Optional[int] = None):
+        a = np.ascontiguousarray(_as_np(a), dtype=np.float32).reshape(-1)
+        if n is not None and a.size != n:
+            raise DmadError('expected %d coefficients, got %d' % (n, a.size))
+        return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+    def wave_smooth(self, x: torch.Tensor, kind: int, window: int) -> torch.Tensor:
+        """dmad_wave_smooth: x [B,L] or [B,1,L] -> [B,L]; kind 0 the zero-padded windowed mean (AS), 1 the median (MS)."""
+        xw = self._wave(x)
+        y = torch.empty_like(xw)
+        for s, e in self._chunks(xw.shape[0]):
+            check(self.lib.dmad_wave_smooth(self._h, _ptr(xw[s:e]), e - s, int(kind), int(window), _ptr(y[s:e]), _stream()))
+        return y
+
+    def wave_smooth_vjp(self, x: torch.Tensor, g_y: torch.Tensor, kind: int, window: int) -> torch.Tensor:
+        """dmad_wave_smooth_vjp: g_x [B,L] of wave_smooth at x for the output gradient g_y (the median routes by the lowest-position rule)."""
+        xw, g = self._wave(x), self._wave(g_y)
+        if g.shape[0] != xw.shape[0]:
+            raise DmadError('g_y has %d rows, x %d' % (g.shape[0], xw.shape[0]))
+        gx = torch.empty_like(xw)
+        for s, e in self._chunks(xw.shape[0]):
+            check(self.lib.dmad_wave_smooth_vjp(self._h, _ptr(xw[s:e]), _ptr(g[s:e]), e - s, int(kind), int(window), _ptr(gx[s:e]), _stream()))
+        return gx
+
+    def wave_resample(self, x: torch.Tensor, ker, stride: int, width: int, L_out: int) -> torch.Tensor:
+        """dmad_wave_resample: x [B, L_in] -> [B, L_out] through the polyphase FIR `ker` (host [phases, taps])."""
+        k = np.ascontiguousarray(_as_np(ker), dtype=np.float32)
+        phases, taps = (1, k.shape[0]) if k.ndim == 1 else k.shape
+        xw = self._rows(x, x.shape[-1])
+        _, kp = self._host_f32(k)
+        y = torch.empty((xw.shape[0], int(L_out)), device=xw.device, dtype=torch.float32)
+        for s, e in self._chunks(xw.shape[0]):
+            check(self.lib.dmad_wave_resample(self._h, _ptr(xw[s:e]), e - s, xw.shape[1], kp, int(phases), int(taps), int(stride), int(width),
+                                              int(L_out), _ptr(y[s:e]), _stream()))
+        return y
+
+    def wave_resample_vjp(self, g_y: torch.Tensor, L_in: int, ker, stride: int, width: int) -> torch.Tensor:
+        """dmad_wave_resample_vjp: the transposed operator, g_y [B, L_out] -> g_x [B, L_in]."""
+        k = np.ascontiguousarray(_as_np(ker), dtype=np.float32)
+        phases, taps = (1, k.shape[0]) if k.ndim == 1 else k.shape
+        g = self._rows(g_y, g_y.shape[-1], 'g_y')
+        _, kp = self._host_f32(k)
+        gx = torch.empty((g.shape[0], int(L_in)), device=g.device, dtype=torch.float32)
+        for s, e in self._chunks(g.shape[0]):
+            check(self.lib.dmad_wave_resample_vjp(self._h, _ptr(g[s:e]), e - s, int(L_in), kp, int(phases), int(taps), int(stride), int(width),
+                                                  g.shape[1], _ptr(gx[s:e]), _stream()))
+        return gx
+
+    def wave_iir(self, x: torch.Tensor, b, a, lo: float = -float('inf'), hi: float = float('inf')) -> torch.Tensor:
+        """dmad_wave_iir: clamp(lfilter(b, a, x), lo, hi) on [B,L] rows; b, a host arrays of order + 1 <= 9 coefficients."""
+        xw = self._wave(x)
+        bb, bp = self._host_f32(b)
+        _, ap = self._host_f32(a, bb.size)
+        y = torch.empty_like(xw)
+        for s, e in self._chunks(xw.shape[0]):
+            check(self.lib.dmad_wave_iir(self._h, _ptr(xw[s:e]), e - s, bp, ap, bb.size - 1, float(lo), float(hi), _ptr(y[s:e]), _stream()))
+        return y
+
+    def wave_iir_vjp(self, x: torch.Tensor, g_y: torch.Tensor, b, a, lo: float = -float('inf'), hi: float = float('inf'),
+                     want_y: bool = False):
+        """dmad_wave_iir_vjp: g_x = flip(lfilter(b, a, flip(g_y * m))), m the in-range mask of the recomputed unclamped forward.
+        want_y: also return the clamped forward, bit-identical to wave_iir."""
+        xw, g = self._wave(x), self._wave(g_y)
+        if g.shape[0] != xw.shape[0]:
+            raise DmadError('g_y has %d rows, x %d' % (g.shape[0], xw.shape[0]))
+        bb, bp = self._host_f32(b)
+        _, ap = self._host_f32(a, bb.size)
+        gx = torch.empty_like(xw)
+        y = torch.empty_like(xw) if want_y else None
+        for s, e in self._chunks(xw.shape[0]):
+            check(self.lib.dmad_wave_iir_vjp(self._h, _ptr(xw[s:e]), _ptr(g[s:e]), e - s, bp, ap, bb.size - 1, float(lo), float(hi),
+                                             _ptr(gx[s:e]), _ptr(None if y is None else y[s:e]), _stream()))
+        return (gx, y) if want_y else gx
+
+    def defense_query_logits(self, x: torch.Tensor, repeats: int, defense: dict):
+        """dmad_defense_query_logits: x [B,1,L] -> (logits [repeats*B, C], decisions int32 [repeats*B]); row r*B+b is clip b through
+        defense -> mel dB -> classifier.  `defense`: dict(kind='AS'|'MS', window=w) | dict(kind='DS', down=(ker, stride, width, L_out),
+        up=(ker, stride, width)) | dict(kind='IIR', b=, a=, lo=, hi=)."""
+        from ._lib import DmadWaveDefense
+        xw = self._wave(x)
+        B = xw.shape[0]
+        kind = defense['kind']
+        d = DmadWaveDefense(kind={'AS': 0, 'MS': 1, 'DS': 2, 'IIR': 3}[kind])
+        keep = []                                   # the host arrays the struct points to
+        if kind in ('AS', 'MS'):
+            d.window = int(defense['window'])
+        elif kind == 'DS':
+            (dk, ds, dw, dl), (uk, us, uw) = defense['down'], defense['up']
+            dk, uk = (np.atleast_2d(np.ascontiguousarray(_as_np(k), dtype=np.float32)) for k in (dk, uk))
+            keep += [dk, uk]
+            d.down_ker, d.up_ker = (k.ctypes.data_as(C.POINTER(C.c_float)) for k in (dk, uk))
+            d.down_phases, d.down_taps, d.down_stride, d.down_width, d.down_len = dk.shape[0], dk.shape[1], int(ds), int(dw), int(dl)
+            d.up_phases, d.up_taps, d.up_stride, d.up_width = uk.shape[0], uk.shape[1], int(us), int(uw)
+        else:
+            bb, bp = self._host_f32(defense['b'])
+            aa, ap = self._host_f32(defense['a'], bb.size)
+            keep += [bb, aa]
+            d.b, d.a, d.order, d.lo, d.hi = bp, ap, bb.size - 1, float(defense['lo']), float(defense['hi'])
+        logits = torch.empty((repeats * B, self.num_classes), device=xw.device, dtype=torch.float32)
+        dec = torch.empty((repeats * B,), device=xw.device, dtype=torch.int32)
+        check(self.lib.dmad_defense_query_logits(self._h, _ptr(xw), B, int(repeats), C.byref(d), _ptr(logits), _ptr(dec), _stream()))
+        del keep
+        return logits, dec
+
     def _owned(self, t: Optional[torch.Tensor], shape, dtype=torch.float32, name='state') -> torch.Tensor:
         """A caller-owned tensor a swarm call updates in place: checked, never copied; None -> a new one."""
         if t is None:

@@ -47,9 +47,14 @@ def check_supported(args):
 def run(args, classifier=None, defender=None, log=print, **attack_overrides):
     """The reference's evaluation loop.  Returns {'total', 'clean_acc', 'denoised_acc', 'robust_acc'} (accuracies in percent)."""
     check_supported(args)
-    from robustness_eval.black_box_attack import SirenAttack
     torch.cuda.set_device(args.gpu)
     AS_MODEL, classifier = white_box.build_system(args, classifier, defender)
+    return white_box.evaluate(args, AS_MODEL, classifier, attacker_factory(args, AS_MODEL, log, **attack_overrides), log)
+
+
+def attacker_factory(args, AS_MODEL, log=print, **attack_overrides):
+    """make_attacker() of evaluate(): the SirenAttack attacker of the driver's flags and constants (shared with baseline_defense_eval.py)."""
+    from robustness_eval.black_box_attack import SirenAttack
 
     def make_attacker():
         k = dict(ATTACKER_CONSTANTS, **attack_overrides)
@@ -58,7 +63,7 @@ def run(args, classifier=None, defender=None, log=print, **attack_overrides):
         log('attack: {} with eps={} & max_epoch={} & iter={} & n_particles={}\n'.format(args.attack, k['epsilon'], k['max_epoch'],
                                                                                       k['max_iter'], k['n_particles']))
         return Attacker
-    return white_box.evaluate(args, AS_MODEL, classifier, make_attacker, log)
+    return make_attacker
 
 
 if __name__ == '__main__':

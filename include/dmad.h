@@ -521,6 +521,74 @@ int dmad_pso_step(dmad_engine* e, const float* x, const float* lower, const floa
 int dmad_pso_update_best(dmad_engine* e, const float* loss, const int64_t* predict, const float* loc, const int64_t* index, int32_t B,
                          int32_t P, float* pbests, float* pbest_loc, float* gbests, float* gbest_loc, int64_t* gbest_predict, dmad_stream s);
 
+/* Baseline waveform defenses of the attack drivers (transforms/time_defense.py: AS l.102-127, MS l.130-157; transforms/
+ * frequency_defense.py: DS l.37-60, LPF l.62-99, BPF l.101-141).  Everything is fp32 on rows [B][len]; an output row is a function of its
+ * own input row only, never of B or of how a caller chunks the rows; there are no atomics, so results are bit-reproducible.  Unlike the
+ * engine's network paths B is not limited by max_batch here (the kernels hold no per-row workspace), except where a VJP recomputes a
+ * forward into the engine workspace (dmad_wave_iir_vjp: B <= max_batch).  A refused argument is DMAD_ERR_INVALID with a message that
+ * names the export.
+ *
+ * Smoothing, odd window w, p = (w - 1) / 2 zeros on both sides (time_defense.py:124 F.conv1d(padding = p); l.151 F.pad(value = 0.) —
+ * MS pads with zeros despite its "replicate" comment).  kind 0, mean, odd w <= 63:  y[t] = sum_k fl(x[t + k - p] * fl(1 / w)), k ascending,
+ * every product and sum rounded on its own.  kind 1, median, w in {3, 5, 7, 9}:  y[t] = the middle element of the sorted window
+ * (torch.median of an odd window, l.156; a window that holds a NaN gives NaN).
+ * VJP of the mean: the same kernel on g_y (the operator is symmetric under zero padding; x is not read and may be null).  VJP of the
+ * median:  g_x[s] = sum_t g_y[t] [src(t) = s],  t ascending, src(t) = the LOWEST window position that holds the median value of window
+ * t (the tie rule; torch leaves it open); a padding position receives nothing.  It is a gather: the thread of s recomputes the medians
+ * of the w windows that contain s. */
+int dmad_wave_smooth(dmad_engine* e, const float* x, int32_t B, int32_t kind, int32_t window, float* y, dmad_stream s);
+int dmad_wave_smooth_vjp(dmad_engine* e, const float* x, const float* g_y, int32_t B, int32_t kind, int32_t window, float* g_x, dmad_stream s);
+
+/* Polyphase FIR resampling (frequency_defense.py:53-56, torchaudio.transforms.Resample: F.conv1d(F.pad(x, (width, width + orig)),
+ * kernel, stride = orig), the phases interleaved, cut to L_out):
+ *   y[i * phases + j] = sum_k ker[j][k] * xpad[i * stride + k],  k ascending, summed in float64 and rounded to fp32 once,
+ * xpad = width zeros | x | width + stride zeros.  ker: HOST fp32 [phases][taps] (phases * taps <= 256; it travels as a kernel argument);
+ * x: device [B][L_in], y: device [B][L_out]; L_in need not be the clip length.  DS is two calls: 16 kHz -> 8 kHz with phases 1, stride 2,
+ * 28 taps, width 13, then 8 kHz -> 16 kHz with phases 2, stride 1, 15 taps, width 7.  The VJP is the transposed operator, written as a
+ * gather over the outputs that read x[m]: g_x [B][L_in] from g_y [B][L_out], frames and phases ascending. */
+int dmad_wave_resample(dmad_engine* e, const float* x, int32_t B, int32_t L_in, const float* ker, int32_t phases, int32_t taps, int32_t stride,
+                       int32_t width, int32_t L_out, float* y, dmad_stream s);
+int dmad_wave_resample_vjp(dmad_engine* e, const float* g_y, int32_t B, int32_t L_in, const float* ker, int32_t phases, int32_t taps,
+                           int32_t stride, int32_t width, int32_t L_out, float* g_x, dmad_stream s);
+
+/* y = clamp(lfilter(b, a, x), lo, hi)  (frequency_defense.py:85-98 / 125-139: Butterworth b, a, torch_lfilter one clip at a time on the
+ * CPU, then clamp) for order n <= 8, parallel along time.  b, a: HOST fp32 [order + 1], a[0] != 0, both divided by a[0] (in float64,
+ * rounded to fp32).  The filter is lfilter's transposed direct form II:  y = b0 x + z0;  z_i = b_{i+1} x - a_{i+1} y + z_{i+1}.  A row is
+ * cut into at most 128 segments of odd length T (125 at clip_len 16000), one thread each, the row staged through LDS: (1) every segment
+ * runs from the zero state and keeps its final state; (2) one thread carries the n-vector across the segments,
+ * z_in(s + 1) = M z_in(s) + z_zero-state(s), M the n x n zero-input transition of T steps, computed on the host in float64; (3) every
+ * segment runs again from its true initial state.  The scheme is exact in exact arithmetic for any pole position (nothing is
+ * truncated); in fp32 the result is the sequential recurrence from an initial state that carries the rounding of step (2).
+ * dmad_wave_iir_vjp:  g_x = flip(lfilter(b, a, flip(g_y * m))),  m[t] = 1 where the UNCLAMPED forward output lies in [lo, hi] (a NaN
+ * is outside), the forward recomputed into the engine workspace (B <= max_batch); y_or_null optionally receives the clamped forward. */
+int dmad_wave_iir(dmad_engine* e, const float* x, int32_t B, const float* b, const float* a, int32_t order, float lo, float hi, float* y,
+                  dmad_stream s);
+int dmad_wave_iir_vjp(dmad_engine* e, const float* x, const float* g_y, int32_t B, const float* b, const float* a, int32_t order, float lo,
+                      float hi, float* g_x, float* y_or_null, dmad_stream s);
+
+/* One defense as dmad_defense_query_logits runs it.  All pointers are HOST arrays.  struct_size = sizeof(dmad_wave_defense). */
+enum dmad_wave_kind { DMAD_WAVE_AS = 0, DMAD_WAVE_MS = 1, DMAD_WAVE_DS = 2, DMAD_WAVE_IIR = 3 };
+typedef struct dmad_wave_defense {
+    int32_t struct_size;
+    int32_t kind;                   /* enum dmad_wave_kind */
+    int32_t window;                 /* AS, MS */
+    int32_t order;                  /* IIR */
+    const float* down_ker;          /* DS: [down_phases][down_taps], clip_len -> down_len */
+    int32_t down_phases, down_taps, down_stride, down_width, down_len;
+    int32_t up_phases, up_taps, up_stride, up_width;
+    const float* up_ker;            /* DS: [up_phases][up_taps], down_len -> clip_len */
+    const float* b;                 /* IIR: [order + 1] */
+    const float* a;
+    float lo, hi;                   /* IIR: clamp range */
+} dmad_wave_defense;
+
+/* dmad_query_logits with a baseline defense in the purifier's place (adaptive_attack_eval.py:190-201 builds
+ * AcousticSystem(classifier, transform, TimeDomainDefense | FreqDomainDefense)): row i = r * B + b is clip x[b] through
+ * defense -> mel dB -> fp32 classifier -> arg-max, max_batch rows at a time.  The defenses are deterministic, so the repeats are copies;
+ * the layout is kept for the callers of dmad_query_logits.  logits: [repeats * B][num_classes]; decisions: optional int32. */
+int dmad_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, const dmad_wave_defense* d, float* logits,
+                              int32_t* decisions, dmad_stream s);
+
 /* counts[argmax_c logits[b][c]] += 1 (first maximum wins) — certified_robust.py:59-65. */
 int dmad_vote(dmad_engine* e, const float* logits, int32_t B, int64_t* counts, dmad_stream s);
 
