@@ -195,7 +195,7 @@ struct dmad_engine {
     int diag[5] = {0, 0, 0, 0, 0};         // dmad_debug_rounding: GemmF32Args::diag of the x3 tier's dil / res / skip / f0 launches, init hi-only
     std::string warn;                      // dmad_last_warning
     std::map<std::string, HostW> hw;
-    std::vector<void*> allocs;
+    std::vector<std::pair<void*, size_t>> allocs;    // every live buffer of alloc() and its bytes
     int64_t bytes = 0;
     int emb_t = -1;
     // optional per-launch timing of the dominant kernel (bench.py roofline): HIP event pairs on the launch stream
@@ -255,7 +255,6 @@ struct dmad_engine {
     // its post-ReLU T1 / T2 and block output Y — [rxvjpB] spectrograms per slot, and six gradient work maps of 32 x 32 x 1024 floats
     struct RxTape { float* c1 = nullptr; float* t1[9] = {}; float* t2[9] = {}; float* y[9] = {}; };
     int rxvjpB = 0;
-    size_t rxvjp_tape_per = 0;             // floats per spectrogram
     float *rxvjp_tape = nullptr, *rxvjp_work = nullptr;
     RxTape rx_tape;
     // mel front-end VJP (dmad_mel_db_vjp): transposed filterbank [kMelLd][32] and DFT [2048][kDftKT] images, gradient maps of
@@ -273,9 +272,12 @@ struct dmad_engine {
         float *w1x = nullptr, *w2x = nullptr, *skwx = nullptr;                      // the same weights in the split-f16 storage format (middle tier)
         float *w1T = nullptr, *w2T = nullptr, *skwT = nullptr;                      // transposed (3x3: tap-flipped) images of w1 / w2 / skw (UNet VJP)
         size_t ss_off = 0;                 // res: offset of its (scale, shift) row [2 * cout] inside a step's row of un_ss_table
+        // its place in the forward order: its input resolution, the saved map of its concatenated input (top: output blocks' first modules), the
+        // saved map whose gradient joins its input gradient (acc: the first module after each input block, which reads hs[acc]) and the saved
+        // map its output is (save: the last module of each input block); -1: none
+        int H = 0, top = -1, acc = -1, save = -1;
     };
-    std::vector<std::vector<UnOp>> un_in, un_out;
-    std::vector<UnOp> un_mid;
+    std::vector<UnOp> un_ops;              // the modules in forward order (input, middle, output blocks): every walk over the network iterates this list; a module's index is its tape slot
     std::vector<int> un_hs_ch, un_hs_hw;   // channels / pixels of the saved input-block outputs
     std::vector<float*> un_hs;
     bool un_final = false;
@@ -303,12 +305,11 @@ struct dmad_engine {
     float* un_st_buf[3] = {nullptr};
     float* un_st_t2 = nullptr;
     std::vector<float*> un_st_hs;
-    // UNet VJP workspace (dmad_reserve_unet_vjp): the tape of the exact-fp32 forward — per module (in forward order over
-    // un_in / un_mid / un_out) its output map, and a ResBlock's conv1 output / an AttentionBlock's qkv — [unvjpB] spectrograms per slot,
+    // UNet VJP workspace (dmad_reserve_unet_vjp): the tape of the exact-fp32 forward — per module (in forward order,
+    // un_ops) its output map, and a ResBlock's conv1 output / an AttentionBlock's qkv — [unvjpB] spectrograms per slot,
     // the gradient maps of the saved skips (g_hs), six work maps and the transposed weight images
-    struct UnTape { std::vector<float*> out, t2, qkv; };
+    struct UnTape { std::vector<float*> out, t2, qkv, hs; };     // hs[i]: the out slot that holds saved map i
     int unvjpB = 0;
-    size_t unvjp_tape_per = 0, unvjp_ghs_per = 0;          // floats per spectrogram
     float *unvjp_tape = nullptr, *unvjp_ghs = nullptr, *unvjp_work = nullptr, *unvjp_zero = nullptr;
     float* unvjp_g2 = nullptr;              // [2][unvjpB][1024]: the ping-pong adjoint of dmad_spec_vpsde_purify_vjp
     float *un_inT = nullptr, *un_outT = nullptr;            // conv_in [9][128] / out.2 [128][9] images, tap-flipped
@@ -324,18 +325,17 @@ struct dmad_engine {
             e = hipMemset(d, 0, n * sizeof(T));
             if (e != hipSuccess) return fail(DMAD_ERR_HIP, "hipMemset failed: %s", hipGetErrorString(e));
         }
-        allocs.push_back(d);
+        allocs.push_back({d, n * sizeof(T)});
         bytes += (int64_t)(n * sizeof(T));
         *p = (T*)d;
         return 0;
     }
     template <typename T>
-    void release(T** p, size_t n) {        // frees a buffer of alloc() (a reservation that is replaced)
+    void release(T** p) {                  // frees a buffer of alloc() (a reservation that is replaced)
         if (!*p) return;
         for (size_t i = 0; i < allocs.size(); ++i)
-            if (allocs[i] == (void*)*p) { allocs.erase(allocs.begin() + i); break; }
+            if (allocs[i].first == (void*)*p) { bytes -= (int64_t)allocs[i].second; allocs.erase(allocs.begin() + i); break; }
         (void)hipFree(*p);
-        bytes -= (int64_t)(n * sizeof(T));
         *p = nullptr;
     }
     template <typename T>
@@ -366,6 +366,70 @@ struct dmad_engine {
 };
 
 namespace {
+
+// ---- preconditions of the entry points: each returns 0, or its error through fail()
+int need_wavenet(const dmad_engine* e) { return e->wn_final ? 0 : fail(DMAD_ERR_STATE, "WaveNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)"); }
+int need_unet(const dmad_engine* e) { return e->un_final ? 0 : fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)"); }
+int need_with_classifier(const dmad_engine* e) { return e->cfg.with_classifier ? 0 : fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0"); }
+int need_classifier(const dmad_engine* e) {      // ... and its weights finalised
+    if (int r = need_with_classifier(e)) return r;
+    return e->cls_final ? 0 : fail(DMAD_ERR_STATE, "classifier weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+}
+int need_batch(const dmad_engine* e, int B) { return B >= 1 && B <= e->maxB ? 0 : fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB); }
+int need_path(const dmad_engine* e, int path) {  // a WaveNet path the caller names (dmad_wavenet_eps_path / dmad_eval_samples)
+    if (path != PATH_DEFAULT && path != PATH_FP32 && path != PATH_X3) return fail(DMAD_ERR_INVALID, "unknown path %d", path);
+    return path == PATH_DEFAULT || (e->bf16 && e->f32) ? 0 : fail(DMAD_ERR_STATE, "explicit WaveNet paths need a DMAD_EXACT engine");
+}
+
+// walks [0, total) in passes of at most `cap`: fn(offset, count) per pass, until one fails
+template <class Fn>
+int for_passes(int64_t total, int64_t cap, Fn fn) {
+    for (int64_t off = 0; off < total; off += cap) CHK(fn(off, (int)(total - off < cap ? total - off : cap)));
+    return 0;
+}
+
+// ---- gemm_f32 argument blocks
+// a plain GEMM over N rows of K floats, ldx apart (mode 0)
+GemmF32Args plain_gemm(const float* A, const float* X, float* C, const float* scale, const float* shift, int M, int K, long N,
+                       int ldc, long ldx, int relu) {
+    GemmF32Args g{};
+    g.A = A; g.X = X; g.C = C; g.scale = scale; g.shift = shift;
+    g.M = M; g.K = K; g.taps = 1; g.ldc = ldc; g.relu = relu; g.N = N; g.mode = 0;
+    g.rows_per_batch = N > 0 ? N : 1; g.batch_stride = 0; g.row_stride = ldx; g.tap_stride = 0;
+    return g;
+}
+
+// the WaveNet's strided 1-D form (mode 0): `rpb` positions per clip, clips / positions / taps batch_stride / row_stride / tap_stride floats apart
+GemmF32Args wn_conv_args(const float* A, const float* X, float* C, const float* shift, int M, int K, int taps, long N, long rpb,
+                         long batch_stride, long row_stride, long tap_stride) {
+    GemmF32Args g{};
+    g.A = A; g.X = X; g.C = C; g.shift = shift; g.M = M; g.K = K; g.taps = taps; g.ldc = M; g.N = N; g.mode = 0;
+    g.rows_per_batch = rpb; g.batch_stride = batch_stride; g.row_stride = row_stride; g.tap_stride = tap_stride;
+    return g;
+}
+
+// a 3x3 (zero padding 1) / 1x1 conv over B NHWC maps of H x H pixels (mode 2); M / K: output / input channels (per group), ldx / ldc: the
+// pixel pitch of X / C (< 0: K / M)
+GemmF32Args nhwc_conv_args(const float* A, const float* scale, const float* shift, const float* X, float* C, int M, int K, int taps, int B,
+                           int H, int stride, const float* res, int relu = 0, int groups = 0, int ldx = -1, int ldc = -1) {
+    GemmF32Args g{};
+    const int Ho = (H - 1) / (stride > 1 ? stride : 1) + 1;
+    g.A = A; g.X = X; g.C = C; g.scale = scale; g.shift = shift; g.M = M; g.K = K; g.taps = taps; g.ldc = ldc < 0 ? M : ldc; g.relu = relu;
+    g.N = (long)B * Ho * Ho; g.mode = 2; g.H = H; g.W = H; g.Cin = K; g.ldx = ldx < 0 ? K : ldx; g.stride = stride; g.groups = groups; g.res = res;
+    return g;
+}
+
+int upload_h16(dmad_engine* e, const std::vector<float>& A, h16_t** wh) {
+    std::vector<uint16_t> H(A.size());
+    for (size_t i = 0; i < A.size(); ++i) H[i] = f2h(A[i]);
+    return e->upload_bf(wh, H);
+}
+
+int upload_split(dmad_engine* e, const std::vector<float>& A, float** wx) {
+    std::vector<float> t(A.size());
+    split_rows(A.data(), A.size(), t.data());
+    return e->upload(wx, t);
+}
 
 // [ksteps][rows][32] bf16 LDS image of W[row][K] (row-major, K = ksteps*32), 64-B rows, swz64 chunks
 // k-step ks of W lands in stage ks * smul + sadd of the image (GEMM1 interleaves the three taps' k-steps)
@@ -599,10 +663,6 @@ int finalize_classifier(dmad_engine* e) {
     return 0;
 }
 
-GemmF32Args plain_gemm(const float* A, const float* X, float* C, const float* scale, const float* shift, int M, int K, long N,
-                       int ldc, long ldx, int relu);
-int upload_split(dmad_engine* e, const std::vector<float>& A, float** wx);
-
 // ResNeXt29 8x64d: names rx.conv1.*, rx.b<i>.{reduce,conv,expand,short}.{w,scale,shift} (i = 3 * stage + bottleneck),
 // rx.fc.{w,b}.  GEMM images: 1x1 convs [M][K]; the grouped 3x3 conv per group [tap][M/8][K/8] (models/resnext.py:23-62).
 int finalize_resnext(dmad_engine* e) {
@@ -705,22 +765,19 @@ int classify_resnext_x3(dmad_engine* e, const float* spec, int B, float* logits,
     for (int i = 0; i < 9; ++i) {
         const dmad_engine::RxBlock& b = e->rx[i];
         const int Ho = (H - 1) / b.stride + 1;
-        const long Nin = (long)B * H * H, Nout = (long)B * Ho * Ho;
-        auto mk = [&](const dmad_engine::RxConv& c, const float* in, float* out, int M, int K, int taps, long N, int Hin, int ldx, int ldc, int stride, int relu,
-                      int out_split) {
-            GemmF32Args g{};
-            g.A = c.wx; g.X = in; g.C = out; g.scale = c.scale; g.shift = c.shift; g.M = M; g.K = K; g.taps = taps; g.ldc = ldc; g.relu = relu; g.N = N;
-            g.mode = 2; g.H = Hin; g.W = Hin; g.Cin = K; g.ldx = ldx; g.stride = stride; g.x3 = 1; g.out_split = out_split;
+        auto mk = [&](const dmad_engine::RxConv& c, const float* in, float* out, int M, int K, int taps, int Hin, int ldx, int ldc, int stride, int relu, int out_split) {
+            GemmF32Args g = nhwc_conv_args(c.wx, c.scale, c.shift, in, out, M, K, taps, B, Hin, stride, nullptr, relu, 0, ldx, ldc);
+            g.x3 = 1; g.out_split = out_split;
             return g;
         };
-        launch_gemm_f32(mk(b.reduce, X, e->rxT1, b.D, b.cin, 1, Nin, H, b.cin, b.D, 1, 1, 1), s);                 // conv_reduce + bn + ReLU
+        launch_gemm_f32(mk(b.reduce, X, e->rxT1, b.D, b.cin, 1, H, b.cin, b.D, 1, 1, 1), s);                 // conv_reduce + bn + ReLU
         const int G = b.D / 8, pair = G < 128 ? 2 : 1;
-        GemmF32Args c = mk(b.conv, e->rxT1, e->rxT2, G * pair, G * pair, 9, Nout, H, b.D, b.D, b.stride, 1, 1);    // grouped 3x3 (stride) + bn + ReLU
+        GemmF32Args c = mk(b.conv, e->rxT1, e->rxT2, G * pair, G * pair, 9, H, b.D, b.D, b.stride, 1, 1);    // grouped 3x3 (stride) + bn + ReLU
         c.groups = 8 / pair;
         launch_gemm_f32(c, s);
-        GemmF32Args x = mk(b.expand, e->rxT2, Y, b.cout, b.D, 1, Nout, Ho, b.D, b.cout, 1, 1, i == 8 ? 0 : 1);    // conv_expand + bn + shortcut, ReLU
+        GemmF32Args x = mk(b.expand, e->rxT2, Y, b.cout, b.D, 1, Ho, b.D, b.cout, 1, 1, i == 8 ? 0 : 1);    // conv_expand + bn + shortcut, ReLU
         if (b.has_short) {
-            launch_gemm_f32(mk(b.shortc, X, e->rxS, b.cout, b.cin, 1, Nout, H, b.cin, b.cout, b.stride, 0, 0), s);  // shortcut conv + bn: fp32
+            launch_gemm_f32(mk(b.shortc, X, e->rxS, b.cout, b.cin, 1, H, b.cin, b.cout, b.stride, 0, 0), s);  // shortcut conv + bn: fp32
             x.res = e->rxS;
         } else {
             x.res = X; x.res_split = 1;                                                                              // the block input exists in the split format only
@@ -795,19 +852,12 @@ int classify_resnext(dmad_engine* e, const float* spec, int B, float* logits, hi
         GemmF32Args g = plain_gemm(b.reduce.w, X, T1, b.reduce.scale, b.reduce.shift, b.D, b.cin, Nin, b.D, b.cin, 1);
         launch_gemm_f32(g, s, e->slab, e->slab_floats, nref_in);
         // conv_conv (3x3, 8 groups, stride) + bn + ReLU
-        GemmF32Args c{};
-        c.A = b.conv.w; c.X = T1; c.C = T2; c.scale = b.conv.scale; c.shift = b.conv.shift;
-        c.M = b.D / 8; c.K = b.D / 8; c.taps = 9; c.ldc = b.D; c.relu = 1; c.N = Nout; c.mode = 2;
-        c.H = H; c.W = H; c.Cin = b.D / 8; c.ldx = b.D; c.stride = b.stride; c.groups = 8;
-        launch_gemm_f32(c, s);
+        launch_gemm_f32(nhwc_conv_args(b.conv.w, b.conv.scale, b.conv.shift, T1, T2, b.D / 8, b.D / 8, 9, B, H, b.stride, nullptr, 1, 8, b.D, b.D), s);
         // shortcut: identity, or 1x1 conv (stride) + BN
         const float* res = X;
         if (b.has_short) {
-            GemmF32Args h{};
-            h.A = b.shortc.w; h.X = X; h.C = e->rxS; h.scale = b.shortc.scale; h.shift = b.shortc.shift;
-            h.M = b.cout; h.K = b.cin; h.taps = 1; h.ldc = b.cout; h.relu = 0; h.N = Nout; h.mode = 2;
-            h.H = H; h.W = H; h.Cin = b.cin; h.ldx = b.cin; h.stride = b.stride;
-            launch_gemm_f32(h, s, e->slab, e->slab_floats, nref_out);
+            launch_gemm_f32(nhwc_conv_args(b.shortc.w, b.shortc.scale, b.shortc.shift, X, e->rxS, b.cout, b.cin, 1, B, H, b.stride, nullptr), s, e->slab,
+                            e->slab_floats, nref_out);
             res = e->rxS;
         }
         // conv_expand + bn_expand, + shortcut, ReLU
@@ -835,18 +885,6 @@ constexpr int kUnMC = 128, kUnTE = 512, kUnHeads = 4, kUnRes = 3;
 constexpr int kUnSsSteps = 1000;         // cached steps (create_improved_diffusion: diffusion_steps = 1000)
 const int kUnMult[4] = {1, 2, 2, 2};
 inline bool un_attn_at(int ds) { return ds == 2 || ds == 4; }
-
-int upload_h16(dmad_engine* e, const std::vector<float>& A, h16_t** wh) {
-    std::vector<uint16_t> H(A.size());
-    for (size_t i = 0; i < A.size(); ++i) H[i] = f2h(A[i]);
-    return e->upload_bf(wh, H);
-}
-
-int upload_split(dmad_engine* e, const std::vector<float>& A, float** wx) {
-    std::vector<float> t(A.size());
-    split_rows(A.data(), A.size(), t.data());
-    return e->upload(wx, t);
-}
 
 int un_conv3(dmad_engine* e, const std::string& name, int cout, int cin, float** w, float** b, h16_t** wh = nullptr, float** wx = nullptr) {
     const HostW* h = e->get(name + ".weight", {cout, cin, 3, 3}); if (!h) return DMAD_ERR_STATE;
@@ -898,44 +936,52 @@ int un_load_op(dmad_engine* e, const std::string& p, dmad_engine::UnOp& o) {
 }
 
 int finalize_unet(dmad_engine* e) {
-    typedef dmad_engine::UnOp Op;
-    auto mk = [](int kind, int cin, int cout) { Op o; o.kind = kind; o.cin = cin; o.cout = cout; return o; };
-    // enumerate the modules exactly as UNetModel.__init__ builds them (unet.py:338-421)
-    std::vector<int> chans{kUnMC};
-    int ch = kUnMC, ds = 1, hw = 1024;
-    e->un_in.push_back({mk(0, 1, kUnMC)});
-    e->un_hs_ch = {kUnMC}; e->un_hs_hw = {1024};
+    // enumerate the modules exactly as UNetModel.__init__ builds them (unet.py:338-421), in forward order; a module's weights are named
+    // after its place there: <prefix of its block>.<index in the block>
+    e->un_ops.clear(); e->un_hs_ch.clear(); e->un_hs_hw.clear();      // (a retry after a finalise that failed on a missing weight starts over)
+    std::vector<std::string> names;
+    std::string prefix;
+    int ch = kUnMC, ds = 1, hw = 1024, H = 32, j = 0, pend = -1;
+    auto block = [&](const char* list, int i) { prefix = std::string("un.") + list + (i < 0 ? "" : "." + std::to_string(i)); j = 0; };
+    auto add = [&](int kind, int cin, int cout, int top = -1) {
+        dmad_engine::UnOp o;
+        o.kind = kind; o.cin = cin; o.cout = cout; o.H = H; o.top = top; o.acc = pend;
+        e->un_ops.push_back(o);
+        names.push_back(prefix + "." + std::to_string(j++));
+        pend = -1;
+        H = kind == 3 ? H / 2 : kind == 4 ? H * 2 : H;
+    };
+    auto saved = [&]() {                    // hs.append(h): the block's output is a saved map, and the next module reads it
+        e->un_ops.back().save = pend = (int)e->un_hs_ch.size();
+        e->un_hs_ch.push_back(ch); e->un_hs_hw.push_back(hw);
+    };
+    int nb = 0;
+    block("input_blocks", nb++); add(0, 1, kUnMC); saved();
     for (int level = 0; level < 4; ++level) {
         for (int r = 0; r < kUnRes; ++r) {
-            std::vector<Op> blk{mk(1, ch, kUnMult[level] * kUnMC)};
+            block("input_blocks", nb++); add(1, ch, kUnMult[level] * kUnMC);
             ch = kUnMult[level] * kUnMC;
-            if (un_attn_at(ds)) blk.push_back(mk(2, ch, ch));
-            e->un_in.push_back(blk);
-            chans.push_back(ch); e->un_hs_ch.push_back(ch); e->un_hs_hw.push_back(hw);
+            if (un_attn_at(ds)) add(2, ch, ch);
+            saved();
         }
         if (level != 3) {
-            e->un_in.push_back({mk(3, ch, ch)});
+            block("input_blocks", nb++); add(3, ch, ch);
             ds *= 2; hw /= 4;
-            chans.push_back(ch); e->un_hs_ch.push_back(ch); e->un_hs_hw.push_back(hw);
+            saved();
         }
     }
-    e->un_mid = {mk(1, ch, ch), mk(2, ch, ch), mk(1, ch, ch)};
+    block("middle_block", -1); add(1, ch, ch); add(2, ch, ch); add(1, ch, ch);
+    int top = (int)e->un_hs_ch.size();      // hs.pop()
+    nb = 0;
     for (int level = 3; level >= 0; --level)
         for (int i = 0; i <= kUnRes; ++i) {
-            std::vector<Op> blk{mk(1, ch + chans.back(), kUnMC * kUnMult[level])};
-            chans.pop_back();
+            --top;
+            block("output_blocks", nb++); add(1, ch + e->un_hs_ch[top], kUnMC * kUnMult[level], top);
             ch = kUnMC * kUnMult[level];
-            if (un_attn_at(ds)) blk.push_back(mk(2, ch, ch));
-            if (level && i == kUnRes) { blk.push_back(mk(4, ch, ch)); ds /= 2; }
-            e->un_out.push_back(blk);
+            if (un_attn_at(ds)) add(2, ch, ch);
+            if (level && i == kUnRes) { add(4, ch, ch); ds /= 2; }
         }
-    for (size_t i = 0; i < e->un_in.size(); ++i)
-        for (size_t j = 0; j < e->un_in[i].size(); ++j)
-            CHK(un_load_op(e, "un.input_blocks." + std::to_string(i) + "." + std::to_string(j), e->un_in[i][j]));
-    for (size_t j = 0; j < e->un_mid.size(); ++j) CHK(un_load_op(e, "un.middle_block." + std::to_string(j), e->un_mid[j]));
-    for (size_t i = 0; i < e->un_out.size(); ++i)
-        for (size_t j = 0; j < e->un_out[i].size(); ++j)
-            CHK(un_load_op(e, "un.output_blocks." + std::to_string(i) + "." + std::to_string(j), e->un_out[i][j]));
+    for (size_t k = 0; k < names.size(); ++k) CHK(un_load_op(e, names[k], e->un_ops[k]));
     CHK(un_dense(e, "un.time_embed.0", kUnTE, kUnMC, &e->un_te0w, &e->un_te0b));
     CHK(un_dense(e, "un.time_embed.2", kUnTE, kUnTE, &e->un_te2w, &e->un_te2b));
     CHK(un_dense(e, "un.out.0", kUnMC, 1, &e->un_outgw, &e->un_outgb));
@@ -1000,24 +1046,11 @@ int unet_prepare_step(dmad_engine* e, int t, hipStream_t s) {
     launch_silu(e->un_emb1, e->un_emb1, kUnTE, s);
     launch_gemm_f32(plain_gemm(e->un_te2w, e->un_emb1, e->un_emb, nullptr, e->un_te2b, kUnTE, kUnTE, 1, kUnTE, kUnTE, 0), s);
     launch_silu(e->un_emb, e->un_semb, kUnTE, s);
-    auto each = [&](dmad_engine::UnOp& o) {
+    for (const auto& o : e->un_ops)
         if (o.kind == 1)
             launch_gemm_f32(plain_gemm(o.embw, e->un_semb, row + o.ss_off, nullptr, o.embb, 2 * o.cout, kUnTE, 1, 2 * o.cout, kUnTE, 0), s);
-    };
-    for (auto& b : e->un_in) for (auto& o : b) each(o);
-    for (auto& o : e->un_mid) each(o);
-    for (auto& b : e->un_out) for (auto& o : b) each(o);
     if (slot < kUnSsSteps) e->un_ss_have[slot] = 1;
     return 0;
-}
-
-GemmF32Args un_conv_args(const float* A, const float* bias, const float* X, float* C, int cout, int cin, int taps, int B, int H, int stride,
-                         const float* res) {
-    GemmF32Args g{};
-    const int Ho = (H - 1) / (stride > 1 ? stride : 1) + 1;
-    g.A = A; g.X = X; g.C = C; g.scale = nullptr; g.shift = bias; g.M = cout; g.K = cin; g.taps = taps; g.ldc = cout; g.relu = 0;
-    g.N = (long)B * Ho * Ho; g.mode = 2; g.H = H; g.W = H; g.Cin = cin; g.ldx = cin; g.stride = stride; g.res = res;
-    return g;
 }
 
 // a dense layer over NHWC rows as a 1x1 conv (mode 2: the form both the fp32 and the split-f16 launch paths serve for any M % 128 == 0)
@@ -1051,7 +1084,7 @@ const float* unet_apply(dmad_engine* e, const dmad_engine::UnOp& o, const float*
     if (o.kind == 1) {                      // ResBlock._forward, unet.py:186-199
         if (in2 && o.cin == o.cout) { fail(DMAD_ERR_STATE, "a concatenated input needs the ResBlock's skip conv"); return nullptr; }
         if (launch_groupnorm_nhwc(in, o.gn1w, o.gn1b, nullptr, 1, T1, B, H * H, o.cin, s, in2, c1, nullptr, nullptr, nullptr, x3)) return gn_fail(H * H, o.cin);
-        gemm(un_conv_args(o.w1, o.b1, T1, T2, o.cout, o.cin, 9, B, H, 1, nullptr), o.w1x, nref);
+        gemm(nhwc_conv_args(o.w1, nullptr, o.b1, T1, T2, o.cout, o.cin, 9, B, H, 1, nullptr), o.w1x, nref);
         if (launch_groupnorm_nhwc(T2, o.gn2w, o.gn2b, e->un_ss_cur + o.ss_off, 1, T1, B, H * H, o.cout, s, nullptr, 0, nullptr, nullptr, nullptr, x3)) return gn_fail(H * H, o.cout);
         const float* skip = in;
         if (o.cin != o.cout) {
@@ -1062,12 +1095,12 @@ const float* unet_apply(dmad_engine* e, const dmad_engine::UnOp& o, const float*
                 sin = QKV;
                 if (in2) { launch_scale(in2, 1.f, ATT, (long)B * H * H * (o.cin - c1), s, true); sin2 = ATT; }
             }
-            GemmF32Args g = un_conv_args(o.skw, o.skb, sin, SK, o.cout, o.cin, 1, B, H, 1, nullptr);
+            GemmF32Args g = nhwc_conv_args(o.skw, nullptr, o.skb, sin, SK, o.cout, o.cin, 1, B, H, 1, nullptr);
             if (in2) { g.ldx = c1; g.X2 = sin2; g.ksplit = c1; g.ldx2 = o.cin - c1; }
             gemm(g, o.skwx, nref);
             skip = SK;
         }
-        gemm(un_conv_args(o.w2, o.b2, T1, out, o.cout, o.cout, 9, B, H, 1, skip), o.w2x, nref);
+        gemm(nhwc_conv_args(o.w2, nullptr, o.b2, T1, out, o.cout, o.cout, 9, B, H, 1, skip), o.w2x, nref);
     } else if (o.kind == 2) {               // AttentionBlock._forward + QKVAttention, unet.py:225-258
         const int C = o.cin, T = H * H;
         if (launch_groupnorm_nhwc(in, o.gn1w, o.gn1b, nullptr, 0, T1, B, T, C, s, nullptr, 0, nullptr, nullptr, nullptr, x3)) return gn_fail(T, C);
@@ -1079,13 +1112,13 @@ const float* unet_apply(dmad_engine* e, const dmad_engine::UnOp& o, const float*
     } else if (o.kind == 3) {               // Downsample: conv 3x3 stride 2, unet.py:82-111
         const float* xin = in;
         if (x3) { launch_scale(in, 1.f, T1, (long)B * H * H * o.cin, s, true); xin = T1; }
-        gemm(un_conv_args(o.w1, o.b1, xin, out, o.cout, o.cin, 9, B, H, 2, nullptr), o.w1x, nref / 4);
+        gemm(nhwc_conv_args(o.w1, nullptr, o.b1, xin, out, o.cout, o.cin, 9, B, H, 2, nullptr), o.w1x, nref / 4);
         H /= 2;
     } else if (o.kind == 4) {               // Upsample: nearest x2 + conv 3x3, unet.py:49-79
         launch_upsample2x_nhwc(in, T1, B, H, H, o.cin, s);
         H *= 2;
         if (x3) launch_scale(T1, 1.f, T1, (long)B * H * H * o.cin, s, true);
-        gemm(un_conv_args(o.w1, o.b1, T1, out, o.cout, o.cin, 9, B, H, 1, nullptr), o.w1x, nref * 4);
+        gemm(nhwc_conv_args(o.w1, nullptr, o.b1, T1, out, o.cout, o.cin, 9, B, H, 1, nullptr), o.w1x, nref * 4);
     } else {
         if (launch_conv1ch_3x3(in, o.w1, o.b1, out, B, o.cout, s)) { fail(DMAD_ERR_STATE, "input conv: %d output channels > 128", o.cout); return nullptr; }
     }
@@ -1188,8 +1221,7 @@ bool unet_apply_h16(dmad_engine* e, const dmad_engine::UnOp& o, UMap in, int B, 
 // tape (exact-fp32 tier only, B <= unvjpB): every module writes its output (and a ResBlock its conv1 output, an AttentionBlock its qkv) to
 // its tape slot instead of the work buffers — the same launches, the same bits (dmad_unet_eps_vjp's forward)
 int unet_eps(dmad_engine* e, const float* x, int t, int B, float* eps, hipStream_t s, int h16 = -1, const dmad_engine::UnTape* tape = nullptr) {
-    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
-    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(need_unet(e)); CHK(need_batch(e, B));
     if (t < 0) return fail(DMAD_ERR_INVALID, "diffusion step %d < 0", t);
     CHK(unet_prepare_step(e, t, s));
     if (h16 < 0) {      // the map-returning surfaces follow dmad_set_waveform_tier like the waveform-returning ones: split-f16 by default on exact-vote engines
@@ -1202,22 +1234,13 @@ int unet_eps(dmad_engine* e, const float* x, int t, int B, float* eps, hipStream
         int H = 32, rot = 0;
         UMap h{x, nullptr, nullptr};
         std::vector<const float*> hs_st(e->un_hs.size(), nullptr);      // the statistics slab each saved map ended up with (16-pixel blocks on the 4x4 maps)
-        for (size_t i = 0; i < e->un_in.size(); ++i)
-            for (size_t j = 0; j < e->un_in[i].size(); ++j) {
-                const bool save = j + 1 == e->un_in[i].size();
-                if (!unet_apply_h16(e, e->un_in[i][j], h, B, H, save ? e->un_hs[i] : nullptr, save ? e->un_hs16[i] : nullptr, save ? e->un_st_hs[i] : nullptr, rot, s, &h)) return DMAD_ERR_STATE;
-                if (save) hs_st[i] = h.st;
-            }
-        for (auto& o : e->un_mid) if (!unet_apply_h16(e, o, h, B, H, nullptr, nullptr, nullptr, rot, s, &h)) return DMAD_ERR_STATE;
-        size_t top = e->un_hs.size();
-        for (auto& blk : e->un_out) {
-            --top;
-            const int c1 = blk[0].cin - e->un_hs_ch[top];
-            const UMap hs{e->un_hs[top], e->un_hs16[top], hs_st[top]};
-            for (size_t j = 0; j < blk.size(); ++j) {
-                const bool ok = j == 0 ? unet_apply_h16(e, blk[0], h, B, H, nullptr, nullptr, nullptr, rot, s, &h, hs, c1) : unet_apply_h16(e, blk[j], h, B, H, nullptr, nullptr, nullptr, rot, s, &h);
-                if (!ok) return DMAD_ERR_STATE;
-            }
+        for (const auto& r : e->un_ops) {
+            const int i = r.save, top = r.top;                  // th.cat([h, hs.pop()], dim=1): h carries c1 channels, the saved map the rest
+            const UMap hs = top >= 0 ? UMap{e->un_hs[top], e->un_hs16[top], hs_st[top]} : UMap{nullptr, nullptr, nullptr};
+            if (!unet_apply_h16(e, r, h, B, H, i >= 0 ? e->un_hs[i] : nullptr, i >= 0 ? e->un_hs16[i] : nullptr, i >= 0 ? e->un_st_hs[i] : nullptr, rot, s, &h, hs,
+                                top >= 0 ? r.cin - e->un_hs_ch[top] : 0))
+                return DMAD_ERR_STATE;
+            if (i >= 0) hs_st[i] = h.st;
         }
         if (un_groupnorm16(h, UMap{nullptr, nullptr, nullptr}, 0, e->un_outgw, e->un_outgb, nullptr, 1, e->un_t1h, nullptr, B, 1024, kUnMC, s)) { gn_fail(1024, kUnMC); return DMAD_ERR_STATE; }
         launch_conv3x3_c128_to1_h16(e->un_t1h, e->un_outw, e->un_outb, eps, B, s);       // (operands f16, fp32 accumulate, like the tier's GEMMs)
@@ -1228,29 +1251,14 @@ int unet_eps(dmad_engine* e, const float* x, int t, int B, float* eps, hipStream
     if (x3 && !e->un_x3) return fail(DMAD_ERR_STATE, "this engine has no split-f16 UNet tier (it needs DMAD_EXACT precision)");
     if (tape && h16 != 0) return fail(DMAD_ERR_STATE, "the UNet tape belongs to the exact-fp32 tier");
     int H = 32, rot = 0;
-    size_t k = 0;                                               // module index in forward order (the tape's slot)
-    auto t2 = [&]() { return tape ? tape->t2[k] : nullptr; };
-    auto qkv = [&]() { return tape ? tape->qkv[k] : nullptr; };
-    std::vector<float*> hsp(e->un_hs);                          // where the saved maps land: un_hs, or their tape slots
+    const std::vector<float*>& hsp = tape ? tape->hs : e->un_hs;   // where the saved maps land: un_hs, or their tape slots
     const float* h = x;
-    for (size_t i = 0; i < e->un_in.size(); ++i)
-        for (size_t j = 0; j < e->un_in[i].size(); ++j, ++k) {
-            const bool last = j + 1 == e->un_in[i].size();
-            if (tape && last) hsp[i] = tape->out[k];
-            if (!(h = unet_apply(e, e->un_in[i][j], h, B, H, tape ? tape->out[k] : last ? e->un_hs[i] : nullptr, rot, s, nullptr, 0, x3, t2(), qkv()))) return DMAD_ERR_STATE;
-        }
-    for (size_t j = 0; j < e->un_mid.size(); ++j, ++k)
-        if (!(h = unet_apply(e, e->un_mid[j], h, B, H, tape ? tape->out[k] : nullptr, rot, s, nullptr, 0, x3, t2(), qkv()))) return DMAD_ERR_STATE;
-    size_t top = e->un_hs.size();
-    for (auto& blk : e->un_out) {
-        --top;
-        const int c1 = blk[0].cin - e->un_hs_ch[top];          // th.cat([h, hs.pop()], dim=1): h carries c1 channels, the saved map the rest
-        const float* hs = hsp[top];
-        for (size_t j = 0; j < blk.size(); ++j, ++k) {
-            float* dst = tape ? tape->out[k] : nullptr;
-            h = j == 0 ? unet_apply(e, blk[0], h, B, H, dst, rot, s, hs, c1, x3, t2(), qkv()) : unet_apply(e, blk[j], h, B, H, dst, rot, s, nullptr, 0, x3, t2(), qkv());
-            if (!h) return DMAD_ERR_STATE;
-        }
+    for (size_t k = 0; k < e->un_ops.size(); ++k) {             // k: the tape's slot
+        const auto& r = e->un_ops[k];
+        const int top = r.top;                                  // th.cat([h, hs.pop()], dim=1): h carries c1 channels, the saved map the rest
+        h = unet_apply(e, r, h, B, H, tape ? tape->out[k] : r.save >= 0 ? e->un_hs[r.save] : nullptr, rot, s, top >= 0 ? hsp[top] : nullptr,
+                       top >= 0 ? r.cin - e->un_hs_ch[top] : 0, x3, tape ? tape->t2[k] : nullptr, tape ? tape->qkv[k] : nullptr);
+        if (!h) return DMAD_ERR_STATE;
     }
     if (launch_groupnorm_nhwc(h, e->un_outgw, e->un_outgb, nullptr, 1, e->un_buf[3], B, 1024, kUnMC, s)) { gn_fail(1024, kUnMC); return DMAD_ERR_STATE; }
     static_assert(kUnMC == 128, "launch_conv3x3_c128_to1 is the 128-channel output layer");
@@ -1260,32 +1268,6 @@ int unet_eps(dmad_engine* e, const float* x, int t, int B, float* eps, hipStream
 }
 
 // ---- the UNet's vector-Jacobian product (dmad_unet_eps_vjp) ----------------------------------------------------------------
-// One module in forward order: its input resolution, its tape slot k, the saved map of its concatenated input (top, output blocks' first
-// modules) and the saved map whose gradient joins its input gradient (acc: the first module after each input block, which reads hs[acc]).
-struct UnRef { const dmad_engine::UnOp* o; int H, top, acc; };
-std::vector<UnRef> un_flat(const dmad_engine* e, std::vector<size_t>* hs_k = nullptr) {
-    std::vector<UnRef> r;
-    int H = 32;
-    for (size_t i = 0; i < e->un_in.size(); ++i) {
-        for (size_t j = 0; j < e->un_in[i].size(); ++j) {
-            const auto& o = e->un_in[i][j];
-            r.push_back({&o, H, -1, j == 0 && i > 0 ? (int)i - 1 : -1});
-            if (o.kind == 3) H /= 2;
-        }
-        if (hs_k) hs_k->push_back(r.size() - 1);
-    }
-    for (size_t j = 0; j < e->un_mid.size(); ++j) r.push_back({&e->un_mid[j], H, -1, j == 0 ? (int)e->un_in.size() - 1 : -1});
-    int top = (int)e->un_hs.size();
-    for (auto& blk : e->un_out) {
-        --top;
-        for (size_t j = 0; j < blk.size(); ++j) {
-            r.push_back({&blk[j], H, j == 0 ? top : -1, -1});
-            if (blk[j].kind == 4) H *= 2;
-        }
-    }
-    return r;
-}
-
 // The weight image of a dense conv's data gradient, packed on the device: w [taps][co][ci] -> wT [taps - 1 - tap][ci][co] (the 3x3 taps
 // flipped; a 1x1 layer: the transpose)
 void un_pack_wT(const float* w, float* wT, int taps, long ci, long co, hipStream_t s) {
@@ -1300,7 +1282,7 @@ int un_conv_dgrad(const float* wT, const float* g, float* gx, int ci, int co, in
                   float* work, hipStream_t s) {
     const float* gin = g;
     if (!up && stride == 2) { launch_dilate2x_nhwc(g, work, B, H / 2, co, s); gin = work; }
-    if (launch_gemm_f32(un_conv_args(wT, nullptr, gin, up ? work : gx, ci, co, taps, B, up ? 2 * H : H, 1, up ? nullptr : acc), s) != 0)
+    if (launch_gemm_f32(nhwc_conv_args(wT, nullptr, nullptr, gin, up ? work : gx, ci, co, taps, B, up ? 2 * H : H, 1, up ? nullptr : acc), s) != 0)
         return fail(DMAD_ERR_STATE, "UNet VJP: no GEMM for M = %d, K = %d, taps = %d", ci, co, taps);
     if (up) launch_upsample2x_bwd_nhwc(work, acc, gx, B, H, ci, s);
     return 0;
@@ -1313,8 +1295,7 @@ int un_conv_dgrad(const float* wT, const float* g, float* gx, int ci, int co, in
 int unet_vjp_pass(dmad_engine* e, const float* x, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s,
                   bool affine = false, float alpha = 1.f, float gamma = 0.f) {
     CHK(unet_eps(e, x, t, B, eps, s, 0, &e->un_tape));
-    std::vector<size_t> hs_k;
-    const std::vector<UnRef> ops = un_flat(e, &hs_k);
+    const std::vector<dmad_engine::UnOp>& ops = e->un_ops;
     const size_t W = (size_t)e->unvjpB * 1024 * 384;
     float* G[6];
     for (int i = 0; i < 6; ++i) G[i] = e->unvjp_work + i * W;
@@ -1329,10 +1310,10 @@ int unet_vjp_pass(dmad_engine* e, const float* x, int t, int B, const float* g_e
     CHK(gnb(tp.out.back(), nullptr, 0, e->un_outgw, e->un_outgb, nullptr, 1, G[2], nullptr, nullptr, G[0], nullptr, 1024, kUnMC));
     float *cur = G[0], *nxt = G[1];
     for (int k = (int)ops.size() - 1; k >= 0; --k) {
-        const auto& o = *ops[k].o;
+        const auto& o = ops[k];
         const int H = ops[k].H, top = ops[k].top;
         const float* in = k ? tp.out[k - 1] : x;
-        const float* in2 = top >= 0 ? tp.out[hs_k[top]] : nullptr;
+        const float* in2 = top >= 0 ? tp.hs[top] : nullptr;
         const int c1 = top >= 0 ? o.cin - e->un_hs_ch[top] : 0;
         float* gin2 = top >= 0 ? e->unvjp_ghs_at[top] : nullptr;
         const float* acc = ops[k].acc >= 0 ? e->unvjp_ghs_at[ops[k].acc] : nullptr;
@@ -1366,16 +1347,14 @@ int unet_vjp_pass(dmad_engine* e, const float* x, int t, int B, const float* g_e
 }
 
 int unet_vjp(dmad_engine* e, const float* x, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s) {
-    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_unet(e));
     if (!e->f32) return fail(DMAD_ERR_STATE, "the UNet VJP runs on the exact-fp32 UNet tier: it needs a DMAD_FP32 or DMAD_EXACT engine");
     if (!e->unvjpB) return fail(DMAD_ERR_STATE, "no UNet VJP workspace: call dmad_reserve_unet_vjp first");
-    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(need_batch(e, B));
     if (t < 0) return fail(DMAD_ERR_INVALID, "diffusion step %d < 0", t);
-    for (int b0 = 0; b0 < B; b0 += e->unvjpB) {
-        const int bb = B - b0 < e->unvjpB ? B - b0 : e->unvjpB;
-        CHK(unet_vjp_pass(e, x + (size_t)b0 * 1024, t, bb, g_eps + (size_t)b0 * 1024, g_x + (size_t)b0 * 1024, eps ? eps + (size_t)b0 * 1024 : e->un_eps, s));
-    }
-    return 0;
+    return for_passes(B, e->unvjpB, [&](int64_t b0, int bb) {
+        return unet_vjp_pass(e, x + b0 * 1024, t, bb, g_eps + b0 * 1024, g_x + b0 * 1024, eps ? eps + b0 * 1024 : e->un_eps, s);
+    });
 }
 
 int ensure_embed(dmad_engine* e, int t, hipStream_t s) {
@@ -1386,34 +1365,19 @@ int ensure_embed(dmad_engine* e, int t, hipStream_t s) {
     return 0;
 }
 
-GemmF32Args plain_gemm(const float* A, const float* X, float* C, const float* scale, const float* shift, int M, int K, long N,
-                       int ldc, long ldx, int relu) {
-    GemmF32Args g{};
-    g.A = A; g.X = X; g.C = C; g.scale = scale; g.shift = shift;
-    g.M = M; g.K = K; g.taps = 1; g.ldc = ldc; g.relu = relu; g.N = N; g.mode = 0;
-    g.rows_per_batch = N > 0 ? N : 1; g.batch_stride = 0; g.row_stride = ldx; g.tap_stride = 0;
-    return g;
-}
-
 // exact32: evaluate on the exact-fp32 path (the only one of a DMAD_FP32 engine; DMAD_MODE_FP32 and the recheck pass of a
 // DMAD_EXACT engine); batches larger than the fp32 workspace are walked in chunks of maxB32 clips
 // save != nullptr (the VJP's forward pass; B <= maxB32, fp32 path): layer n reads its residual stream from slot n of `save`
 // ([NL][vjpB][LP][256]) and writes the next one to slot n + 1 instead of the A / B ping-pong — the same launches, the same bits
 int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipStream_t s, int path = PATH_DEFAULT, float* save = nullptr) {
-    if (!e->wn_final) return fail(DMAD_ERR_STATE, "WaveNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
-    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(need_wavenet(e)); CHK(need_batch(e, B));
     if (t < 0) return fail(DMAD_ERR_INVALID, "diffusion step %d < 0", t);
     CHK(ensure_embed(e, t, s));
     const int L = e->L, LP = e->LP, NL = e->NL;
     const bool use32 = !e->bf16 || (e->f32 && (path != PATH_DEFAULT || e->mode == DMAD_MODE_FP32));
     const bool x3 = use32 && path == PATH_X3 && e->wdil_x3;     // fp32 pipeline on split-f16 operands (three MFMAs per product)
-    if (use32 && B > e->maxB32) {
-        for (int b0 = 0; b0 < B; b0 += e->maxB32) {
-            const int bb = B - b0 < e->maxB32 ? B - b0 : e->maxB32;
-            CHK(wavenet_eps(e, x_t + (size_t)b0 * L, t, bb, eps + (size_t)b0 * L, s, x3 ? PATH_X3 : PATH_FP32));
-        }
-        return 0;
-    }
+    if (use32 && B > e->maxB32)
+        return for_passes(B, e->maxB32, [&](int64_t b0, int bb) { return wavenet_eps(e, x_t + b0 * L, t, bb, eps + b0 * L, s, x3 ? PATH_X3 : PATH_FP32); });
     if (!use32) {
         launch_wn_init_bf16(x_t, e->init_w, e->init_b, e->emb_table, e->hA, B, L, LP, e->f16, s);
         for (int n = 0; n < NL; ++n) {
@@ -1450,12 +1414,10 @@ int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipS
             const int d = 1 << (n % e->cfg.dilation_cycle);
             const bool last = n == NL - 1;
             float* gout = e->gstore32 + (size_t)n * slab;
-            GemmF32Args g{};
-            g.A = (x3 ? e->wdil_x3 : e->wdil) + (size_t)n * 3 * 512 * 256; g.X = hin + (size_t)kPad * kC; g.scale = nullptr;
+            GemmF32Args g = wn_conv_args((x3 ? e->wdil_x3 : e->wdil) + (size_t)n * 3 * 512 * 256, hin + (size_t)kPad * kC, gout, e->bdil + (size_t)n * 512,
+                                         512, 256, 3, N, L, (long)LP * kC, kC, (long)d * kC);
             g.x3 = x3; g.diag = x3 ? e->diag[0] : 0;
-            g.shift = e->bdil + (size_t)n * 512; g.M = 512; g.K = 256; g.taps = 3; g.ldc = 512; g.relu = 0; g.N = N; g.mode = 0;
-            g.rows_per_batch = L; g.batch_stride = (long)LP * kC; g.row_stride = kC; g.tap_stride = (long)d * kC;
-            g.epi = 1; g.C = gout;               // tanh * sigmoid in the epilogue: H never goes to HBM
+            g.epi = 1;                           // tanh * sigmoid in the epilogue: H never goes to HBM
             launch_gemm_f32(g, s);
             if (last) continue;                  // the last layer's residual output is never consumed (WaveNet.py:131-135)
             // res conv with the residual update in its epilogue; the skip convs run as one GEMM after the loop
@@ -1467,10 +1429,9 @@ int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipS
             launch_gemm_f32(u, s);
         }
         {   // skip = sum_n W_skip_n g_n + sum_n b_skip_n: taps = layers, tap stride = one slab (taps are centred on NL / 2)
-            GemmF32Args k{};
-            k.A = x3 ? e->wskip_x3 : e->wskip32; k.X = e->gstore32 + (size_t)(NL >> 1) * slab; k.C = e->skip32; k.scale = nullptr;
-            k.shift = e->bskip32; k.M = 256; k.K = 256; k.taps = NL; k.ldc = 256; k.relu = 0; k.N = N; k.mode = 0; k.x3 = x3; k.diag = x3 ? e->diag[2] : 0;
-            k.rows_per_batch = N; k.batch_stride = 0; k.row_stride = 256; k.tap_stride = (long)slab;
+            GemmF32Args k = wn_conv_args(x3 ? e->wskip_x3 : e->wskip32, e->gstore32 + (size_t)(NL >> 1) * slab, e->skip32, e->bskip32, 256, 256, NL, N, N, 0,
+                                         256, (long)slab);
+            k.x3 = x3; k.diag = x3 ? e->diag[2] : 0;
             launch_gemm_f32(k, s);
         }
         launch_scale(e->skip32, (float)sqrt(1.0 / NL), e->g32, N * 256, s, x3);
@@ -1506,23 +1467,17 @@ int wavenet_vjp_pass(dmad_engine* e, const float* x_t, int t, int B, const float
         float* g_hout = e->vjp_G + (size_t)r_out * RS;
         float* g_hin = e->vjp_G + (size_t)r_in * RS;
         // g_gate = W_skip^T g_s + sqrt(1/2) W_res^T g_h(n+1)   (the last layer: the first term alone)
-        GemmF32Args gg{};
-        gg.A = e->vjp_wgT + (size_t)n * 2 * 256 * 256; gg.X = (last ? e->vjp_G : g_hout) + (size_t)kPad * kC; gg.C = e->vjp_gg;
-        gg.M = 256; gg.K = 256; gg.taps = last ? 1 : 2; gg.ldc = 256; gg.N = N; gg.mode = 0;
-        gg.rows_per_batch = L; gg.batch_stride = (long)LP * kC; gg.row_stride = kC; gg.tap_stride = last ? 0 : (long)r_out * (long)RS;
+        const GemmF32Args gg = wn_conv_args(e->vjp_wgT + (size_t)n * 2 * 256 * 256, (last ? e->vjp_G : g_hout) + (size_t)kPad * kC, e->vjp_gg, nullptr, 256, 256,
+                                            last ? 1 : 2, N, L, (long)LP * kC, kC, last ? 0 : (long)r_out * (long)RS);
         CHK(launch_gemm_f32(gg, s) ? fail(DMAD_ERR_INVALID, "VJP: no kernel for the gate gradient") : 0);
         // g_H from the recomputed H (epi 3), into the zero-padded [B][LP][512] map
-        GemmF32Args g3{};
-        g3.A = e->wdil + (size_t)n * 3 * 512 * 256; g3.X = e->vjp_save + n * sslot + (size_t)kPad * kC; g3.shift = e->bdil + (size_t)n * 512;
-        g3.M = 512; g3.K = 256; g3.taps = 3; g3.ldc = 512; g3.N = N; g3.mode = 0;
-        g3.rows_per_batch = L; g3.batch_stride = (long)LP * kC; g3.row_stride = kC; g3.tap_stride = (long)d * kC;
+        GemmF32Args g3 = wn_conv_args(e->wdil + (size_t)n * 3 * 512 * 256, e->vjp_save + n * sslot + (size_t)kPad * kC, nullptr, e->bdil + (size_t)n * 512, 512,
+                                      256, 3, N, L, (long)LP * kC, kC, (long)d * kC);
         g3.epi = 3; g3.L = L; g3.LP = LP; g3.hin = e->vjp_gg; g3.hout = e->vjp_gH;
         CHK(launch_gemm_f32(g3, s) ? fail(DMAD_ERR_INVALID, "VJP: no kernel for the gate backward") : 0);
         // g_h(n) = sqrt(1/2) g_h(n+1) + transposed dilated conv of g_H (taps flipped in the image), epi 4
-        GemmF32Args g4{};
-        g4.A = e->vjp_wdilT + (size_t)n * 3 * 256 * 512; g4.X = e->vjp_gH + (size_t)kPad * 512;
-        g4.M = 256; g4.K = 512; g4.taps = 3; g4.ldc = 256; g4.N = N; g4.mode = 0;
-        g4.rows_per_batch = L; g4.batch_stride = (long)LP * 512; g4.row_stride = 512; g4.tap_stride = (long)d * 512;
+        GemmF32Args g4 = wn_conv_args(e->vjp_wdilT + (size_t)n * 3 * 256 * 512, e->vjp_gH + (size_t)kPad * 512, nullptr, nullptr, 256, 512, 3, N, L,
+                                      (long)LP * 512, 512, (long)d * 512);
         g4.epi = 4; g4.L = L; g4.LP = LP; g4.hin = last ? nullptr : g_hout; g4.hout = g_hin;
         CHK(launch_gemm_f32(g4, s) ? fail(DMAD_ERR_INVALID, "VJP: no kernel for the transposed dilated conv") : 0);
     }
@@ -1533,21 +1488,18 @@ int wavenet_vjp_pass(dmad_engine* e, const float* x_t, int t, int B, const float
 
 int wavenet_vjp(dmad_engine* e, const float* x_t, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s) {
     if (!e->f32) return fail(DMAD_ERR_STATE, "the WaveNet VJP runs on the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights");
-    if (!e->wn_final) return fail(DMAD_ERR_STATE, "WaveNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_wavenet(e));
     if (!e->vjpB) return fail(DMAD_ERR_STATE, "no VJP workspace: call dmad_reserve_vjp first");
-    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(need_batch(e, B));
     if (t < 0) return fail(DMAD_ERR_INVALID, "diffusion step %d < 0", t);
     const size_t L = e->L;
-    for (int b0 = 0; b0 < B; b0 += e->vjpB) {
-        const int bb = B - b0 < e->vjpB ? B - b0 : e->vjpB;
-        CHK(wavenet_vjp_pass(e, x_t + b0 * L, t, bb, g_eps + b0 * L, g_x + b0 * L, (eps ? eps : e->eps) + b0 * L, s));
-    }
-    return 0;
+    return for_passes(B, e->vjpB, [&](int64_t b0, int bb) {
+        return wavenet_vjp_pass(e, x_t + b0 * L, t, bb, g_eps + b0 * L, g_x + b0 * L, (eps ? eps : e->eps) + b0 * L, s);
+    });
 }
 
 int mel_db(dmad_engine* e, const float* x, int B, float* spec, hipStream_t s, int to_db = 1) {
-    if (!e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
-    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(need_with_classifier(e)); CHK(need_batch(e, B));
     const long rows = (long)B * 32;
     launch_mel_pad(x, e->mel_xp, B, e->L, e->LPm, s);
     GemmF32Args g{};
@@ -1590,9 +1542,8 @@ int rx_conv_dgrad(const float* wT, const float* g, float* gx, int M, int K, int 
     const bool dil_in = stride == 2 && taps == 9, dil_out = stride == 2 && taps == 1;
     if (dil_in) launch_dilate2x_nhwc(g, work, B, Ho, groups * K, s);
     const int H = dil_in ? 2 * Ho : Ho;
-    GemmF32Args a{};
-    a.A = wT; a.X = dil_in ? work : g; a.C = dil_out ? work : gx; a.M = M; a.K = K; a.taps = taps; a.ldc = groups * M; a.N = (long)B * H * H; a.mode = 2;
-    a.H = H; a.W = H; a.Cin = K; a.ldx = groups * K; a.stride = 1; a.groups = groups; a.res = dil_out ? nullptr : res;
+    const GemmF32Args a = nhwc_conv_args(wT, nullptr, nullptr, dil_in ? work : g, dil_out ? work : gx, M, K, taps, B, H, 1, dil_out ? nullptr : res, 0, groups,
+                                         groups * K, groups * M);
     if (launch_gemm_f32(a, s) != 0) return fail(DMAD_ERR_STATE, "classifier VJP: no GEMM for M = %d, K = %d, taps = %d", M, K, taps);
     if (dil_out) launch_dilate2x_nhwc(work, gx, B, Ho, M, s);
     return 0;
@@ -1634,18 +1585,14 @@ int rx_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits,
 }
 
 int classify_vjp(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
-    if (!e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
-    if (!e->cls_final) return fail(DMAD_ERR_STATE, "classifier weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_classifier(e));
     if (e->cls_kind != 1) return fail(DMAD_ERR_STATE, "the classifier VJP serves ResNeXt29 only: this engine holds VGG19_bn");
     if (!e->rxvjpB) return fail(DMAD_ERR_STATE, "no classifier VJP workspace: call dmad_reserve_classifier_vjp first");
-    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(need_batch(e, B));
     const int nc = e->cfg.num_classes;
-    for (int b0 = 0; b0 < B; b0 += e->rxvjpB) {
-        const int bb = B - b0 < e->rxvjpB ? B - b0 : e->rxvjpB;
-        CHK(rx_vjp_pass(e, spec + (size_t)b0 * 1024, bb, g_logits + (size_t)b0 * nc, g_spec + (size_t)b0 * 1024,
-                        logits ? logits + (size_t)b0 * nc : e->logits, s));
-    }
-    return 0;
+    return for_passes(B, e->rxvjpB, [&](int64_t b0, int bb) {
+        return rx_vjp_pass(e, spec + b0 * 1024, bb, g_logits + b0 * nc, g_spec + b0 * 1024, logits ? logits + b0 * nc : e->logits, s);
+    });
 }
 
 // first call: the transposed filterbank / DFT images and the gradient maps of up to 64 clips per pass
@@ -1685,24 +1632,18 @@ int mel_vjp_pass(dmad_engine* e, const float* x, int B, const float* g_spec, flo
 }
 
 int mel_db_vjp(dmad_engine* e, const float* x, int B, const float* g_spec, float* g_x, float* spec, hipStream_t s) {
-    if (!e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
-    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(need_with_classifier(e)); CHK(need_batch(e, B));
     CHK(mel_vjp_prepare(e));
-    for (int b0 = 0; b0 < B; b0 += e->melvjpB) {
-        const int bb = B - b0 < e->melvjpB ? B - b0 : e->melvjpB;
-        CHK(mel_vjp_pass(e, x + (size_t)b0 * e->L, bb, g_spec + (size_t)b0 * 1024, g_x + (size_t)b0 * e->L,
-                         spec ? spec + (size_t)b0 * 1024 : e->spec, s));
-    }
-    return 0;
+    return for_passes(B, e->melvjpB, [&](int64_t b0, int bb) {
+        return mel_vjp_pass(e, x + b0 * e->L, bb, g_spec + b0 * 1024, g_x + b0 * e->L, spec ? spec + b0 * 1024 : e->spec, s);
+    });
 }
 
 // h16 = 1: the classifier's 16-bit tier where one is resident (ResNeXt29 on engines with a 16-bit side) — the fast mode's; 2: its
 // split-f16 tier (exact-vote engines) — tier 1 of the exact-vote loops; every other caller (dmad_classify, the recheck tiers) gets the
 // fp32 matrix cores
 int classify(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, int h16 = 0) {
-    if (!e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
-    if (!e->cls_final) return fail(DMAD_ERR_STATE, "classifier weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
-    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(need_classifier(e)); CHK(need_batch(e, B));
     if (e->cls_kind == 1) return (h16 == 1 && e->rx_h16) ? classify_resnext_h16(e, spec, B, logits, s)
                                  : (h16 == 2 && e->rx_x3) ? classify_resnext_x3(e, spec, B, logits, s) : classify_resnext(e, spec, B, logits, s);
     float *cur = e->act0, *nxt = e->act1;
@@ -1714,11 +1655,8 @@ int classify(dmad_engine* e, const float* spec, int B, float* logits, hipStream_
             launch_maxpool2_nhwc(cur, nxt, B, H, H, cin, s);
             H >>= 1;
         } else {
-            GemmF32Args g{};
-            g.A = e->vconvw[li]; g.X = cur; g.C = nxt; g.scale = e->vscale[li]; g.shift = e->vshift[li];
-            g.M = v; g.K = cin; g.taps = 9; g.ldc = v; g.relu = 1; g.N = (long)B * H * H; g.mode = 2;
-            g.H = H; g.W = H; g.Cin = cin;
-            launch_gemm_f32(g, s, e->slab, e->slab_floats, (long)e->maxB * H * H);
+            launch_gemm_f32(nhwc_conv_args(e->vconvw[li], e->vscale[li], e->vshift[li], cur, nxt, v, cin, 9, B, H, 0, nullptr, 1, 0, 0), s, e->slab,
+                            e->slab_floats, (long)e->maxB * H * H);      // (stride and ldx 0: the kernel's defaults, 1 and Cin)
             cin = v;
             ++li;
         }
@@ -1893,7 +1831,7 @@ void dmad_destroy(dmad_engine* e) {
     for (hipEvent_t ev : e->prof_ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->prof_ev_f) (void)hipEventDestroy(ev);
     if (e->rc_n_host) (void)hipHostFree(e->rc_n_host);
-    for (void* p : e->allocs) (void)hipFree(p);
+    for (auto& a : e->allocs) (void)hipFree(a.first);
     delete e;
 }
 
@@ -2023,7 +1961,7 @@ int dmad_ddpm_step(dmad_engine* e, float* x, int32_t t, float c_eps, float c_div
 int dmad_diffuse(dmad_engine* e, const float* x0, float c_a, float c_b, const float* z, uint64_t seed, uint64_t sample0,
                  int32_t B, float* x_t, dmad_stream s) {
     if (!e || !x0 || !x_t) return fail(DMAD_ERR_INVALID, "null argument");
-    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(need_batch(e, B));
     const float* zz = z;
     if (!zz) {
         launch_philox_normal(seed, sample0, 0xD1FFu, e->znoise, B, e->L, (hipStream_t)s);
@@ -2133,7 +2071,7 @@ int dmad_vpsde_purify(dmad_engine* e, const float* x0, int32_t B, int32_t n_step
     if (B < 1) return fail(DMAD_ERR_INVALID, "batch %d < 1", B);
     if (path != 0 && path != 1) return fail(DMAD_ERR_INVALID, "unknown path %d (0 the mode's default, 1 exact fp32)", path);
     if (path == 1 && !e->f32) return fail(DMAD_ERR_STATE, "path 1 is the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights");
-    if (!e->wn_final) return fail(DMAD_ERR_STATE, "WaveNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_wavenet(e));
     for (int n = 0; n < n_steps; ++n)
         if (k[n] < 0) return fail(DMAD_ERR_INVALID, "step %d: k = %d < 0", n, k[n]);
     const int wp = path == 1 ? PATH_FP32 : wave_path(e);
@@ -2149,9 +2087,9 @@ int dmad_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int32_t 
     if (g_out == g_x0) return fail(DMAD_ERR_INVALID, "g_out and g_x0 must not alias");
     if (n_steps < 1) return fail(DMAD_ERR_INVALID, "n_steps %d < 1", n_steps);
     if (!e->f32) return fail(DMAD_ERR_STATE, "the WaveNet VJP runs on the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights");
-    if (!e->wn_final) return fail(DMAD_ERR_STATE, "WaveNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_wavenet(e));
     if (!e->vjpB) return fail(DMAD_ERR_STATE, "no VJP workspace: call dmad_reserve_vjp first");
-    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(need_batch(e, B));
     for (int n = 0; n < n_steps; ++n)
         if (k[n] < 0) return fail(DMAD_ERR_INVALID, "step %d: k = %d < 0", n, k[n]);
     auto vjp = [=](const float* x, int kn, int bb, const float* g, float* dst, float alpha, float gamma) {
@@ -2168,7 +2106,7 @@ int dmad_spec_vpsde_purify(dmad_engine* e, const float* x0, int32_t B, int32_t n
     if (B < 1) return fail(DMAD_ERR_INVALID, "batch %d < 1", B);
     if (path != 0 && path != 1) return fail(DMAD_ERR_INVALID, "unknown path %d (0 the mode's UNet map tier, 1 exact fp32)", path);
     if (path == 1 && !e->f32) return fail(DMAD_ERR_STATE, "path 1 is the exact-fp32 UNet tier: a DMAD_BF16 engine holds no fp32 weights");
-    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_unet(e));
     for (int n = 0; n < n_steps; ++n)
         if (k[n] < 0 || k[n] > kUnSsSteps) return fail(DMAD_ERR_INVALID, "step %d: k = %d outside [0, %d]", n, k[n], kUnSsSteps);
     const int tier = path == 1 ? 0 : -1;
@@ -2184,9 +2122,9 @@ int dmad_spec_vpsde_purify_vjp(dmad_engine* e, const float* traj, int32_t B, int
     if (g_out == g_x0) return fail(DMAD_ERR_INVALID, "g_out and g_x0 must not alias");
     if (n_steps < 1) return fail(DMAD_ERR_INVALID, "n_steps %d < 1", n_steps);
     if (!e->f32) return fail(DMAD_ERR_STATE, "the UNet VJP runs on the exact-fp32 UNet tier: it needs a DMAD_FP32 or DMAD_EXACT engine");
-    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_unet(e));
     if (!e->unvjpB) return fail(DMAD_ERR_STATE, "no UNet VJP workspace: call dmad_reserve_unet_vjp first");
-    if (B < 1 || B > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB);
+    CHK(need_batch(e, B));
     for (int n = 0; n < n_steps; ++n)
         if (k[n] < 0 || k[n] > kUnSsSteps) return fail(DMAD_ERR_INVALID, "step %d: k = %d outside [0, %d]", n, k[n], kUnSsSteps);
     auto vjp = [=](const float* x, int kn, int bb, const float* g, float* dst, float alpha, float gamma) {
@@ -2267,11 +2205,8 @@ int dmad_conv_x3(const float* x, const float* x2, int32_t ksplit, const float* w
     if (!x || !w || !out) return fail(DMAD_ERR_INVALID, "null argument");
     if (B < 1 || H < 1 || M < 1 || K < 1 || groups < 1 || (stride != 1 && stride != 2) || (groups > 1 && x2)) return fail(DMAD_ERR_INVALID, "bad geometry");
     if (int r = gemm_x3_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, split-f16 tier) failed: %d", r);
-    const int Ho = (H - 1) / stride + 1;
-    GemmF32Args g{};
-    g.A = w; g.X = x; g.C = out; g.shift = bias; g.res = res; g.M = M; g.K = K; g.taps = taps; g.ldc = groups * M; g.relu = relu; g.N = (long)B * Ho * Ho;
-    g.mode = 2; g.H = H; g.W = H; g.Cin = K; g.ldx = x2 ? ksplit : groups * K; g.stride = stride; g.x3 = 1; g.out_split = out_split; g.res_split = res_split;
-    g.groups = groups;
+    GemmF32Args g = nhwc_conv_args(w, nullptr, bias, x, out, M, K, taps, B, H, stride, res, relu, groups, x2 ? ksplit : groups * K, groups * M);
+    g.x3 = 1; g.out_split = out_split; g.res_split = res_split;
     if (x2) { g.X2 = x2; g.ksplit = ksplit; g.ldx2 = K - ksplit; }
     launch_gemm_f32(g, (hipStream_t)s);
     LASTCHK();
@@ -2318,9 +2253,7 @@ int dmad_conv_f32(const float* x, const float* x2, int32_t ksplit, const float* 
         g = plain_gemm(w, x, out, scale, shift, M, K, B, M, K, relu);
         g.res = res;
     } else {
-        const int Ho = (H - 1) / stride + 1;
-        g.A = w; g.X = x; g.C = out; g.scale = scale; g.shift = shift; g.res = res; g.M = M; g.K = K; g.taps = taps; g.ldc = groups * M; g.relu = relu;
-        g.N = (long)B * Ho * Ho; g.mode = 2; g.H = H; g.W = H; g.Cin = K; g.ldx = x2 ? ksplit : groups * K; g.stride = stride; g.groups = groups;
+        g = nhwc_conv_args(w, scale, shift, x, out, M, K, taps, B, H, stride, res, relu, groups, x2 ? ksplit : groups * K, groups * M);
         if (x2) { g.X2 = x2; g.ksplit = ksplit; g.ldx2 = K - ksplit; }
     }
     if (launch_gemm_f32(g, (hipStream_t)s, slab, (long)slab_floats, (long)n_ref) != 0) {
@@ -2469,14 +2402,12 @@ int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch) {
     if (!e) return fail(DMAD_ERR_INVALID, "null engine");
     if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
     if (!e->f32) return fail(DMAD_ERR_STATE, "the WaveNet VJP runs on the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights");
-    if (!e->wn_final) return fail(DMAD_ERR_STATE, "WaveNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_wavenet(e));
     const int vB = max_batch < e->maxB32 ? max_batch : e->maxB32;
     if (vB <= e->vjpB) return 0;
     const size_t LP = e->LP, NL = e->NL;
     if (e->vjpB) {                          // a larger reservation replaces the present one
-        const size_t ob = e->vjpB;
-        e->release(&e->vjp_save, NL * ob * LP * kC); e->release(&e->vjp_gH, ob * LP * 512);
-        e->release(&e->vjp_G, 3 * ob * LP * kC); e->release(&e->vjp_gg, ob * e->L * kC); e->release(&e->vjp_g2, 2 * ob * e->L);
+        e->release(&e->vjp_save); e->release(&e->vjp_gH); e->release(&e->vjp_G); e->release(&e->vjp_gg); e->release(&e->vjp_g2);
         e->vjpB = 0;
     }
     if (!e->vjp_wdilT) {
@@ -2503,16 +2434,15 @@ int dmad_wavenet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B,
 int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch) {
     if (!e) return fail(DMAD_ERR_INVALID, "null engine");
     if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
-    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_unet(e));
     if (!e->f32) return fail(DMAD_ERR_STATE, "the UNet VJP runs on the exact-fp32 UNet tier: it needs a DMAD_FP32 or DMAD_EXACT engine");
     const int vB = max_batch < e->maxB32 ? max_batch : e->maxB32;
     if (vB <= e->unvjpB) return 0;
     // tape slots and saved-map gradients, in floats per spectrogram
     std::vector<size_t> out_off, t2_off, qkv_off, ghs_off;
     size_t tape = 0, ghs = 0;
-    for (const UnRef& r : un_flat(e)) {
-        const auto& o = *r.o;
-        const size_t px = (size_t)r.H * r.H, opx = o.kind == 3 ? px / 4 : o.kind == 4 ? px * 4 : px;
+    for (const auto& o : e->un_ops) {
+        const size_t px = (size_t)o.H * o.H, opx = o.kind == 3 ? px / 4 : o.kind == 4 ? px * 4 : px;
         t2_off.push_back(o.kind == 1 ? tape : SIZE_MAX); if (o.kind == 1) tape += px * o.cout;
         qkv_off.push_back(o.kind == 2 ? tape : SIZE_MAX); if (o.kind == 2) tape += px * 3 * o.cin;
         out_off.push_back(tape); tape += opx * o.cout;
@@ -2520,9 +2450,7 @@ int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch) {
     for (size_t i = 0; i < e->un_hs_ch.size(); ++i) { ghs_off.push_back(ghs); ghs += (size_t)e->un_hs_hw[i] * e->un_hs_ch[i]; }
     const size_t W = (size_t)1024 * 384;
     if (e->unvjpB) {                        // a larger reservation replaces the present one
-        const size_t ob = e->unvjpB;
-        e->release(&e->unvjp_tape, ob * e->unvjp_tape_per); e->release(&e->unvjp_ghs, ob * e->unvjp_ghs_per); e->release(&e->unvjp_work, 6 * ob * W);
-        e->release(&e->unvjp_g2, 2 * ob * 1024);
+        e->release(&e->unvjp_tape); e->release(&e->unvjp_ghs); e->release(&e->unvjp_work); e->release(&e->unvjp_g2);
         e->unvjpB = 0;
     }
     if (!e->unvjp_zero) {                   // transposed weight images, packed on the device from the resident fp32 images
@@ -2543,9 +2471,7 @@ int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch) {
             }
             return 0;
         };
-        for (auto& b : e->un_in) for (auto& o : b) CHK(pack(o));
-        for (auto& o : e->un_mid) CHK(pack(o));
-        for (auto& b : e->un_out) for (auto& o : b) CHK(pack(o));
+        for (auto& o : e->un_ops) CHK(pack(o));
         CHK(e->alloc(&e->un_outT, 9 * kUnMC)); launch_unvjp_pack(e->un_outw, e->un_outT, kUnMC, 9, 1, 1, kUnMC, 0, 2, nullptr);   // [9][128] -> [128][9], flipped
         HIPCHK(hipGetLastError());
         if (int r = unvjp_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, attention backward) failed: %d", r);
@@ -2554,10 +2480,12 @@ int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch) {
     CHK(e->alloc(&e->unvjp_ghs, (size_t)vB * ghs));
     CHK(e->alloc(&e->unvjp_work, 6 * (size_t)vB * W));
     CHK(e->alloc(&e->unvjp_g2, 2 * (size_t)vB * 1024));
-    e->unvjp_tape_per = tape; e->unvjp_ghs_per = ghs;
     auto at = [&](size_t off) { return off == SIZE_MAX ? nullptr : e->unvjp_tape + off * vB; };
     e->un_tape = dmad_engine::UnTape{};
-    for (size_t k = 0; k < out_off.size(); ++k) { e->un_tape.out.push_back(at(out_off[k])); e->un_tape.t2.push_back(at(t2_off[k])); e->un_tape.qkv.push_back(at(qkv_off[k])); }
+    for (size_t k = 0; k < out_off.size(); ++k) {
+        e->un_tape.out.push_back(at(out_off[k])); e->un_tape.t2.push_back(at(t2_off[k])); e->un_tape.qkv.push_back(at(qkv_off[k]));
+        if (e->un_ops[k].save >= 0) e->un_tape.hs.push_back(e->un_tape.out[k]);
+    }
     e->unvjp_ghs_at.clear();
     for (size_t off : ghs_off) e->unvjp_ghs_at.push_back(e->unvjp_ghs + off * vB);
     HIPCHK(hipDeviceSynchronize());
@@ -2573,8 +2501,7 @@ int dmad_unet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, co
 int dmad_reserve_classifier_vjp(dmad_engine* e, int32_t max_batch) {
     if (!e) return fail(DMAD_ERR_INVALID, "null engine");
     if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
-    if (!e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
-    if (!e->cls_final) return fail(DMAD_ERR_STATE, "classifier weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_classifier(e));
     if (e->cls_kind != 1) return fail(DMAD_ERR_STATE, "the classifier VJP serves ResNeXt29 only: this engine holds VGG19_bn");
     const int vB = max_batch < e->maxB ? max_batch : e->maxB;
     if (vB <= e->rxvjpB) return 0;
@@ -2592,8 +2519,7 @@ int dmad_reserve_classifier_vjp(dmad_engine* e, int32_t max_batch) {
     size_t work = 0;
     for (size_t w : kRxWork) work += w;
     if (e->rxvjpB) {                        // a larger reservation replaces the present one
-        const size_t ob = e->rxvjpB;
-        e->release(&e->rxvjp_tape, ob * e->rxvjp_tape_per); e->release(&e->rxvjp_work, ob * work);
+        e->release(&e->rxvjp_tape); e->release(&e->rxvjp_work);
         e->rxvjpB = 0;
     }
     if (!e->rx[0].reduce.wT) {              // transposed images with the BN scale folded in, packed on the device from the fp32 images
@@ -2615,7 +2541,6 @@ int dmad_reserve_classifier_vjp(dmad_engine* e, int32_t max_batch) {
     }
     CHK(e->alloc(&e->rxvjp_tape, (size_t)vB * tape));
     CHK(e->alloc(&e->rxvjp_work, (size_t)vB * work));
-    e->rxvjp_tape_per = tape;
     auto at = [&](size_t off) { return e->rxvjp_tape + off * vB; };
     e->rx_tape.c1 = at(c1_off);
     for (int i = 0; i < 9; ++i) { e->rx_tape.t1[i] = at(t1_off[i]); e->rx_tape.t2[i] = at(t2_off[i]); e->rx_tape.y[i] = at(y_off[i]); }
@@ -2636,8 +2561,7 @@ int dmad_mel_db_vjp(dmad_engine* e, const float* x, int32_t B, const float* g_sp
 
 int dmad_wavenet_eps_path(dmad_engine* e, const float* x_t, int32_t t, int32_t B, int32_t path, float* eps, dmad_stream s) {
     if (!e || !x_t || !eps) return fail(DMAD_ERR_INVALID, "null argument");
-    if (path != PATH_DEFAULT && path != PATH_FP32 && path != PATH_X3) return fail(DMAD_ERR_INVALID, "unknown path %d", path);
-    if (path != PATH_DEFAULT && !(e->bf16 && e->f32)) return fail(DMAD_ERR_STATE, "explicit WaveNet paths need a DMAD_EXACT engine");
+    CHK(need_path(e, path));
     return wavenet_eps(e, x_t, t, B, eps, (hipStream_t)s, path);
 }
 
@@ -2765,16 +2689,13 @@ int dmad_eval_samples(dmad_engine* e, const float* clip, float sigma, float sqrt
                       float* x0_out, dmad_stream s) {
     if (!e || !clip || !idx || (!logits_out && !x0_out)) return fail(DMAD_ERR_INVALID, "null argument");
     if (n < 0) return fail(DMAD_ERR_INVALID, "n < 0");
-    if (path != PATH_DEFAULT && path != PATH_FP32 && path != PATH_X3) return fail(DMAD_ERR_INVALID, "unknown path %d", path);
-    if (path != PATH_DEFAULT && !(e->bf16 && e->f32)) return fail(DMAD_ERR_STATE, "explicit WaveNet paths need a DMAD_EXACT engine");
-    if (logits_out && !e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
+    CHK(need_path(e, path));
+    if (logits_out) CHK(need_with_classifier(e));
     const WaveJob job{clip, delta, sigma, sqrt_alpha_bar_star, t, c_a, c_b, seed, sample0, nullptr};
-    const int cap = path == PATH_DEFAULT ? e->maxB : e->maxB32;
-    for (int64_t done = 0; done < n; done += cap) {
-        const int B = (int)(n - done < cap ? n - done : cap);
-        CHK(wave_rows(e, job, 0, (const long long*)idx + done, B, path, x0_out ? x0_out + done * e->L : e->x0,
-                      logits_out ? logits_out + done * e->cfg.num_classes : nullptr, (hipStream_t)s));
-    }
+    CHK(for_passes(n, path == PATH_DEFAULT ? e->maxB : e->maxB32, [&](int64_t done, int B) {
+        return wave_rows(e, job, 0, (const long long*)idx + done, B, path, x0_out ? x0_out + done * e->L : e->x0,
+                         logits_out ? logits_out + done * e->cfg.num_classes : nullptr, (hipStream_t)s);
+    }));
     LASTCHK();
     return 0;
 }
@@ -2841,6 +2762,27 @@ int spec_chain(dmad_engine* e, const SpecJob& j, uint64_t s0, const long long* i
     return spec_chain_from_xt(e, j, s0, idx, B, h16, h16 == 1 ? cls_tier(e) : 0, sp, lg, st);      // the recheck tiers: the fp32 classifier
 }
 
+// The loop of the three query exports over the B * repeats query rows (row r = clip r % B, AcousticSystem's repeat layout), in passes of
+// up to max_batch rows: the rows into e->xt, logits_of(nb, r0, lg) -- the export's defense and classifier -- and the optional decisions
+template <class Logits>
+int query_loop(dmad_engine* e, const float* x, int B, int repeats, float* logits, int32_t* decisions, hipStream_t st, Logits logits_of) {
+    const int C = e->cfg.num_classes;
+    CHK(for_passes((int64_t)B * repeats, e->maxB, [&](int64_t r0, int nb) -> int {
+        launch_repeat_rows(x, e->xt, B, (long)r0, nb, e->L, st);
+        CHK(logits_of(nb, r0, logits + r0 * C));
+        if (decisions) launch_vote(logits + r0 * C, nb, C, nullptr, decisions + r0, st);
+        return 0;
+    }));
+    LASTCHK();
+    return 0;
+}
+
+// purified waveforms -> mel dB -> the fp32 classifier, like AcousticSystem.forward's own call
+int wave_logits(dmad_engine* e, const float* pur, int nb, float* lg, hipStream_t st) {
+    CHK(mel_db(e, pur, nb, e->spec, st));
+    return classify(e, e->spec, nb, lg, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2850,7 +2792,7 @@ int dmad_spec_smooth_votes(dmad_engine* e, const float* clip, float sigma, int32
                            int32_t batch, uint64_t seed, uint64_t sample0, int64_t* counts, float* logits_out, float* spec_out, dmad_stream s) {
     if (!e || !clip || !counts || !c_a || !c_b || !c_1 || !c_2 || !c_sig) return fail(DMAD_ERR_INVALID, "null argument");
     if (!e->cfg.with_classifier || !e->cls_final) return fail(DMAD_ERR_STATE, "the spec-domain vote loop needs the mel front-end and a finalised classifier");
-    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_unet(e));
     if (n < 0 || batch < 1 || batch > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d] or n < 0", batch, e->maxB);
     if (t_star < 0) return fail(DMAD_ERR_INVALID, "t_star %d < 0", t_star);
     if (!(mel_hi > mel_lo)) return fail(DMAD_ERR_INVALID, "empty mel range");
@@ -2881,7 +2823,7 @@ int dmad_spec_eval_samples(dmad_engine* e, const float* clip, float sigma, int32
                            const int64_t* idx, int64_t n, int32_t tier, float* logits_out, float* spec_out, dmad_stream s) {
     if (!e || !clip || !idx || !c_a || !c_b || !c_1 || !c_2 || !c_sig || (!logits_out && !spec_out)) return fail(DMAD_ERR_INVALID, "null argument");
     if (!e->cfg.with_classifier || !e->cls_final) return fail(DMAD_ERR_STATE, "the spec-domain chain needs the mel front-end and a finalised classifier");
-    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_unet(e));
     if (n < 0 || t_star < 0 || !(mel_hi > mel_lo)) return fail(DMAD_ERR_INVALID, "bad argument");
     if (tier != 0 && tier != 1 && tier != 2) return fail(DMAD_ERR_INVALID, "unknown UNet tier %d (0 exact fp32, 1 16-bit, 2 split-f16)", tier);
     if (tier == 1 && !e->un_h16) return fail(DMAD_ERR_STATE, "this engine has no 16-bit UNet tier (DMAD_FP32 precision)");
@@ -2889,12 +2831,10 @@ int dmad_spec_eval_samples(dmad_engine* e, const float* clip, float sigma, int32
     hipStream_t st = (hipStream_t)s;
     const int C = e->cfg.num_classes;
     const SpecJob job{clip, sigma, t_star, q_a, q_b, c_a, c_b, c_1, c_2, c_sig, mel_lo, mel_hi, seed};
-    for (int64_t done = 0; done < n; done += e->maxB) {
-        const int B = (int)(n - done < e->maxB ? n - done : e->maxB);
-        float* sp = spec_out ? spec_out + done * 1024 : e->spec;
-        float* lg = logits_out ? logits_out + done * C : e->logits;
-        CHK(spec_chain(e, job, 0, (const long long*)idx + done, B, tier, sp, lg, st));
-    }
+    CHK(for_passes(n, e->maxB, [&](int64_t done, int B) {
+        return spec_chain(e, job, 0, (const long long*)idx + done, B, tier, spec_out ? spec_out + done * 1024 : e->spec,
+                          logits_out ? logits_out + done * C : e->logits, st);
+    }));
     LASTCHK();
     return 0;
 }
@@ -2907,28 +2847,20 @@ int dmad_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats
     if (sampler < 0 || sampler > 2) return fail(DMAD_ERR_INVALID, "unknown sampler %d (0 none, 1 DDPM, 2 one-shot)", sampler);
     if (sampler && t_star < 1) return fail(DMAD_ERR_INVALID, "t_star %d < 1", t_star);
     if (sampler == 1 && (!c_eps || !c_div || !c_sig)) return fail(DMAD_ERR_INVALID, "the DDPM sampler needs its coefficient arrays");
-    if (!e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
+    CHK(need_with_classifier(e));
     hipStream_t st = (hipStream_t)s;
-    const int L = e->L, C = e->cfg.num_classes;
-    const long rows = (long)B * repeats;
-    for (long r0 = 0; r0 < rows; r0 += e->maxB) {
-        const int nb = (int)(rows - r0 < e->maxB ? rows - r0 : e->maxB);
-        launch_repeat_rows(x, e->xt, B, r0, nb, L, st);
+    return query_loop(e, x, B, repeats, logits, decisions, st, [&](int nb, int64_t r0, float* lg) -> int {
         const float* pur = e->xt;
         if (sampler == 1) {
             CHK(dmad_ddpm_purify(e, e->xt, t_star, c_a, c_b, c_eps, c_div, c_sig, seed, sample0 + (uint64_t)r0, nb, e->x0, s));
             pur = e->x0;
         } else if (sampler == 2) {
             CHK(wavenet_eps(e, e->xt, t_star - 1, nb, e->eps, st, wave_path(e)));
-            launch_lincomb(0, e->xt, e->eps, nullptr, c_a, c_b, 0.f, e->x0, (long)nb * L, st);
+            launch_lincomb(0, e->xt, e->eps, nullptr, c_a, c_b, 0.f, e->x0, (long)nb * e->L, st);
             pur = e->x0;
         }
-        CHK(mel_db(e, pur, nb, e->spec, st));
-        CHK(classify(e, e->spec, nb, logits + r0 * C, st));       // the fp32 classifier, like AcousticSystem.forward's own call
-        if (decisions) launch_vote(logits + r0 * C, nb, C, nullptr, decisions + r0, st);
-    }
-    LASTCHK();
-    return 0;
+        return wave_logits(e, pur, nb, lg, st);
+    });
 }
 
 int dmad_spec_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, int32_t t_star, float q_a, float q_b, const float* c_a,
@@ -2937,22 +2869,15 @@ int dmad_spec_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t re
     if (!e || !x || !logits || !c_a || !c_b || !c_1 || !c_2 || !c_sig) return fail(DMAD_ERR_INVALID, "null argument");
     if (B < 1 || repeats < 1) return fail(DMAD_ERR_INVALID, "B and repeats must be >= 1");
     if (!e->cfg.with_classifier || !e->cls_final) return fail(DMAD_ERR_STATE, "the spec-domain query needs the mel front-end and a finalised classifier");
-    if (!e->un_final) return fail(DMAD_ERR_STATE, "UNet weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
+    CHK(need_unet(e));
     if (t_star < 0 || !(mel_hi > mel_lo)) return fail(DMAD_ERR_INVALID, "bad argument");
     hipStream_t st = (hipStream_t)s;
-    const int L = e->L, C = e->cfg.num_classes;
     const SpecJob job{nullptr, 0.f, t_star, q_a, q_b, c_a, c_b, c_1, c_2, c_sig, mel_lo, mel_hi, seed};
-    const long rows = (long)B * repeats;
-    for (long r0 = 0; r0 < rows; r0 += e->maxB) {
-        const int nb = (int)(rows - r0 < e->maxB ? rows - r0 : e->maxB);
-        launch_repeat_rows(x, e->xt, B, r0, nb, L, st);
+    return query_loop(e, x, B, repeats, logits, decisions, st, [&](int nb, int64_t r0, float* lg) {
         // the UNet tier of the map-returning surfaces (unet_eps, h16 = -1: on an exact-vote engine the dmad_set_waveform_tier tier, split-f16
         // by default), the fp32 classifier: like dmad_query_logits, a query hands logits back and has no recheck
-        CHK(spec_chain_from_xt(e, job, sample0 + (uint64_t)r0, nullptr, nb, -1, 0, e->spec, logits + r0 * C, st));
-        if (decisions) launch_vote(logits + r0 * C, nb, C, nullptr, decisions + r0, st);
-    }
-    LASTCHK();
-    return 0;
+        return spec_chain_from_xt(e, job, sample0 + (uint64_t)r0, nullptr, nb, -1, 0, e->spec, lg, st);
+    });
 }
 
 // _NES.py:19-25 (noise = cat(noise, -noise), the zero probe in front, eval_input = noise * sigma + x), a chunk of rows at a time
@@ -3099,13 +3024,10 @@ int dmad_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t
     if (B < 1 || repeats < 1) return fail(DMAD_ERR_INVALID, "dmad_defense_query_logits: B and repeats must be >= 1");
     IirPlan plan;
     if (const char* m = wave_defense_check(d, e->L, &plan)) return fail(DMAD_ERR_INVALID, "dmad_defense_query_logits: %s", m);
-    if (!e->cfg.with_classifier) return fail(DMAD_ERR_STATE, "engine was created with with_classifier = 0");
+    CHK(need_with_classifier(e));
     hipStream_t st = (hipStream_t)s;
-    const int L = e->L, C = e->cfg.num_classes;
-    const long rows = (long)B * repeats;
-    for (long r0 = 0; r0 < rows; r0 += e->maxB) {
-        const int nb = (int)(rows - r0 < e->maxB ? rows - r0 : e->maxB);
-        launch_repeat_rows(x, e->xt, B, r0, nb, L, st);
+    const int L = e->L;
+    return query_loop(e, x, B, repeats, logits, decisions, st, [&](int nb, int64_t, float* lg) -> int {
         switch (d->kind) {
         case DMAD_WAVE_AS: launch_wave_smooth(e->xt, nb, L, 0, d->window, e->x0, st); break;
         case DMAD_WAVE_MS: launch_wave_smooth(e->xt, nb, L, 1, d->window, e->x0, st); break;
@@ -3115,12 +3037,8 @@ int dmad_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t
             break;
         default: HIPCHK((hipError_t)launch_wave_iir(plan, e->xt, nullptr, nb, L, d->lo, d->hi, 0, e->x0, nullptr, st)); break;
         }
-        CHK(mel_db(e, e->x0, nb, e->spec, st));
-        CHK(classify(e, e->spec, nb, logits + r0 * C, st));       // the fp32 classifier, like dmad_query_logits
-        if (decisions) launch_vote(logits + r0 * C, nb, C, nullptr, decisions + r0, st);
-    }
-    LASTCHK();
-    return 0;
+        return wave_logits(e, e->x0, nb, lg, st);
+    });
 }
 
 int dmad_philox_raw(dmad_engine* e, uint64_t seed, uint64_t sample, uint32_t stream, uint32_t nblocks, uint32_t* out, dmad_stream s) {

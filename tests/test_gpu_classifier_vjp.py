@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import vjp_reservation
 from dmad_hip import synth
 
 pytestmark = pytest.mark.gpu
@@ -240,6 +241,7 @@ def test_every_precision_and_refusals(sd, prec):
     with pytest.raises(DmadError):
         e.reserve_classifier_vjp(2)                      # no classifier loaded yet
     e.load_resnext29(sd)
+    vjp_reservation.check(e, e.reserve_classifier_vjp, vjp_reservation.grow(e, e.reserve_classifier_vjp, (1, 2, 3), []))
     e.reserve_classifier_vjp(4)
     x = specs(3, 11).cuda()
     g = torch.randn(3, 10, generator=torch.Generator().manual_seed(11)).cuda()

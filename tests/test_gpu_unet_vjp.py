@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import vjp_reservation
 from dmad_hip import synth
 
 pytestmark = pytest.mark.gpu
@@ -81,6 +82,7 @@ def test_unet_vjp_deterministic_and_batch_independent(sd):
     e = E.Engine(max_batch=5, precision=E.FP32, with_classifier=False, with_wavenet=False)
     try:
         create_improved_diffusion(None, reverse_timestep=3, state_dict=sd, engine=e)
+        grown = vjp_reservation.grow(e, e.reserve_unet_vjp, (1, 2), [])      # dmad_device_bytes after reserve(1), (2) and, at the end, (3)
         e.reserve_unet_vjp(2)                   # B = 5 runs in passes of 2
         x, g = specs(5, 7).cuda(), specs(5, 8).cuda()
         a = e.unet_eps_vjp(x, 40, g)
@@ -89,6 +91,7 @@ def test_unet_vjp_deterministic_and_batch_independent(sd):
             assert torch.equal(e.unet_eps_vjp(x[r:r + 1].contiguous(), 40, g[r:r + 1].contiguous()), a[r:r + 1]), r
         e.reserve_unet_vjp(1)                   # a smaller reservation keeps the present one
         assert e.unet_eps_vjp(x, 40, g).equal(a)
+        vjp_reservation.check(e, e.reserve_unet_vjp, vjp_reservation.grow(e, e.reserve_unet_vjp, (3,), grown))
     finally:
         e.close()
 

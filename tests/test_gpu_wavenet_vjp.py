@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import vjp_reservation
 from dmad_hip import synth
 
 pytestmark = pytest.mark.gpu
@@ -72,6 +73,7 @@ def test_vjp_against_float64_small_geometry(orc):
     sd = kink_free(synth.wavenet_state_dict(77, cfg))
     eng = E.Engine(wavenet_config=cfg, max_batch=3, precision=E.FP32, with_classifier=False)
     eng.load_wavenet(sd)
+    vjp_reservation.check(eng, eng.reserve_vjp, vjp_reservation.grow(eng, eng.reserve_vjp, (1, 2, 3), []))
     eng.reserve_vjp(3)
     x = clips([0, 7])
     g_eps = torch.randn(x.shape, generator=torch.Generator().manual_seed(11))
