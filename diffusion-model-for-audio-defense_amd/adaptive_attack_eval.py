@@ -15,8 +15,8 @@ black_box_attack_eval.py and siren_attack_eval.py; the baseline defenses AS, MS,
 Additions to the reference's flags:
   * `--classifier_path`: the classifier checkpoint; its default is the path the reference hard-codes (it overrides
     `--classifier_model` / `--classifier_type`, which are kept for compatibility and otherwise unused, as in the reference);
-  * `--grad_backend {hip,torch}` (default hip): the gradient of the ResNeXt29 classifier and of the mel front-end — the engine's
-    vector-Jacobian products, or the torch layers (DESIGN §14); a VGG19_bn classifier always takes the torch branch;
+  * `--grad_backend {hip,torch}` (default hip): the gradient of the classifier (ResNeXt29 or VGG19_bn) and of the mel front-end — the
+    engine's vector-Jacobian products, or the torch layers (DESIGN §14, §18);
   * `--score_grad`: passed to the SDE purifiers (default: their module defaults, 'none' for RevDiffWave, 'hip' for
     RevImprovedDiffusion).
 `--save_path` writes the clean / purified / adversarial waveforms as 16-bit WAV files (standard library only); the reference's
@@ -90,7 +90,7 @@ def build_parser():
     parser.add_argument('--eot_defense_size', type=int, default=1)
     parser.add_argument('--verbose', type=int, default=1)
     parser.add_argument('--grad_backend', choices=['hip', 'torch'], default='hip',
-                        help='gradient of the ResNeXt29 classifier and of the mel front-end: the engine VJPs or the torch layers')
+                        help='gradient of the classifier (ResNeXt29, VGG19_bn) and of the mel front-end: the engine VJPs or the torch layers')
     # device arguments
     parser.add_argument("--dataload_workers_nums", type=int, default=8, help='number of workers for dataloader')
     parser.add_argument("--batch_size", type=int, default=20, help='batch size')
@@ -173,7 +173,7 @@ def build_front(args, classifier=None):
     classifier.cuda()
     if hasattr(classifier, 'bind_engine') and 'engine' not in classifier.__dict__:
         classifier.bind_engine()
-    if 'torch' in getattr(classifier, 'GRAD_BACKENDS', ()) and 'hip' in classifier.GRAD_BACKENDS:    # ResNeXt29 (VGG19_bn: torch layers)
+    if 'torch' in getattr(classifier, 'GRAD_BACKENDS', ()) and 'hip' in classifier.GRAD_BACKENDS:    # ResNeXt29 and VGG19_bn
         classifier.grad_backend = args.grad_backend
     return classifier, MelSpectrogramDB(classifier.__dict__.get('engine'), grad_backend=args.grad_backend)
 

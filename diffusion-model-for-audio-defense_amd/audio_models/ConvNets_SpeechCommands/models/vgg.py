@@ -3,7 +3,8 @@ HIP-backed module.  The parameter containers (`features`, `classifier`) keep the
 that state dicts and pickled checkpoints (`models.vgg.VGG` inside a DataParallel) load unchanged; the
 forward pass runs in libdmad_hip.so: 3x3 convs as implicit GEMM on the fp32 matrix cores over NHWC
 activations with eval-mode BatchNorm folded into a per-channel scale/shift, 2x2 max-pools, and the
-three Linear layers."""
+three Linear layers.  The gradient branch (x.requires_grad) runs the module's own layers, or with grad_backend = 'hip' the
+engine's input VJP (dmad_vgg_vjp)."""
 import math
 
 import torch
@@ -41,6 +42,21 @@ class VGG(nn.Module):
                 elif isinstance(m, nn.Linear):
                     m.weight.data.normal_(0, 0.01); m.bias.data.zero_()
 
+    GRAD_BACKENDS = ('auto', 'torch', 'hip')
+
+    @property
+    def grad_backend(self):
+        """Backend of the gradient branch (x.requires_grad under autograd): 'torch' = the module's own layers (reference l.48-52; MIOpen,
+        weight gradients included), 'hip' = the engine's fp32 tier and VGG19_bn VJP (dmad_hip.autograd.VGGHIP; input gradient only),
+        'auto' (the default) = 'torch'."""
+        return self.__dict__.get('_grad_backend', 'auto')
+
+    @grad_backend.setter
+    def grad_backend(self, value):
+        if value not in self.GRAD_BACKENDS:
+            raise ValueError('grad_backend must be one of %s, not %r' % (self.GRAD_BACKENDS, value))
+        self.__dict__['_grad_backend'] = value
+
     # -- HIP engine binding ---------------------------------------------------------------------
     def bind_engine(self, engine=None):
         """Fold BatchNorm (eval statistics) and upload the weights into the engine (once).  An explicit `engine` that
@@ -54,6 +70,11 @@ class VGG(nn.Module):
     def forward(self, x):
         if self.training:
             raise NotImplementedError('the HIP VGG19_bn is inference-only: call .eval() first')
+        if torch.is_grad_enabled() and x.requires_grad and self.grad_backend == 'hip':
+            if 'engine' not in self.__dict__:
+                self.bind_engine()
+            from dmad_hip.autograd import vgg_hip
+            return vgg_hip(self.__dict__['engine'], x)
         if torch.is_grad_enabled() and x.requires_grad:
             # callers that differentiate through the system: the module's own layers are the torch restatement of
             # reference models/vgg.py:48-52 (eval mode: BatchNorm on its running statistics, Dropout inactive); CUDA tensors only

@@ -8,7 +8,9 @@ three attacks this package runs.
   --defense  AS | MS (transforms/time_defense.py)  DS | LPF | BPF (transforms/frequency_defense.py)
 
 The flags and constants are the reference driver's (adaptive_attack_eval.py there offers these defenses next to the diffusion ones), the
-evaluation loop is adaptive_attack_eval.evaluate, and the attacker is built by the driver that owns the attack.  One flag is added:
+evaluation loop is adaptive_attack_eval.evaluate, and the attacker is built by the driver that owns the attack.  Under CW the gradient of
+the classifier (ResNeXt29 or VGG19_bn) and of the mel front-end follows adaptive_attack_eval's `--grad_backend` (default hip: the engine's
+vector-Jacobian products).  One flag is added:
   * `--defense_backend {hip,host}` (default hip): the engine's kernels (dmad_wave_*, with their VJPs under CW and one
     dmad_defense_query_logits call per batch of queries under the query-only attacks), or the host operators (torch, and scipy's lfilter
     on the CPU as in the reference).

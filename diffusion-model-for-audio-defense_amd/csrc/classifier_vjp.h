@@ -1,5 +1,6 @@
-// Small kernels of the classifier-side vector-Jacobian products (classifier_vjp.hip, DESIGN §14): the ResNeXt29 input VJP
-// (dmad_classify_vjp) and the mel front-end VJP (dmad_mel_db_vjp).  Their convs and 1x1 layers / DFT and filterbank products are
+// Small kernels of the classifier-side vector-Jacobian products (classifier_vjp.hip, DESIGN §14 and §18): the ResNeXt29 input VJP
+// (dmad_classify_vjp), the VGG19_bn input VJP (dmad_vgg_vjp) and the mel front-end VJP (dmad_mel_db_vjp).  Their convs, 1x1 and Linear
+// layers / DFT and filterbank products are
 // gemm_f32.hip launches on transposed weight images packed here.  Every reduction runs in a fixed order (no atomics): results do not
 // depend on the batch.
 #pragma once
@@ -12,6 +13,12 @@ namespace dmad {
 void launch_cvjp_transpose(const float* src, int rows, int cols, long lds, const float* scale, float* dst, int ldd, hipStream_t s);
 // the grouped 3x3 conv's backward image: src [g][tap][m][k] (G x G per group, 8 groups) -> dst[g][8 - tap][k][m] * scale[g * G + m]
 void launch_cvjp_pack_grouped(const float* src, const float* scale, float* dst, int G, hipStream_t s);
+// the dense 3x3 conv's backward image (VGG19_bn): src [tap][M][K] -> dst[8 - tap][k][m] * scale[m]
+void launch_cvjp_pack_dense(const float* src, const float* scale, float* dst, int M, int K, hipStream_t s);
+// 2x2 max-pool and the ReLU in front of it, backward: y [B][H][H][C] the saved post-ReLU map (the pool's input), g [B][H/2][H/2][C] ->
+// gpre [B][H][H][C], the gradient at the ReLU's input.  Each window's g goes to its maximum, the first in scan order (top-left, top-right,
+// bottom-left, bottom-right) on a tie, and only where that maximum is > 0; every element of gpre is written once.  H even, C % 4 == 0
+void launch_vgg_pool_relu_bwd(const float* g, const float* y, float* gpre, int B, int H, int C, hipStream_t s);
 // ReLU backward on the saved post-ReLU map: out[i] = y[i] > 0 ? g[i] : 0 (torch's threshold_backward); out may alias g; n % 4 == 0
 void launch_relu_mask(const float* g, const float* y, float* out, long n, hipStream_t s);
 // head backward: gz[b][p][c] = y[b][p][c] > 0 ? (sum_k W[k][c] g[b][k]) / HW : 0 — the FC (W [ncls][C]), the HW-pixel average pool and

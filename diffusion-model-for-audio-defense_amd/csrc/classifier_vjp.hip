@@ -32,6 +32,52 @@ __global__ void cvjp_pack_grouped_kernel(const float* __restrict__ src, const fl
     dst[i] = src[(((long)g * 9 + (8 - t)) * G + m) * G + k] * scale[g * G + m];
 }
 
+__global__ void cvjp_pack_dense_kernel(const float* __restrict__ src, const float* __restrict__ scale, float* __restrict__ dst, int M, int K,
+                                       long total) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;     // one element of dst [tap][k][m]
+    if (i >= total) return;
+    const int m = (int)(i % M);
+    const long r = i / M;
+    const int k = (int)(r % K), t = (int)(r / K);
+    dst[i] = src[((long)(8 - t) * M + m) * K + k] * scale[m];
+}
+
+// one float4 of channels of one pooled pixel: the window's first maximum in scan order takes g if it is > 0 (torch's max_pool2d keeps
+// the earlier entry on a tie and lets a NaN win; threshold_backward passes where y > 0)
+__global__ void vgg_pool_relu_bwd_kernel(const float4* __restrict__ g, const float4* __restrict__ y, float4* __restrict__ gpre, int H, int C4,
+                                         long total4) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total4) return;
+    const int Hp = H >> 1;
+    const int c = (int)(i % C4);
+    long r = i / C4;
+    const int px = (int)(r % Hp);
+    r /= Hp;
+    const int py = (int)(r % Hp);
+    const long b = r / Hp;
+    const long p00 = ((b * H + 2 * py) * H + 2 * px) * C4 + c, p10 = p00 + (long)H * C4;
+    const float4 gv = g[i];
+    const float4 v[4] = {y[p00], y[p00 + C4], y[p10], y[p10 + C4]};
+    float4 o[4];
+    const float ga[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float w[4] = {(&v[0].x)[j], (&v[1].x)[j], (&v[2].x)[j], (&v[3].x)[j]};
+        float m = w[0];
+        int a = 0;
+#pragma unroll
+        for (int q = 1; q < 4; ++q)
+            if (w[q] > m || w[q] != w[q]) { m = w[q]; a = q; }
+        const float t = m > 0.f ? ga[j] : 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) (&o[q].x)[j] = a == q ? t : 0.f;
+    }
+    gpre[p00] = o[0];
+    gpre[p00 + C4] = o[1];
+    gpre[p10] = o[2];
+    gpre[p10 + C4] = o[3];
+}
+
 __global__ void relu_mask_kernel(const float4* __restrict__ g, const float4* __restrict__ y, float4* out, long n4) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
@@ -119,6 +165,17 @@ void launch_cvjp_transpose(const float* src, int rows, int cols, long lds, const
 void launch_cvjp_pack_grouped(const float* src, const float* scale, float* dst, int G, hipStream_t s) {
     const long total = 8l * 9 * G * G;
     hipLaunchKernelGGL(cvjp_pack_grouped_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, src, scale, dst, G, total);
+}
+
+void launch_cvjp_pack_dense(const float* src, const float* scale, float* dst, int M, int K, hipStream_t s) {
+    const long total = 9l * M * K;
+    hipLaunchKernelGGL(cvjp_pack_dense_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, src, scale, dst, M, K, total);
+}
+
+void launch_vgg_pool_relu_bwd(const float* g, const float* y, float* gpre, int B, int H, int C, hipStream_t s) {
+    const long total4 = (long)B * (H / 2) * (H / 2) * (C / 4);
+    hipLaunchKernelGGL(vgg_pool_relu_bwd_kernel, dim3(nblk(total4, 256)), dim3(256), 0, s, (const float4*)g, (const float4*)y, (float4*)gpre, H,
+                       C / 4, total4);
 }
 
 void launch_relu_mask(const float* g, const float* y, float* out, long n, hipStream_t s) {

@@ -257,6 +257,15 @@ struct dmad_engine {
     int rxvjpB = 0;
     float *rxvjp_tape = nullptr, *rxvjp_work = nullptr;
     RxTape rx_tape;
+    // VGG19_bn VJP workspace (dmad_reserve_vgg_vjp): the tape of the fp32 forward — the 16 post-ReLU conv maps and the two
+    // post-ReLU FC vectors — [vgvjpB] spectrograms per slot, two gradient ping-pong maps of 32 x 32 x 64 floats per spectrogram and the
+    // backward weight images: convs 1 - 15 tap-flipped and transposed with the BN scale folded in, classifier.0 / .3 transposed
+    struct VggTape { float* c[16] = {}; float* f[2] = {}; };
+    int vgvjpB = 0, vgvjp_lastB = 0;       // lastB: rows of the last pass when the last call ran as one pass (dmad_vgg_vjp_tape), else 0
+    float *vgvjp_tape = nullptr, *vgvjp_work = nullptr;
+    float* vconvwT[16] = {nullptr};
+    float* vfcwT[2] = {nullptr};
+    VggTape vg_tape;
     // mel front-end VJP (dmad_mel_db_vjp): transposed filterbank [kMelLd][32] and DFT [2048][kDftKT] images, gradient maps of
     // melvjpB clips per pass (allocated on the first call)
     int melvjpB = 0;
@@ -1642,15 +1651,17 @@ int mel_db_vjp(dmad_engine* e, const float* x, int B, const float* g_spec, float
 // h16 = 1: the classifier's 16-bit tier where one is resident (ResNeXt29 on engines with a 16-bit side) — the fast mode's; 2: its
 // split-f16 tier (exact-vote engines) — tier 1 of the exact-vote loops; every other caller (dmad_classify, the recheck tiers) gets the
 // fp32 matrix cores
-int classify(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, int h16 = 0) {
-    CHK(need_classifier(e)); CHK(need_batch(e, B));
-    if (e->cls_kind == 1) return (h16 == 1 && e->rx_h16) ? classify_resnext_h16(e, spec, B, logits, s)
-                                 : (h16 == 2 && e->rx_x3) ? classify_resnext_x3(e, spec, B, logits, s) : classify_resnext(e, spec, B, logits, s);
-    float *cur = e->act0, *nxt = e->act1;
+// VGG19_bn on the fp32 matrix cores.  tape (the VJP's forward): every conv writes its post-ReLU map and the first two Linear layers
+// their post-ReLU vectors into the tape's slots in place of act0 / act1 — the same launches with the same n_ref, so the same bits —
+// and only the pooled maps pass through act0
+int classify_vgg(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, const dmad_engine::VggTape* tape = nullptr) {
+    auto spare = [&](const float* in) { return in == e->act0 ? e->act1 : e->act0; };      // the work map `in` does not occupy
+    float* cur = tape ? tape->c[0] : e->act0;
     launch_vgg_conv1(spec, e->vconv1w, e->vscale[0], e->vshift[0], cur, B, s);
     int H = 32, cin = 64, li = 1;
     for (int i = 1; i < kVggCfgLen; ++i) {
         const int v = kVggCfg[i];
+        float* nxt = (tape && v > 0) ? tape->c[li] : spare(cur);
         if (v < 0) {
             launch_maxpool2_nhwc(cur, nxt, B, H, H, cin, s);
             H >>= 1;
@@ -1660,16 +1671,99 @@ int classify(dmad_engine* e, const float* spec, int B, float* logits, hipStream_
             cin = v;
             ++li;
         }
-        float* t = cur; cur = nxt; nxt = t;
+        cur = nxt;
     }
     const int fin[3] = {512, 4096, 4096}, fout[3] = {4096, 4096, e->cfg.num_classes};
     for (int j = 0; j < 3; ++j) {
-        float* dst = (j == 2) ? logits : nxt;
+        float* dst = (j == 2) ? logits : tape ? tape->f[j] : spare(cur);
         launch_gemm_f32(plain_gemm(e->vfcw[j], cur, dst, nullptr, e->vfcb[j], fout[j], fin[j], B, fout[j], fin[j], j < 2), s, e->slab,
                         e->slab_floats, (long)e->maxB);
-        float* t = cur; cur = nxt; nxt = t;
+        cur = dst;
     }
     LASTCHK();
+    return 0;
+}
+
+int classify(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, int h16 = 0) {
+    CHK(need_classifier(e)); CHK(need_batch(e, B));
+    if (e->cls_kind == 1) return (h16 == 1 && e->rx_h16) ? classify_resnext_h16(e, spec, B, logits, s)
+                                 : (h16 == 2 && e->rx_x3) ? classify_resnext_x3(e, spec, B, logits, s) : classify_resnext(e, spec, B, logits, s);
+    return classify_vgg(e, spec, B, logits, s);
+}
+
+// floats per spectrogram of the VGG19_bn tape's slots: the 16 post-ReLU conv maps, then the two post-ReLU FC vectors (311 296 in all)
+size_t vgg_tape_floats(int index) {
+    if (index >= 16) return 4096;
+    int H = 32, li = 0;
+    for (int i = 0; i < kVggCfgLen; ++i) {
+        if (kVggCfg[i] < 0) { H >>= 1; continue; }
+        if (li++ == index) return (size_t)H * H * kVggCfg[i];
+    }
+    return 0;
+}
+constexpr size_t kVggWork = 65536;       // floats per spectrogram of one gradient ping-pong map: 32 x 32 x 64, the largest map
+
+// The data gradient of a dense VGG19_bn 3x3 conv on its packed image (launch_cvjp_pack_dense): g [B][H][H][M] -> gx [B][H][H][K], the
+// forward's GEMM with M and K exchanged.  slab / n_ref as the forward passes them: the split count follows from the layer and the
+// engine's max_batch, never from B
+int vgg_conv_dgrad(const float* wT, const float* g, float* gx, int M, int K, int B, int H, float* slab, long slab_floats, long n_ref, hipStream_t s) {
+    if (launch_gemm_f32(nhwc_conv_args(wT, nullptr, nullptr, g, gx, K, M, 9, B, H, 1, nullptr), s, slab, slab_floats, n_ref) != 0)
+        return fail(DMAD_ERR_STATE, "VGG19_bn VJP: no GEMM for M = %d, K = %d", K, M);
+    return 0;
+}
+
+// g_spec = (d logits / d spec)^T g_logits of classify_vgg; logits: the forward it recomputes (B <= vgvjpB)
+int vgg_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
+    const dmad_engine::VggTape& tp = e->vg_tape;
+    CHK(classify_vgg(e, spec, B, logits, s, &tp));
+    float *cur = e->vgvjp_work, *nxt = e->vgvjp_work + kVggWork * e->vgvjpB;
+    auto rows = [&](const float* wT, const float* g, float* out, int M, int K) -> int {      // out [B][M] = g [B][K] wT[M][K]^T
+        if (launch_gemm_f32(plain_gemm(wT, g, out, nullptr, nullptr, M, K, B, M, K, 0), s, e->slab, e->slab_floats, (long)e->maxB) != 0)
+            return fail(DMAD_ERR_STATE, "VGG19_bn VJP: no GEMM for M = %d, K = %d", M, K);
+        return 0;
+    };
+    // classifier.6 (num_classes reduction elements, k ascending) with classifier.4's ReLU, then classifier.3 / .0 on their transposed images
+    launch_rx_head_bwd(g_logits, e->vfcw[2], tp.f[1], cur, B, e->cfg.num_classes, 1, 4096, s);
+    CHK(rows(e->vfcwT[1], cur, nxt, 4096, 4096));
+    launch_relu_mask(nxt, tp.f[0], nxt, (long)B * 4096, s);
+    CHK(rows(e->vfcwT[0], nxt, cur, 512, 4096));                                             // the gradient at the last pool's output
+    int H = 1, li = 16;
+    bool masked = false;                 // cur is the gradient at a ReLU's input (after a pool) / at its output (after a conv)
+    for (int i = kVggCfgLen - 1; i >= 1; --i) {
+        const int v = kVggCfg[i];
+        if (v < 0) {                     // the pool and the ReLU of conv li - 1 in front of it
+            H <<= 1;
+            launch_vgg_pool_relu_bwd(cur, tp.c[li - 1], nxt, B, H, kVggCfg[i - 1], s);
+            masked = true;
+        } else {                         // conv li - 1 (its input: conv li - 2's map, or a pooled one) with its BN scale
+            --li;
+            if (!masked) launch_relu_mask(cur, tp.c[li], cur, (long)B * H * H * v, s);
+            const int cin = kVggCfg[i - 1] > 0 ? kVggCfg[i - 1] : kVggCfg[i - 2];
+            CHK(vgg_conv_dgrad(e->vconvwT[li], cur, nxt, v, cin, B, H, e->slab, e->slab_floats, (long)e->maxB * H * H, s));
+            masked = false;
+        }
+        std::swap(cur, nxt);
+    }
+    launch_rx_conv1_bwd(cur, tp.c[0], e->vconv1w, e->vscale[0], g_spec, B, s);               // conv 0's ReLU, bn and 1 <- 64 3x3 conv
+    LASTCHK();
+    return 0;
+}
+
+int need_vgg(const dmad_engine* e) {
+    CHK(need_classifier(e));
+    return e->cls_kind == 0 ? 0 : fail(DMAD_ERR_STATE, "the VGG19_bn VJP serves VGG19_bn only: this engine holds ResNeXt29 (dmad_classify_vjp)");
+}
+
+int vgg_vjp(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
+    CHK(need_vgg(e));
+    if (!e->vgvjpB) return fail(DMAD_ERR_STATE, "no VGG19_bn VJP workspace: call dmad_reserve_vgg_vjp first");
+    CHK(need_batch(e, B));
+    const int nc = e->cfg.num_classes;
+    e->vgvjp_lastB = 0;
+    CHK(for_passes(B, e->vgvjpB, [&](int64_t b0, int bb) {
+        return vgg_vjp_pass(e, spec + b0 * 1024, bb, g_logits + b0 * nc, g_spec + b0 * 1024, logits ? logits + b0 * nc : e->logits, s);
+    }));
+    if (B <= e->vgvjpB) e->vgvjp_lastB = B;
     return 0;
 }
 
@@ -2269,14 +2363,25 @@ int dmad_conv_f32_vjp(const float* g_y, const float* w, const float* scale, cons
                       int32_t M, int32_t K, int32_t taps, int32_t stride, int32_t groups, int32_t form, int32_t ldt, float* wT, float* gm,
                       float* work, float* g_x, dmad_stream s) {
     if (!g_y || !w || !wT || !g_x) return fail(DMAD_ERR_INVALID, "null argument");
-    if (B < 1 || H < 1 || M < 16 || K < 4 || (M % 16) || (K % 4) || (stride != 1 && stride != 2) || (taps != 1 && taps != 9) || form < 0 || form > 2)
-        return fail(DMAD_ERR_INVALID, "bad geometry (M a multiple of 16, K of 4, taps 1 or 9, stride 1 or 2, form 0 - 2)");
+    if (B < 1 || H < 1 || M < 16 || K < 4 || (M % 16) || (K % 4) || (stride != 1 && stride != 2) || (taps != 1 && taps != 9) || form < 0 || form > 3)
+        return fail(DMAD_ERR_INVALID, "bad geometry (M a multiple of 16, K of 4, taps 1 or 9, stride 1 or 2, form 0 - 3)");
     if (stride == 2 && (H & 1)) return fail(DMAD_ERR_INVALID, "a stride-2 gradient is dilated to an even map: H = %d", H);
     if ((stride == 2 || form == 1) && !work) return fail(DMAD_ERR_INVALID, "this form needs the work map");
     if (int r = gemm_f32_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, fp32 narrow tile) failed: %d", r);
     const hipStream_t st = (hipStream_t)s;
     const int Ho = form == 1 ? 2 * H : (H - 1) / stride + 1;
-    if (form < 2) {                              // the UNet's forms
+    if (form == 3) {                             // VGG19_bn's form
+        if (taps != 9 || stride != 1 || groups != 1 || !scale || ldt || acc || (K % 16))
+            return fail(DMAD_ERR_INVALID, "VGG19_bn's form: a dense 3x3 with stride 1, a scale, K a multiple of 16, no acc and no padded pitch");
+        const float* g = g_y;
+        if (mask_y) {
+            if (!gm) return fail(DMAD_ERR_INVALID, "the ReLU mask needs its output map");
+            launch_relu_mask(g_y, mask_y, gm, (long)B * H * H * M, st);
+            g = gm;
+        }
+        launch_cvjp_pack_dense(w, scale, wT, M, K, st);
+        CHK(vgg_conv_dgrad(wT, g, g_x, M, K, B, H, nullptr, 0, 0, st));
+    } else if (form < 2) {                       // the UNet's forms
         if (groups != 1 || scale || mask_y || gm || ldt || (form == 1 && (taps != 9 || stride != 1)))
             return fail(DMAD_ERR_INVALID, "the UNet's forms are dense, unscaled and unmasked (Upsample: 3x3, stride 1)");
         un_pack_wT(w, wT, taps, K, M, st);
@@ -2552,6 +2657,74 @@ int dmad_reserve_classifier_vjp(dmad_engine* e, int32_t max_batch) {
 int dmad_classify_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s) {
     if (!e || !spec || !g_logits || !g_spec) return fail(DMAD_ERR_INVALID, "null argument");
     return classify_vjp(e, spec, B, g_logits, g_spec, logits, (hipStream_t)s);
+}
+
+int dmad_reserve_vgg_vjp(dmad_engine* e, int32_t max_batch) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
+    if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
+    CHK(need_vgg(e));
+    const int vB = max_batch < e->maxB ? max_batch : e->maxB;
+    if (vB <= e->vgvjpB) return 0;
+    if (e->vgvjpB) {                        // a larger reservation replaces the present one
+        e->release(&e->vgvjp_tape); e->release(&e->vgvjp_work);
+        e->vgvjpB = e->vgvjp_lastB = 0;
+    }
+    // the backward images, packed on the device from the resident fp32 images — each one once: a call that failed part of the way
+    // (out of memory) leaves the images it had packed in place, and the next call allocates only the missing ones
+    int cin = 64, li = 1;
+    for (int i = 1; i < kVggCfgLen; ++i) {
+        const int v = kVggCfg[i];
+        if (v < 0) continue;
+        if (!e->vconvwT[li]) {
+            CHK(e->alloc(&e->vconvwT[li], (size_t)9 * cin * v));          // [tap][v][cin] -> [8 - tap][cin][v] * scale[v]
+            launch_cvjp_pack_dense(e->vconvw[li], e->vscale[li], e->vconvwT[li], v, cin, nullptr);
+        }
+        cin = v;
+        ++li;
+    }
+    if (!e->vfcwT[1]) {
+        CHK(e->alloc(&e->vfcwT[1], (size_t)4096 * 4096));                 // classifier.3 [4096][4096] -> transposed
+        launch_cvjp_transpose(e->vfcw[1], 4096, 4096, 4096, nullptr, e->vfcwT[1], 4096, nullptr);
+    }
+    if (!e->vfcwT[0]) {
+        CHK(e->alloc(&e->vfcwT[0], (size_t)512 * 4096));                  // classifier.0 [4096][512] -> [512][4096]
+        launch_cvjp_transpose(e->vfcw[0], 4096, 512, 512, nullptr, e->vfcwT[0], 4096, nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    size_t tape = 0, off[18];
+    for (int k = 0; k < 18; ++k) { off[k] = tape; tape += vgg_tape_floats(k); }
+    CHK(e->alloc(&e->vgvjp_tape, (size_t)vB * tape));
+    if (int r = e->alloc(&e->vgvjp_work, (size_t)vB * 2 * kVggWork)) {    // no half reservation stays behind
+        e->release(&e->vgvjp_tape);
+        return r;
+    }
+    for (int k = 0; k < 18; ++k) (k < 16 ? e->vg_tape.c[k] : e->vg_tape.f[k - 16]) = e->vgvjp_tape + off[k] * vB;
+    HIPCHK(hipDeviceSynchronize());
+    e->vgvjpB = vB;
+    return 0;
+}
+
+int dmad_vgg_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s) {
+    if (!e || !spec || !g_logits || !g_spec) return fail(DMAD_ERR_INVALID, "null argument");
+    return vgg_vjp(e, spec, B, g_logits, g_spec, logits, (hipStream_t)s);
+}
+
+int dmad_vgg_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s) {
+    if (!e || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(need_vgg(e));
+    if (index < 0 || index > 17) return fail(DMAD_ERR_INVALID, "tape map %d outside [0, 17]", index);
+    if (B < 1 || B > e->vgvjp_lastB) return fail(DMAD_ERR_STATE, "the tape holds %d rows of a one-pass dmad_vgg_vjp call, not %d", e->vgvjp_lastB, B);
+    const float* src = index < 16 ? e->vg_tape.c[index] : e->vg_tape.f[index - 16];
+    HIPCHK(hipMemcpyAsync(out, src, (size_t)B * vgg_tape_floats(index) * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)s));
+    return 0;
+}
+
+int dmad_vgg_pool_relu_bwd(const float* g, const float* y, int32_t B, int32_t H, int32_t C, float* gpre, dmad_stream s) {
+    if (!g || !y || !gpre) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || H < 2 || (H & 1) || C < 4 || (C & 3)) return fail(DMAD_ERR_INVALID, "bad geometry (H even, C a multiple of 4)");
+    launch_vgg_pool_relu_bwd(g, y, gpre, B, H, C, (hipStream_t)s);
+    LASTCHK();
+    return 0;
 }
 
 int dmad_mel_db_vjp(dmad_engine* e, const float* x, int32_t B, const float* g_spec, float* g_x, float* spec, dmad_stream s) {

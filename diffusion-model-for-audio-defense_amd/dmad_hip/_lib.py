@@ -83,6 +83,7 @@ _SIGNATURES = {
     'dmad_qkv_attention_bwd': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_rx_head_bwd': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_rx_conv1_bwd': (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P]),
+    'dmad_vgg_pool_relu_bwd': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_smooth_votes': (C.c_int, [_P, _P, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_int64, C.c_int32,
                                     C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P]),
     'dmad_set_mode': (C.c_int, [_P, C.c_int32]),
@@ -98,6 +99,9 @@ _SIGNATURES = {
     'dmad_reserve_classifier_vjp': (C.c_int, [_P, C.c_int32]),
     'dmad_classify_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     'dmad_mel_db_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    'dmad_reserve_vgg_vjp': (C.c_int, [_P, C.c_int32]),
+    'dmad_vgg_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    'dmad_vgg_vjp_tape': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
     'dmad_vpsde_purify': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64,
                                     C.c_int32, _P, _P, _P]),
     'dmad_vpsde_purify_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P, _P, _P, _P]),

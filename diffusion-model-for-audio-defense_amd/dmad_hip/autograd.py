@@ -229,6 +229,37 @@ def resnext_hip(engine, spec: torch.Tensor) -> torch.Tensor:
     return ResNeXtHIP.apply(spec, engine)
 
 
+class VGGHIP(torch.autograd.Function):
+    """logits = VGG19_bn(spec [B,1,32,32]) on the engine's fp32 tier (classify_tier(spec, 0)), differentiable in `spec` through the
+    engine's VJP.  Saves only the input; the backward re-runs the forward with its tape saved (dmad_vgg_vjp).  The VJP workspace is
+    reserved on first use.  No weight gradients.  First-order only: create_graph=True raises."""
+
+    @staticmethod
+    def forward(ctx, spec, engine):
+        _require_cuda(spec)
+        logits = engine.classify_tier(spec, 0)
+        ctx.engine = engine
+        ctx.save_for_backward(spec)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g_logits):
+        if torch.is_grad_enabled():
+            raise DmadError('the HIP VGG19_bn VJP is first-order only: create_graph=True (double backward) is not supported; '
+                            "use grad_backend='torch' for higher derivatives")
+        spec, = ctx.saved_tensors
+        eng, B = ctx.engine, spec.shape[0]
+        if eng.vgg_vjp_batch < min(B, eng.max_batch):
+            eng.reserve_vgg_vjp(B)
+        g = eng.vgg_vjp(spec, g_logits.contiguous())
+        return g.view(spec.shape).to(spec.dtype), None
+
+
+def vgg_hip(engine, spec: torch.Tensor) -> torch.Tensor:
+    """logits = VGG19_bn(spec [B,1,32,32]) on the engine's fp32 tier, differentiable in `spec` (VGGHIP)."""
+    return VGGHIP.apply(spec, engine)
+
+
 class MelDBHIP(torch.autograd.Function):
     """[B,1,16000] -> [B,1,32,32] dB mel spectrogram on the engine (mel_db), differentiable in `x` through the engine's mel VJP
     (dmad_mel_db_vjp, which recomputes the forward).  Saves only the input.  First-order only: create_graph=True raises."""

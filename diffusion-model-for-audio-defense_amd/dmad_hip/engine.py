@@ -56,6 +56,8 @@ DEFAULT_SPEC_RECHECK_MARGIN2 = 5e-4          # 2.2 x the largest leader-differen
 # sample (error beyond the bound AND an exact margin small enough to be overturned) at or below 1e-9.
 TAIL_Z = 5.4
 VGG19_CFG = [64, 64, 'M', 128, 128, 'M', 256, 256, 256, 256, 'M', 512, 512, 512, 512, 'M', 512, 512, 512, 512, 'M']
+# (H, C) of VGG19_bn's 16 post-ReLU conv maps on a 32 x 32 spectrogram: the conv slots of the VJP's tape (vgg_vjp_tape)
+VGG_TAPE_MAPS = ((32, 64),) * 2 + ((16, 128),) * 2 + ((8, 256),) * 4 + ((4, 512),) * 4 + ((2, 512),) * 4
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -206,7 +208,7 @@ class Engine:
         self.has_wavenet = False
         self.has_classifier = False
         self.has_unet = False
-        self.vjp_batch = self.unet_vjp_batch = self.classifier_vjp_batch = 0     # rows per pass the VJP workspaces are reserved for
+        self.vjp_batch = self.unet_vjp_batch = self.classifier_vjp_batch = self.vgg_vjp_batch = 0     # rows per pass the VJP workspaces are reserved for
         # which weights are resident (state_fingerprint): a module that binds to an engine holding OTHER weights must
         # not silently run them
         self.wavenet_owner = self.classifier_owner = self.unet_owner = None
@@ -750,6 +752,43 @@ class Engine:
                                              _ptr(None if lg is None else lg[s:e]), _stream()))
         return (gs, lg) if want_logits else gs
 
+    def reserve_vgg_vjp(self, max_batch: int):
+        """dmad_reserve_vgg_vjp: the workspace of vgg_vjp (the VGG19_bn forward's tape, the gradient maps and, once, the backward weight
+        images) for up to max_batch spectrograms per pass (capped at max_batch; a larger reservation replaces a smaller one).  VGG19_bn
+        engines of every precision; DmadError otherwise."""
+        check(self.lib.dmad_reserve_vgg_vjp(self._h, int(max_batch)))
+        self.vgg_vjp_batch = max(self.vgg_vjp_batch, min(int(max_batch), self.max_batch))
+
+    def vgg_vjp(self, spec: torch.Tensor, g_logits: torch.Tensor, want_logits: bool = False):
+        """g_spec = (d logits / d spec)^T g_logits for logits = VGG19_bn(spec) on the fp32 tier ([B,1,32,32] or [B,32,32] -> [B,32,32]).
+        want_logits: also return the logits, bit-identical to classify_tier(spec, 0).  Without a reservation the first call reserves
+        its own rows (capped at max_batch); a present reservation is kept and a larger call runs in passes of its size, with the same
+        bits (reserve_vgg_vjp chooses the pass size; autograd.VGGHIP grows it to the batch it meets).  VGG19_bn engines only."""
+        sp = self._spec(spec)
+        B = sp.shape[0]
+        if not g_logits.is_cuda or tuple(g_logits.shape) != (B, self.num_classes):
+            raise DmadError('g_logits must be a CUDA tensor [%d, %d], not %s' % (B, self.num_classes, tuple(g_logits.shape)))
+        if not self.vgg_vjp_batch:
+            self.reserve_vgg_vjp(B)
+        g = g_logits.detach().contiguous().float()
+        gs = torch.empty_like(sp)
+        lg = torch.empty((B, self.num_classes), device=sp.device, dtype=torch.float32) if want_logits else None
+        for s, e in self._chunks(B):
+            check(self.lib.dmad_vgg_vjp(self._h, _ptr(sp[s:e]), e - s, _ptr(g[s:e]), _ptr(gs[s:e]),
+                                        _ptr(None if lg is None else lg[s:e]), _stream()))
+        return (gs, lg) if want_logits else gs
+
+    def vgg_vjp_tape(self, index: int, B: int) -> torch.Tensor:
+        """dmad_vgg_vjp_tape: map `index` of the last vgg_vjp call's tape, rows [0, B) — 0 - 15 the post-ReLU conv maps [B,H,H,C] (NHWC),
+        16 - 17 the post-ReLU FC vectors [B,4096] (test hook; that call must have run as one pass)."""
+        if index < 16:
+            H, C = VGG_TAPE_MAPS[index]
+            out = torch.empty((int(B), H, H, C), device='cuda', dtype=torch.float32)
+        else:
+            out = torch.empty((int(B), 4096), device='cuda', dtype=torch.float32)
+        check(self.lib.dmad_vgg_vjp_tape(self._h, int(index), int(B), _ptr(out), _stream()))
+        return out
+
     def mel_db_vjp(self, x: torch.Tensor, g_spec: torch.Tensor, want_spec: bool = False):
         """g_x = (d melDB / d x)^T g_spec for the dB mel front-end of mel_db ([B,1,L] or [B,L] -> [B,L]; g_spec [B,1,32,32] or [B,32,32]).
         want_spec: also return the spectrogram [B,1,32,32], bit-identical to mel_db(x).  The forward is recomputed; the first call
@@ -1277,7 +1316,7 @@ def conv_f32(x: torch.Tensor, w: torch.Tensor, shift: Optional[torch.Tensor] = N
 def conv_f32_vjp(g_y: torch.Tensor, w: torch.Tensor, H: int, form: int = 0, stride: int = 1, groups: int = 1,
                  scale: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None, acc: Optional[torch.Tensor] = None, ldt: int = 0):
     """dmad_conv_f32_vjp — the data gradient of an NHWC conv (test hook; forms of include/dmad.h: 0 UNet conv, 1 UNet Upsample, 2
-    ResNeXt29).  g_y fp32 [B,Ho,Ho,groups*M] (ldt channels with a padded 1x1 image), w [groups, taps, M, K] in the forward layout, H the
+    ResNeXt29, 3 VGG19_bn's dense 3x3 with its BN scale).  g_y fp32 [B,Ho,Ho,groups*M] (ldt channels with a padded 1x1 image), w [groups, taps, M, K] in the forward layout, H the
     forward conv's input resolution.  Returns (g_x, wT, gm | None, work | None): the gradient, the packed weight image as the pack kernel
     wrote it, the masked gradient, and the dilated / pre-sum work map."""
     lib = _lib.load()
@@ -1377,6 +1416,18 @@ def rx_head_bwd(g_logits: torch.Tensor, W: torch.Tensor, y: torch.Tensor) -> tor
     gz = torch.empty_like(y)
     check(lib.dmad_rx_head_bwd(_ptr(g_logits), _ptr(W), _ptr(y), B, int(W.shape[0]), HW, Cn, _ptr(gz), _stream()))
     return gz
+
+
+def vgg_pool_relu_bwd(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """dmad_vgg_pool_relu_bwd: g [B,H/2,H/2,C], y [B,H,H,C] (the saved post-ReLU map) -> gpre [B,H,H,C] (2x2 max-pool and the ReLU in front
+    of it, backward) (test hook)."""
+    lib = _lib.load()
+    g, y = _f32(g), _f32(y)
+    B, H, _, Cn = y.shape
+    assert y.is_cuda and y.shape[2] == H and tuple(g.shape) == (B, H // 2, H // 2, Cn)
+    gpre = torch.empty_like(y)
+    check(lib.dmad_vgg_pool_relu_bwd(_ptr(g), _ptr(y), B, H, Cn, _ptr(gpre), _stream()))
+    return gpre
 
 
 def rx_conv1_bwd(g: torch.Tensor, a: torch.Tensor, w: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:

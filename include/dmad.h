@@ -284,7 +284,8 @@ int dmad_unet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, co
  * transposed weight images (1x1 convs transposed, the grouped 3x3 conv tap-flipped with m / k swapped per group, every eval-BatchNorm
  * scale folded in; as large as the resident fp32 images), packed on the device from those.  max_batch is capped at the engine's
  * max_batch.  A larger reservation replaces a smaller one; a smaller one keeps the present.  Counted by dmad_device_bytes.
- * DMAD_ERR_STATE before the classifier weights are finalised, or for an engine that holds VGG19_bn.
+ * DMAD_ERR_STATE before the classifier weights are finalised, or for an engine that holds VGG19_bn (its pair is dmad_reserve_vgg_vjp /
+ * dmad_vgg_vjp below).
  *
  * dmad_classify_vjp:  g_spec = (d logits / d spec)^T g_logits  for logits = CifarResNeXt(spec) (models/resnext.py:133-142) on the fp32
  * tier.  spec, g_spec: device fp32 [B][32][32]; g_logits: device fp32 [B][num_classes].  logits: optional (NULL) device fp32
@@ -294,7 +295,7 @@ int dmad_unet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, co
  * images (a stride-2 3x3 on the zero-dilated gradient; the stride-2 shortcut at the output resolution, scattered into the even
  * pixels), every ReLU as g * [y > 0] on the saved map, the shortcut gradient summed in the reduce conv's epilogue; head and conv1 as
  * small kernels.  No atomics, no split-K: g_spec is bit-identical across calls and independent of the batch.  DMAD_ERR_STATE without a
- * reservation or for a VGG19_bn engine.
+ * reservation or for a VGG19_bn engine (use dmad_vgg_vjp).
  *
  * dmad_mel_db_vjp:  g_x = (d melDB / d x)^T g_spec  for melDB = AmplitudeToDB(MelSpectrogram(x)) (certified_robustness_eval.py:85-87, the
  * forward of dmad_mel_db).  x, g_x: device fp32 [B][clip_len]; g_spec: device fp32 [B][32][32].  spec: optional (NULL) device fp32
@@ -305,6 +306,35 @@ int dmad_unet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, co
 int dmad_reserve_classifier_vjp(dmad_engine* e, int32_t max_batch);
 int dmad_classify_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s);
 int dmad_mel_db_vjp(dmad_engine* e, const float* x, int32_t B, const float* g_spec, float* g_x, float* spec, dmad_stream s);
+
+/* The same pair for the other classifier with a forward on the engine, VGG19_bn (models/vgg.py:31-52).  DESIGN §18.
+ *
+ * dmad_reserve_vgg_vjp reserves the VGG19_bn VJP workspace for up to max_batch spectrograms per pass: the TAPE of the fp32 forward — the
+ * 16 post-ReLU conv maps and the two post-ReLU FC vectors, 311 296 floats (1.25 MB) per spectrogram —, two gradient ping-pong maps
+ * (131 072 floats, 0.5 MB per spectrogram) and, on the first reservation, the backward weight images: convs 1 - 15 tap-flipped with m / k
+ * swapped and the eval-BatchNorm scale folded in (wT[8 - tap][k][m] = w[tap][m][k] * scale[m]), classifier.0 and classifier.3 transposed
+ * (38.9 M floats, 155 MB: as large as the resident fp32 images), packed on the device from those.  max_batch is capped at the engine's
+ * max_batch.  A larger reservation replaces a smaller one; a smaller one keeps the present.  Counted by dmad_device_bytes.
+ * DMAD_ERR_STATE before the classifier weights are finalised, or for an engine that holds ResNeXt29.
+ *
+ * dmad_vgg_vjp:  g_spec = (d logits / d spec)^T g_logits  for logits = VGG19_bn(spec) on the fp32 tier.  Shapes as dmad_classify_vjp.
+ * logits: optional (NULL), bit-identical to dmad_classify_tier(.., tier = 0, ..): the forward runs dmad_classify's launches with the
+ * tape's slots in place of its work maps.  Every engine precision.  The input gradient only.  B in [1, max_batch], processed in passes
+ * of the reservation's size.  The backward walks the layers in reverse: classifier.6 and classifier.4's ReLU as one small kernel (k
+ * ascending), classifier.3 / .0 as row-form fp32 GEMMs on the transposed images, each 2x2 max-pool together with the ReLU in front of
+ * it as one kernel (the window's gradient goes to its first maximum in scan order — torch's max_pool2d rule — and only where that is
+ * > 0; the arg-max is recomputed from the tape), every other ReLU as g * [y > 0], every 3x3 conv as the forward's fp32 GEMM on the
+ * packed image, conv 0 as dmad_rx_conv1_bwd's kernel.  No atomics.  The deep layers use the forward's split-K slab with the forward's
+ * reference row count (max_batch * H * H), so the split count follows from the layer and the engine: g_spec is bit-identical across
+ * calls and does not depend on B, on the row's place in the batch or on the reservation's size.  DMAD_ERR_STATE without a reservation
+ * or for a ResNeXt29 engine.
+ *
+ * dmad_vgg_vjp_tape (test hook): copies map `index` of the last dmad_vgg_vjp call's tape, rows [0, B), to out (device): index 0 - 15 the
+ * conv maps, NHWC [B][H][H][C]; 16 - 17 the FC vectors [B][4096].  Valid when that call ran as one pass (its B <= the reservation) and
+ * B <= its B; DMAD_ERR_STATE otherwise. */
+int dmad_reserve_vgg_vjp(dmad_engine* e, int32_t max_batch);
+int dmad_vgg_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s);
+int dmad_vgg_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s);
 
 /* The reverse VP-SDE purifier of the reference's adaptive-attack driver (adaptive_attack_eval.py --defense Diffusion ->
  * diffusion_models/diffwave_sde.py RevDiffWave.audio_editing_sample: torchsde.sdeint_adjoint(RevVPSDE, method='euler', dt = 1/T)).
@@ -673,6 +703,8 @@ int dmad_conv_x3(const float* x, const float* x2, int32_t ksplit, const float* w
  *           [g][8 - tap][k][m]).  mask_y (optional, g_y's shape): g_y is first masked by mask_y > 0 into gm (the ReLU backward).  Stride 2:
  *           the 3x3 runs on the zero-dilated gradient (work [B][H][H][8 * M]); the 1x1 shortcut runs at Ho (work [B][Ho][Ho][K]) and is
  *           scattered into the even pixels of g_x.  acc: the GEMM's residual (not with the stride-2 1x1).
+ *   form 3  VGG19_bn's dense 3x3 convs (stride 1, one group, K % 16 == 0) with the eval-mode BN scale [M] folded into the image: wT
+ *           [8 - tap][k][m] = w[tap][m][k] * scale[m]; mask_y (optional, g_y's shape) as in form 2; no acc, no ldt.
  * M % 16 == 0, K % 4 == 0; H even with stride 2.  wT, gm and work are left as the kernels wrote them (the tests read them). */
 int dmad_conv_f32(const float* x, const float* x2, int32_t ksplit, const float* w, const float* scale, const float* shift, const float* res,
                   int32_t B, int32_t H, int32_t M, int32_t K, int32_t taps, int32_t stride, int32_t groups, int32_t relu, float* slab,
@@ -697,6 +729,10 @@ int dmad_qkv_attention_bwd(const float* qkv, const float* go, int32_t B, int32_t
  * [B][32][32][64]. */
 int dmad_rx_head_bwd(const float* g_logits, const float* W, const float* y, int32_t B, int32_t ncls, int32_t HW, int32_t C, float* gz, dmad_stream s);
 int dmad_rx_conv1_bwd(const float* g, const float* a, const float* w, const float* scale, int32_t B, float* gspec, dmad_stream s);
+/* VGG19_bn's 2x2 max-pool and the ReLU in front of it, backward: y [B][H][H][C] the saved post-ReLU map, g [B][H/2][H/2][C] -> gpre
+ * [B][H][H][C], every element written once: a window's g at its first maximum in scan order (top-left, top-right, bottom-left,
+ * bottom-right) where that maximum is > 0, zero elsewhere.  H even, C % 4 == 0. */
+int dmad_vgg_pool_relu_bwd(const float* g, const float* y, int32_t B, int32_t H, int32_t C, float* gpre, dmad_stream s);
 
 /* Bytes of device memory held by the engine. */
 int64_t dmad_device_bytes(const dmad_engine* e);
