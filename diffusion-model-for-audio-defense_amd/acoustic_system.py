@@ -7,8 +7,9 @@ package (DiffWave, MelSpectrogramDB, VGG) or any callables the caller passes.
 `repeats` times with fresh purification noise.  When the three stages are this package's HIP stages on one engine it is
 ONE C-ABI call — dmad_query_logits for defense_type 'wave' (repeat -> DDPM purify -> mel dB -> classifier -> arg-max),
 dmad_defense_query_logits for a baseline waveform defense (TimeDomainDefense / FreqDomainDefense on backend 'hip'),
-dmad_spec_query_logits for 'spec' (repeat -> mel dB -> spec-domain purifier -> classifier -> arg-max); otherwise it loops over
-forward()."""
+dmad_spec_query_logits for 'spec' (repeat -> mel dB -> spec-domain purifier -> classifier -> arg-max).  With transform None and an
+M5 that use_engine() put on the engine the 'wave' chains are dmad_m5_query_logits / dmad_m5_defense_query_logits (the same rows and
+Philox keys, M5 in the place of mel dB -> classifier).  Otherwise it loops over forward()."""
 import torch
 
 
@@ -43,22 +44,35 @@ class AcousticSystem(torch.nn.Module):
     # ------------------------------------------------------------------------------------------------------------
     def _engine_chain(self, defend):
         """The engine that can run this system as one dmad_query_logits call, with the sampler id, or (None, 0)."""
-        from diffusion_models.diffwave_ddpm import DiffWave
         from dmad_hip.transforms import MelSpectrogramDB
         cls, tr, den = self.classifier, self.transform, self.defender
         eng = getattr(cls, 'engine', None) if 'engine' in getattr(cls, '__dict__', {}) else None
-        if eng is None or not eng.has_classifier:
+        if eng is None:
+            return None, 0
+        if tr is None:                                                # waveform classifier: an M5 on the engine (M5.use_engine)
+            from audio_models.M5.M5Net import is_m5
+            if not (is_m5(cls) and eng.has_m5 and not cls.training and self.defense_type == 'wave'):
+                return None, 0
+            return self._wave_sampler(eng, defend)                    # the same samplers; query() calls the engine's m5_* pair for them
+        if not eng.has_classifier:
             return None, 0
         mel = isinstance(tr, MelSpectrogramDB) and tr.engine is eng
         if not mel:
             mel = [getattr(t, '_dmad_stage', None) for t in getattr(tr, 'transforms', [])] == ['mel_power', 'power_to_db']
         if not mel:
             return None, 0
-        if not (defend == True and den is not None):                  # noqa: E712
-            return eng, 0
-        if self.defense_type == 'spec':                               # sampler 3: the spec-domain chain (dmad_spec_query_logits)
+        if self.defense_type == 'spec' and defend == True and den is not None:   # noqa: E712  sampler 3: the spec-domain chain (dmad_spec_query_logits)
             from diffusion_models.improved_diffusion_ddpm import SpecPurifier
             return (eng, 3) if (type(den) is SpecPurifier and den.engine is eng) else (None, 0)
+        return self._wave_sampler(eng, defend)
+
+    def _wave_sampler(self, eng, defend):
+        """(eng, sampler) of the waveform defender in front of the engine's classifier stage: 0 none, 1 DiffWave on device noise, 4 a
+        baseline waveform defense on backend 'hip'; (None, 0) for anything else."""
+        from diffusion_models.diffwave_ddpm import DiffWave
+        den = self.defender
+        if not (defend == True and den is not None):                  # noqa: E712
+            return eng, 0
         if type(den) is DiffWave and den.noise_source == 'device' and den.engine is eng and eng.has_wavenet:
             return eng, 1
         from transforms.time_defense import TimeDomainDefense
@@ -79,10 +93,12 @@ class AcousticSystem(torch.nn.Module):
         B = x.shape[0]
         eng, sampler = self._engine_chain(defend)
         if eng is not None and x.is_cuda:
+            # a chain without a transform is an M5 on the engine: the same rows and keys, M5 in the place of mel dB -> classifier
+            pre = 'm5_' if self.transform is None else ''
             if sampler == 1:
                 den = self.defender
                 ts, c_a, c_b, c_eps, c_div, c_sig = den.purify_coefficients()
-                logits, dec = eng.query_logits(x, repeats, 1, ts, c_a, c_b, c_eps, c_div, c_sig, seed=den.seed, sample0=den._draws)
+                logits, dec = getattr(eng, pre + 'query_logits')(x, repeats, 1, ts, c_a, c_b, c_eps, c_div, c_sig, seed=den.seed, sample0=den._draws)
                 den._draws += repeats * B
             elif sampler == 3:
                 from diffusion_models.Improved_Diffusion_Unconditional.improved_diffusion.sc09_spectrogram_dataset import MEL_LOWER_BOUND, MEL_UPPER_BOUND
@@ -92,9 +108,9 @@ class AcousticSystem(torch.nn.Module):
                 den._draws += repeats * B
             elif sampler == 4:
                 den = self.defender
-                logits, dec = eng.defense_query_logits(x, repeats, den.engine_defense(x))
+                logits, dec = getattr(eng, pre + 'defense_query_logits')(x, repeats, den.engine_defense(x))
             else:
-                logits, dec = eng.query_logits(x, repeats, 0)
+                logits, dec = getattr(eng, pre + 'query_logits')(x, repeats, 0)
             return logits.view(repeats, B, -1), dec.view(repeats, B).long()
         per_call = per_call or repeats
         assert repeats % per_call == 0

@@ -15,8 +15,9 @@ black_box_attack_eval.py and siren_attack_eval.py; the baseline defenses AS, MS,
 Additions to the reference's flags:
   * `--classifier_path`: the classifier checkpoint; its default is the path the reference hard-codes (it overrides
     `--classifier_model` / `--classifier_type`, which are kept for compatibility and otherwise unused, as in the reference);
-  * `--grad_backend {hip,torch}` (default hip): the gradient of the classifier (ResNeXt29 or VGG19_bn) and of the mel front-end — the
-    engine's vector-Jacobian products, or the torch layers (DESIGN §14, §18);
+  * `--grad_backend {hip,torch}` (default hip): the gradient of the classifier (ResNeXt29, VGG19_bn or M5) and of the mel front-end — the
+    engine's vector-Jacobian products, or the torch layers.  An M5 checkpoint (`M5Net.M5`) classifies the raw
+    waveform: the system is AcousticSystem(classifier, transform=None, ...) as in the reference, and `--defense Diffusion-Spec` is refused;
   * `--score_grad`: passed to the SDE purifiers (default: their module defaults, 'none' for RevDiffWave, 'hip' for
     RevImprovedDiffusion).
 `--save_path` writes the clean / purified / adversarial waveforms as 16-bit WAV files (standard library only); the reference's
@@ -90,7 +91,7 @@ def build_parser():
     parser.add_argument('--eot_defense_size', type=int, default=1)
     parser.add_argument('--verbose', type=int, default=1)
     parser.add_argument('--grad_backend', choices=['hip', 'torch'], default='hip',
-                        help='gradient of the classifier (ResNeXt29, VGG19_bn) and of the mel front-end: the engine VJPs or the torch layers')
+                        help='gradient of the classifier (ResNeXt29, VGG19_bn, M5) and of the mel front-end: the engine VJPs or the torch layers')
     # device arguments
     parser.add_argument("--dataload_workers_nums", type=int, default=8, help='number of workers for dataloader')
     parser.add_argument("--batch_size", type=int, default=20, help='batch size')
@@ -164,13 +165,34 @@ def build_system(args, classifier=None, defender=None):
     return system, classifier
 
 
+def _is_m5(classifier):
+    from audio_models.M5.M5Net import is_m5
+    return is_m5(classifier)
+
+
+def check_classifier_defense(args, classifier):
+    """NotImplementedError for a defense the loaded classifier cannot stand behind."""
+    if args.defense == 'Diffusion-Spec' and _is_m5(classifier):
+        raise NotImplementedError('--defense Diffusion-Spec purifies the mel spectrogram, and the M5 checkpoint classifies the raw waveform '
+                                  '(AcousticSystem(classifier, transform=None, ...)): a spectrogram purifier cannot stand in front of a '
+                                  'waveform classifier (supported with M5: None, Diffusion, and the baseline defenses of baseline_defense_eval.py)')
+
+
 def build_front(args, classifier=None):
-    """The classifier of the driver's flags on its engine, and the mel front-end on the same engine (shared with baseline_defense_eval.py)."""
+    """The classifier of the driver's flags on its engine, and the mel front-end on the same engine (shared with baseline_defense_eval.py);
+    for an M5 checkpoint the classifier on its engine (M5.use_engine) and None: it has no front-end."""
     from audio_models.ConvNets_SpeechCommands.create_model import create_model
     from dmad_hip.transforms import MelSpectrogramDB
     if classifier is None:
         classifier = create_model(args.classifier_path)
+    check_classifier_defense(args, classifier)
     classifier.cuda()
+    if _is_m5(classifier):               # reference l.121-122, 169-170: M5 takes the raw audio, AcousticSystem(classifier, transform=None, ...)
+        classifier.eval()
+        if 'engine' not in classifier.__dict__:
+            classifier.use_engine()
+        classifier.grad_backend = args.grad_backend
+        return classifier, None
     if hasattr(classifier, 'bind_engine') and 'engine' not in classifier.__dict__:
         classifier.bind_engine()
     if 'torch' in getattr(classifier, 'GRAD_BACKENDS', ()) and 'hip' in classifier.GRAD_BACKENDS:    # ResNeXt29 and VGG19_bn

@@ -18,6 +18,7 @@
 #include "unet_ops.h"
 #include "elementwise.h"
 #include "wave_defense.h"
+#include "m5.h"
 #include "gemm_f32.h"
 #include "gemm_h16.h"
 #include "wn_bf16.h"
@@ -324,6 +325,12 @@ struct dmad_engine {
     float *un_inT = nullptr, *un_outT = nullptr;            // conv_in [9][128] / out.2 [128][9] images, tap-flipped
     UnTape un_tape;
     std::vector<float*> unvjp_ghs_at;
+    // M5 raw-waveform classifier (m5.h): a part of its own, exact fp32 on every precision.  One buffer of weight images;
+    // the kernels keep a clip's activations in LDS, so there is no workspace
+    bool m5_final = false;
+    float* m5_buf = nullptr;
+    M5Weights m5w;
+    M5Geom m5g;
 
     template <typename T>
     int alloc(T** p, size_t n, bool zero = false) {
@@ -384,6 +391,7 @@ int need_classifier(const dmad_engine* e) {      // ... and its weights finalise
     if (int r = need_with_classifier(e)) return r;
     return e->cls_final ? 0 : fail(DMAD_ERR_STATE, "classifier weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
 }
+int need_m5(const dmad_engine* e) { return e->m5_final ? 0 : fail(DMAD_ERR_STATE, "M5 weights are not finalised (dmad_load_weight + dmad_finalize_weights)"); }
 int need_batch(const dmad_engine* e, int B) { return B >= 1 && B <= e->maxB ? 0 : fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB); }
 int need_path(const dmad_engine* e, int path) {  // a WaveNet path the caller names (dmad_wavenet_eps_path / dmad_eval_samples)
     if (path != PATH_DEFAULT && path != PATH_FP32 && path != PATH_X3) return fail(DMAD_ERR_INVALID, "unknown path %d", path);
@@ -1811,6 +1819,74 @@ int read_recheck_stats(dmad_engine* e, bool spec, int64_t* samples, int64_t* rec
     return 0;
 }
 
+// M5: checks the geometry against what m5.hip serves and packs the weight images of both directions into one buffer
+int finalize_m5(dmad_engine* e) {
+    auto find = [&](const char* name) -> const HostW* {
+        auto it = e->hw.find(name);
+        if (it == e->hw.end()) { fail(DMAD_ERR_STATE, "weight '%s' was not loaded", name); return nullptr; }
+        return &it->second;
+    };
+    const HostW* c1 = find("m5.conv1.w");
+    const HostW* st = find("m5.stride");
+    const HostW* fw = find("m5.fc.w");
+    if (!c1 || !st || !fw) return DMAD_ERR_STATE;
+    if (c1->shape.size() != 3) return fail(DMAD_ERR_SHAPE, "M5: conv1.weight must be [n_channel][n_input][first_kernel_size]");
+    if (c1->shape[1] != 1) return fail(DMAD_ERR_SHAPE, "M5: n_input = %lld is not supported (only 1)", (long long)c1->shape[1]);
+    if (c1->shape[0] != kM5Ch) return fail(DMAD_ERR_SHAPE, "M5: n_channel = %lld is not supported (only %d)", (long long)c1->shape[0], kM5Ch);
+    if (st->v[0] != (float)kM5Stride) return fail(DMAD_ERR_SHAPE, "M5: stride = %g is not supported (only %d)", st->v[0], kM5Stride);
+    const int K1 = (int)c1->shape[2];
+    if (K1 != 80 && K1 != 160) return fail(DMAD_ERR_SHAPE, "M5: first_kernel_size = %d is not supported (80 or 160)", K1);
+    if (fw->shape.size() != 2 || fw->shape[1] != 2 * kM5Ch) return fail(DMAD_ERR_SHAPE, "M5: fc1.weight must be [n_output][%d] (n_channel = %d)", 2 * kM5Ch, kM5Ch);
+    const int NO = (int)fw->shape[0];
+    if (NO > kM5MaxOut) return fail(DMAD_ERR_SHAPE, "M5: n_output = %d is not supported (at most %d)", NO, kM5MaxOut);
+    if (const char* m = m5_geometry(e->L, K1, NO, &e->m5g)) return fail(DMAD_ERR_SHAPE, "M5: %s (clip_len %d, first_kernel_size %d, n_output %d)", m, e->L, K1, NO);
+    const int cin[4] = {1, 32, 32, 64}, cout[4] = {32, 32, 64, 64};
+    std::vector<float> img;
+    size_t off[18];
+    int n = 0;
+    auto put = [&](size_t count) { off[n++] = img.size(); img.resize(img.size() + ((count + 3) & ~(size_t)3), 0.f); return img.data() + off[n - 1]; };
+    {
+        float* t = put((size_t)K1 * kM5Ch);                  // [k][c]
+        for (int c = 0; c < kM5Ch; ++c) for (int k = 0; k < K1; ++k) t[k * kM5Ch + c] = c1->v[(size_t)c * K1 + k];
+        t = put((size_t)K1 * kM5Ch);                         // [c][k]
+        memcpy(t, c1->v.data(), (size_t)K1 * kM5Ch * sizeof(float));
+    }
+    for (int l = 1; l < 4; ++l) {
+        char name[32];
+        snprintf(name, sizeof name, "m5.conv%d.w", l + 1);
+        const HostW* w = e->get(name, {cout[l], cin[l], 3});
+        if (!w) return DMAD_ERR_SHAPE;
+        float* f = put((size_t)cout[l] * cin[l] * 3);        // [ci][tap][co]
+        for (int co = 0; co < cout[l]; ++co) for (int ci = 0; ci < cin[l]; ++ci) for (int t = 0; t < 3; ++t)
+            f[((size_t)ci * 3 + t) * cout[l] + co] = w->v[((size_t)co * cin[l] + ci) * 3 + t];
+        float* b = put((size_t)cout[l] * cin[l] * 3);        // [co][tap][ci]
+        for (int co = 0; co < cout[l]; ++co) for (int ci = 0; ci < cin[l]; ++ci) for (int t = 0; t < 3; ++t)
+            b[((size_t)co * 3 + t) * cin[l] + ci] = w->v[((size_t)co * cin[l] + ci) * 3 + t];
+    }
+    for (int l = 0; l < 4; ++l)
+        for (int k = 0; k < 2; ++k) {
+            char name[32];
+            snprintf(name, sizeof name, k ? "m5.shift%d" : "m5.scale%d", l + 1);
+            const HostW* w = e->get(name, {cout[l]});
+            if (!w) return DMAD_ERR_SHAPE;
+            memcpy(put((size_t)cout[l]), w->v.data(), (size_t)cout[l] * sizeof(float));
+        }
+    memcpy(put(fw->v.size()), fw->v.data(), fw->v.size() * sizeof(float));
+    const HostW* fb = e->get("m5.fc.b", {NO});
+    if (!fb) return DMAD_ERR_SHAPE;
+    memcpy(put((size_t)NO), fb->v.data(), (size_t)NO * sizeof(float));
+    CHK(e->upload(&e->m5_buf, img));
+    const float* d = e->m5_buf;
+    M5Weights& W = e->m5w;
+    n = 0;
+    W.w1t = d + off[n++]; W.w1c = d + off[n++];
+    for (int l = 0; l < 3; ++l) { W.wf[l] = d + off[n++]; W.wb[l] = d + off[n++]; }
+    for (int l = 0; l < 4; ++l) { W.scale[l] = d + off[n++]; W.shift[l] = d + off[n++]; }
+    W.fcw = d + off[n++]; W.fcb = d + off[n++];
+    if (int r = m5_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, M5) failed: %d", r);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2014,6 +2090,13 @@ int dmad_finalize_weights(dmad_engine* e) {
         }
         CHK(finalize_unet(e));
         e->un_final = true; did = true;
+    }
+    if (!e->m5_final && e->hw.count("m5.conv1.w")) {
+        if (int r = finalize_m5(e)) {        // a refused set leaves nothing behind: the next finalise (of any part) must not retry it
+            for (auto it = e->hw.begin(); it != e->hw.end();) it = it->first.compare(0, 3, "m5.") == 0 ? e->hw.erase(it) : std::next(it);
+            return r;
+        }
+        e->m5_final = true; did = true;
     }
     if (!did) return fail(DMAD_ERR_STATE, "nothing to finalise: no complete weight set was loaded");
     e->hw.clear();
@@ -2938,8 +3021,9 @@ int spec_chain(dmad_engine* e, const SpecJob& j, uint64_t s0, const long long* i
 // The loop of the three query exports over the B * repeats query rows (row r = clip r % B, AcousticSystem's repeat layout), in passes of
 // up to max_batch rows: the rows into e->xt, logits_of(nb, r0, lg) -- the export's defense and classifier -- and the optional decisions
 template <class Logits>
-int query_loop(dmad_engine* e, const float* x, int B, int repeats, float* logits, int32_t* decisions, hipStream_t st, Logits logits_of) {
-    const int C = e->cfg.num_classes;
+int query_loop(dmad_engine* e, const float* x, int B, int repeats, float* logits, int32_t* decisions, hipStream_t st, Logits logits_of,
+               int row_width = 0) {
+    const int C = row_width ? row_width : e->cfg.num_classes;      // the M5 exports: n_output log-probabilities per row
     CHK(for_passes((int64_t)B * repeats, e->maxB, [&](int64_t r0, int nb) -> int {
         launch_repeat_rows(x, e->xt, B, (long)r0, nb, e->L, st);
         CHK(logits_of(nb, r0, logits + r0 * C));
@@ -2954,6 +3038,31 @@ int query_loop(dmad_engine* e, const float* x, int B, int repeats, float* logits
 int wave_logits(dmad_engine* e, const float* pur, int nb, float* lg, hipStream_t st) {
     CHK(mel_db(e, pur, nb, e->spec, st));
     return classify(e, e->spec, nb, lg, st);
+}
+
+// the purifier of dmad_query_logits / dmad_m5_query_logits on the nb rows of e->xt (rows r0 ...): where the purified rows are
+int run_query_sampler(dmad_engine* e, int sampler, int t_star, float c_a, float c_b, const float* c_eps, const float* c_div, const float* c_sig,
+                      uint64_t seed, uint64_t sample0, int64_t r0, int nb, hipStream_t st, const float** pur) {
+    *pur = e->xt;
+    if (sampler == 1) {
+        CHK(dmad_ddpm_purify(e, e->xt, t_star, c_a, c_b, c_eps, c_div, c_sig, seed, sample0 + (uint64_t)r0, nb, e->x0, (dmad_stream)st));
+        *pur = e->x0;
+    } else if (sampler == 2) {
+        CHK(wavenet_eps(e, e->xt, t_star - 1, nb, e->eps, st, wave_path(e)));
+        launch_lincomb(0, e->xt, e->eps, nullptr, c_a, c_b, 0.f, e->x0, (long)nb * e->L, st);
+        *pur = e->x0;
+    }
+    return 0;
+}
+
+int query_args(const void* e, const void* x, const void* logits, int B, int repeats, int sampler, int t_star, const float* c_eps,
+               const float* c_div, const float* c_sig) {
+    if (!e || !x || !logits) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || repeats < 1) return fail(DMAD_ERR_INVALID, "B and repeats must be >= 1");
+    if (sampler < 0 || sampler > 2) return fail(DMAD_ERR_INVALID, "unknown sampler %d (0 none, 1 DDPM, 2 one-shot)", sampler);
+    if (sampler && t_star < 1) return fail(DMAD_ERR_INVALID, "t_star %d < 1", t_star);
+    if (sampler == 1 && (!c_eps || !c_div || !c_sig)) return fail(DMAD_ERR_INVALID, "the DDPM sampler needs its coefficient arrays");
+    return 0;
 }
 
 }  // namespace
@@ -3015,23 +3124,12 @@ int dmad_spec_eval_samples(dmad_engine* e, const float* clip, float sigma, int32
 int dmad_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, int32_t sampler, int32_t t_star, float c_a, float c_b,
                       const float* c_eps, const float* c_div, const float* c_sig, uint64_t seed, uint64_t sample0, float* logits,
                       int32_t* decisions, dmad_stream s) {
-    if (!e || !x || !logits) return fail(DMAD_ERR_INVALID, "null argument");
-    if (B < 1 || repeats < 1) return fail(DMAD_ERR_INVALID, "B and repeats must be >= 1");
-    if (sampler < 0 || sampler > 2) return fail(DMAD_ERR_INVALID, "unknown sampler %d (0 none, 1 DDPM, 2 one-shot)", sampler);
-    if (sampler && t_star < 1) return fail(DMAD_ERR_INVALID, "t_star %d < 1", t_star);
-    if (sampler == 1 && (!c_eps || !c_div || !c_sig)) return fail(DMAD_ERR_INVALID, "the DDPM sampler needs its coefficient arrays");
+    CHK(query_args(e, x, logits, B, repeats, sampler, t_star, c_eps, c_div, c_sig));
     CHK(need_with_classifier(e));
     hipStream_t st = (hipStream_t)s;
     return query_loop(e, x, B, repeats, logits, decisions, st, [&](int nb, int64_t r0, float* lg) -> int {
-        const float* pur = e->xt;
-        if (sampler == 1) {
-            CHK(dmad_ddpm_purify(e, e->xt, t_star, c_a, c_b, c_eps, c_div, c_sig, seed, sample0 + (uint64_t)r0, nb, e->x0, s));
-            pur = e->x0;
-        } else if (sampler == 2) {
-            CHK(wavenet_eps(e, e->xt, t_star - 1, nb, e->eps, st, wave_path(e)));
-            launch_lincomb(0, e->xt, e->eps, nullptr, c_a, c_b, 0.f, e->x0, (long)nb * e->L, st);
-            pur = e->x0;
-        }
+        const float* pur;
+        CHK(run_query_sampler(e, sampler, t_star, c_a, c_b, c_eps, c_div, c_sig, seed, sample0, r0, nb, st, &pur));
         return wave_logits(e, pur, nb, lg, st);
     });
 }
@@ -3189,6 +3287,37 @@ int dmad_wave_iir_vjp(dmad_engine* e, const float* x, const float* g_y, int32_t 
     return 0;
 }
 
+}  // extern "C"
+
+namespace {
+
+// one baseline defense on the nb rows of e->xt -> e->x0 (DS goes through e->eps)
+int run_wave_defense(dmad_engine* e, const dmad_wave_defense* d, const IirPlan& plan, int nb, hipStream_t st) {
+    const int L = e->L;
+    switch (d->kind) {
+    case DMAD_WAVE_AS: launch_wave_smooth(e->xt, nb, L, 0, d->window, e->x0, st); break;
+    case DMAD_WAVE_MS: launch_wave_smooth(e->xt, nb, L, 1, d->window, e->x0, st); break;
+    case DMAD_WAVE_DS:
+        launch_wave_resample(e->xt, nb, L, d->down_ker, d->down_phases, d->down_taps, d->down_stride, d->down_width, d->down_len, e->eps, st);
+        launch_wave_resample(e->eps, nb, d->down_len, d->up_ker, d->up_phases, d->up_taps, d->up_stride, d->up_width, L, e->x0, st);
+        break;
+    default: HIPCHK((hipError_t)launch_wave_iir(plan, e->xt, nullptr, nb, L, d->lo, d->hi, 0, e->x0, nullptr, st)); break;
+    }
+    return 0;
+}
+
+int m5_launch(dmad_engine* e, const float* x, int B, float* logp, int32_t* cls, const float* g_logp, float* g_x, int layer, float* pooled,
+              uint8_t* dec, hipStream_t st) {
+    if ((uintptr_t)x & 15) return fail(DMAD_ERR_INVALID, "M5: x must be 16-byte aligned (the clip is read as float4)");
+    launch_m5(e->m5w, e->m5g, x, B, logp, cls, g_logp, g_x, layer, pooled, dec, st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
 // adaptive_attack_eval.py:190-201 (AcousticSystem with a Time / FreqDomainDefense as its defender) behind the query layout of
 // dmad_query_logits
 int dmad_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, const dmad_wave_defense* d, float* logits,
@@ -3199,19 +3328,63 @@ int dmad_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t
     if (const char* m = wave_defense_check(d, e->L, &plan)) return fail(DMAD_ERR_INVALID, "dmad_defense_query_logits: %s", m);
     CHK(need_with_classifier(e));
     hipStream_t st = (hipStream_t)s;
-    const int L = e->L;
     return query_loop(e, x, B, repeats, logits, decisions, st, [&](int nb, int64_t, float* lg) -> int {
-        switch (d->kind) {
-        case DMAD_WAVE_AS: launch_wave_smooth(e->xt, nb, L, 0, d->window, e->x0, st); break;
-        case DMAD_WAVE_MS: launch_wave_smooth(e->xt, nb, L, 1, d->window, e->x0, st); break;
-        case DMAD_WAVE_DS:
-            launch_wave_resample(e->xt, nb, L, d->down_ker, d->down_phases, d->down_taps, d->down_stride, d->down_width, d->down_len, e->eps, st);
-            launch_wave_resample(e->eps, nb, d->down_len, d->up_ker, d->up_phases, d->up_taps, d->up_stride, d->up_width, L, e->x0, st);
-            break;
-        default: HIPCHK((hipError_t)launch_wave_iir(plan, e->xt, nullptr, nb, L, d->lo, d->hi, 0, e->x0, nullptr, st)); break;
-        }
+        CHK(run_wave_defense(e, d, plan, nb, st));
         return wave_logits(e, e->x0, nb, lg, st);
     });
+}
+
+// ---- M5 (audio_models/M5/M5Net.py:21-38): forward, input VJP, tape hook and the two query exports
+
+int dmad_m5_logits(dmad_engine* e, const float* x, int32_t B, float* logp, int32_t* decisions, dmad_stream s) {
+    if (!e || !x || !logp) return fail(DMAD_ERR_INVALID, "dmad_m5_logits: null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "dmad_m5_logits: B must be >= 1");
+    CHK(need_m5(e));
+    return m5_launch(e, x, B, logp, decisions, nullptr, nullptr, 0, nullptr, nullptr, (hipStream_t)s);
+}
+
+int dmad_m5_vjp(dmad_engine* e, const float* x, int32_t B, const float* g_logp, float* g_x, float* logp, dmad_stream s) {
+    if (!e || !x || !g_logp || !g_x) return fail(DMAD_ERR_INVALID, "dmad_m5_vjp: null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "dmad_m5_vjp: B must be >= 1");
+    CHK(need_m5(e));
+    return m5_launch(e, x, B, logp, nullptr, g_logp, g_x, 0, nullptr, nullptr, (hipStream_t)s);
+}
+
+int dmad_m5_tape(dmad_engine* e, const float* x, int32_t B, int32_t layer, float* pooled, uint8_t* decisions, dmad_stream s) {
+    if (!e || !x || !pooled || !decisions) return fail(DMAD_ERR_INVALID, "dmad_m5_tape: null argument");
+    if (B < 1 || layer < 1 || layer > 4) return fail(DMAD_ERR_INVALID, "dmad_m5_tape: B must be >= 1 and layer in 1..4");
+    CHK(need_m5(e));
+    return m5_launch(e, x, B, nullptr, nullptr, nullptr, nullptr, layer, pooled, decisions, (hipStream_t)s);
+}
+
+int dmad_m5_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, int32_t sampler, int32_t t_star, float c_a, float c_b,
+                         const float* c_eps, const float* c_div, const float* c_sig, uint64_t seed, uint64_t sample0, float* logits,
+                         int32_t* decisions, dmad_stream s) {
+    CHK(query_args(e, x, logits, B, repeats, sampler, t_star, c_eps, c_div, c_sig));
+    CHK(need_m5(e));
+    if (sampler) CHK(need_wavenet(e));
+    hipStream_t st = (hipStream_t)s;
+    const int NO = e->m5g.n_out;
+    // the arg-max comes out of the M5 launch itself, so query_loop's vote is not asked for
+    return query_loop(e, x, B, repeats, logits, nullptr, st, [&](int nb, int64_t r0, float* lg) -> int {
+        const float* pur;
+        CHK(run_query_sampler(e, sampler, t_star, c_a, c_b, c_eps, c_div, c_sig, seed, sample0, r0, nb, st, &pur));
+        return m5_launch(e, pur, nb, lg, decisions ? decisions + r0 : nullptr, nullptr, nullptr, 0, nullptr, nullptr, st);
+    }, NO);
+}
+
+int dmad_m5_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, const dmad_wave_defense* d, float* logits,
+                                 int32_t* decisions, dmad_stream s) {
+    if (!e || !x || !logits || !d) return fail(DMAD_ERR_INVALID, "dmad_m5_defense_query_logits: null argument");
+    if (B < 1 || repeats < 1) return fail(DMAD_ERR_INVALID, "dmad_m5_defense_query_logits: B and repeats must be >= 1");
+    IirPlan plan;
+    if (const char* m = wave_defense_check(d, e->L, &plan)) return fail(DMAD_ERR_INVALID, "dmad_m5_defense_query_logits: %s", m);
+    CHK(need_m5(e));
+    hipStream_t st = (hipStream_t)s;
+    return query_loop(e, x, B, repeats, logits, nullptr, st, [&](int nb, int64_t r0, float* lg) -> int {
+        CHK(run_wave_defense(e, d, plan, nb, st));
+        return m5_launch(e, e->x0, nb, lg, decisions ? decisions + r0 : nullptr, nullptr, nullptr, 0, nullptr, nullptr, st);
+    }, e->m5g.n_out);
 }
 
 int dmad_philox_raw(dmad_engine* e, uint64_t seed, uint64_t sample, uint32_t stream, uint32_t nblocks, uint32_t* out, dmad_stream s) {

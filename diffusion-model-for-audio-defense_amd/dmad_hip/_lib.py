@@ -137,6 +137,12 @@ _SIGNATURES = {
     'dmad_wave_iir': (C.c_int, [_P, _P, C.c_int32, _PF, _PF, C.c_int32, C.c_float, C.c_float, _P, _P]),
     'dmad_wave_iir_vjp': (C.c_int, [_P, _P, _P, C.c_int32, _PF, _PF, C.c_int32, C.c_float, C.c_float, _P, _P, _P]),
     'dmad_defense_query_logits': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(DmadWaveDefense), _P, _P, _P]),
+    'dmad_m5_logits': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
+    'dmad_m5_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    'dmad_m5_tape': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    'dmad_m5_query_logits': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P,
+                                       C.c_uint64, C.c_uint64, _P, _P, _P]),
+    'dmad_m5_defense_query_logits': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(DmadWaveDefense), _P, _P, _P]),
     'dmad_vote': (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     'dmad_philox_raw': (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     'dmad_philox_normal': (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, _P, _P]),

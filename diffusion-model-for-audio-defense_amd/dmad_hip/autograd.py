@@ -260,6 +260,33 @@ def vgg_hip(engine, spec: torch.Tensor) -> torch.Tensor:
     return VGGHIP.apply(spec, engine)
 
 
+class M5HIP(torch.autograd.Function):
+    """log-probabilities = M5(x [B,1,L]) on the engine (m5_logits), differentiable in `x` through the engine's VJP (dmad_m5_vjp, which
+    recomputes the forward and keeps only the pool / ReLU decisions).  Saves only the input; nothing is reserved.  No weight gradients.
+    First-order only: create_graph=True raises."""
+
+    @staticmethod
+    def forward(ctx, x, engine):
+        _require_cuda(x)
+        ctx.engine = engine
+        ctx.save_for_backward(x)
+        return engine.m5_logits(x)
+
+    @staticmethod
+    def backward(ctx, g_logp):
+        if torch.is_grad_enabled():
+            raise DmadError('the HIP M5 VJP is first-order only: create_graph=True (double backward) is not supported; '
+                            "use grad_backend='torch' for higher derivatives")
+        x, = ctx.saved_tensors
+        g = ctx.engine.m5_vjp(x, g_logp.contiguous())
+        return g.view(x.shape).to(x.dtype), None
+
+
+def m5_hip(engine, x: torch.Tensor) -> torch.Tensor:
+    """log-probabilities = M5(x [B,1,L]) on the engine, differentiable in `x` (M5HIP)."""
+    return M5HIP.apply(x, engine)
+
+
 class MelDBHIP(torch.autograd.Function):
     """[B,1,16000] -> [B,1,32,32] dB mel spectrogram on the engine (mel_db), differentiable in `x` through the engine's mel VJP
     (dmad_mel_db_vjp, which recomputes the forward).  Saves only the input.  First-order only: create_graph=True raises."""

@@ -169,6 +169,28 @@ def fold_resnext29_state_dict(sd: Dict[str, object], eps: float = 1e-5) -> Dict[
     return {k: _as_np(v) for k, v in out.items()}
 
 
+M5_CHANNELS = (32, 32, 64, 64)                     # output channels of M5's four conv blocks (n_channel = 32)
+
+
+def fold_m5_state_dict(sd: Dict[str, object], stride: int = 16, eps: float = 1e-5) -> Dict[str, np.ndarray]:
+    """M5Net.M5 state dict -> the `m5.*` arrays of include/dmad.h: the conv weights as they are, each eval-BatchNorm folded (in float64)
+    into s = gamma / sqrt(var + eps) and shift = beta + (bias - mean) * s, fc1, and conv1's stride (the one geometry field no tensor
+    shape shows).  The geometry is checked by dmad_finalize_weights (DMAD_ERR_SHAPE)."""
+    def A(k):
+        v = sd[k]
+        return v.detach().cpu().double().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64)
+
+    out = {'m5.stride': np.array([float(stride)], dtype=np.float32)}
+    for i in (1, 2, 3, 4):
+        s_ = A('bn%d.weight' % i) / np.sqrt(A('bn%d.running_var' % i) + eps)
+        out['m5.conv%d.w' % i] = A('conv%d.weight' % i).astype(np.float32)
+        out['m5.scale%d' % i] = s_.astype(np.float32)
+        out['m5.shift%d' % i] = (A('bn%d.bias' % i) + (A('conv%d.bias' % i) - A('bn%d.running_mean' % i)) * s_).astype(np.float32)
+    out['m5.fc.w'] = A('fc1.weight').astype(np.float32)
+    out['m5.fc.b'] = A('fc1.bias').astype(np.float32)
+    return out
+
+
 class Engine:
     """One libdmad_hip engine bound to the current CUDA(HIP) device."""
 
@@ -208,6 +230,8 @@ class Engine:
         self.has_wavenet = False
         self.has_classifier = False
         self.has_unet = False
+        self.has_m5 = False
+        self.m5_owner, self.m5_classes, self.m5_maps = None, 0, ()
         self.vjp_batch = self.unet_vjp_batch = self.classifier_vjp_batch = self.vgg_vjp_batch = 0     # rows per pass the VJP workspaces are reserved for
         # which weights are resident (state_fingerprint): a module that binds to an engine holding OTHER weights must
         # not silently run them
@@ -269,8 +293,22 @@ class Engine:
         self.has_classifier = True
         self.classifier_owner, self.classifier_kind = state_fingerprint(state_dict), 'vgg19_bn'
 
+    def load_m5(self, state_dict, stride: int = 16):
+        """M5Net.M5 state dict -> engine (names prefixed 'm5.'); a part of its own beside the spectrogram classifier.  stride: conv1's."""
+        if self.has_m5:
+            raise DmadError('M5 weights are already loaded into this engine')
+        arrays = fold_m5_state_dict(state_dict, stride)
+        self._load(arrays)
+        self.has_m5 = True
+        self.m5_owner, self.m5_classes = state_fingerprint(state_dict), int(arrays['m5.fc.w'].shape[0])
+        t, maps = (self.L - arrays['m5.conv1.w'].shape[2]) // 16 + 1, []
+        for c in M5_CHANNELS:                 # (channels, pooled frames) of the four blocks: the shapes of m5_tape
+            maps.append((c, t // 4))
+            t = t // 4 - 2
+        self.m5_maps = tuple(maps)
+
     def bind(self, part: str, state_dict, loader) -> None:
-        """Make `state_dict` the resident weights of `part` ('wavenet' / 'classifier' / 'unet'): upload them if the
+        """Make `state_dict` the resident weights of `part` ('wavenet' / 'classifier' / 'unet' / 'm5'): upload them if the
         part is empty, accept them if they ARE the resident ones, refuse anything else (an engine holds one weight set per
         part for its lifetime; use get_engine(fresh=True) / Engine(...) for a second model)."""
         owner = getattr(self, part + '_owner')
@@ -789,6 +827,66 @@ class Engine:
         check(self.lib.dmad_vgg_vjp_tape(self._h, int(index), int(B), _ptr(out), _stream()))
         return out
 
+    # ------------------------------------------------------------------ M5 (dmad_m5_*): waveform in, log-probabilities out
+    def _m5_width(self) -> int:
+        return self.m5_classes if self.has_m5 else 1        # before load_m5 the calls themselves refuse (DMAD_ERR_STATE)
+
+    def m5_logits(self, x: torch.Tensor, want_decisions: bool = False):
+        """dmad_m5_logits: x [B,1,L] or [B,L] -> log-probabilities [B, m5_classes] (and, want_decisions, their int32 arg-max).  One
+        launch whatever B is: M5 has no workspace that max_batch would size, and a clip's bits do not depend on the batch (a pass of
+        max_batch rows would leave most CUs idle: one workgroup per clip)."""
+        xw = self._wave(x)
+        B = xw.shape[0]
+        out = torch.empty((B, self._m5_width()), device=xw.device, dtype=torch.float32)
+        dec = torch.empty((B,), device=xw.device, dtype=torch.int32) if want_decisions else None
+        check(self.lib.dmad_m5_logits(self._h, _ptr(xw), B, _ptr(out), _ptr(dec), _stream()))
+        return (out, dec) if want_decisions else out
+
+    def m5_vjp(self, x: torch.Tensor, g: torch.Tensor, want_logits: bool = False):
+        """dmad_m5_vjp: g_x [B,L] = (d logp / d x)^T g for logp = M5(x), g [B, m5_classes].  want_logits: also the log-probabilities,
+        bit-identical to m5_logits(x).  The forward is recomputed inside the call; nothing is saved or reserved."""
+        xw = self._wave(x)
+        B = xw.shape[0]
+        if not g.is_cuda or (self.has_m5 and tuple(g.shape) != (B, self.m5_classes)):
+            raise DmadError('g must be a CUDA tensor [%d, %d], not %s' % (B, self.m5_classes, tuple(g.shape)))
+        gl = g.detach().contiguous().float()
+        gx = torch.empty((B, self.L), device=xw.device, dtype=torch.float32)
+        lp = torch.empty((B, self._m5_width()), device=xw.device, dtype=torch.float32) if want_logits else None
+        check(self.lib.dmad_m5_vjp(self._h, _ptr(xw), B, _ptr(gl), _ptr(gx), _ptr(lp), _stream()))
+        return (gx, lp) if want_logits else gx
+
+    def m5_tape(self, x: torch.Tensor, layer: int):
+        """dmad_m5_tape (test hook): block `layer` (1..4) -> (pooled post-ReLU map [B,C,T] float32, decisions [B,C,T] uint8 = arg | on << 2)
+        as the launch of m5_vjp produces them."""
+        xw = self._wave(x)
+        B = xw.shape[0]
+        if layer not in (1, 2, 3, 4):
+            raise DmadError('layer must be 1..4, not %r' % (layer,))
+        c, t = self.m5_maps[layer - 1] if self.has_m5 else (1, 1)       # before load_m5 the call itself refuses (DMAD_ERR_STATE)
+        pooled = torch.empty((B, c, t), device=xw.device, dtype=torch.float32)
+        dec = torch.empty((B, c, t), device=xw.device, dtype=torch.uint8)
+        check(self.lib.dmad_m5_tape(self._h, _ptr(xw), B, int(layer), _ptr(pooled), _ptr(dec), _stream()))
+        return pooled, dec
+
+    def m5_query_logits(self, x: torch.Tensor, repeats: int, sampler: int = 0, t_star: int = 0, c_a: float = 0.0, c_b: float = 0.0,
+                        c_eps=None, c_div=None, c_sig=None, seed: int = 0, sample0: int = 0):
+        """dmad_m5_query_logits: query_logits with M5 in the place of mel dB -> classifier; (log-probabilities [repeats*B, m5_classes],
+        decisions int32 [repeats*B]); row r*B+b is clip b."""
+        xw = self._wave(x)
+        B = xw.shape[0]
+        logits = torch.empty((repeats * B, self._m5_width()), device=xw.device, dtype=torch.float32)
+        dec = torch.empty((repeats * B,), device=xw.device, dtype=torch.int32)
+        arrs = [None, None, None]
+        if sampler == 1:
+            arrs = [(C.c_float * t_star)(*[float(v) for v in a]) for a in (c_eps, c_div, c_sig)]
+        check(self.lib.dmad_m5_query_logits(self._h, _ptr(xw), B, int(repeats), int(sampler), int(t_star), float(c_a), float(c_b),
+                                            arrs[0], arrs[1], arrs[2], int(seed), int(sample0), _ptr(logits), _ptr(dec), _stream()))
+        return logits, dec
+
+    def m5_defense_query_logits(self, x: torch.Tensor, repeats: int, defense: dict):
+        """dmad_m5_defense_query_logits: defense_query_logits with M5 in the place of mel dB -> classifier (`defense` as there)."""
+        return self._defense_query(self.lib.dmad_m5_defense_query_logits, self._m5_width(), x, repeats, defense)
+
     def mel_db_vjp(self, x: torch.Tensor, g_spec: torch.Tensor, want_spec: bool = False):
         """g_x = (d melDB / d x)^T g_spec for the dB mel front-end of mel_db ([B,1,L] or [B,L] -> [B,L]; g_spec [B,1,32,32] or [B,32,32]).
         want_spec: also return the spectrogram [B,1,32,32], bit-identical to mel_db(x).  The forward is recomputed; the first call
@@ -994,6 +1092,9 @@ class Engine:
         """dmad_defense_query_logits: x [B,1,L] -> (logits [repeats*B, C], decisions int32 [repeats*B]); row r*B+b is clip b through
         defense -> mel dB -> classifier.  `defense`: dict(kind='AS'|'MS', window=w) | dict(kind='DS', down=(ker, stride, width, L_out),
         up=(ker, stride, width)) | dict(kind='IIR', b=, a=, lo=, hi=)."""
+        return self._defense_query(self.lib.dmad_defense_query_logits, self.num_classes, x, repeats, defense)
+
+    def _defense_query(self, fn, width: int, x: torch.Tensor, repeats: int, defense: dict):
         from ._lib import DmadWaveDefense
         xw = self._wave(x)
         B = xw.shape[0]
@@ -1014,9 +1115,9 @@ class Engine:
             aa, ap = self._host_f32(defense['a'], bb.size)
             keep += [bb, aa]
             d.b, d.a, d.order, d.lo, d.hi = bp, ap, bb.size - 1, float(defense['lo']), float(defense['hi'])
-        logits = torch.empty((repeats * B, self.num_classes), device=xw.device, dtype=torch.float32)
+        logits = torch.empty((repeats * B, width), device=xw.device, dtype=torch.float32)
         dec = torch.empty((repeats * B,), device=xw.device, dtype=torch.int32)
-        check(self.lib.dmad_defense_query_logits(self._h, _ptr(xw), B, int(repeats), C.byref(d), _ptr(logits), _ptr(dec), _stream()))
+        check(fn(self._h, _ptr(xw), B, int(repeats), C.byref(d), _ptr(logits), _ptr(dec), _stream()))
         del keep
         return logits, dec
 
@@ -1452,6 +1553,17 @@ def bind_classifier(state_dict, loader_name: str, engine: Optional[Engine] = Non
     if eng.has_classifier and eng.classifier_owner != state_fingerprint(state_dict):
         eng = Engine(dict(eng.wavenet_geometry), max_batch=eng.max_batch, precision=eng.precision)
     eng.bind('classifier', state_dict, getattr(eng, loader_name))
+    return eng
+
+
+def bind_m5(state_dict, stride: int = 16, engine: Optional[Engine] = None) -> Engine:
+    """Engine that holds exactly `state_dict` as its M5 part: `engine` (refused if it holds another M5), else the shared engine (so
+    that a DiffWave purifier and M5 meet in ONE engine and a query is one call), else -- when the shared engine already serves a
+    different M5 -- an engine of this module's own."""
+    eng = engine if engine is not None else get_engine()
+    if engine is None and eng.has_m5 and eng.m5_owner != state_fingerprint(state_dict):
+        eng = Engine(dict(eng.wavenet_geometry), max_batch=eng.max_batch, precision=eng.precision)
+    eng.bind('m5', state_dict, lambda sd: eng.load_m5(sd, stride))
     return eng
 
 

@@ -144,6 +144,26 @@ def synthetic_clip(seed: int = 0, length: int = 16000) -> np.ndarray:
     return _f32(x[None, :])
 
 
+def m5_state_dict(seed: int = 7, first_kernel_size: int = 80, n_output: int = 35, n_channel: int = 32):
+    """fp32 numpy state dict for audio_models/M5/M5Net.py M5(n_input=1, first_kernel_size, n_output, stride=16, n_channel): He-scaled
+    conv weights, BatchNorm statistics sized so that each block stays O(1) on synthetic_clip()'s amplitudes (conv1 of a |x| <= 0.5 clip
+    has a spread of about 0.2) and roughly half of the ReLUs are alive: a stand-in for the geometry no committed checkpoint has."""
+    rng = np.random.default_rng(seed)
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    widths = [(1, n_channel, first_kernel_size), (n_channel, n_channel, 3), (n_channel, 2 * n_channel, 3), (2 * n_channel, 2 * n_channel, 3)]
+    for i, (cin, cout, k) in enumerate(widths, start=1):
+        sd['conv%d.weight' % i] = _f32(rng.standard_normal((cout, cin, k)) * np.sqrt(2.0 / (cin * k)))
+        sd['conv%d.bias' % i] = _f32(rng.standard_normal(cout) * 0.05)
+        sd['bn%d.weight' % i] = _f32(rng.uniform(0.6, 1.4, size=cout))
+        sd['bn%d.bias' % i] = _f32(rng.standard_normal(cout) * 0.2)
+        sd['bn%d.running_mean' % i] = _f32(rng.standard_normal(cout) * (0.05 if i == 1 else 0.3))
+        sd['bn%d.running_var' % i] = _f32(rng.uniform(0.02, 0.06, size=cout) if i == 1 else rng.uniform(0.5, 1.5, size=cout))
+        sd['bn%d.num_batches_tracked' % i] = np.array(1, dtype=np.int64)
+    sd['fc1.weight'] = _f32(rng.standard_normal((n_output, 2 * n_channel)) * np.sqrt(1.0 / (2 * n_channel)))
+    sd['fc1.bias'] = _f32(rng.standard_normal(n_output) * 0.1)
+    return sd
+
+
 def resnext29_state_dict(seed: int = 2929, num_classes: int = 10, in_channels: int = 1, calibrated: bool = True):
     """fp32 numpy state dict for models/resnext.py CifarResNeXt(nlabels=10, cardinality=8, depth=29, base_width=64,
     widen_factor=4, in_channels=1): kaiming (fan_out) conv weights, BatchNorm affine/statistics drawn so that the

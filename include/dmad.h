@@ -28,7 +28,8 @@ enum dmad_status {
     DMAD_OK = 0,
     DMAD_ERR_INVALID = -1,      /* bad argument / unsupported configuration */
     DMAD_ERR_STATE = -2,        /* weights not finalised, batch larger than max_batch, ... */
-    DMAD_ERR_HIP = -3           /* a HIP runtime call failed */
+    DMAD_ERR_HIP = -3,          /* a HIP runtime call failed */
+    DMAD_ERR_SHAPE = -4         /* a weight set whose geometry no kernel serves (the M5 part); the message names the field */
 };
 
 enum dmad_precision {
@@ -618,6 +619,46 @@ typedef struct dmad_wave_defense {
  * the layout is kept for the callers of dmad_query_logits.  logits: [repeats * B][num_classes]; decisions: optional int32. */
 int dmad_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, const dmad_wave_defense* d, float* logits,
                               int32_t* decisions, dmad_stream s);
+
+/* ---- M5, the raw-waveform classifier (audio_models/M5/M5Net.py:4-38): a part of its own beside the WaveNet, the spectrogram
+ * classifier and the UNet; an engine may hold VGG19_bn or ResNeXt29 AND M5.  In the reference driver it makes the system
+ * AcousticSystem(classifier, transform=None, ...) (adaptive_attack_eval.py:121-122, 169-170): waveform in, log-probabilities out, no mel front-end.
+ *
+ * Weights (dmad_load_weight, BatchNorm folded on the host: s = gamma / sqrt(var + 1e-5), shift = beta + (bias - mean) * s):
+ *   m5.conv1.w [32][1][k1]   m5.conv2.w [32][32][3]   m5.conv3.w [64][32][3]   m5.conv4.w [64][64][3]   m5.scale<i> / m5.shift<i> [C_i], i = 1..4
+ *   m5.fc.w [n_output][64]   m5.fc.b [n_output]   m5.stride [1] (conv1's stride, as a float)
+ * dmad_finalize_weights packs them.  Supported: n_input = 1, stride = 16, n_channel = 32, first_kernel_size k1 = 80 or 160,
+ * n_output <= 64 and the engine's clip_len; anything else is DMAD_ERR_SHAPE with a message that names the field.  M5 is exact fp32 on
+ * every engine precision.  Its kernels keep every activation of a clip in the LDS of one workgroup and use NO workspace in device
+ * memory: nothing is reserved at finalisation (whatever max_batch is) and no call allocates.  Every sum runs in a fixed order inside
+ * the clip's workgroup, so a clip's bits do not depend on B, on its row or on the call.  Any B >= 1 (no max_batch limit).
+ * x must be 16-byte aligned (the clip is read 16 bytes at a time; clip_len is a multiple of 128, so every row then is):
+ * DMAD_ERR_INVALID otherwise.
+ * All of the calls below return DMAD_ERR_STATE before the M5 weights are finalised.
+ *
+ * dmad_m5_logits (M5Net.py:21-38 M5.forward in eval mode):  x device fp32 [B][clip_len] -> logp [B][n_output], the log-probabilities;
+ * decisions: optional int32 [B], the arg-max (the first maximum wins).
+ *
+ * dmad_m5_vjp (what loss.backward() runs through M5.forward, white_box_attack.py:438, 562):  g_x = (d logp / d x)^T g_logp, [B][clip_len],
+ * for g_logp [B][n_output].  The forward is recomputed in the same launch and only the decision of each pooled unit is kept (its
+ * arg-max among the 4 frames, the first maximum winning, and whether that maximum is > 0: ReLU'(0) = 0).  logp: optional, bit-identical
+ * to dmad_m5_logits.  First order only, no weight gradients.
+ *
+ * dmad_m5_tape (test hook):  layer 1..4 -> pooled [B][C][T] floats, that block's pooled post-ReLU map, and decisions [B][C][T] bytes,
+ * arg | on << 2, both written by the launch dmad_m5_vjp makes (C, T: 32 x 247 / 32 x 61 / 64 x 14 / 64 x 3 at k1 = 160, clip_len 16000). */
+int dmad_m5_logits(dmad_engine* e, const float* x, int32_t B, float* logp, int32_t* decisions, dmad_stream s);
+int dmad_m5_vjp(dmad_engine* e, const float* x, int32_t B, const float* g_logp, float* g_x, float* logp, dmad_stream s);
+int dmad_m5_tape(dmad_engine* e, const float* x, int32_t B, int32_t layer, float* pooled, uint8_t* decisions, dmad_stream s);
+
+/* dmad_query_logits with M5 in the place of  mel dB -> classifier  (EOT.forward on AcousticSystem(M5, None, defender),
+ * robustness_eval/_EOT.py:30-64): the same arguments, samplers 0 / 1 / 2, row layout and Philox keys; logits: [repeats * B][n_output]
+ * log-probabilities.  Samplers 1 and 2 return DMAD_ERR_STATE when the engine holds no WaveNet. */
+int dmad_m5_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, int32_t sampler, int32_t t_star, float c_a, float c_b,
+                         const float* c_eps, const float* c_div, const float* c_sig, uint64_t seed, uint64_t sample0, float* logits,
+                         int32_t* decisions, dmad_stream s);
+/* dmad_defense_query_logits with M5 in the place of  mel dB -> classifier  (adaptive_attack_eval.py:169-170 with a Time / FreqDomainDefense). */
+int dmad_m5_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, const dmad_wave_defense* d, float* logits,
+                                 int32_t* decisions, dmad_stream s);
 
 /* counts[argmax_c logits[b][c]] += 1 (first maximum wins) — certified_robust.py:59-65. */
 int dmad_vote(dmad_engine* e, const float* logits, int32_t B, int64_t* counts, dmad_stream s);
