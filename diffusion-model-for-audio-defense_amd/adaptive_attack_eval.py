@@ -9,8 +9,9 @@ AcousticSystem(classifier, MelSpectrogramDB, defender) with the defenses
   * Diffusion       RevDiffWave (the reverse VP-SDE on the waveform, diffusion_models/diffwave_sde.py);
   * Diffusion-Spec  RevImprovedDiffusion (the reverse VP-SDE on the spectrogram, diffusion_models/improved_diffusion_sde.py).
 Every other attack (Qin-I, Kenansville, FAKEBOB, SirenAttack) and defense (AS, MS, DS, LPF, BPF, FeCo, DefenseGAN) raises
-NotImplementedError naming the piece this package does not have, or the driver that runs it (FAKEBOB and SirenAttack:
-black_box_attack_eval.py and siren_attack_eval.py; the baseline defenses AS, MS, DS, LPF, BPF: baseline_defense_eval.py).
+NotImplementedError naming the piece this package does not have, or the driver that runs it (Qin-I and `--max_iter_2` > 0:
+imperceptible_attack_eval.py; FAKEBOB and SirenAttack: black_box_attack_eval.py and siren_attack_eval.py; the baseline defenses AS, MS,
+DS, LPF, BPF: baseline_defense_eval.py).
 
 Additions to the reference's flags:
   * `--classifier_path`: the classifier checkpoint; its default is the path the reference hard-codes (it overrides
@@ -36,10 +37,10 @@ REFERENCE_CLASSIFIER_PATH = ('audio_models/ConvNets_SpeechCommands/checkpoints/j
 ATTACKS = ['CW', 'Qin-I', 'Kenansville', 'FAKEBOB', 'SirenAttack']
 DEFENSES = ['Diffusion', 'Diffusion-Spec', 'AS', 'MS', 'DS', 'LPF', 'BPF', 'FeCo', 'DefenseGAN', 'None']
 _MISSING_ATTACK = {
-    'Qin-I': 'AudioAttack stage 2 (the psychoacoustic masker of white_box_attack.py)',
     'Kenansville': 'the black-box attacks (robustness_eval/black_box_attack.py)',
 }
-_OTHER_DRIVER = {'FAKEBOB': 'black_box_attack_eval.py', 'SirenAttack': 'siren_attack_eval.py'}    # attacks run by a driver of their own
+_OTHER_DRIVER = {'FAKEBOB': 'black_box_attack_eval.py', 'SirenAttack': 'siren_attack_eval.py'}    # query-only attacks run by a driver of their own
+QIN_DRIVER = 'imperceptible_attack_eval.py'       # Qin-I (AudioAttack stage 2, max_iter_2 > 0)
 BASELINE_DEFENSES = ['AS', 'MS', 'DS', 'LPF', 'BPF']                # transforms/time_defense.py, transforms/frequency_defense.py
 _MISSING_DEFENSE = {
     'FeCo': 'the feature-compression defense (transforms/feature_defense.py)',
@@ -106,6 +107,9 @@ def check_supported(args):
     if args.attack in _OTHER_DRIVER:
         raise NotImplementedError('--attack %s is a query-only attack: %s runs it, this white-box driver does not'
                                   % (args.attack, _OTHER_DRIVER[args.attack]))
+    if args.attack == 'Qin-I':
+        raise NotImplementedError('--attack Qin-I is the two-stage imperceptible attack: %s runs it, this driver runs stage 1 (CW) only'
+                                  % QIN_DRIVER)
     if args.attack in _MISSING_ATTACK:
         raise NotImplementedError('--attack %s needs %s, which this package does not provide (supported: CW)'
                                   % (args.attack, _MISSING_ATTACK[args.attack]))
@@ -113,7 +117,7 @@ def check_supported(args):
         raise NotImplementedError('unknown attack: %s' % args.attack)
     check_defense(args)
     if args.max_iter_2 > 0:
-        raise NotImplementedError('--max_iter_2 > 0 runs AudioAttack stage 2 (Qin-I), which this package does not provide')
+        raise NotImplementedError('--max_iter_2 > 0 runs AudioAttack stage 2 (Qin-I): %s runs it, this driver runs stage 1 only' % QIN_DRIVER)
 
 
 def check_defense(args):

@@ -43,8 +43,8 @@ def build_parser():
 def check_supported(args):
     """NotImplementedError for every attack, defense and option this driver does not run."""
     if args.attack not in ATTACKS:
-        raise NotImplementedError('--attack %s: this driver runs CW, FAKEBOB and SirenAttack (Kenansville and Qin-I are not provided)'
-                                  % args.attack)
+        raise NotImplementedError('--attack %s: this driver runs CW, FAKEBOB and SirenAttack (Qin-I: imperceptible_attack_eval.py, without a baseline defense; Kenansville '
+                                  'is not provided)' % args.attack)
     if args.defense in ('None', 'Diffusion', 'Diffusion-Spec'):
         raise NotImplementedError('--defense %s: %s runs it under --attack %s, this driver runs the baseline defenses %s'
                                   % (args.defense, _ATTACK_DRIVER[args.attack], args.attack, ', '.join(DEFENSES)))
@@ -54,7 +54,7 @@ def check_supported(args):
     if args.defense not in DEFENSES:
         raise NotImplementedError('unknown defense: %s' % args.defense)
     if args.attack == 'CW' and args.max_iter_2 > 0:
-        raise NotImplementedError('--max_iter_2 > 0 runs AudioAttack stage 2 (Qin-I), which this package does not provide')
+        raise NotImplementedError('--max_iter_2 > 0 runs AudioAttack stage 2 (Qin-I): imperceptible_attack_eval.py runs it, this driver does not')
 
 
 def build_defender(args, engine=None):

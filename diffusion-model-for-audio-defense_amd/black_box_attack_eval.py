@@ -36,7 +36,7 @@ def check_supported(args):
     """NotImplementedError for anything but FAKEBOB, and for a defense / option adaptive_attack_eval.py refuses for every attack."""
     if args.attack != 'FAKEBOB':
         raise NotImplementedError('--attack %s: this driver runs FAKEBOB only (CW: adaptive_attack_eval.py; SirenAttack: '
-                                  'siren_attack_eval.py; Kenansville and Qin-I are not provided)' % args.attack)
+                                  'siren_attack_eval.py; Qin-I: imperceptible_attack_eval.py; Kenansville is not provided)' % args.attack)
     white_box.check_defense(args)
 
 

@@ -19,6 +19,7 @@
 #include "elementwise.h"
 #include "wave_defense.h"
 #include "m5.h"
+#include "masking.h"
 #include "gemm_f32.h"
 #include "gemm_h16.h"
 #include "wn_bf16.h"
@@ -1656,6 +1657,28 @@ int mel_db_vjp(dmad_engine* e, const float* x, int B, const float* g_spec, float
     });
 }
 
+// Masking loss of the imperceptible attack and its gradient, or the attack's update (masking.h), in passes of melvjpB clips
+// on the mel front-end's DFT map and the mel VJP's gradient maps; melvjp_gM holds the per-frame hinge sums
+int masking(dmad_engine* e, const float* delta, int B, const float* theta, const float* psd_scale, float* g_delta, float* loss, float* psd,
+            const MaskingStep* step, hipStream_t s) {
+    CHK(need_with_classifier(e)); CHK(need_batch(e, B));
+    const int F = masking_frames(e->L);
+    if (F < 1) return fail(DMAD_ERR_STATE, "masking loss: clip_len %d < the %d-sample window", e->L, kMaskWin);
+    if (F > kMaskMaxFrames || (e->L & 3)) return fail(DMAD_ERR_STATE, "masking loss: clip_len %d gives %d frames (at most %d, clip_len a multiple of 4)", e->L, F, kMaskMaxFrames);
+    CHK(mel_vjp_prepare(e));
+    const MaskingWork w{e->dftA, e->mel_dftAT, e->dftD, e->melvjp_gD, e->melvjp_gF, e->melvjp_gM, kDftLd, kDftKT};
+    const size_t L = e->L, TF = (size_t)kMaskBins * F;
+    return for_passes(B, e->melvjpB, [&](int64_t b0, int bb) {
+        MaskingStep st{};
+        if (step) st = MaskingStep{step->x + b0 * L, step->delta + b0 * L, step->g_net + b0 * L, step->alpha + b0, step->signed_lr};
+        if (masking_pass(w, delta + b0 * L, bb, (int)L, theta + b0 * TF, psd_scale + b0, loss + b0, psd ? psd + b0 * TF : nullptr,
+                         step ? nullptr : g_delta + b0 * L, step ? &st : nullptr, s) != 0)
+            return fail(DMAD_ERR_STATE, "masking loss: no GEMM for %d frame rows", bb * F);
+        LASTCHK();
+        return 0;
+    });
+}
+
 // h16 = 1: the classifier's 16-bit tier where one is resident (ResNeXt29 on engines with a 16-bit side) — the fast mode's; 2: its
 // split-f16 tier (exact-vote engines) — tier 1 of the exact-vote loops; every other caller (dmad_classify, the recheck tiers) gets the
 // fp32 matrix cores
@@ -2813,6 +2836,19 @@ int dmad_vgg_pool_relu_bwd(const float* g, const float* y, int32_t B, int32_t H,
 int dmad_mel_db_vjp(dmad_engine* e, const float* x, int32_t B, const float* g_spec, float* g_x, float* spec, dmad_stream s) {
     if (!e || !x || !g_spec || !g_x) return fail(DMAD_ERR_INVALID, "null argument");
     return mel_db_vjp(e, x, B, g_spec, g_x, spec, (hipStream_t)s);
+}
+
+int dmad_masking_loss_vjp(dmad_engine* e, const float* delta, int32_t B, const float* theta, const float* psd_scale, float* g_delta, float* loss,
+                          float* psd, dmad_stream s) {
+    if (!e || !delta || !theta || !psd_scale || !g_delta || !loss) return fail(DMAD_ERR_INVALID, "null argument");
+    return masking(e, delta, B, theta, psd_scale, g_delta, loss, psd, nullptr, (hipStream_t)s);
+}
+
+int dmad_masking_step(dmad_engine* e, const float* x, float* delta, const float* g_net, const float* alpha, float signed_lr, int32_t B,
+                      const float* theta, const float* psd_scale, float* loss, dmad_stream s) {
+    if (!e || !x || !delta || !g_net || !alpha || !theta || !psd_scale || !loss) return fail(DMAD_ERR_INVALID, "null argument");
+    const MaskingStep st{x, delta, g_net, alpha, signed_lr};
+    return masking(e, delta, B, theta, psd_scale, nullptr, loss, nullptr, &st, (hipStream_t)s);
 }
 
 int dmad_wavenet_eps_path(dmad_engine* e, const float* x_t, int32_t t, int32_t B, int32_t path, float* eps, dmad_stream s) {

@@ -99,6 +99,8 @@ _SIGNATURES = {
     'dmad_reserve_classifier_vjp': (C.c_int, [_P, C.c_int32]),
     'dmad_classify_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     'dmad_mel_db_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    'dmad_masking_loss_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    'dmad_masking_step': (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_int32, _P, _P, _P, _P]),
     'dmad_reserve_vgg_vjp': (C.c_int, [_P, C.c_int32]),
     'dmad_vgg_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     'dmad_vgg_vjp_tape': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),

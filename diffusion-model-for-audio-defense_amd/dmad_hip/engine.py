@@ -902,6 +902,55 @@ class Engine:
                                            _ptr(None if sp is None else sp[s:e]), _stream()))
         return (gx, sp) if want_spec else gx
 
+    def masking_frames(self) -> int:
+        """frames of torch.stft(n_fft=2048, hop_length=512, center=False) on a clip of this engine"""
+        return (self.L - 2048) // 512 + 1
+
+    def _masking_args(self, B, theta, psd_scale):
+        F = self.masking_frames()
+        if not (theta.is_cuda and psd_scale.is_cuda):
+            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
+        if tuple(theta.shape) != (B, 1025, F) or psd_scale.numel() != B:
+            raise DmadError('theta must be [%d, 1025, %d] and psd_scale [%d], not %s and %s'
+                            % (B, F, B, tuple(theta.shape), tuple(psd_scale.shape)))
+        return theta.detach().contiguous().float(), psd_scale.detach().reshape(B).contiguous().float()
+
+    def masking_loss_vjp(self, delta: torch.Tensor, theta: torch.Tensor, psd_scale: torch.Tensor, want_psd: bool = False):
+        """dmad_masking_loss_vjp (DESIGN §20): the masking loss of the imperceptible attack and its gradient.  delta [B,1,L] or [B,L];
+        theta [B,1025,F]: the stabilised threshold 10^(threshold / 10); psd_scale [B]: 10^9.6 / psd_maximum_stabilized.  Returns
+        (g_delta [B,L], loss [B]) and, with want_psd, the normalised PSD estimate [B,1025,F]."""
+        dw = self._wave(delta)
+        B = dw.shape[0]
+        th, sc = self._masking_args(B, theta, psd_scale)
+        g = torch.empty_like(dw)
+        loss = torch.empty((B,), device=dw.device, dtype=torch.float32)
+        psd = torch.empty_like(th) if want_psd else None
+        for s, e in self._chunks(B):
+            check(self.lib.dmad_masking_loss_vjp(self._h, _ptr(dw[s:e]), e - s, _ptr(th[s:e]), _ptr(sc[s:e]), _ptr(g[s:e]), _ptr(loss[s:e]),
+                                                 _ptr(None if psd is None else psd[s:e]), _stream()))
+        return (g, loss, psd) if want_psd else (g, loss)
+
+    def masking_step(self, x: torch.Tensor, delta: torch.Tensor, g_net: torch.Tensor, alpha: torch.Tensor, signed_lr: float,
+                     theta: torch.Tensor, psd_scale: torch.Tensor) -> torch.Tensor:
+        """dmad_masking_step: one update of stage 2, delta <- clamp(x + delta + signed_lr (g_net + alpha g_theta), -1, 1) - x IN PLACE
+        (delta: a contiguous float32 CUDA tensor [B,1,L] or [B,L]; signed_lr = -lr targeted, +lr untargeted; alpha [B]).  Returns the
+        masking loss [B] of delta before the update."""
+        if not (delta.is_cuda and delta.dtype == torch.float32 and delta.is_contiguous()):
+            raise DmadError('delta is updated in place: it must be a contiguous float32 tensor on the GPU (the dmad engine has no CPU path)')
+        dw = self._wave(delta)
+        assert dw.data_ptr() == delta.data_ptr()
+        B = dw.shape[0]
+        xw, gn = self._wave(x), self._wave(g_net)
+        if xw.shape[0] != B or gn.shape[0] != B or alpha.numel() != B or not alpha.is_cuda:
+            raise DmadError('x, g_net and alpha must hold %d rows on the GPU' % B)
+        al = alpha.detach().reshape(B).contiguous().float()
+        th, sc = self._masking_args(B, theta, psd_scale)
+        loss = torch.empty((B,), device=dw.device, dtype=torch.float32)
+        for s, e in self._chunks(B):
+            check(self.lib.dmad_masking_step(self._h, _ptr(xw[s:e]), _ptr(dw[s:e]), _ptr(gn[s:e]), _ptr(al[s:e]), float(signed_lr), e - s,
+                                             _ptr(th[s:e]), _ptr(sc[s:e]), _ptr(loss[s:e]), _stream()))
+        return loss
+
     def vote(self, logits: torch.Tensor, counts: torch.Tensor):
         lg = logits.detach().contiguous().float()
         assert lg.is_cuda and counts.is_cuda and counts.dtype == torch.int64 and lg.shape[1] == self.num_classes

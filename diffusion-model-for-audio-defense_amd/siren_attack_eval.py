@@ -40,7 +40,7 @@ def check_supported(args):
     """NotImplementedError for anything but SirenAttack, and for a defense / option adaptive_attack_eval.py refuses for every attack."""
     if args.attack != 'SirenAttack':
         raise NotImplementedError('--attack %s: this driver runs SirenAttack only (CW: adaptive_attack_eval.py; FAKEBOB: '
-                                  'black_box_attack_eval.py; Kenansville and Qin-I are not provided)' % args.attack)
+                                  'black_box_attack_eval.py; Qin-I: imperceptible_attack_eval.py; Kenansville is not provided)' % args.attack)
     white_box.check_defense(args)
 
 

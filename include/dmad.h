@@ -308,6 +308,32 @@ int dmad_reserve_classifier_vjp(dmad_engine* e, int32_t max_batch);
 int dmad_classify_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s);
 int dmad_mel_db_vjp(dmad_engine* e, const float* x, int32_t B, const float* g_spec, float* g_x, float* spec, dmad_stream s);
 
+/* The masking loss of the imperceptible attack (Qin et al. 2019; stage 2 of AudioAttack, the driver's --attack Qin-I) and its gradient
+ * with respect to the perturbation.  DESIGN §20.  With L = clip_len, F = (L - 2048) / 512 + 1 frames and K = 1025 bins:
+ *
+ * dmad_masking_loss_vjp replaces _loss_gradient_masking_threshold and _approximate_power_spectral_density
+ * (robustness_eval/white_box_attack.py:606-678): torch.stft(n_fft = 2048, hop = 512, hann, center = False) of delta, the normalised
+ * PSD estimate psd[b][k][f] = psd_scale[b] (8/3) / 2048^2 |stft|^2, loss[b] = mean over (k, f) of max(psd - theta[b][k][f], 0), and
+ * g_delta = d sum(loss) / d delta.  delta, g_delta: device fp32 [B][L]; theta: device fp32 [B][K][F], the stabilised threshold
+ * 10^(threshold / 10); psd_scale: device fp32 [B], 10^9.6 / psd_maximum_stabilized; loss: device fp32 [B]; psd: optional (NULL)
+ * device fp32 [B][K][F].  The frames are read in place by the fp32 GEMM on the mel front-end's windowed DFT image, the hinge is one
+ * kernel between that GEMM and the one on the transposed image (gradient where psd > theta, strictly: torch's ReLU), the
+ * overlap-add of the uncentred framing sums the frames that cover a sample in ascending order; samples p >= 512 (F - 1) + 2048 lie
+ * in no frame and get exactly 0.  Every sum has a fixed order (no atomics, no split-K): loss and g_delta are bit-identical across
+ * calls and independent of the batch.  Nothing is kept across calls; the forward is not stored.  Works in the buffers of
+ * dmad_mel_db_vjp (allocated on the first call of either), in passes of up to 64 clips.  B in [1, max_batch].  DMAD_ERR_STATE for an
+ * engine without a classifier part (with_classifier = 0: no mel constants), B outside [1, max_batch], clip_len < 2048 or more than
+ * 32 frames.
+ *
+ * dmad_masking_step is the same pass with the attack's update (white_box_attack.py:569-573) written in place of the gradient:
+ * delta[b][p] = clamp(x + delta + signed_lr (g_net + alpha[b] g_theta), -1, 1) - x, g_theta the g_delta above; signed_lr = -lr for a
+ * targeted attack, +lr otherwise.  x, g_net: device fp32 [B][L]; delta: device fp32 [B][L], updated in place; alpha: device fp32 [B].
+ * loss as above (of delta before the update), bit-identical to dmad_masking_loss_vjp's. */
+int dmad_masking_loss_vjp(dmad_engine* e, const float* delta, int32_t B, const float* theta, const float* psd_scale, float* g_delta, float* loss,
+                          float* psd, dmad_stream s);
+int dmad_masking_step(dmad_engine* e, const float* x, float* delta, const float* g_net, const float* alpha, float signed_lr, int32_t B,
+                      const float* theta, const float* psd_scale, float* loss, dmad_stream s);
+
 /* The same pair for the other classifier with a forward on the engine, VGG19_bn (models/vgg.py:31-52).  DESIGN §18.
  *
  * dmad_reserve_vgg_vjp reserves the VGG19_bn VJP workspace for up to max_batch spectrograms per pass: the TAPE of the fp32 forward — the
