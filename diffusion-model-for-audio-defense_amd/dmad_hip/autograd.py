@@ -46,6 +46,13 @@ def _require_cuda(x):
         raise DmadError('input must live on the GPU (this package has no CPU path, the differentiation branch included)')
 
 
+def _first_order_only(name: str, torch_hint: bool = True):
+    """the refusal every backward below starts with; torch_hint: a torch restatement exists to fall back to"""
+    if torch.is_grad_enabled():
+        raise DmadError('the HIP %s VJP is first-order only: create_graph=True (double backward) is not supported' % name
+                        + ("; use grad_backend='torch' for higher derivatives" if torch_hint else ''))
+
+
 class FoldedWaveNet:
     """Folded fp32 WaveNet weights (dmad_hip.engine.fold_wavenet_state_dict) as device tensors, created on first use."""
 
@@ -144,9 +151,7 @@ class WaveNetEpsHIP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_eps):
-        if torch.is_grad_enabled():
-            raise DmadError('the HIP WaveNet VJP is first-order only: create_graph=True (double backward) is not supported; '
-                            "use grad_backend='torch' for higher derivatives")
+        _first_order_only('WaveNet')
         audio, = ctx.saved_tensors
         eng, B = ctx.engine, audio.shape[0]
         if eng.vjp_batch < B:
@@ -183,8 +188,7 @@ class UNetEpsHIP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_eps):
-        if torch.is_grad_enabled():
-            raise DmadError('the HIP UNet VJP is first-order only: create_graph=True (double backward) is not supported')
+        _first_order_only('UNet', torch_hint=False)
         x, = ctx.saved_tensors
         eng, B = ctx.engine, x.shape[0]
         if eng.unet_vjp_batch < B:
@@ -198,24 +202,24 @@ def unet_eps_hip(engine, x: torch.Tensor, t: int) -> torch.Tensor:
     return UNetEpsHIP.apply(x, engine, int(t))
 
 
+def _classifier_forward(ctx, spec, engine):
+    """the forward of ResNeXtHIP and VGGHIP: the resident classifier's fp32 tier"""
+    _require_cuda(spec)
+    logits = engine.classify_tier(spec, 0)
+    ctx.engine = engine
+    ctx.save_for_backward(spec)
+    return logits
+
+
 class ResNeXtHIP(torch.autograd.Function):
     """logits = CifarResNeXt(spec [B,1,32,32]) on the engine's fp32 ResNeXt29 tier (classify_tier(spec, 0)), differentiable in `spec`
     through the engine's VJP.  Saves only the input; the backward re-runs the forward with its tape saved (dmad_classify_vjp).  The VJP
     workspace is reserved on first use.  No weight gradients.  First-order only: create_graph=True raises."""
-
-    @staticmethod
-    def forward(ctx, spec, engine):
-        _require_cuda(spec)
-        logits = engine.classify_tier(spec, 0)
-        ctx.engine = engine
-        ctx.save_for_backward(spec)
-        return logits
+    forward = staticmethod(_classifier_forward)
 
     @staticmethod
     def backward(ctx, g_logits):
-        if torch.is_grad_enabled():
-            raise DmadError('the HIP ResNeXt29 VJP is first-order only: create_graph=True (double backward) is not supported; '
-                            "use grad_backend='torch' for higher derivatives")
+        _first_order_only('ResNeXt29')
         spec, = ctx.saved_tensors
         eng, B = ctx.engine, spec.shape[0]
         if eng.classifier_vjp_batch < B:
@@ -233,20 +237,11 @@ class VGGHIP(torch.autograd.Function):
     """logits = VGG19_bn(spec [B,1,32,32]) on the engine's fp32 tier (classify_tier(spec, 0)), differentiable in `spec` through the
     engine's VJP.  Saves only the input; the backward re-runs the forward with its tape saved (dmad_vgg_vjp).  The VJP workspace is
     reserved on first use.  No weight gradients.  First-order only: create_graph=True raises."""
-
-    @staticmethod
-    def forward(ctx, spec, engine):
-        _require_cuda(spec)
-        logits = engine.classify_tier(spec, 0)
-        ctx.engine = engine
-        ctx.save_for_backward(spec)
-        return logits
+    forward = staticmethod(_classifier_forward)
 
     @staticmethod
     def backward(ctx, g_logits):
-        if torch.is_grad_enabled():
-            raise DmadError('the HIP VGG19_bn VJP is first-order only: create_graph=True (double backward) is not supported; '
-                            "use grad_backend='torch' for higher derivatives")
+        _first_order_only('VGG19_bn')
         spec, = ctx.saved_tensors
         eng, B = ctx.engine, spec.shape[0]
         if eng.vgg_vjp_batch < min(B, eng.max_batch):
@@ -274,9 +269,7 @@ class M5HIP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_logp):
-        if torch.is_grad_enabled():
-            raise DmadError('the HIP M5 VJP is first-order only: create_graph=True (double backward) is not supported; '
-                            "use grad_backend='torch' for higher derivatives")
+        _first_order_only('M5')
         x, = ctx.saved_tensors
         g = ctx.engine.m5_vjp(x, g_logp.contiguous())
         return g.view(x.shape).to(x.dtype), None
@@ -300,9 +293,7 @@ class MelDBHIP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_spec):
-        if torch.is_grad_enabled():
-            raise DmadError('the HIP mel VJP is first-order only: create_graph=True (double backward) is not supported; '
-                            "use grad_backend='torch' for higher derivatives")
+        _first_order_only('mel')
         x, = ctx.saved_tensors
         g = ctx.engine.mel_db_vjp(x, g_spec.contiguous())
         return g.view(x.shape).to(x.dtype), None

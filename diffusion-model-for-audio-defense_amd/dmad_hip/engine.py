@@ -1,7 +1,12 @@
 """Host-side handle on one dmad_engine (one per process per GPU).
 
 PyTorch is plumbing here: device memory (torch tensors), the current HIP stream and
-torch.distributed.  All arithmetic of the hot path runs inside libdmad_hip.so."""
+torch.distributed.  All arithmetic of the hot path runs inside libdmad_hip.so.
+
+Order of this file: constants and the argument helpers; the weight loaders (fingerprint, fold functions); class Engine — construction,
+weights, the pass walker and the shapers, then one section per part in the order of include/dmad.h (WaveNet, mel front-end, UNet,
+spectrogram classifiers, the vote loops and their exact-vote mode, the query surfaces, NES / particle swarm, the baseline waveform
+defenses, M5, Philox and measurement hooks); the standalone op hooks; bind_* / get_engine."""
 from __future__ import annotations
 
 import ctypes as C
@@ -58,6 +63,10 @@ TAIL_Z = 5.4
 VGG19_CFG = [64, 64, 'M', 128, 128, 'M', 256, 256, 256, 256, 'M', 512, 512, 512, 512, 'M', 512, 512, 512, 512, 'M']
 # (H, C) of VGG19_bn's 16 post-ReLU conv maps on a 32 x 32 spectrogram: the conv slots of the VJP's tape (vgg_vjp_tape)
 VGG_TAPE_MAPS = ((32, 64),) * 2 + ((16, 128),) * 2 + ((8, 256),) * 4 + ((4, 512),) * 4 + ((2, 512),) * 4
+M5_CHANNELS = (32, 32, 64, 64)                     # output channels of M5's four conv blocks (n_channel = 32)
+# the WaveNet geometry an engine is created with unless the caller names another one
+DEFAULT_WAVENET = dict(res_channels=256, skip_channels=256, num_res_layers=36, dilation_cycle=12,
+                       diffusion_step_embed_dim_in=128, diffusion_step_embed_dim_mid=512, diffusion_step_embed_dim_out=512)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -74,6 +83,59 @@ def _as_np(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _f32(t):
+    return None if t is None else t.detach().contiguous().float()
+
+
+def _f64(v) -> np.ndarray:
+    """a state dict entry in float64 on the host: what the fold functions compute in"""
+    return v.detach().cpu().double().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64)
+
+
+def _on_gpu(*tensors):
+    if not all(t.is_cuda for t in tensors):
+        raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
+
+
+def _floats(n: int, *seqs):
+    """host coefficient sequences -> one (C.c_float * n) each"""
+    return [(C.c_float * n)(*[float(v) for v in a]) for a in seqs]
+
+
+# What Engine._passes evaluates once per pass, as a(s, e) for the rows [s, e) of the batch:
+def _per(t: Optional[torch.Tensor], k: int = 1):
+    """a per-row tensor (contiguous): the pointer to its rows [k * s, k * e) (k rows per clip: the VP-SDE trajectory); None stays None"""
+    if t is None:
+        return None
+    base, step = t.data_ptr(), k * t.stride(0) * t.element_size()
+    return lambda s, e: C.c_void_p(base + s * step)
+
+
+def _cols(z: Optional[torch.Tensor]):
+    """the explicit noise [S + 1, B, W] of a VP-SDE chain: the pointer to z[:, s:e] as a fresh contiguous copy per pass, which lives
+    until the next pass replaces it; None stays None"""
+    if z is None:
+        return None
+    held = []
+
+    def cut(s, e):
+        held[:] = [z[:, s:e].contiguous()]
+        return _ptr(held[0])
+    return cut
+
+
+def _N(s, e):
+    """the row count of the pass"""
+    return e - s
+
+
+def _key(sample0):
+    """the Philox key offset of the pass's first row"""
+    sample0 = int(sample0)
+    return lambda s, e: sample0 + s
+
+
+# ---------------------------------------------------------------------- weights: fingerprint and the fold functions
 def state_fingerprint(sd: Dict[str, object]) -> str:
     """Content hash of a state dict (names, shapes, bytes; BatchNorm's num_batches_tracked counters excepted: they do not
     enter inference): identifies WHICH weights an engine holds."""
@@ -113,82 +175,66 @@ def fold_wavenet_state_dict(sd: Dict[str, object], num_res_layers: int) -> Dict[
     return {k: _as_np(v) for k, v in out.items()}
 
 
+def _fold_bn(sd, bn: str, eps: float, conv_bias: Optional[str] = None):
+    """eval-mode BatchNorm `bn` behind a conv -> (scale, shift) in float64: scale = gamma / sqrt(var + eps),
+    shift = (bias - mean) * scale + beta (a conv without bias: -mean * scale + beta, the same bits as beta - mean * scale)."""
+    scale = _f64(sd[bn + '.weight']) / np.sqrt(_f64(sd[bn + '.running_var']) + eps)
+    mean = _f64(sd[bn + '.running_mean'])
+    return scale, (-mean if conv_bias is None else _f64(sd[conv_bias]) - mean) * scale + _f64(sd[bn + '.bias'])
+
+
 def fold_vgg19_bn_state_dict(sd: Dict[str, object], eps: float = 1e-5) -> Dict[str, np.ndarray]:
     """models/vgg.py vgg19_bn state dict -> conv weights + eval-mode BatchNorm folded to scale/shift
     (float64 on the host, rounded once):  y = scale * conv(x) + shift,
     scale = gamma / sqrt(var + eps), shift = (bias - mean) * scale + beta."""
-    def A(k):
-        v = sd[k]
-        return (v.detach().cpu().double().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64))
     out, idx, li = {}, 0, 0
     for v in VGG19_CFG:
         if v == 'M':
             idx += 1
             continue
-        b = idx + 1
-        scale = A('features.%d.weight' % b) / np.sqrt(A('features.%d.running_var' % b) + eps)
-        shift = (A('features.%d.bias' % idx) - A('features.%d.running_mean' % b)) * scale + A('features.%d.bias' % b)
-        out['vgg.conv%d.w' % li] = A('features.%d.weight' % idx)
-        out['vgg.conv%d.scale' % li] = scale
-        out['vgg.conv%d.shift' % li] = shift
+        out['vgg.conv%d.w' % li] = _f64(sd['features.%d.weight' % idx])
+        out['vgg.conv%d.scale' % li], out['vgg.conv%d.shift' % li] = _fold_bn(sd, 'features.%d' % (idx + 1), eps, 'features.%d.bias' % idx)
         idx += 3
         li += 1
     for j, i in enumerate((0, 3, 6)):
-        out['vgg.fc%d.w' % j] = A('classifier.%d.weight' % i)
-        out['vgg.fc%d.b' % j] = A('classifier.%d.bias' % i)
+        out['vgg.fc%d.w' % j] = _f64(sd['classifier.%d.weight' % i])
+        out['vgg.fc%d.b' % j] = _f64(sd['classifier.%d.bias' % i])
     return {k: _as_np(v) for k, v in out.items()}
 
 
 def fold_resnext29_state_dict(sd: Dict[str, object], eps: float = 1e-5) -> Dict[str, np.ndarray]:
     """models/resnext.py CifarResNeXt (8x64d, depth 29) state dict -> conv weights + eval-mode BatchNorm folded to
     scale/shift per conv (float64 on the host, rounded once); bottleneck i = 3 * (stage - 1) + k."""
-    def A(k):
-        v = sd[k]
-        return (v.detach().cpu().double().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64))
-
-    def bn(prefix):
-        scale = A(prefix + '.weight') / np.sqrt(A(prefix + '.running_var') + eps)
-        return scale, A(prefix + '.bias') - A(prefix + '.running_mean') * scale
-
-    out = {'rx.conv1.w': A('conv_1_3x3.weight')}
-    out['rx.conv1.scale'], out['rx.conv1.shift'] = bn('bn_1')
+    out = {'rx.conv1.w': _f64(sd['conv_1_3x3.weight'])}
+    out['rx.conv1.scale'], out['rx.conv1.shift'] = _fold_bn(sd, 'bn_1', eps)
     for st in (1, 2, 3):
         for k in range(3):
             src = 'stage_%d.stage_%d_bottleneck_%d.' % (st, st, k)
             dst = 'rx.b%d.' % (3 * (st - 1) + k)
             for conv, norm, name in (('conv_reduce', 'bn_reduce', 'reduce'), ('conv_conv', 'bn', 'conv'), ('conv_expand', 'bn_expand', 'expand')):
-                w = A(src + conv + '.weight')
+                w = _f64(sd[src + conv + '.weight'])
                 out[dst + name + '.w'] = w.reshape(w.shape[0], w.shape[1]) if name != 'conv' else w
-                out[dst + name + '.scale'], out[dst + name + '.shift'] = bn(src + norm)
+                out[dst + name + '.scale'], out[dst + name + '.shift'] = _fold_bn(sd, src + norm, eps)
             if src + 'shortcut.shortcut_conv.weight' in sd:
-                w = A(src + 'shortcut.shortcut_conv.weight')
+                w = _f64(sd[src + 'shortcut.shortcut_conv.weight'])
                 out[dst + 'short.w'] = w.reshape(w.shape[0], w.shape[1])
-                out[dst + 'short.scale'], out[dst + 'short.shift'] = bn(src + 'shortcut.shortcut_bn')
-    out['rx.fc.w'] = A('classifier.weight')
-    out['rx.fc.b'] = A('classifier.bias')
+                out[dst + 'short.scale'], out[dst + 'short.shift'] = _fold_bn(sd, src + 'shortcut.shortcut_bn', eps)
+    out['rx.fc.w'] = _f64(sd['classifier.weight'])
+    out['rx.fc.b'] = _f64(sd['classifier.bias'])
     return {k: _as_np(v) for k, v in out.items()}
-
-
-M5_CHANNELS = (32, 32, 64, 64)                     # output channels of M5's four conv blocks (n_channel = 32)
 
 
 def fold_m5_state_dict(sd: Dict[str, object], stride: int = 16, eps: float = 1e-5) -> Dict[str, np.ndarray]:
     """M5Net.M5 state dict -> the `m5.*` arrays of include/dmad.h: the conv weights as they are, each eval-BatchNorm folded (in float64)
     into s = gamma / sqrt(var + eps) and shift = beta + (bias - mean) * s, fc1, and conv1's stride (the one geometry field no tensor
     shape shows).  The geometry is checked by dmad_finalize_weights (DMAD_ERR_SHAPE)."""
-    def A(k):
-        v = sd[k]
-        return v.detach().cpu().double().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64)
-
     out = {'m5.stride': np.array([float(stride)], dtype=np.float32)}
     for i in (1, 2, 3, 4):
-        s_ = A('bn%d.weight' % i) / np.sqrt(A('bn%d.running_var' % i) + eps)
-        out['m5.conv%d.w' % i] = A('conv%d.weight' % i).astype(np.float32)
-        out['m5.scale%d' % i] = s_.astype(np.float32)
-        out['m5.shift%d' % i] = (A('bn%d.bias' % i) + (A('conv%d.bias' % i) - A('bn%d.running_mean' % i)) * s_).astype(np.float32)
-    out['m5.fc.w'] = A('fc1.weight').astype(np.float32)
-    out['m5.fc.b'] = A('fc1.bias').astype(np.float32)
-    return out
+        out['m5.conv%d.w' % i] = _f64(sd['conv%d.weight' % i])
+        out['m5.scale%d' % i], out['m5.shift%d' % i] = _fold_bn(sd, 'bn%d' % i, eps, 'conv%d.bias' % i)
+    out['m5.fc.w'] = _f64(sd['fc1.weight'])
+    out['m5.fc.b'] = _f64(sd['fc1.bias'])
+    return {k: _as_np(v) for k, v in out.items()}
 
 
 class Engine:
@@ -196,8 +242,7 @@ class Engine:
 
     @staticmethod
     def geometry(wavenet_config: Optional[dict]) -> tuple:
-        wc = dict(res_channels=256, skip_channels=256, num_res_layers=36, dilation_cycle=12,
-                  diffusion_step_embed_dim_in=128, diffusion_step_embed_dim_mid=512, diffusion_step_embed_dim_out=512)
+        wc = dict(DEFAULT_WAVENET)
         wc.update({k: v for k, v in (wavenet_config or {}).items() if k in wc})
         return tuple(sorted(wc.items()))
 
@@ -207,8 +252,7 @@ class Engine:
         if not torch.cuda.is_available():
             raise DmadError('no MI355X/HIP device visible: the dmad engine has no CPU path')
         self.lib = _lib.load()
-        wc = dict(res_channels=256, skip_channels=256, num_res_layers=36, dilation_cycle=12,
-                  diffusion_step_embed_dim_in=128, diffusion_step_embed_dim_mid=512, diffusion_step_embed_dim_out=512)
+        wc = dict(DEFAULT_WAVENET)
         wc.update(wavenet_config or {})
         if wc.get('in_channels', 1) != 1 or wc.get('out_channels', 1) != 1:
             raise DmadError('only in_channels = out_channels = 1 is supported')
@@ -286,12 +330,31 @@ class Engine:
         self.has_wavenet = True
         self.wavenet_owner = state_fingerprint(state_dict)
 
+    def load_unet(self, state_dict):
+        """improved_diffusion.unet.UNetModel state dict (synth.UNET_CONFIG geometry) -> engine, names prefixed 'un.'."""
+        if self.has_unet:
+            raise DmadError('UNet weights are already loaded into this engine')
+        self._load({'un.' + k: _as_np(_f64(v)) for k, v in state_dict.items()})
+        self.has_unet = True
+        self.unet_owner = state_fingerprint(state_dict)
+
     def load_vgg19_bn(self, state_dict):
         if self.has_classifier:
             raise DmadError('classifier weights are already loaded into this engine')
         self._load(fold_vgg19_bn_state_dict(state_dict))
         self.has_classifier = True
         self.classifier_owner, self.classifier_kind = state_fingerprint(state_dict), 'vgg19_bn'
+
+    def load_resnext29(self, state_dict):
+        if self.has_classifier:
+            raise DmadError('classifier weights are already loaded into this engine')
+        self._load(fold_resnext29_state_dict(state_dict))
+        self.has_classifier = True
+        self.classifier_owner, self.classifier_kind = state_fingerprint(state_dict), 'resnext29'
+        if self.precision == EXACT:            # the committed bound for this classifier kind (widen-only, like a calibration)
+            self.floor1 = max(self.floor1, self._committed_margin1())
+            if self.recheck_margin < self.floor1:
+                self.set_recheck_margin(self.floor1, calibrated=True)
 
     def load_m5(self, state_dict, stride: int = 16):
         """M5Net.M5 state dict -> engine (names prefixed 'm5.'); a part of its own beside the spectrogram classifier.  stride: conv1's."""
@@ -320,7 +383,421 @@ class Engine:
             raise DmadError('this engine already holds different %s weights (resident %s..., offered %s...): bind the module to '
                             'its own engine (dmad_hip.engine.get_engine(fresh=True))' % (part, str(owner)[:10], fp[:10]))
 
-    # ------------------------------------------------------------------ exact-vote mode (EXACT engines)
+    # ------------------------------------------------------------------ the pass walker, the shapers, the output builders
+    def _passes(self, fn, B: int, *args):
+        """Run the export `fn` on B rows in passes of max_batch: the one place where a batch is cut.  args: the export's arguments
+        between the handle and the stream, in its order.  A callable among them is evaluated once per pass as a(s, e) for the rows
+        [s, e) (_per, _cols, _N, _key above) and its value goes in; everything else, None included, is passed as it is."""
+        call = [self._h, *args, _stream()]
+        live = [(i, a) for i, a in enumerate(call) if callable(a)]
+        for s in range(0, B, self.max_batch):
+            e = min(B, s + self.max_batch)
+            for i, a in live:
+                call[i] = a(s, e)
+            check(fn(*call))
+
+    def _mapped(self, fn, x: torch.Tensor, *mid) -> torch.Tensor:
+        """the exports that take the rows first and write an output of their shape last: walk `fn` over x, -> that output"""
+        out = torch.empty_like(x)
+        self._passes(fn, x.shape[0], _per(x), *mid, _per(out))
+        return out
+
+    def _wave(self, x: torch.Tensor) -> torch.Tensor:
+        _on_gpu(x)
+        x = x.detach()
+        if x.dim() == 3:
+            assert x.shape[1] == 1, 'expected [B,1,L]'
+            x = x[:, 0]
+        assert x.dim() == 2 and x.shape[1] == self.L, 'expected [B,%d], got %s' % (self.L, tuple(x.shape))
+        return x.contiguous().float()
+
+    def _spec(self, x: torch.Tensor) -> torch.Tensor:
+        _on_gpu(x)
+        x = x.detach()
+        if x.dim() == 4:
+            assert x.shape[1] == 1, 'expected [B,1,32,32]'
+            x = x[:, 0]
+        assert x.dim() == 3 and tuple(x.shape[1:]) == (32, 32), 'expected [B,32,32], got %s' % (tuple(x.shape),)
+        return x.contiguous().float()
+
+    @staticmethod
+    def _rows(x: torch.Tensor, width: int, name: str = 'x') -> torch.Tensor:
+        _on_gpu(x)
+        x = x.detach()
+        if x.dim() != 2 or x.shape[1] != width:
+            raise DmadError('%s must be [B, %d], not %s' % (name, width, tuple(x.shape)))
+        return x.contiguous().float()
+
+    def _clip(self, clip: torch.Tensor) -> torch.Tensor:
+        """the one clip of a vote loop / eval_samples call"""
+        clip = clip.detach().reshape(-1).contiguous().float()
+        assert clip.is_cuda and clip.numel() == self.L
+        return clip
+
+    @staticmethod
+    def _logits_pair(rows: int, width: int, device):
+        """(logits [rows, width] float32, decisions int32 [rows]) of the query surfaces"""
+        return torch.empty((rows, width), device=device, dtype=torch.float32), torch.empty((rows,), device=device, dtype=torch.int32)
+
+    def _reserve(self, name: str, max_batch: int, recorded: Optional[int] = None):
+        """dmad_reserve_<name>: the four VJP workspaces; <name>_batch keeps the largest reservation made"""
+        check(getattr(self.lib, 'dmad_reserve_' + name)(self._h, int(max_batch)))
+        setattr(self, name + '_batch', max(getattr(self, name + '_batch'), int(max_batch) if recorded is None else recorded))
+
+    # ------------------------------------------------------------------ WaveNet (the DiffWave purifiers)
+    def wavenet_eps(self, x_t: torch.Tensor, t: int) -> torch.Tensor:
+        return self._mapped(self.lib.dmad_wavenet_eps, self._wave(x_t), int(t), _N)
+
+    def wavenet_eps_path(self, x_t: torch.Tensor, t: int, path: int) -> torch.Tensor:
+        """eps-network on an explicit path of an EXACT engine: 0 mode default, 1 exact fp32, 2 split-f16 (three MFMAs per product)."""
+        return self._mapped(self.lib.dmad_wavenet_eps_path, self._wave(x_t), int(t), _N, int(path))
+
+    def one_shot(self, x_t: torch.Tensor, t: int, c_a: float, c_b: float) -> torch.Tensor:
+        return self._mapped(self.lib.dmad_one_shot, self._wave(x_t), int(t), float(c_a), float(c_b), _N)
+
+    def ddpm_step(self, x: torch.Tensor, t: int, c_eps: float, c_div: float, c_sig: float, z: Optional[torch.Tensor],
+                  seed: int = 0, sample0: int = 0):
+        """in place on x ([B, L] contiguous fp32 CUDA)."""
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
+        zz = None if z is None else self._wave(z)
+        self._passes(self.lib.dmad_ddpm_step, x.shape[0], _per(x), int(t), float(c_eps), float(c_div), float(c_sig), _per(zz), int(seed),
+                     _key(sample0), _N)
+        return x
+
+    def diffuse(self, x0: torch.Tensor, c_a: float, c_b: float, z: Optional[torch.Tensor], seed: int = 0, sample0: int = 0):
+        x = self._wave(x0)
+        zz = None if z is None else self._wave(z)
+        return self._mapped(self.lib.dmad_diffuse, x, float(c_a), float(c_b), _per(zz), int(seed), _key(sample0), _N)
+
+    def ddpm_purify(self, x0: torch.Tensor, t_star: int, c_a: float, c_b: float, c_eps, c_div, c_sig, seed: int = 0, sample0: int = 0):
+        """DiffWave.forward with device noise in one library call per chunk; c_eps / c_div / c_sig: t_star floats each."""
+        return self._mapped(self.lib.dmad_ddpm_purify, self._wave(x0), int(t_star), float(c_a), float(c_b), *_floats(t_star, c_eps, c_div, c_sig),
+                            int(seed), _key(sample0), _N)
+
+    def reserve_vjp(self, max_batch: int):
+        """dmad_reserve_vjp: the workspace of wavenet_eps_vjp for up to max_batch clips per pass (capped at the engine's fp32 pass
+        size; a larger reservation replaces a smaller one).  FP32 / EXACT engines; DmadError otherwise."""
+        self._reserve('vjp', max_batch)
+
+    def _eps_vjp(self, fn, shaper, x_t, t, g_eps, want_eps):
+        """wavenet_eps_vjp / unet_eps_vjp: the export `fn` on maps that `shaper` (_wave / _spec) checks"""
+        x, g = shaper(x_t), shaper(g_eps)
+        if g.shape != x.shape:
+            raise DmadError('g_eps has shape %s, x_t %s' % (tuple(g.shape), tuple(x.shape)))
+        gx = torch.empty_like(x)
+        eps = torch.empty_like(x) if want_eps else None
+        self._passes(fn, x.shape[0], _per(x), int(t), _N, _per(g), _per(gx), _per(eps))
+        return (gx, eps) if want_eps else gx
+
+    def wavenet_eps_vjp(self, x_t: torch.Tensor, t: int, g_eps: torch.Tensor, want_eps: bool = False):
+        """g_x = (d eps / d x_t)^T g_eps for eps = WaveNet((x_t, t * ones)) on the exact-fp32 path ([B,L] or [B,1,L] -> [B,L]).
+        want_eps: also return eps, bit-identical to wavenet_eps_path(x_t, t, 1).  Needs reserve_vjp first (DmadError otherwise)."""
+        return self._eps_vjp(self.lib.dmad_wavenet_eps_vjp, self._wave, x_t, t, g_eps, want_eps)
+
+    def vpsde_purify(self, x0: torch.Tensor, c_a: float, c_b: float, k, h, hb, q, gs, z: Optional[torch.Tensor] = None, seed: int = 0,
+                     sample0: int = 0, path: int = 0, want_traj: bool = False):
+        """dmad_vpsde_purify: the reverse VP-SDE chain (diffusion to the start, then one Euler-Maruyama step per entry of k / h / hb /
+        q / gs), one library call per chunk of max_batch clips.  path 0: the mode's default WaveNet path, 1: exact fp32.  z: optional
+        explicit noise [S + 1, B, L] (slot 0 the diffusion draw, slot n + 1 step n); None = Philox keyed (seed, sample0 + row).
+        want_traj: also return the trajectory for vpsde_purify_vjp, a [(S + 1) * B, L] tensor stored chunk by chunk: rows
+        [(S + 1) * s, (S + 1) * e) hold the [S + 1][e - s][L] slots of the chunk [s, e)."""
+        return self._vpsde_chain(self.lib.dmad_vpsde_purify, self._wave, self.L, x0, c_a, c_b, k, h, hb, q, gs, z, seed, sample0, path, want_traj)
+
+    def vpsde_purify_vjp(self, traj: torch.Tensor, c_a: float, k, h, hb, q, g_out: torch.Tensor) -> torch.Tensor:
+        """dmad_vpsde_purify_vjp: g_x0 = (d out / d x0)^T g_out of the chain vpsde_purify(.., path=1, want_traj=True) ran, the draws held
+        fixed ([B, L] or [B, 1, L] -> [B, L]).  traj: that call's trajectory.  Needs reserve_vjp first (DmadError otherwise)."""
+        return self._vpsde_chain_vjp(self.lib.dmad_vpsde_purify_vjp, self._wave, self.L, 'L', 'vpsde_purify', traj, c_a, k, h, hb, q, g_out)
+
+    def _vpsde_chain(self, fn, shaper, width, x0, c_a, c_b, k, h, hb, q, gs, z, seed, sample0, path, want_traj):
+        """vpsde_purify / spec_vpsde_purify: the library's chain `fn` on rows of `width` floats that `shaper` (_wave / _spec) checks."""
+        x = shaper(x0)
+        B, S = x.shape[0], len(k)
+        out = torch.empty_like(x)
+        traj = torch.empty(((S + 1) * B, width), dtype=torch.float32, device=x.device) if want_traj else None
+        sched = self._vpsde_arrays(k, h, hb, q, gs)
+        if z is not None:
+            z = z.detach()
+            if not z.is_cuda or tuple(z.shape) != (S + 1, B, width):
+                raise DmadError('z must be a CUDA tensor [%d, %d, %d], not %s' % (S + 1, B, width, tuple(z.shape)))
+            z = z.float()
+        self._passes(fn, B, _per(x), _N, S, float(c_a), float(c_b), *sched, _cols(z), int(seed), _key(sample0), int(path), _per(out),
+                     _per(traj, S + 1))
+        return (out, traj) if want_traj else out
+
+    def _vpsde_chain_vjp(self, fn, shaper, width, width_name, forward_name, traj, c_a, k, h, hb, q, g_out):
+        """vpsde_purify_vjp / spec_vpsde_purify_vjp: the library's reverse walk `fn` over the chunk-by-chunk trajectory of `forward_name`."""
+        g = shaper(g_out)
+        B, S = g.shape[0], len(k)
+        if not traj.is_cuda or tuple(traj.shape) != ((S + 1) * B, width):
+            raise DmadError('traj must be the [(S + 1) * B, %s] = [%d, %d] trajectory of %s, not %s'
+                            % (width_name, (S + 1) * B, width, forward_name, tuple(traj.shape)))
+        gx = torch.empty_like(g)
+        self._passes(fn, B, _per(traj, S + 1), _N, S, float(c_a), *self._vpsde_arrays(k, h, hb, q, h)[:4], _per(g), _per(gx))
+        return gx
+
+    @staticmethod
+    def _vpsde_arrays(k, h, hb, q, gs):
+        S = len(k)
+        if not (len(h) == len(hb) == len(q) == len(gs) == S) or S < 1:
+            raise DmadError('the schedule arrays k / h / hb / q / gs must have one entry per Euler step (%d)' % S)
+        return [(C.c_int32 * S)(*[int(v) for v in k])] + _floats(S, h, hb, q, gs)
+
+    # ------------------------------------------------------------------ mel front-end (and the masking loss on its STFT)
+    def _mel(self, fn, x):
+        x = self._wave(x)
+        out = torch.empty((x.shape[0], 1, 32, 32), device=x.device, dtype=torch.float32)
+        self._passes(fn, x.shape[0], _per(x), _N, _per(out))
+        return out
+
+    def mel_db(self, x: torch.Tensor) -> torch.Tensor:
+        return self._mel(self.lib.dmad_mel_db, x)
+
+    def mel_power(self, x: torch.Tensor) -> torch.Tensor:
+        return self._mel(self.lib.dmad_mel_power, x)
+
+    def power_to_db(self, x: torch.Tensor) -> torch.Tensor:
+        _on_gpu(x)
+        xc = _f32(x)
+        out = torch.empty_like(xc)
+        check(self.lib.dmad_power_to_db(self._h, _ptr(xc), xc.numel(), _ptr(out), _stream()))
+        return out
+
+    def mel_db_vjp(self, x: torch.Tensor, g_spec: torch.Tensor, want_spec: bool = False):
+        """g_x = (d melDB / d x)^T g_spec for the dB mel front-end of mel_db ([B,1,L] or [B,L] -> [B,L]; g_spec [B,1,32,32] or [B,32,32]).
+        want_spec: also return the spectrogram [B,1,32,32], bit-identical to mel_db(x).  The forward is recomputed; the first call
+        allocates the workspace."""
+        xw = self._wave(x)
+        g = self._spec(g_spec)
+        if g.shape[0] != xw.shape[0]:
+            raise DmadError('g_spec has %d rows, x %d' % (g.shape[0], xw.shape[0]))
+        gx = torch.empty_like(xw)
+        sp = torch.empty((xw.shape[0], 1, 32, 32), device=xw.device, dtype=torch.float32) if want_spec else None
+        self._passes(self.lib.dmad_mel_db_vjp, xw.shape[0], _per(xw), _N, _per(g), _per(gx), _per(sp))
+        return (gx, sp) if want_spec else gx
+
+    def masking_frames(self) -> int:
+        """frames of torch.stft(n_fft=2048, hop_length=512, center=False) on a clip of this engine"""
+        return (self.L - 2048) // 512 + 1
+
+    def _masking_args(self, B, theta, psd_scale):
+        F = self.masking_frames()
+        _on_gpu(theta, psd_scale)
+        if tuple(theta.shape) != (B, 1025, F) or psd_scale.numel() != B:
+            raise DmadError('theta must be [%d, 1025, %d] and psd_scale [%d], not %s and %s'
+                            % (B, F, B, tuple(theta.shape), tuple(psd_scale.shape)))
+        return _f32(theta), psd_scale.detach().reshape(B).contiguous().float()
+
+    def masking_loss_vjp(self, delta: torch.Tensor, theta: torch.Tensor, psd_scale: torch.Tensor, want_psd: bool = False):
+        """dmad_masking_loss_vjp (DESIGN §20): the masking loss of the imperceptible attack and its gradient.  delta [B,1,L] or [B,L];
+        theta [B,1025,F]: the stabilised threshold 10^(threshold / 10); psd_scale [B]: 10^9.6 / psd_maximum_stabilized.  Returns
+        (g_delta [B,L], loss [B]) and, with want_psd, the normalised PSD estimate [B,1025,F]."""
+        dw = self._wave(delta)
+        B = dw.shape[0]
+        th, sc = self._masking_args(B, theta, psd_scale)
+        g = torch.empty_like(dw)
+        loss = torch.empty((B,), device=dw.device, dtype=torch.float32)
+        psd = torch.empty_like(th) if want_psd else None
+        self._passes(self.lib.dmad_masking_loss_vjp, B, _per(dw), _N, _per(th), _per(sc), _per(g), _per(loss), _per(psd))
+        return (g, loss, psd) if want_psd else (g, loss)
+
+    def masking_step(self, x: torch.Tensor, delta: torch.Tensor, g_net: torch.Tensor, alpha: torch.Tensor, signed_lr: float,
+                     theta: torch.Tensor, psd_scale: torch.Tensor) -> torch.Tensor:
+        """dmad_masking_step: one update of stage 2, delta <- clamp(x + delta + signed_lr (g_net + alpha g_theta), -1, 1) - x IN PLACE
+        (delta: a contiguous float32 CUDA tensor [B,1,L] or [B,L]; signed_lr = -lr targeted, +lr untargeted; alpha [B]).  Returns the
+        masking loss [B] of delta before the update."""
+        if not (delta.is_cuda and delta.dtype == torch.float32 and delta.is_contiguous()):
+            raise DmadError('delta is updated in place: it must be a contiguous float32 tensor on the GPU (the dmad engine has no CPU path)')
+        dw = self._wave(delta)
+        assert dw.data_ptr() == delta.data_ptr()
+        B = dw.shape[0]
+        xw, gn = self._wave(x), self._wave(g_net)
+        if xw.shape[0] != B or gn.shape[0] != B or alpha.numel() != B or not alpha.is_cuda:
+            raise DmadError('x, g_net and alpha must hold %d rows on the GPU' % B)
+        al = alpha.detach().reshape(B).contiguous().float()
+        th, sc = self._masking_args(B, theta, psd_scale)
+        loss = torch.empty((B,), device=dw.device, dtype=torch.float32)
+        self._passes(self.lib.dmad_masking_step, B, _per(xw), _per(dw), _per(gn), _per(al), float(signed_lr), _N, _per(th), _per(sc), _per(loss))
+        return loss
+
+    # ------------------------------------------------------------------ UNet (the spectrogram-domain purifiers)
+    def unet_eps(self, x_t: torch.Tensor, t: int, tier: Optional[int] = None) -> torch.Tensor:
+        """eps = UNetModel(x_t, t * ones): [B,1,32,32] or [B,32,32] -> [B,32,32].  tier: None = the mode's tier of the map-returning
+        surfaces (dmad_unet_eps); 0 exact fp32 / 1 16-bit / 2 split-f16 explicitly (dmad_unet_eps_tier)."""
+        if tier is None:
+            return self._mapped(self.lib.dmad_unet_eps, self._spec(x_t), int(t), _N)
+        return self._mapped(self.lib.dmad_unet_eps_tier, self._spec(x_t), int(t), _N, int(tier))
+
+    def unet_p_sample(self, x: torch.Tensor, t: int, c_a: float, c_b: float, c_1: float, c_2: float, c_sig: float,
+                      z: Optional[torch.Tensor] = None, seed: int = 0, sample0: int = 0, want_x0: bool = False):
+        """in place on x ([B,32,32] contiguous fp32 CUDA); returns pred_xstart when asked."""
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and tuple(x.shape[1:]) == (32, 32)
+        x0 = torch.empty_like(x) if want_x0 else None
+        zz = None if z is None else self._spec(z)
+        self._passes(self.lib.dmad_unet_p_sample, x.shape[0], _per(x), int(t), float(c_a), float(c_b), float(c_1), float(c_2), float(c_sig),
+                     _per(zz), int(seed), _key(sample0), _N, _per(x0))
+        return x0
+
+    def reserve_unet_vjp(self, max_batch: int):
+        """dmad_reserve_unet_vjp: the workspace of unet_eps_vjp (the forward's tape) for up to max_batch spectrograms per pass (capped at
+        the engine's fp32 pass size; a larger reservation replaces a smaller one).  FP32 / EXACT engines; DmadError otherwise."""
+        self._reserve('unet_vjp', max_batch)
+
+    def unet_eps_vjp(self, x_t: torch.Tensor, t: int, g_eps: torch.Tensor, want_eps: bool = False):
+        """g_x = (d eps / d x_t)^T g_eps for eps = UNetModel(x_t, t * ones) on the exact-fp32 tier ([B,1,32,32] or [B,32,32] -> [B,32,32]).
+        want_eps: also return eps, bit-identical to unet_eps(x_t, t, tier=0).  Needs reserve_unet_vjp first (DmadError otherwise)."""
+        return self._eps_vjp(self.lib.dmad_unet_eps_vjp, self._spec, x_t, t, g_eps, want_eps)
+
+    def spec_vpsde_purify(self, x0: torch.Tensor, c_a: float, c_b: float, k, h, hb, q, gs, z: Optional[torch.Tensor] = None, seed: int = 0,
+                          sample0: int = 0, path: int = 0, want_traj: bool = False):
+        """dmad_spec_vpsde_purify: vpsde_purify's chain on standardised spectrograms with the UNet as the eps-network ([B,1,32,32] or
+        [B,32,32] -> [B,32,32]), one library call per chunk of max_batch.  path 0: the mode's UNet map tier (unet_eps(tier=None)), 1: exact
+        fp32.  z: optional explicit noise [S + 1, B, 1024]; None = Philox keyed (seed, sample0 + row).  want_traj: also return the
+        trajectory for spec_vpsde_purify_vjp, [(S + 1) * B, 1024] stored chunk by chunk as in vpsde_purify."""
+        return self._vpsde_chain(self.lib.dmad_spec_vpsde_purify, self._spec, 1024, x0, c_a, c_b, k, h, hb, q, gs, z, seed, sample0, path, want_traj)
+
+    def spec_vpsde_purify_vjp(self, traj: torch.Tensor, c_a: float, k, h, hb, q, g_out: torch.Tensor) -> torch.Tensor:
+        """dmad_spec_vpsde_purify_vjp: g_x0 = (d out / d x0)^T g_out of the chain spec_vpsde_purify(.., path=1, want_traj=True) ran, the
+        draws held fixed ([B,1,32,32] or [B,32,32] -> [B,32,32]).  traj: that call's trajectory.  Needs reserve_unet_vjp first."""
+        return self._vpsde_chain_vjp(self.lib.dmad_spec_vpsde_purify_vjp, self._spec, 1024, '1024', 'spec_vpsde_purify', traj, c_a, k, h, hb, q, g_out)
+
+    # ------------------------------------------------------------------ spectrogram classifiers (VGG19_bn / ResNeXt29)
+    def _classify(self, fn, spec, *tier):
+        _on_gpu(spec)
+        sp = spec.detach().reshape(spec.shape[0], 32 * 32).contiguous().float()
+        out = torch.empty((sp.shape[0], self.num_classes), device=sp.device, dtype=torch.float32)
+        self._passes(fn, sp.shape[0], _per(sp), _N, *tier, _per(out))
+        return out
+
+    def classify(self, spec: torch.Tensor) -> torch.Tensor:
+        return self._classify(self.lib.dmad_classify, spec)
+
+    def classify_tier(self, spec: torch.Tensor, tier: int) -> torch.Tensor:
+        """dmad_classify_tier: the classifier on an explicit tier (0 fp32, 1 the 16-bit tier / 2 the split-f16 tier of ResNeXt29) — test / measurement hook."""
+        return self._classify(self.lib.dmad_classify_tier, spec, int(tier))
+
+    def reserve_classifier_vjp(self, max_batch: int):
+        """dmad_reserve_classifier_vjp: the workspace of classify_vjp (the ResNeXt29 forward's tape) for up to max_batch spectrograms per
+        pass (capped at max_batch; a larger reservation replaces a smaller one).  ResNeXt29 engines of every precision; DmadError otherwise."""
+        self._reserve('classifier_vjp', max_batch)
+
+    def _logits_vjp(self, fn, spec, g_logits, want_logits, reserve=None):
+        """classify_vjp / vgg_vjp: the export `fn`; reserve: called with B when no workspace is reserved yet (vgg_vjp)"""
+        sp = self._spec(spec)
+        B = sp.shape[0]
+        if not g_logits.is_cuda or tuple(g_logits.shape) != (B, self.num_classes):
+            raise DmadError('g_logits must be a CUDA tensor [%d, %d], not %s' % (B, self.num_classes, tuple(g_logits.shape)))
+        if reserve is not None:
+            reserve(B)
+        g = _f32(g_logits)
+        gs = torch.empty_like(sp)
+        lg = torch.empty((B, self.num_classes), device=sp.device, dtype=torch.float32) if want_logits else None
+        self._passes(fn, B, _per(sp), _N, _per(g), _per(gs), _per(lg))
+        return (gs, lg) if want_logits else gs
+
+    def classify_vjp(self, spec: torch.Tensor, g_logits: torch.Tensor, want_logits: bool = False):
+        """g_spec = (d logits / d spec)^T g_logits for logits = CifarResNeXt(spec) on the fp32 tier ([B,1,32,32] or [B,32,32] -> [B,32,32]).
+        want_logits: also return the logits, bit-identical to classify_tier(spec, 0).  Needs reserve_classifier_vjp first (DmadError
+        otherwise); ResNeXt29 engines only."""
+        return self._logits_vjp(self.lib.dmad_classify_vjp, spec, g_logits, want_logits)
+
+    def reserve_vgg_vjp(self, max_batch: int):
+        """dmad_reserve_vgg_vjp: the workspace of vgg_vjp (the VGG19_bn forward's tape, the gradient maps and, once, the backward weight
+        images) for up to max_batch spectrograms per pass (capped at max_batch; a larger reservation replaces a smaller one).  VGG19_bn
+        engines of every precision; DmadError otherwise."""
+        self._reserve('vgg_vjp', max_batch, min(int(max_batch), self.max_batch))
+
+    def vgg_vjp(self, spec: torch.Tensor, g_logits: torch.Tensor, want_logits: bool = False):
+        """g_spec = (d logits / d spec)^T g_logits for logits = VGG19_bn(spec) on the fp32 tier ([B,1,32,32] or [B,32,32] -> [B,32,32]).
+        want_logits: also return the logits, bit-identical to classify_tier(spec, 0).  Without a reservation the first call reserves
+        its own rows (capped at max_batch); a present reservation is kept and a larger call runs in passes of its size, with the same
+        bits (reserve_vgg_vjp chooses the pass size; autograd.VGGHIP grows it to the batch it meets).  VGG19_bn engines only."""
+        return self._logits_vjp(self.lib.dmad_vgg_vjp, spec, g_logits, want_logits, None if self.vgg_vjp_batch else self.reserve_vgg_vjp)
+
+    def vgg_vjp_tape(self, index: int, B: int) -> torch.Tensor:
+        """dmad_vgg_vjp_tape: map `index` of the last vgg_vjp call's tape, rows [0, B) — 0 - 15 the post-ReLU conv maps [B,H,H,C] (NHWC),
+        16 - 17 the post-ReLU FC vectors [B,4096] (test hook; that call must have run as one pass)."""
+        if index < 16:
+            H, C = VGG_TAPE_MAPS[index]
+            out = torch.empty((int(B), H, H, C), device='cuda', dtype=torch.float32)
+        else:
+            out = torch.empty((int(B), 4096), device='cuda', dtype=torch.float32)
+        check(self.lib.dmad_vgg_vjp_tape(self._h, int(index), int(B), _ptr(out), _stream()))
+        return out
+
+    # ------------------------------------------------------------------ the vote loops and their exact-vote mode (EXACT engines)
+    def vote(self, logits: torch.Tensor, counts: torch.Tensor):
+        lg = logits.detach().contiguous().float()
+        assert lg.is_cuda and counts.is_cuda and counts.dtype == torch.int64 and lg.shape[1] == self.num_classes
+        check(self.lib.dmad_vote(self._h, _ptr(lg), lg.shape[0], _ptr(counts), _stream()))
+
+    def _vote_state(self, clip, batch, counts):
+        """smooth_votes / spec_smooth_votes: the clip, the pass size (at most max_batch) and the counts to add to"""
+        clip = self._clip(clip)
+        if counts is None:
+            counts = torch.zeros(self.num_classes, dtype=torch.int64, device=clip.device)
+        return clip, min(batch or self.max_batch, self.max_batch), counts
+
+    def smooth_votes(self, clip: torch.Tensor, sigma: float, sqrt_abar_star: float, t: int, c_a: float, c_b: float,
+                     n: int, batch: Optional[int] = None, seed: int = 0, sample0: int = 0,
+                     delta: Optional[torch.Tensor] = None, want_logits: bool = False, want_x0: bool = False,
+                     counts: Optional[torch.Tensor] = None):
+        """The fused Monte Carlo loop (dmad_smooth_votes).  Returns (counts[int64, C] on device, logits|None, x0|None)."""
+        clip, batch, counts = self._vote_state(clip, batch, counts)
+        logits = torch.empty((n, self.num_classes), device=clip.device) if want_logits else None
+        x0 = torch.empty((n, self.L), device=clip.device) if want_x0 else None
+        if delta is not None:
+            delta = delta.detach().reshape(n, self.L).contiguous().float()
+            assert delta.is_cuda
+        check(self.lib.dmad_smooth_votes(self._h, _ptr(clip), float(sigma), float(sqrt_abar_star), int(t), float(c_a), float(c_b),
+                                         int(n), int(batch), int(seed), int(sample0), _ptr(delta), _ptr(counts), _ptr(logits),
+                                         _ptr(x0), _stream()))
+        return counts, logits, x0
+
+    def eval_samples(self, clip: torch.Tensor, sigma: float, sqrt_abar_star: float, t: int, c_a: float, c_b: float,
+                     idx: torch.Tensor, path: int = 0, seed: int = 0, sample0: int = 0, delta: Optional[torch.Tensor] = None,
+                     want_x0: bool = False):
+        """dmad_eval_samples: logits [len(idx), C] (and x0 [len(idx), L] when asked) of the Monte Carlo samples with GLOBAL indices
+        `idx` (int64, device) on WaveNet path 0 (the mode's default) / 1 (exact fp32) / 2 (split-f16).  Nothing votes."""
+        clip = self._clip(clip)
+        idx = idx.detach().to(device=clip.device, dtype=torch.int64).contiguous()
+        n = idx.numel()
+        logits = torch.empty((n, self.num_classes), device=clip.device)
+        x0 = torch.empty((n, self.L), device=clip.device) if want_x0 else None
+        if delta is not None:
+            delta = delta.detach().reshape(-1, self.L).contiguous().float()
+            assert delta.is_cuda
+        check(self.lib.dmad_eval_samples(self._h, _ptr(clip), float(sigma), float(sqrt_abar_star), int(t), float(c_a), float(c_b),
+                                         int(seed), int(sample0), _ptr(delta), _ptr(idx), int(n), int(path), _ptr(logits), _ptr(x0),
+                                         _stream()))
+        return (logits, x0) if want_x0 else logits
+
+    def spec_smooth_votes(self, clip: torch.Tensor, sigma: float, t_star: int, q_a: float, q_b: float, c_a, c_b, c_1, c_2, c_sig,
+                          mel_lo: float, mel_hi: float, n: int, batch: Optional[int] = None, seed: int = 0, sample0: int = 0,
+                          want_logits: bool = False, want_spec: bool = False, counts: Optional[torch.Tensor] = None):
+        """dmad_spec_smooth_votes (BASELINE C5): the vote loop with the spec-domain UNet purifier.  Coefficient sequences
+        c_*: t_star + 1 floats each (p_sample at t = 0..t_star).  Returns (counts, logits|None, purified spec|None)."""
+        clip, batch, counts = self._vote_state(clip, batch, counts)
+        logits = torch.empty((n, self.num_classes), device=clip.device) if want_logits else None
+        spec = torch.empty((n, 1, 32, 32), device=clip.device) if want_spec else None
+        check(self.lib.dmad_spec_smooth_votes(self._h, _ptr(clip), float(sigma), int(t_star), float(q_a), float(q_b),
+                                              *_floats(t_star + 1, c_a, c_b, c_1, c_2, c_sig), float(mel_lo), float(mel_hi), int(n), int(batch),
+                                              int(seed), int(sample0), _ptr(counts), _ptr(logits), _ptr(spec), _stream()))
+        return counts, logits, spec
+
+    def spec_eval_samples(self, clip: torch.Tensor, sigma: float, t_star: int, q_a: float, q_b: float, c_a, c_b, c_1, c_2, c_sig,
+                          mel_lo: float, mel_hi: float, idx: torch.Tensor, tier: int, seed: int = 0, want_spec: bool = False):
+        """dmad_spec_eval_samples: logits [len(idx), C] (and the purified dB spectrograms when asked) of the spec-domain chain for
+        the Monte Carlo samples with GLOBAL indices `idx` on UNet tier 0 (exact fp32) / 1 (16-bit) / 2 (split-f16).  Nothing votes."""
+        clip = self._clip(clip)
+        idx = idx.detach().to(device=clip.device, dtype=torch.int64).contiguous()
+        n = idx.numel()
+        logits = torch.empty((n, self.num_classes), device=clip.device)
+        spec = torch.empty((n, 1, 32, 32), device=clip.device) if want_spec else None
+        check(self.lib.dmad_spec_eval_samples(self._h, _ptr(clip), float(sigma), int(t_star), float(q_a), float(q_b),
+                                              *_floats(t_star + 1, c_a, c_b, c_1, c_2, c_sig), float(mel_lo), float(mel_hi), int(seed), _ptr(idx),
+                                              int(n), int(tier), _ptr(logits), _ptr(spec), _stream()))
+        return (logits, spec) if want_spec else logits
+
     def set_mode(self, mode: int):
         check(self.lib.dmad_set_mode(self._h, int(mode)))
         self.mode = int(mode)
@@ -361,18 +838,19 @@ class Engine:
         self._set_margin(self.lib.dmad_set_spec_recheck_margin2, 'spec_recheck_margin2', 'floor_spec2', DEFAULT_SPEC_RECHECK_MARGIN2, tau2,
                          calibrated)
 
-    def spec_recheck_stats(self, reset: bool = False, detail: bool = False):
-        """-> (samples voted by spec_smooth_votes, samples whose chain left the 16-bit tier) since the last reset; detail: + the samples
-        that reached the exact-fp32 UNet."""
+    def _stats(self, fn, reset, detail):
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        check(self.lib.dmad_spec_recheck_stats2(self._h, C.byref(a), C.byref(b), C.byref(c), 1 if reset else 0))
+        check(fn(self._h, C.byref(a), C.byref(b), C.byref(c), 1 if reset else 0))
         return (int(a.value), int(b.value), int(c.value)) if detail else (int(a.value), int(b.value))
 
     def recheck_stats(self, reset: bool = False, detail: bool = False):
         """-> (samples voted, samples that left the 16-bit pass) since the last reset; detail: + samples that reached fp32."""
-        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        check(self.lib.dmad_recheck_stats(self._h, C.byref(a), C.byref(b), C.byref(c), 1 if reset else 0))
-        return (int(a.value), int(b.value), int(c.value)) if detail else (int(a.value), int(b.value))
+        return self._stats(self.lib.dmad_recheck_stats, reset, detail)
+
+    def spec_recheck_stats(self, reset: bool = False, detail: bool = False):
+        """-> (samples voted by spec_smooth_votes, samples whose chain left the 16-bit tier) since the last reset; detail: + the samples
+        that reached the exact-fp32 UNet."""
+        return self._stats(self.lib.dmad_spec_recheck_stats2, reset, detail)
 
     def _measure_tiers(self, what: str, clips: list, n: int, n_fp32: int, seed: int, tiers: list):
         """The measurement behind both loops' calibrations.  tiers = evaluators (clip, idx, seed) -> logits of the loop's first pass, its
@@ -406,6 +884,12 @@ class Engine:
             self.set_mode(mode)
         return e1, s1, e2
 
+    @staticmethod
+    def _widened(floor1: float, floor2: float, headroom: float, e1: float, s1: float, e2: float):
+        """the bound rule of both calibrations (calibrate_recheck's docstring): -> (first-pass bound, split-f16 tier's bound), widen-only"""
+        new2 = max(floor2, headroom * e2)
+        return max(floor1, headroom * e1 + new2, TAIL_Z * s1 + new2), new2
+
     def calibrate_recheck(self, clip, sigma: float, sqrt_abar_star: float, t: int, c_a: float, c_b: float,
                           n: int = 1024, n_fp32: int = 512, headroom: float = 1.5, seed: int = 0xCA11B):
         """Measure, for THE RESIDENT WEIGHTS, what the defaults were measured for on the synthetic VGG19_bn (see
@@ -430,29 +914,12 @@ class Engine:
             return lambda x, idx, sd: self.eval_samples(x, sigma, sqrt_abar_star, t, c_a, c_b, idx, path=p, seed=sd)
         e1, s1, e2 = self._measure_tiers('calibrate_recheck', clips, n, n_fp32, seed, [path(0), path(2), path(1)])
         floor1, floor2 = self.floor1, self.floor2         # the committed defaults, or a wider bound the caller put in force
-        new2 = max(floor2, headroom * e2)
-        new1 = max(floor1, headroom * e1 + new2, TAIL_Z * s1 + new2)
+        new1, new2 = self._widened(floor1, floor2, headroom, e1, s1, e2)
         self.set_recheck_margin(new1, calibrated=True); self.set_recheck_margin2(new2, calibrated=True)
         self.calibration = {'e1': e1, 'e2': e2, 's1': s1, 'tau1': new1, 'tau2': new2, 'n': n, 'n_fp32': n_fp32, 'clips': len(clips),
                             'headroom': headroom, 'floor1': floor1, 'floor2': floor2,
                             'previous': (tau1, tau2)}
         return new1, new2, e1, e2
-
-    def spec_eval_samples(self, clip: torch.Tensor, sigma: float, t_star: int, q_a: float, q_b: float, c_a, c_b, c_1, c_2, c_sig,
-                          mel_lo: float, mel_hi: float, idx: torch.Tensor, tier: int, seed: int = 0, want_spec: bool = False):
-        """dmad_spec_eval_samples: logits [len(idx), C] (and the purified dB spectrograms when asked) of the spec-domain chain for
-        the Monte Carlo samples with GLOBAL indices `idx` on UNet tier 0 (exact fp32) / 1 (16-bit) / 2 (split-f16).  Nothing votes."""
-        clip = clip.detach().reshape(-1).contiguous().float()
-        assert clip.is_cuda and clip.numel() == self.L
-        idx = idx.detach().to(device=clip.device, dtype=torch.int64).contiguous()
-        n = idx.numel()
-        logits = torch.empty((n, self.num_classes), device=clip.device)
-        spec = torch.empty((n, 1, 32, 32), device=clip.device) if want_spec else None
-        arrs = [(C.c_float * (t_star + 1))(*[float(v) for v in a]) for a in (c_a, c_b, c_1, c_2, c_sig)]
-        check(self.lib.dmad_spec_eval_samples(self._h, _ptr(clip), float(sigma), int(t_star), float(q_a), float(q_b), arrs[0], arrs[1], arrs[2],
-                                              arrs[3], arrs[4], float(mel_lo), float(mel_hi), int(seed), _ptr(idx), int(n), int(tier),
-                                              _ptr(logits), _ptr(spec), _stream()))
-        return (logits, spec) if want_spec else logits
 
     def calibrate_spec_recheck(self, clip, sigma: float, chain_args: tuple, n: int = 256, headroom: float = 1.5, seed: int = 0x5BECCA1,
                                n_fp32: Optional[int] = None):
@@ -471,542 +938,33 @@ class Engine:
             return lambda x, idx, sd: self.spec_eval_samples(x, sigma, *chain_args, idx, tier=k, seed=sd)
         e, s, e2 = self._measure_tiers('calibrate_spec_recheck', clips, n, n_fp32, seed, [tier(1), tier(2), tier(0)])
         previous, floor, floor2 = (self.spec_recheck_margin, self.spec_recheck_margin2), self.floor_spec, self.floor_spec2
-        new2 = max(floor2, headroom * e2)
-        new = max(floor, headroom * e + new2, TAIL_Z * s + new2)
+        new, new2 = self._widened(floor, floor2, headroom, e, s, e2)
         self.set_spec_recheck_margin(new, calibrated=True); self.set_spec_recheck_margin2(new2, calibrated=True)
         self.spec_calibration = {'e': e, 's': s, 'e2': e2, 'tau_spec': new, 'tau_spec2': new2, 'n': n, 'n_fp32': n_fp32, 'clips': len(clips),
                                  'headroom': headroom, 'floor': floor, 'floor2': floor2, 'previous': previous, 'sigma': sigma,
                                  't_star': int(chain_args[0])}
         return new, e, s
 
-    def eval_samples(self, clip: torch.Tensor, sigma: float, sqrt_abar_star: float, t: int, c_a: float, c_b: float,
-                     idx: torch.Tensor, path: int = 0, seed: int = 0, sample0: int = 0, delta: Optional[torch.Tensor] = None,
-                     want_x0: bool = False):
-        """dmad_eval_samples: logits [len(idx), C] (and x0 [len(idx), L] when asked) of the Monte Carlo samples with GLOBAL indices
-        `idx` (int64, device) on WaveNet path 0 (the mode's default) / 1 (exact fp32) / 2 (split-f16).  Nothing votes."""
-        clip = clip.detach().reshape(-1).contiguous().float()
-        assert clip.is_cuda and clip.numel() == self.L
-        idx = idx.detach().to(device=clip.device, dtype=torch.int64).contiguous()
-        n = idx.numel()
-        logits = torch.empty((n, self.num_classes), device=clip.device)
-        x0 = torch.empty((n, self.L), device=clip.device) if want_x0 else None
-        if delta is not None:
-            delta = delta.detach().reshape(-1, self.L).contiguous().float()
-            assert delta.is_cuda
-        check(self.lib.dmad_eval_samples(self._h, _ptr(clip), float(sigma), float(sqrt_abar_star), int(t), float(c_a), float(c_b),
-                                         int(seed), int(sample0), _ptr(delta), _ptr(idx), int(n), int(path), _ptr(logits), _ptr(x0),
-                                         _stream()))
-        return (logits, x0) if want_x0 else logits
-
     def debug_rounding(self, dil: int = 0, res: int = 0, skip: int = 0, f0: int = 0, init: int = 0):
         """dmad_debug_rounding (measurement hook): single roundings of the 16-bit path switched on inside the split-f16 tier."""
         m = (C.c_int32 * 5)(int(dil), int(res), int(skip), int(f0), int(init))
         check(self.lib.dmad_debug_rounding(self._h, m))
 
-    def wavenet_eps_path(self, x_t: torch.Tensor, t: int, path: int) -> torch.Tensor:
-        """eps-network on an explicit path of an EXACT engine: 0 mode default, 1 exact fp32, 2 split-f16 (three MFMAs per product)."""
-        x = self._wave(x_t)
-        out = torch.empty_like(x)
-        for s, e in self._chunks(x.shape[0]):
-            check(self.lib.dmad_wavenet_eps_path(self._h, _ptr(x[s:e]), int(t), e - s, int(path), _ptr(out[s:e]), _stream()))
-        return out
-
-    def reserve_vjp(self, max_batch: int):
-        """dmad_reserve_vjp: the workspace of wavenet_eps_vjp for up to max_batch clips per pass (capped at the engine's fp32 pass
-        size; a larger reservation replaces a smaller one).  FP32 / EXACT engines; DmadError otherwise."""
-        check(self.lib.dmad_reserve_vjp(self._h, int(max_batch)))
-        self.vjp_batch = max(self.vjp_batch, int(max_batch))
-
-    def wavenet_eps_vjp(self, x_t: torch.Tensor, t: int, g_eps: torch.Tensor, want_eps: bool = False):
-        """g_x = (d eps / d x_t)^T g_eps for eps = WaveNet((x_t, t * ones)) on the exact-fp32 path ([B,L] or [B,1,L] -> [B,L]).
-        want_eps: also return eps, bit-identical to wavenet_eps_path(x_t, t, 1).  Needs reserve_vjp first (DmadError otherwise)."""
-        x, g = self._wave(x_t), self._wave(g_eps)
-        if g.shape != x.shape:
-            raise DmadError('g_eps has shape %s, x_t %s' % (tuple(g.shape), tuple(x.shape)))
-        gx = torch.empty_like(x)
-        eps = torch.empty_like(x) if want_eps else None
-        for s, e in self._chunks(x.shape[0]):
-            check(self.lib.dmad_wavenet_eps_vjp(self._h, _ptr(x[s:e]), int(t), e - s, _ptr(g[s:e]), _ptr(gx[s:e]),
-                                                _ptr(None if eps is None else eps[s:e]), _stream()))
-        return (gx, eps) if want_eps else gx
-
-    def vpsde_purify(self, x0: torch.Tensor, c_a: float, c_b: float, k, h, hb, q, gs, z: Optional[torch.Tensor] = None, seed: int = 0,
-                     sample0: int = 0, path: int = 0, want_traj: bool = False):
-        """dmad_vpsde_purify: the reverse VP-SDE chain (diffusion to the start, then one Euler-Maruyama step per entry of k / h / hb /
-        q / gs), one library call per chunk of max_batch clips.  path 0: the mode's default WaveNet path, 1: exact fp32.  z: optional
-        explicit noise [S + 1, B, L] (slot 0 the diffusion draw, slot n + 1 step n); None = Philox keyed (seed, sample0 + row).
-        want_traj: also return the trajectory for vpsde_purify_vjp, a [(S + 1) * B, L] tensor stored chunk by chunk: rows
-        [(S + 1) * s, (S + 1) * e) hold the [S + 1][e - s][L] slots of the chunk [s, e)."""
-        return self._vpsde_chain(self.lib.dmad_vpsde_purify, self._wave, self.L, x0, c_a, c_b, k, h, hb, q, gs, z, seed, sample0, path, want_traj)
-
-    def vpsde_purify_vjp(self, traj: torch.Tensor, c_a: float, k, h, hb, q, g_out: torch.Tensor) -> torch.Tensor:
-        """dmad_vpsde_purify_vjp: g_x0 = (d out / d x0)^T g_out of the chain vpsde_purify(.., path=1, want_traj=True) ran, the draws held
-        fixed ([B, L] or [B, 1, L] -> [B, L]).  traj: that call's trajectory.  Needs reserve_vjp first (DmadError otherwise)."""
-        return self._vpsde_chain_vjp(self.lib.dmad_vpsde_purify_vjp, self._wave, self.L, 'L', 'vpsde_purify', traj, c_a, k, h, hb, q, g_out)
-
-    def _vpsde_chain(self, fn, shaper, width, x0, c_a, c_b, k, h, hb, q, gs, z, seed, sample0, path, want_traj):
-        """vpsde_purify / spec_vpsde_purify: the library's chain `fn` on rows of `width` floats that `shaper` (_wave / _spec) checks."""
-        x = shaper(x0)
-        B, S = x.shape[0], len(k)
-        out = torch.empty_like(x)
-        traj = torch.empty(((S + 1) * B, width), dtype=torch.float32, device=x.device) if want_traj else None
-        ka, ha, hba, qa, gsa = self._vpsde_arrays(k, h, hb, q, gs)
-        if z is not None:
-            z = z.detach()
-            if not z.is_cuda or tuple(z.shape) != (S + 1, B, width):
-                raise DmadError('z must be a CUDA tensor [%d, %d, %d], not %s' % (S + 1, B, width, tuple(z.shape)))
-            z = z.float()
-        for s, e in self._chunks(B):
-            zz = None if z is None else z[:, s:e].contiguous()
-            tr = None if traj is None else traj[(S + 1) * s:(S + 1) * e]
-            check(fn(self._h, _ptr(x[s:e]), e - s, S, float(c_a), float(c_b), ka, ha, hba, qa, gsa, _ptr(zz), int(seed), int(sample0) + s,
-                     int(path), _ptr(out[s:e]), _ptr(tr), _stream()))
-        return (out, traj) if want_traj else out
-
-    def _vpsde_chain_vjp(self, fn, shaper, width, width_name, forward_name, traj, c_a, k, h, hb, q, g_out):
-        """vpsde_purify_vjp / spec_vpsde_purify_vjp: the library's reverse walk `fn` over the chunk-by-chunk trajectory of `forward_name`."""
-        g = shaper(g_out)
-        B, S = g.shape[0], len(k)
-        if not traj.is_cuda or tuple(traj.shape) != ((S + 1) * B, width):
-            raise DmadError('traj must be the [(S + 1) * B, %s] = [%d, %d] trajectory of %s, not %s'
-                            % (width_name, (S + 1) * B, width, forward_name, tuple(traj.shape)))
-        gx = torch.empty_like(g)
-        ka, ha, hba, qa, _ = self._vpsde_arrays(k, h, hb, q, h)
-        for s, e in self._chunks(B):
-            check(fn(self._h, _ptr(traj[(S + 1) * s:(S + 1) * e]), e - s, S, float(c_a), ka, ha, hba, qa, _ptr(g[s:e]), _ptr(gx[s:e]), _stream()))
-        return gx
-
-    @staticmethod
-    def _vpsde_arrays(k, h, hb, q, gs):
-        S = len(k)
-        if not (len(h) == len(hb) == len(q) == len(gs) == S) or S < 1:
-            raise DmadError('the schedule arrays k / h / hb / q / gs must have one entry per Euler step (%d)' % S)
-        return ((C.c_int32 * S)(*[int(v) for v in k]),) + tuple((C.c_float * S)(*[float(v) for v in a]) for a in (h, hb, q, gs))
-
-    def load_unet(self, state_dict):
-        """improved_diffusion.unet.UNetModel state dict (synth.UNET_CONFIG geometry) -> engine, names prefixed 'un.'."""
-        if self.has_unet:
-            raise DmadError('UNet weights are already loaded into this engine')
-        self._load({'un.' + k: _as_np(v.detach().cpu().double().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64))
-                    for k, v in state_dict.items()})
-        self.has_unet = True
-        self.unet_owner = state_fingerprint(state_dict)
-
-    def load_resnext29(self, state_dict):
-        if self.has_classifier:
-            raise DmadError('classifier weights are already loaded into this engine')
-        self._load(fold_resnext29_state_dict(state_dict))
-        self.has_classifier = True
-        self.classifier_owner, self.classifier_kind = state_fingerprint(state_dict), 'resnext29'
-        if self.precision == EXACT:            # the committed bound for this classifier kind (widen-only, like a calibration)
-            self.floor1 = max(self.floor1, self._committed_margin1())
-            if self.recheck_margin < self.floor1:
-                self.set_recheck_margin(self.floor1, calibrated=True)
-
-    # ------------------------------------------------------------------ helpers
-    def _wave(self, x: torch.Tensor) -> torch.Tensor:
-        if not x.is_cuda:
-            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
-        x = x.detach()
-        if x.dim() == 3:
-            assert x.shape[1] == 1, 'expected [B,1,L]'
-            x = x[:, 0]
-        assert x.dim() == 2 and x.shape[1] == self.L, 'expected [B,%d], got %s' % (self.L, tuple(x.shape))
-        return x.contiguous().float()
-
-    def _chunks(self, B):
-        for s in range(0, B, self.max_batch):
-            yield s, min(B, s + self.max_batch)
-
-    # ------------------------------------------------------------------ hot path
-    def wavenet_eps(self, x_t: torch.Tensor, t: int) -> torch.Tensor:
-        x = self._wave(x_t)
-        out = torch.empty_like(x)
-        for s, e in self._chunks(x.shape[0]):
-            check(self.lib.dmad_wavenet_eps(self._h, _ptr(x[s:e]), int(t), e - s, _ptr(out[s:e]), _stream()))
-        return out
-
-    def one_shot(self, x_t: torch.Tensor, t: int, c_a: float, c_b: float) -> torch.Tensor:
-        x = self._wave(x_t)
-        out = torch.empty_like(x)
-        for s, e in self._chunks(x.shape[0]):
-            check(self.lib.dmad_one_shot(self._h, _ptr(x[s:e]), int(t), float(c_a), float(c_b), e - s, _ptr(out[s:e]), _stream()))
-        return out
-
-    def ddpm_step(self, x: torch.Tensor, t: int, c_eps: float, c_div: float, c_sig: float, z: Optional[torch.Tensor],
-                  seed: int = 0, sample0: int = 0):
-        """in place on x ([B, L] contiguous fp32 CUDA)."""
-        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
-        for s, e in self._chunks(x.shape[0]):
-            zz = None if z is None else self._wave(z)[s:e].contiguous()
-            check(self.lib.dmad_ddpm_step(self._h, _ptr(x[s:e]), int(t), float(c_eps), float(c_div), float(c_sig), _ptr(zz),
-                                          int(seed), int(sample0) + s, e - s, _stream()))
-        return x
-
-    def diffuse(self, x0: torch.Tensor, c_a: float, c_b: float, z: Optional[torch.Tensor], seed: int = 0, sample0: int = 0):
-        x = self._wave(x0)
-        out = torch.empty_like(x)
-        for s, e in self._chunks(x.shape[0]):
-            zz = None if z is None else self._wave(z)[s:e].contiguous()
-            check(self.lib.dmad_diffuse(self._h, _ptr(x[s:e]), float(c_a), float(c_b), _ptr(zz), int(seed), int(sample0) + s,
-                                        e - s, _ptr(out[s:e]), _stream()))
-        return out
-
-    def ddpm_purify(self, x0: torch.Tensor, t_star: int, c_a: float, c_b: float, c_eps, c_div, c_sig, seed: int = 0, sample0: int = 0):
-        """DiffWave.forward with device noise in one library call per chunk; c_eps / c_div / c_sig: t_star floats each."""
-        x = self._wave(x0)
-        out = torch.empty_like(x)
-        arrs = [(C.c_float * t_star)(*[float(v) for v in a]) for a in (c_eps, c_div, c_sig)]
-        for s, e in self._chunks(x.shape[0]):
-            check(self.lib.dmad_ddpm_purify(self._h, _ptr(x[s:e]), int(t_star), float(c_a), float(c_b), arrs[0], arrs[1], arrs[2],
-                                            int(seed), int(sample0) + s, e - s, _ptr(out[s:e]), _stream()))
-        return out
-
-    def _spec(self, x: torch.Tensor) -> torch.Tensor:
-        if not x.is_cuda:
-            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
-        x = x.detach()
-        if x.dim() == 4:
-            assert x.shape[1] == 1, 'expected [B,1,32,32]'
-            x = x[:, 0]
-        assert x.dim() == 3 and tuple(x.shape[1:]) == (32, 32), 'expected [B,32,32], got %s' % (tuple(x.shape),)
-        return x.contiguous().float()
-
-    def unet_eps(self, x_t: torch.Tensor, t: int, tier: Optional[int] = None) -> torch.Tensor:
-        """eps = UNetModel(x_t, t * ones): [B,1,32,32] or [B,32,32] -> [B,32,32].  tier: None = the mode's tier of the map-returning
-        surfaces (dmad_unet_eps); 0 exact fp32 / 1 16-bit / 2 split-f16 explicitly (dmad_unet_eps_tier)."""
-        x = self._spec(x_t)
-        out = torch.empty_like(x)
-        for s, e in self._chunks(x.shape[0]):
-            if tier is None:
-                check(self.lib.dmad_unet_eps(self._h, _ptr(x[s:e]), int(t), e - s, _ptr(out[s:e]), _stream()))
-            else:
-                check(self.lib.dmad_unet_eps_tier(self._h, _ptr(x[s:e]), int(t), e - s, int(tier), _ptr(out[s:e]), _stream()))
-        return out
-
-    def reserve_unet_vjp(self, max_batch: int):
-        """dmad_reserve_unet_vjp: the workspace of unet_eps_vjp (the forward's tape) for up to max_batch spectrograms per pass (capped at
-        the engine's fp32 pass size; a larger reservation replaces a smaller one).  FP32 / EXACT engines; DmadError otherwise."""
-        check(self.lib.dmad_reserve_unet_vjp(self._h, int(max_batch)))
-        self.unet_vjp_batch = max(self.unet_vjp_batch, int(max_batch))
-
-    def unet_eps_vjp(self, x_t: torch.Tensor, t: int, g_eps: torch.Tensor, want_eps: bool = False):
-        """g_x = (d eps / d x_t)^T g_eps for eps = UNetModel(x_t, t * ones) on the exact-fp32 tier ([B,1,32,32] or [B,32,32] -> [B,32,32]).
-        want_eps: also return eps, bit-identical to unet_eps(x_t, t, tier=0).  Needs reserve_unet_vjp first (DmadError otherwise)."""
-        x, g = self._spec(x_t), self._spec(g_eps)
-        if g.shape != x.shape:
-            raise DmadError('g_eps has shape %s, x_t %s' % (tuple(g.shape), tuple(x.shape)))
-        gx = torch.empty_like(x)
-        eps = torch.empty_like(x) if want_eps else None
-        for s, e in self._chunks(x.shape[0]):
-            check(self.lib.dmad_unet_eps_vjp(self._h, _ptr(x[s:e]), int(t), e - s, _ptr(g[s:e]), _ptr(gx[s:e]),
-                                             _ptr(None if eps is None else eps[s:e]), _stream()))
-        return (gx, eps) if want_eps else gx
-
-    def spec_vpsde_purify(self, x0: torch.Tensor, c_a: float, c_b: float, k, h, hb, q, gs, z: Optional[torch.Tensor] = None, seed: int = 0,
-                          sample0: int = 0, path: int = 0, want_traj: bool = False):
-        """dmad_spec_vpsde_purify: vpsde_purify's chain on standardised spectrograms with the UNet as the eps-network ([B,1,32,32] or
-        [B,32,32] -> [B,32,32]), one library call per chunk of max_batch.  path 0: the mode's UNet map tier (unet_eps(tier=None)), 1: exact
-        fp32.  z: optional explicit noise [S + 1, B, 1024]; None = Philox keyed (seed, sample0 + row).  want_traj: also return the
-        trajectory for spec_vpsde_purify_vjp, [(S + 1) * B, 1024] stored chunk by chunk as in vpsde_purify."""
-        return self._vpsde_chain(self.lib.dmad_spec_vpsde_purify, self._spec, 1024, x0, c_a, c_b, k, h, hb, q, gs, z, seed, sample0, path, want_traj)
-
-    def spec_vpsde_purify_vjp(self, traj: torch.Tensor, c_a: float, k, h, hb, q, g_out: torch.Tensor) -> torch.Tensor:
-        """dmad_spec_vpsde_purify_vjp: g_x0 = (d out / d x0)^T g_out of the chain spec_vpsde_purify(.., path=1, want_traj=True) ran, the
-        draws held fixed ([B,1,32,32] or [B,32,32] -> [B,32,32]).  traj: that call's trajectory.  Needs reserve_unet_vjp first."""
-        return self._vpsde_chain_vjp(self.lib.dmad_spec_vpsde_purify_vjp, self._spec, 1024, '1024', 'spec_vpsde_purify', traj, c_a, k, h, hb, q, g_out)
-
-    def unet_p_sample(self, x: torch.Tensor, t: int, c_a: float, c_b: float, c_1: float, c_2: float, c_sig: float,
-                      z: Optional[torch.Tensor] = None, seed: int = 0, sample0: int = 0, want_x0: bool = False):
-        """in place on x ([B,32,32] contiguous fp32 CUDA); returns pred_xstart when asked."""
-        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and tuple(x.shape[1:]) == (32, 32)
-        x0 = torch.empty_like(x) if want_x0 else None
-        for s, e in self._chunks(x.shape[0]):
-            zz = None if z is None else self._spec(z)[s:e].contiguous()
-            check(self.lib.dmad_unet_p_sample(self._h, _ptr(x[s:e]), int(t), float(c_a), float(c_b), float(c_1), float(c_2), float(c_sig),
-                                              _ptr(zz), int(seed), int(sample0) + s, e - s, _ptr(x0[s:e]) if want_x0 else None, _stream()))
-        return x0
-
-    def mel_db(self, x: torch.Tensor) -> torch.Tensor:
-        x = self._wave(x)
-        out = torch.empty((x.shape[0], 1, 32, 32), device=x.device, dtype=torch.float32)
-        for s, e in self._chunks(x.shape[0]):
-            check(self.lib.dmad_mel_db(self._h, _ptr(x[s:e]), e - s, _ptr(out[s:e]), _stream()))
-        return out
-
-    def mel_power(self, x: torch.Tensor) -> torch.Tensor:
-        x = self._wave(x)
-        out = torch.empty((x.shape[0], 1, 32, 32), device=x.device, dtype=torch.float32)
-        for s, e in self._chunks(x.shape[0]):
-            check(self.lib.dmad_mel_power(self._h, _ptr(x[s:e]), e - s, _ptr(out[s:e]), _stream()))
-        return out
-
-    def power_to_db(self, x: torch.Tensor) -> torch.Tensor:
-        if not x.is_cuda:
-            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
-        xc = x.detach().contiguous().float()
-        out = torch.empty_like(xc)
-        check(self.lib.dmad_power_to_db(self._h, _ptr(xc), xc.numel(), _ptr(out), _stream()))
-        return out
-
-    def classify(self, spec: torch.Tensor) -> torch.Tensor:
-        if not spec.is_cuda:
-            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
-        sp = spec.detach().reshape(spec.shape[0], 32 * 32).contiguous().float()
-        out = torch.empty((sp.shape[0], self.num_classes), device=sp.device, dtype=torch.float32)
-        for s, e in self._chunks(sp.shape[0]):
-            check(self.lib.dmad_classify(self._h, _ptr(sp[s:e]), e - s, _ptr(out[s:e]), _stream()))
-        return out
-
-    def classify_tier(self, spec: torch.Tensor, tier: int) -> torch.Tensor:
-        """dmad_classify_tier: the classifier on an explicit tier (0 fp32, 1 the 16-bit tier / 2 the split-f16 tier of ResNeXt29) — test / measurement hook."""
-        if not spec.is_cuda:
-            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
-        sp = spec.detach().reshape(spec.shape[0], 32 * 32).contiguous().float()
-        out = torch.empty((sp.shape[0], self.num_classes), device=sp.device, dtype=torch.float32)
-        for s, e in self._chunks(sp.shape[0]):
-            check(self.lib.dmad_classify_tier(self._h, _ptr(sp[s:e]), e - s, int(tier), _ptr(out[s:e]), _stream()))
-        return out
-
-    def reserve_classifier_vjp(self, max_batch: int):
-        """dmad_reserve_classifier_vjp: the workspace of classify_vjp (the ResNeXt29 forward's tape) for up to max_batch spectrograms per
-        pass (capped at max_batch; a larger reservation replaces a smaller one).  ResNeXt29 engines of every precision; DmadError otherwise."""
-        check(self.lib.dmad_reserve_classifier_vjp(self._h, int(max_batch)))
-        self.classifier_vjp_batch = max(self.classifier_vjp_batch, int(max_batch))
-
-    def classify_vjp(self, spec: torch.Tensor, g_logits: torch.Tensor, want_logits: bool = False):
-        """g_spec = (d logits / d spec)^T g_logits for logits = CifarResNeXt(spec) on the fp32 tier ([B,1,32,32] or [B,32,32] -> [B,32,32]).
-        want_logits: also return the logits, bit-identical to classify_tier(spec, 0).  Needs reserve_classifier_vjp first (DmadError
-        otherwise); ResNeXt29 engines only."""
-        sp = self._spec(spec)
-        B = sp.shape[0]
-        if not g_logits.is_cuda or tuple(g_logits.shape) != (B, self.num_classes):
-            raise DmadError('g_logits must be a CUDA tensor [%d, %d], not %s' % (B, self.num_classes, tuple(g_logits.shape)))
-        g = g_logits.detach().contiguous().float()
-        gs = torch.empty_like(sp)
-        lg = torch.empty((B, self.num_classes), device=sp.device, dtype=torch.float32) if want_logits else None
-        for s, e in self._chunks(B):
-            check(self.lib.dmad_classify_vjp(self._h, _ptr(sp[s:e]), e - s, _ptr(g[s:e]), _ptr(gs[s:e]),
-                                             _ptr(None if lg is None else lg[s:e]), _stream()))
-        return (gs, lg) if want_logits else gs
-
-    def reserve_vgg_vjp(self, max_batch: int):
-        """dmad_reserve_vgg_vjp: the workspace of vgg_vjp (the VGG19_bn forward's tape, the gradient maps and, once, the backward weight
-        images) for up to max_batch spectrograms per pass (capped at max_batch; a larger reservation replaces a smaller one).  VGG19_bn
-        engines of every precision; DmadError otherwise."""
-        check(self.lib.dmad_reserve_vgg_vjp(self._h, int(max_batch)))
-        self.vgg_vjp_batch = max(self.vgg_vjp_batch, min(int(max_batch), self.max_batch))
-
-    def vgg_vjp(self, spec: torch.Tensor, g_logits: torch.Tensor, want_logits: bool = False):
-        """g_spec = (d logits / d spec)^T g_logits for logits = VGG19_bn(spec) on the fp32 tier ([B,1,32,32] or [B,32,32] -> [B,32,32]).
-        want_logits: also return the logits, bit-identical to classify_tier(spec, 0).  Without a reservation the first call reserves
-        its own rows (capped at max_batch); a present reservation is kept and a larger call runs in passes of its size, with the same
-        bits (reserve_vgg_vjp chooses the pass size; autograd.VGGHIP grows it to the batch it meets).  VGG19_bn engines only."""
-        sp = self._spec(spec)
-        B = sp.shape[0]
-        if not g_logits.is_cuda or tuple(g_logits.shape) != (B, self.num_classes):
-            raise DmadError('g_logits must be a CUDA tensor [%d, %d], not %s' % (B, self.num_classes, tuple(g_logits.shape)))
-        if not self.vgg_vjp_batch:
-            self.reserve_vgg_vjp(B)
-        g = g_logits.detach().contiguous().float()
-        gs = torch.empty_like(sp)
-        lg = torch.empty((B, self.num_classes), device=sp.device, dtype=torch.float32) if want_logits else None
-        for s, e in self._chunks(B):
-            check(self.lib.dmad_vgg_vjp(self._h, _ptr(sp[s:e]), e - s, _ptr(g[s:e]), _ptr(gs[s:e]),
-                                        _ptr(None if lg is None else lg[s:e]), _stream()))
-        return (gs, lg) if want_logits else gs
-
-    def vgg_vjp_tape(self, index: int, B: int) -> torch.Tensor:
-        """dmad_vgg_vjp_tape: map `index` of the last vgg_vjp call's tape, rows [0, B) — 0 - 15 the post-ReLU conv maps [B,H,H,C] (NHWC),
-        16 - 17 the post-ReLU FC vectors [B,4096] (test hook; that call must have run as one pass)."""
-        if index < 16:
-            H, C = VGG_TAPE_MAPS[index]
-            out = torch.empty((int(B), H, H, C), device='cuda', dtype=torch.float32)
-        else:
-            out = torch.empty((int(B), 4096), device='cuda', dtype=torch.float32)
-        check(self.lib.dmad_vgg_vjp_tape(self._h, int(index), int(B), _ptr(out), _stream()))
-        return out
-
-    # ------------------------------------------------------------------ M5 (dmad_m5_*): waveform in, log-probabilities out
-    def _m5_width(self) -> int:
-        return self.m5_classes if self.has_m5 else 1        # before load_m5 the calls themselves refuse (DMAD_ERR_STATE)
-
-    def m5_logits(self, x: torch.Tensor, want_decisions: bool = False):
-        """dmad_m5_logits: x [B,1,L] or [B,L] -> log-probabilities [B, m5_classes] (and, want_decisions, their int32 arg-max).  One
-        launch whatever B is: M5 has no workspace that max_batch would size, and a clip's bits do not depend on the batch (a pass of
-        max_batch rows would leave most CUs idle: one workgroup per clip)."""
+    # ------------------------------------------------------------------ the query surfaces of the black-box attacks
+    def _query(self, fn, width, x, repeats, sampler, t_star, c_a, c_b, c_eps, c_div, c_sig, seed, sample0):
+        """query_logits / m5_query_logits: the export `fn`, whose logits are `width` wide"""
         xw = self._wave(x)
         B = xw.shape[0]
-        out = torch.empty((B, self._m5_width()), device=xw.device, dtype=torch.float32)
-        dec = torch.empty((B,), device=xw.device, dtype=torch.int32) if want_decisions else None
-        check(self.lib.dmad_m5_logits(self._h, _ptr(xw), B, _ptr(out), _ptr(dec), _stream()))
-        return (out, dec) if want_decisions else out
-
-    def m5_vjp(self, x: torch.Tensor, g: torch.Tensor, want_logits: bool = False):
-        """dmad_m5_vjp: g_x [B,L] = (d logp / d x)^T g for logp = M5(x), g [B, m5_classes].  want_logits: also the log-probabilities,
-        bit-identical to m5_logits(x).  The forward is recomputed inside the call; nothing is saved or reserved."""
-        xw = self._wave(x)
-        B = xw.shape[0]
-        if not g.is_cuda or (self.has_m5 and tuple(g.shape) != (B, self.m5_classes)):
-            raise DmadError('g must be a CUDA tensor [%d, %d], not %s' % (B, self.m5_classes, tuple(g.shape)))
-        gl = g.detach().contiguous().float()
-        gx = torch.empty((B, self.L), device=xw.device, dtype=torch.float32)
-        lp = torch.empty((B, self._m5_width()), device=xw.device, dtype=torch.float32) if want_logits else None
-        check(self.lib.dmad_m5_vjp(self._h, _ptr(xw), B, _ptr(gl), _ptr(gx), _ptr(lp), _stream()))
-        return (gx, lp) if want_logits else gx
-
-    def m5_tape(self, x: torch.Tensor, layer: int):
-        """dmad_m5_tape (test hook): block `layer` (1..4) -> (pooled post-ReLU map [B,C,T] float32, decisions [B,C,T] uint8 = arg | on << 2)
-        as the launch of m5_vjp produces them."""
-        xw = self._wave(x)
-        B = xw.shape[0]
-        if layer not in (1, 2, 3, 4):
-            raise DmadError('layer must be 1..4, not %r' % (layer,))
-        c, t = self.m5_maps[layer - 1] if self.has_m5 else (1, 1)       # before load_m5 the call itself refuses (DMAD_ERR_STATE)
-        pooled = torch.empty((B, c, t), device=xw.device, dtype=torch.float32)
-        dec = torch.empty((B, c, t), device=xw.device, dtype=torch.uint8)
-        check(self.lib.dmad_m5_tape(self._h, _ptr(xw), B, int(layer), _ptr(pooled), _ptr(dec), _stream()))
-        return pooled, dec
-
-    def m5_query_logits(self, x: torch.Tensor, repeats: int, sampler: int = 0, t_star: int = 0, c_a: float = 0.0, c_b: float = 0.0,
-                        c_eps=None, c_div=None, c_sig=None, seed: int = 0, sample0: int = 0):
-        """dmad_m5_query_logits: query_logits with M5 in the place of mel dB -> classifier; (log-probabilities [repeats*B, m5_classes],
-        decisions int32 [repeats*B]); row r*B+b is clip b."""
-        xw = self._wave(x)
-        B = xw.shape[0]
-        logits = torch.empty((repeats * B, self._m5_width()), device=xw.device, dtype=torch.float32)
-        dec = torch.empty((repeats * B,), device=xw.device, dtype=torch.int32)
-        arrs = [None, None, None]
-        if sampler == 1:
-            arrs = [(C.c_float * t_star)(*[float(v) for v in a]) for a in (c_eps, c_div, c_sig)]
-        check(self.lib.dmad_m5_query_logits(self._h, _ptr(xw), B, int(repeats), int(sampler), int(t_star), float(c_a), float(c_b),
-                                            arrs[0], arrs[1], arrs[2], int(seed), int(sample0), _ptr(logits), _ptr(dec), _stream()))
+        logits, dec = self._logits_pair(repeats * B, width, xw.device)
+        arrs = _floats(t_star, c_eps, c_div, c_sig) if sampler == 1 else [None, None, None]
+        check(fn(self._h, _ptr(xw), B, int(repeats), int(sampler), int(t_star), float(c_a), float(c_b), *arrs, int(seed), int(sample0),
+                 _ptr(logits), _ptr(dec), _stream()))
         return logits, dec
-
-    def m5_defense_query_logits(self, x: torch.Tensor, repeats: int, defense: dict):
-        """dmad_m5_defense_query_logits: defense_query_logits with M5 in the place of mel dB -> classifier (`defense` as there)."""
-        return self._defense_query(self.lib.dmad_m5_defense_query_logits, self._m5_width(), x, repeats, defense)
-
-    def mel_db_vjp(self, x: torch.Tensor, g_spec: torch.Tensor, want_spec: bool = False):
-        """g_x = (d melDB / d x)^T g_spec for the dB mel front-end of mel_db ([B,1,L] or [B,L] -> [B,L]; g_spec [B,1,32,32] or [B,32,32]).
-        want_spec: also return the spectrogram [B,1,32,32], bit-identical to mel_db(x).  The forward is recomputed; the first call
-        allocates the workspace."""
-        xw = self._wave(x)
-        g = self._spec(g_spec)
-        if g.shape[0] != xw.shape[0]:
-            raise DmadError('g_spec has %d rows, x %d' % (g.shape[0], xw.shape[0]))
-        gx = torch.empty_like(xw)
-        sp = torch.empty((xw.shape[0], 1, 32, 32), device=xw.device, dtype=torch.float32) if want_spec else None
-        for s, e in self._chunks(xw.shape[0]):
-            check(self.lib.dmad_mel_db_vjp(self._h, _ptr(xw[s:e]), e - s, _ptr(g[s:e]), _ptr(gx[s:e]),
-                                           _ptr(None if sp is None else sp[s:e]), _stream()))
-        return (gx, sp) if want_spec else gx
-
-    def masking_frames(self) -> int:
-        """frames of torch.stft(n_fft=2048, hop_length=512, center=False) on a clip of this engine"""
-        return (self.L - 2048) // 512 + 1
-
-    def _masking_args(self, B, theta, psd_scale):
-        F = self.masking_frames()
-        if not (theta.is_cuda and psd_scale.is_cuda):
-            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
-        if tuple(theta.shape) != (B, 1025, F) or psd_scale.numel() != B:
-            raise DmadError('theta must be [%d, 1025, %d] and psd_scale [%d], not %s and %s'
-                            % (B, F, B, tuple(theta.shape), tuple(psd_scale.shape)))
-        return theta.detach().contiguous().float(), psd_scale.detach().reshape(B).contiguous().float()
-
-    def masking_loss_vjp(self, delta: torch.Tensor, theta: torch.Tensor, psd_scale: torch.Tensor, want_psd: bool = False):
-        """dmad_masking_loss_vjp (DESIGN §20): the masking loss of the imperceptible attack and its gradient.  delta [B,1,L] or [B,L];
-        theta [B,1025,F]: the stabilised threshold 10^(threshold / 10); psd_scale [B]: 10^9.6 / psd_maximum_stabilized.  Returns
-        (g_delta [B,L], loss [B]) and, with want_psd, the normalised PSD estimate [B,1025,F]."""
-        dw = self._wave(delta)
-        B = dw.shape[0]
-        th, sc = self._masking_args(B, theta, psd_scale)
-        g = torch.empty_like(dw)
-        loss = torch.empty((B,), device=dw.device, dtype=torch.float32)
-        psd = torch.empty_like(th) if want_psd else None
-        for s, e in self._chunks(B):
-            check(self.lib.dmad_masking_loss_vjp(self._h, _ptr(dw[s:e]), e - s, _ptr(th[s:e]), _ptr(sc[s:e]), _ptr(g[s:e]), _ptr(loss[s:e]),
-                                                 _ptr(None if psd is None else psd[s:e]), _stream()))
-        return (g, loss, psd) if want_psd else (g, loss)
-
-    def masking_step(self, x: torch.Tensor, delta: torch.Tensor, g_net: torch.Tensor, alpha: torch.Tensor, signed_lr: float,
-                     theta: torch.Tensor, psd_scale: torch.Tensor) -> torch.Tensor:
-        """dmad_masking_step: one update of stage 2, delta <- clamp(x + delta + signed_lr (g_net + alpha g_theta), -1, 1) - x IN PLACE
-        (delta: a contiguous float32 CUDA tensor [B,1,L] or [B,L]; signed_lr = -lr targeted, +lr untargeted; alpha [B]).  Returns the
-        masking loss [B] of delta before the update."""
-        if not (delta.is_cuda and delta.dtype == torch.float32 and delta.is_contiguous()):
-            raise DmadError('delta is updated in place: it must be a contiguous float32 tensor on the GPU (the dmad engine has no CPU path)')
-        dw = self._wave(delta)
-        assert dw.data_ptr() == delta.data_ptr()
-        B = dw.shape[0]
-        xw, gn = self._wave(x), self._wave(g_net)
-        if xw.shape[0] != B or gn.shape[0] != B or alpha.numel() != B or not alpha.is_cuda:
-            raise DmadError('x, g_net and alpha must hold %d rows on the GPU' % B)
-        al = alpha.detach().reshape(B).contiguous().float()
-        th, sc = self._masking_args(B, theta, psd_scale)
-        loss = torch.empty((B,), device=dw.device, dtype=torch.float32)
-        for s, e in self._chunks(B):
-            check(self.lib.dmad_masking_step(self._h, _ptr(xw[s:e]), _ptr(dw[s:e]), _ptr(gn[s:e]), _ptr(al[s:e]), float(signed_lr), e - s,
-                                             _ptr(th[s:e]), _ptr(sc[s:e]), _ptr(loss[s:e]), _stream()))
-        return loss
-
-    def vote(self, logits: torch.Tensor, counts: torch.Tensor):
-        lg = logits.detach().contiguous().float()
-        assert lg.is_cuda and counts.is_cuda and counts.dtype == torch.int64 and lg.shape[1] == self.num_classes
-        check(self.lib.dmad_vote(self._h, _ptr(lg), lg.shape[0], _ptr(counts), _stream()))
-
-    def smooth_votes(self, clip: torch.Tensor, sigma: float, sqrt_abar_star: float, t: int, c_a: float, c_b: float,
-                     n: int, batch: Optional[int] = None, seed: int = 0, sample0: int = 0,
-                     delta: Optional[torch.Tensor] = None, want_logits: bool = False, want_x0: bool = False,
-                     counts: Optional[torch.Tensor] = None):
-        """The fused Monte Carlo loop (dmad_smooth_votes).  Returns (counts[int64, C] on device, logits|None, x0|None)."""
-        clip = clip.detach().reshape(-1).contiguous().float()
-        assert clip.is_cuda and clip.numel() == self.L
-        batch = min(batch or self.max_batch, self.max_batch)
-        if counts is None:
-            counts = torch.zeros(self.num_classes, dtype=torch.int64, device=clip.device)
-        logits = torch.empty((n, self.num_classes), device=clip.device) if want_logits else None
-        x0 = torch.empty((n, self.L), device=clip.device) if want_x0 else None
-        if delta is not None:
-            delta = delta.detach().reshape(n, self.L).contiguous().float()
-            assert delta.is_cuda
-        check(self.lib.dmad_smooth_votes(self._h, _ptr(clip), float(sigma), float(sqrt_abar_star), int(t), float(c_a), float(c_b),
-                                         int(n), int(batch), int(seed), int(sample0), _ptr(delta), _ptr(counts), _ptr(logits),
-                                         _ptr(x0), _stream()))
-        return counts, logits, x0
-
-    def spec_smooth_votes(self, clip: torch.Tensor, sigma: float, t_star: int, q_a: float, q_b: float, c_a, c_b, c_1, c_2, c_sig,
-                          mel_lo: float, mel_hi: float, n: int, batch: Optional[int] = None, seed: int = 0, sample0: int = 0,
-                          want_logits: bool = False, want_spec: bool = False, counts: Optional[torch.Tensor] = None):
-        """dmad_spec_smooth_votes (BASELINE C5): the vote loop with the spec-domain UNet purifier.  Coefficient sequences
-        c_*: t_star + 1 floats each (p_sample at t = 0..t_star).  Returns (counts, logits|None, purified spec|None)."""
-        clip = clip.detach().reshape(-1).contiguous().float()
-        assert clip.is_cuda and clip.numel() == self.L
-        batch = min(batch or self.max_batch, self.max_batch)
-        if counts is None:
-            counts = torch.zeros(self.num_classes, dtype=torch.int64, device=clip.device)
-        logits = torch.empty((n, self.num_classes), device=clip.device) if want_logits else None
-        spec = torch.empty((n, 1, 32, 32), device=clip.device) if want_spec else None
-        arrs = [(C.c_float * (t_star + 1))(*[float(v) for v in a]) for a in (c_a, c_b, c_1, c_2, c_sig)]
-        check(self.lib.dmad_spec_smooth_votes(self._h, _ptr(clip), float(sigma), int(t_star), float(q_a), float(q_b), arrs[0], arrs[1], arrs[2],
-                                              arrs[3], arrs[4], float(mel_lo), float(mel_hi), int(n), int(batch), int(seed), int(sample0),
-                                              _ptr(counts), _ptr(logits), _ptr(spec), _stream()))
-        return counts, logits, spec
 
     def query_logits(self, x: torch.Tensor, repeats: int, sampler: int = 0, t_star: int = 0, c_a: float = 0.0, c_b: float = 0.0,
                      c_eps=None, c_div=None, c_sig=None, seed: int = 0, sample0: int = 0):
         """dmad_query_logits: x [B,1,L] -> (logits [repeats*B, C], decisions int32 [repeats*B]); row r*B+b is clip b."""
-        xw = self._wave(x)
-        B = xw.shape[0]
-        logits = torch.empty((repeats * B, self.num_classes), device=xw.device, dtype=torch.float32)
-        dec = torch.empty((repeats * B,), device=xw.device, dtype=torch.int32)
-        arrs = [None, None, None]
-        if sampler == 1:
-            arrs = [(C.c_float * t_star)(*[float(v) for v in a]) for a in (c_eps, c_div, c_sig)]
-        check(self.lib.dmad_query_logits(self._h, _ptr(xw), B, int(repeats), int(sampler), int(t_star), float(c_a), float(c_b),
-                                         arrs[0], arrs[1], arrs[2], int(seed), int(sample0), _ptr(logits), _ptr(dec), _stream()))
-        return logits, dec
+        return self._query(self.lib.dmad_query_logits, self.num_classes, x, repeats, sampler, t_star, c_a, c_b, c_eps, c_div, c_sig, seed, sample0)
 
     def spec_query_logits(self, x: torch.Tensor, repeats: int, t_star: int, q_a: float, q_b: float, c_a, c_b, c_1, c_2, c_sig,
                           mel_lo: float, mel_hi: float, seed: int = 0, sample0: int = 0):
@@ -1014,14 +972,13 @@ class Engine:
         (mel dB -> standardise -> q_sample(t*) -> p_sample steps -> un-standardise -> classifier); row r*B+b is clip b."""
         xw = self._wave(x)
         B = xw.shape[0]
-        logits = torch.empty((repeats * B, self.num_classes), device=xw.device, dtype=torch.float32)
-        dec = torch.empty((repeats * B,), device=xw.device, dtype=torch.int32)
-        arrs = [(C.c_float * (t_star + 1))(*[float(v) for v in a]) for a in (c_a, c_b, c_1, c_2, c_sig)]
-        check(self.lib.dmad_spec_query_logits(self._h, _ptr(xw), B, int(repeats), int(t_star), float(q_a), float(q_b), arrs[0], arrs[1], arrs[2],
-                                              arrs[3], arrs[4], float(mel_lo), float(mel_hi), int(seed), int(sample0), _ptr(logits), _ptr(dec),
-                                              _stream()))
+        logits, dec = self._logits_pair(repeats * B, self.num_classes, xw.device)
+        check(self.lib.dmad_spec_query_logits(self._h, _ptr(xw), B, int(repeats), int(t_star), float(q_a), float(q_b),
+                                              *_floats(t_star + 1, c_a, c_b, c_1, c_2, c_sig), float(mel_lo), float(mel_hi), int(seed), int(sample0),
+                                              _ptr(logits), _ptr(dec), _stream()))
         return logits, dec
 
+    # ------------------------------------------------------------------ NES probes and the particle swarm (FAKEBOB, SirenAttack)
     def nes_probes(self, x: torch.Tensor, P: int, sigma: float, with_origin: bool, seed: int = 0, draw0: int = 0, row0: int = 0,
                    rows: Optional[int] = None) -> torch.Tensor:
         """dmad_nes_probes: x [B,1,L] -> query rows [row0, row0 + rows) of the NES layout, [rows, L] (clip-major, P + with_origin rows per
@@ -1039,9 +996,8 @@ class Engine:
     def nes_grad(self, w: torch.Tensor, P: int, scale: float, seed: int = 0, draw0: int = 0, grad: Optional[torch.Tensor] = None) -> torch.Tensor:
         """dmad_nes_grad: w [B, P] probe losses (+ probes first) -> scale * sum_j (w[b][j] - w[b][P/2 + j]) u_{b,j}, [B, L], the directions
         regenerated on the device.  With `grad` ([B, L] contiguous fp32 CUDA) the estimate is added to it in place."""
-        if not w.is_cuda:
-            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
-        w = w.detach().contiguous().float()
+        _on_gpu(w)
+        w = _f32(w)
         assert w.dim() == 2 and w.shape[1] == int(P), 'expected w [B,%d], got %s' % (int(P), tuple(w.shape))
         B = w.shape[0]
         accumulate = grad is not None
@@ -1052,130 +1008,11 @@ class Engine:
         check(self.lib.dmad_nes_grad(self._h, _ptr(w), B, int(P), float(scale), int(seed), int(draw0), int(accumulate), _ptr(grad), _stream()))
         return grad
 
-    # ------------------------------------------------------------------ baseline waveform defenses (dmad_wave_*)
-    @staticmethod
-    def _rows(x: torch.Tensor, width: int, name: str = 'x') -> torch.Tensor:
-        if not x.is_cuda:
-            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
-        x = x.detach()
-        if x.dim() != 2 or x.shape[1] != width:
-            raise DmadError('%s must be [B, %d], not %s' % (name, width, tuple(x.shape)))
-        return x.contiguous().float()
-
-    @staticmethod
-    def _host_f32(a, n: Optional[int] = None):
-        a = np.ascontiguousarray(_as_np(a), dtype=np.float32).reshape(-1)
-        if n is not None and a.size != n:
-            raise DmadError('expected %d coefficients, got %d' % (n, a.size))
-        return a, a.ctypes.data_as(C.POINTER(C.c_float))
-
-    def wave_smooth(self, x: torch.Tensor, kind: int, window: int) -> torch.Tensor:
-        """dmad_wave_smooth: x [B,L] or [B,1,L] -> [B,L]; kind 0 the zero-padded windowed mean (AS), 1 the median (MS)."""
-        xw = self._wave(x)
-        y = torch.empty_like(xw)
-        for s, e in self._chunks(xw.shape[0]):
-            check(self.lib.dmad_wave_smooth(self._h, _ptr(xw[s:e]), e - s, int(kind), int(window), _ptr(y[s:e]), _stream()))
-        return y
-
-    def wave_smooth_vjp(self, x: torch.Tensor, g_y: torch.Tensor, kind: int, window: int) -> torch.Tensor:
-        """dmad_wave_smooth_vjp: g_x [B,L] of wave_smooth at x for the output gradient g_y (the median routes by the lowest-position rule)."""
-        xw, g = self._wave(x), self._wave(g_y)
-        if g.shape[0] != xw.shape[0]:
-            raise DmadError('g_y has %d rows, x %d' % (g.shape[0], xw.shape[0]))
-        gx = torch.empty_like(xw)
-        for s, e in self._chunks(xw.shape[0]):
-            check(self.lib.dmad_wave_smooth_vjp(self._h, _ptr(xw[s:e]), _ptr(g[s:e]), e - s, int(kind), int(window), _ptr(gx[s:e]), _stream()))
-        return gx
-
-    def wave_resample(self, x: torch.Tensor, ker, stride: int, width: int, L_out: int) -> torch.Tensor:
-        """dmad_wave_resample: x [B, L_in] -> [B, L_out] through the polyphase FIR `ker` (host [phases, taps])."""
-        k = np.ascontiguousarray(_as_np(ker), dtype=np.float32)
-        phases, taps = (1, k.shape[0]) if k.ndim == 1 else k.shape
-        xw = self._rows(x, x.shape[-1])
-        _, kp = self._host_f32(k)
-        y = torch.empty((xw.shape[0], int(L_out)), device=xw.device, dtype=torch.float32)
-        for s, e in self._chunks(xw.shape[0]):
-            check(self.lib.dmad_wave_resample(self._h, _ptr(xw[s:e]), e - s, xw.shape[1], kp, int(phases), int(taps), int(stride), int(width),
-                                              int(L_out), _ptr(y[s:e]), _stream()))
-        return y
-
-    def wave_resample_vjp(self, g_y: torch.Tensor, L_in: int, ker, stride: int, width: int) -> torch.Tensor:
-        """dmad_wave_resample_vjp: the transposed operator, g_y [B, L_out] -> g_x [B, L_in]."""
-        k = np.ascontiguousarray(_as_np(ker), dtype=np.float32)
-        phases, taps = (1, k.shape[0]) if k.ndim == 1 else k.shape
-        g = self._rows(g_y, g_y.shape[-1], 'g_y')
-        _, kp = self._host_f32(k)
-        gx = torch.empty((g.shape[0], int(L_in)), device=g.device, dtype=torch.float32)
-        for s, e in self._chunks(g.shape[0]):
-            check(self.lib.dmad_wave_resample_vjp(self._h, _ptr(g[s:e]), e - s, int(L_in), kp, int(phases), int(taps), int(stride), int(width),
-                                                  g.shape[1], _ptr(gx[s:e]), _stream()))
-        return gx
-
-    def wave_iir(self, x: torch.Tensor, b, a, lo: float = -float('inf'), hi: float = float('inf')) -> torch.Tensor:
-        """dmad_wave_iir: clamp(lfilter(b, a, x), lo, hi) on [B,L] rows; b, a host arrays of order + 1 <= 9 coefficients."""
-        xw = self._wave(x)
-        bb, bp = self._host_f32(b)
-        _, ap = self._host_f32(a, bb.size)
-        y = torch.empty_like(xw)
-        for s, e in self._chunks(xw.shape[0]):
-            check(self.lib.dmad_wave_iir(self._h, _ptr(xw[s:e]), e - s, bp, ap, bb.size - 1, float(lo), float(hi), _ptr(y[s:e]), _stream()))
-        return y
-
-    def wave_iir_vjp(self, x: torch.Tensor, g_y: torch.Tensor, b, a, lo: float = -float('inf'), hi: float = float('inf'),
-                     want_y: bool = False):
-        """dmad_wave_iir_vjp: g_x = flip(lfilter(b, a, flip(g_y * m))), m the in-range mask of the recomputed unclamped forward.
-        want_y: also return the clamped forward, bit-identical to wave_iir."""
-        xw, g = self._wave(x), self._wave(g_y)
-        if g.shape[0] != xw.shape[0]:
-            raise DmadError('g_y has %d rows, x %d' % (g.shape[0], xw.shape[0]))
-        bb, bp = self._host_f32(b)
-        _, ap = self._host_f32(a, bb.size)
-        gx = torch.empty_like(xw)
-        y = torch.empty_like(xw) if want_y else None
-        for s, e in self._chunks(xw.shape[0]):
-            check(self.lib.dmad_wave_iir_vjp(self._h, _ptr(xw[s:e]), _ptr(g[s:e]), e - s, bp, ap, bb.size - 1, float(lo), float(hi),
-                                             _ptr(gx[s:e]), _ptr(None if y is None else y[s:e]), _stream()))
-        return (gx, y) if want_y else gx
-
-    def defense_query_logits(self, x: torch.Tensor, repeats: int, defense: dict):
-        """dmad_defense_query_logits: x [B,1,L] -> (logits [repeats*B, C], decisions int32 [repeats*B]); row r*B+b is clip b through
-        defense -> mel dB -> classifier.  `defense`: dict(kind='AS'|'MS', window=w) | dict(kind='DS', down=(ker, stride, width, L_out),
-        up=(ker, stride, width)) | dict(kind='IIR', b=, a=, lo=, hi=)."""
-        return self._defense_query(self.lib.dmad_defense_query_logits, self.num_classes, x, repeats, defense)
-
-    def _defense_query(self, fn, width: int, x: torch.Tensor, repeats: int, defense: dict):
-        from ._lib import DmadWaveDefense
-        xw = self._wave(x)
-        B = xw.shape[0]
-        kind = defense['kind']
-        d = DmadWaveDefense(kind={'AS': 0, 'MS': 1, 'DS': 2, 'IIR': 3}[kind])
-        keep = []                                   # the host arrays the struct points to
-        if kind in ('AS', 'MS'):
-            d.window = int(defense['window'])
-        elif kind == 'DS':
-            (dk, ds, dw, dl), (uk, us, uw) = defense['down'], defense['up']
-            dk, uk = (np.atleast_2d(np.ascontiguousarray(_as_np(k), dtype=np.float32)) for k in (dk, uk))
-            keep += [dk, uk]
-            d.down_ker, d.up_ker = (k.ctypes.data_as(C.POINTER(C.c_float)) for k in (dk, uk))
-            d.down_phases, d.down_taps, d.down_stride, d.down_width, d.down_len = dk.shape[0], dk.shape[1], int(ds), int(dw), int(dl)
-            d.up_phases, d.up_taps, d.up_stride, d.up_width = uk.shape[0], uk.shape[1], int(us), int(uw)
-        else:
-            bb, bp = self._host_f32(defense['b'])
-            aa, ap = self._host_f32(defense['a'], bb.size)
-            keep += [bb, aa]
-            d.b, d.a, d.order, d.lo, d.hi = bp, ap, bb.size - 1, float(defense['lo']), float(defense['hi'])
-        logits = torch.empty((repeats * B, width), device=xw.device, dtype=torch.float32)
-        dec = torch.empty((repeats * B,), device=xw.device, dtype=torch.int32)
-        check(fn(self._h, _ptr(xw), B, int(repeats), C.byref(d), _ptr(logits), _ptr(dec), _stream()))
-        del keep
-        return logits, dec
-
     def _owned(self, t: Optional[torch.Tensor], shape, dtype=torch.float32, name='state') -> torch.Tensor:
         """A caller-owned tensor a swarm call updates in place: checked, never copied; None -> a new one."""
         if t is None:
             return torch.empty(shape, device=self.device, dtype=dtype)
-        if not t.is_cuda:
-            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
+        _on_gpu(t)
         assert t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == tuple(shape), \
             '%s: expected contiguous %s %s, got %s %s' % (name, dtype, tuple(shape), t.dtype, tuple(t.shape))
         return t
@@ -1220,11 +1057,10 @@ class Engine:
         loc; then the first arg-min k of pbests[b] replaces the global best of row i = index[b] (b without index) of gbests [N],
         gbest_loc [N,L] / [N,1,L], gbest_predict int64 [N] where pbests[b][k] < gbests[i].  The five best tensors are updated in place and
         returned."""
-        if not loss.is_cuda:
-            raise DmadError('input must live on the GPU (the dmad engine has no CPU path)')
+        _on_gpu(loss)
         assert loss.dim() == 2, 'expected loss [B,P], got %s' % (tuple(loss.shape),)
         B, P = loss.shape
-        loss = self._owned(loss.detach().contiguous().float(), (B, P), name='loss')
+        loss = self._owned(_f32(loss), (B, P), name='loss')
         predict = self._owned(predict.contiguous(), (B, P), torch.int64, 'predict')
         loc, pbest_loc = self._owned(loc, (B * P, self.L), name='loc'), self._owned(pbest_loc, (B * P, self.L), name='pbest_loc')
         pbests = self._owned(pbests, (B, P), name='pbests')
@@ -1241,20 +1077,175 @@ class Engine:
                                             _ptr(gbests), _ptr(gbest_loc), _ptr(gbest_predict), _stream()))
         return pbests, pbest_loc, gbests, gbest_loc, gbest_predict
 
+    # ------------------------------------------------------------------ baseline waveform defenses (dmad_wave_*)
+    @staticmethod
+    def _host_f32(a, n: Optional[int] = None):
+        a = np.ascontiguousarray(_as_np(a), dtype=np.float32).reshape(-1)
+        if n is not None and a.size != n:
+            raise DmadError('expected %d coefficients, got %d' % (n, a.size))
+        return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+    @staticmethod
+    def _fir(ker):
+        """a polyphase FIR on the host -> (the array its pointer needs alive, pointer, phases, taps)"""
+        k = np.ascontiguousarray(_as_np(ker), dtype=np.float32)
+        phases, taps = (1, k.shape[0]) if k.ndim == 1 else k.shape
+        return Engine._host_f32(k) + (int(phases), int(taps))
+
+    def _iir(self, b, a):
+        """the coefficients of an IIR filter -> (b, a on the host, their pointers, the order)"""
+        bb, bp = self._host_f32(b)
+        aa, ap = self._host_f32(a, bb.size)
+        return bb, aa, bp, ap, bb.size - 1
+
+    def wave_smooth(self, x: torch.Tensor, kind: int, window: int) -> torch.Tensor:
+        """dmad_wave_smooth: x [B,L] or [B,1,L] -> [B,L]; kind 0 the zero-padded windowed mean (AS), 1 the median (MS)."""
+        return self._mapped(self.lib.dmad_wave_smooth, self._wave(x), _N, int(kind), int(window))
+
+    def wave_smooth_vjp(self, x: torch.Tensor, g_y: torch.Tensor, kind: int, window: int) -> torch.Tensor:
+        """dmad_wave_smooth_vjp: g_x [B,L] of wave_smooth at x for the output gradient g_y (the median routes by the lowest-position rule)."""
+        xw, g = self._wave(x), self._wave(g_y)
+        if g.shape[0] != xw.shape[0]:
+            raise DmadError('g_y has %d rows, x %d' % (g.shape[0], xw.shape[0]))
+        gx = torch.empty_like(xw)
+        self._passes(self.lib.dmad_wave_smooth_vjp, xw.shape[0], _per(xw), _per(g), _N, int(kind), int(window), _per(gx))
+        return gx
+
+    def wave_resample(self, x: torch.Tensor, ker, stride: int, width: int, L_out: int) -> torch.Tensor:
+        """dmad_wave_resample: x [B, L_in] -> [B, L_out] through the polyphase FIR `ker` (host [phases, taps])."""
+        _, kp, phases, taps = self._fir(ker)
+        xw = self._rows(x, x.shape[-1])
+        y = torch.empty((xw.shape[0], int(L_out)), device=xw.device, dtype=torch.float32)
+        self._passes(self.lib.dmad_wave_resample, xw.shape[0], _per(xw), _N, xw.shape[1], kp, phases, taps, int(stride), int(width), int(L_out),
+                     _per(y))
+        return y
+
+    def wave_resample_vjp(self, g_y: torch.Tensor, L_in: int, ker, stride: int, width: int) -> torch.Tensor:
+        """dmad_wave_resample_vjp: the transposed operator, g_y [B, L_out] -> g_x [B, L_in]."""
+        _, kp, phases, taps = self._fir(ker)
+        g = self._rows(g_y, g_y.shape[-1], 'g_y')
+        gx = torch.empty((g.shape[0], int(L_in)), device=g.device, dtype=torch.float32)
+        self._passes(self.lib.dmad_wave_resample_vjp, g.shape[0], _per(g), _N, int(L_in), kp, phases, taps, int(stride), int(width), g.shape[1],
+                     _per(gx))
+        return gx
+
+    def wave_iir(self, x: torch.Tensor, b, a, lo: float = -float('inf'), hi: float = float('inf')) -> torch.Tensor:
+        """dmad_wave_iir: clamp(lfilter(b, a, x), lo, hi) on [B,L] rows; b, a host arrays of order + 1 <= 9 coefficients."""
+        xw = self._wave(x)
+        _, _, bp, ap, order = self._iir(b, a)
+        return self._mapped(self.lib.dmad_wave_iir, xw, _N, bp, ap, order, float(lo), float(hi))
+
+    def wave_iir_vjp(self, x: torch.Tensor, g_y: torch.Tensor, b, a, lo: float = -float('inf'), hi: float = float('inf'),
+                     want_y: bool = False):
+        """dmad_wave_iir_vjp: g_x = flip(lfilter(b, a, flip(g_y * m))), m the in-range mask of the recomputed unclamped forward.
+        want_y: also return the clamped forward, bit-identical to wave_iir."""
+        xw, g = self._wave(x), self._wave(g_y)
+        if g.shape[0] != xw.shape[0]:
+            raise DmadError('g_y has %d rows, x %d' % (g.shape[0], xw.shape[0]))
+        _, _, bp, ap, order = self._iir(b, a)
+        gx = torch.empty_like(xw)
+        y = torch.empty_like(xw) if want_y else None
+        self._passes(self.lib.dmad_wave_iir_vjp, xw.shape[0], _per(xw), _per(g), _N, bp, ap, order, float(lo), float(hi), _per(gx), _per(y))
+        return (gx, y) if want_y else gx
+
+    def defense_query_logits(self, x: torch.Tensor, repeats: int, defense: dict):
+        """dmad_defense_query_logits: x [B,1,L] -> (logits [repeats*B, C], decisions int32 [repeats*B]); row r*B+b is clip b through
+        defense -> mel dB -> classifier.  `defense`: dict(kind='AS'|'MS', window=w) | dict(kind='DS', down=(ker, stride, width, L_out),
+        up=(ker, stride, width)) | dict(kind='IIR', b=, a=, lo=, hi=)."""
+        return self._defense_query(self.lib.dmad_defense_query_logits, self.num_classes, x, repeats, defense)
+
+    def _defense_query(self, fn, width: int, x: torch.Tensor, repeats: int, defense: dict):
+        from ._lib import DmadWaveDefense
+        xw = self._wave(x)
+        B = xw.shape[0]
+        kind = defense['kind']
+        d = DmadWaveDefense(kind={'AS': 0, 'MS': 1, 'DS': 2, 'IIR': 3}[kind])
+        keep = []                                   # the host arrays the struct points to
+        if kind in ('AS', 'MS'):
+            d.window = int(defense['window'])
+        elif kind == 'DS':
+            (dk, ds, dw, dl), (uk, us, uw) = defense['down'], defense['up']
+            dk, uk = (np.atleast_2d(np.ascontiguousarray(_as_np(k), dtype=np.float32)) for k in (dk, uk))
+            keep += [dk, uk]
+            d.down_ker, d.up_ker = (k.ctypes.data_as(C.POINTER(C.c_float)) for k in (dk, uk))
+            d.down_phases, d.down_taps, d.down_stride, d.down_width, d.down_len = dk.shape[0], dk.shape[1], int(ds), int(dw), int(dl)
+            d.up_phases, d.up_taps, d.up_stride, d.up_width = uk.shape[0], uk.shape[1], int(us), int(uw)
+        else:
+            bb, aa, d.b, d.a, d.order = self._iir(defense['b'], defense['a'])
+            keep += [bb, aa]
+            d.lo, d.hi = float(defense['lo']), float(defense['hi'])
+        logits, dec = self._logits_pair(repeats * B, width, xw.device)
+        check(fn(self._h, _ptr(xw), B, int(repeats), C.byref(d), _ptr(logits), _ptr(dec), _stream()))
+        del keep
+        return logits, dec
+
+    # ------------------------------------------------------------------ M5 (dmad_m5_*): waveform in, log-probabilities out
+    def _m5_width(self) -> int:
+        return self.m5_classes if self.has_m5 else 1        # before load_m5 the calls themselves refuse (DMAD_ERR_STATE)
+
+    def m5_logits(self, x: torch.Tensor, want_decisions: bool = False):
+        """dmad_m5_logits: x [B,1,L] or [B,L] -> log-probabilities [B, m5_classes] (and, want_decisions, their int32 arg-max).  One
+        launch whatever B is: M5 has no workspace that max_batch would size, and a clip's bits do not depend on the batch (a pass of
+        max_batch rows would leave most CUs idle: one workgroup per clip)."""
+        xw = self._wave(x)
+        B = xw.shape[0]
+        out = torch.empty((B, self._m5_width()), device=xw.device, dtype=torch.float32)
+        dec = torch.empty((B,), device=xw.device, dtype=torch.int32) if want_decisions else None
+        check(self.lib.dmad_m5_logits(self._h, _ptr(xw), B, _ptr(out), _ptr(dec), _stream()))
+        return (out, dec) if want_decisions else out
+
+    def m5_vjp(self, x: torch.Tensor, g: torch.Tensor, want_logits: bool = False):
+        """dmad_m5_vjp: g_x [B,L] = (d logp / d x)^T g for logp = M5(x), g [B, m5_classes].  want_logits: also the log-probabilities,
+        bit-identical to m5_logits(x).  The forward is recomputed inside the call; nothing is saved or reserved."""
+        xw = self._wave(x)
+        B = xw.shape[0]
+        if not g.is_cuda or (self.has_m5 and tuple(g.shape) != (B, self.m5_classes)):
+            raise DmadError('g must be a CUDA tensor [%d, %d], not %s' % (B, self.m5_classes, tuple(g.shape)))
+        gl = _f32(g)
+        gx = torch.empty((B, self.L), device=xw.device, dtype=torch.float32)
+        lp = torch.empty((B, self._m5_width()), device=xw.device, dtype=torch.float32) if want_logits else None
+        check(self.lib.dmad_m5_vjp(self._h, _ptr(xw), B, _ptr(gl), _ptr(gx), _ptr(lp), _stream()))
+        return (gx, lp) if want_logits else gx
+
+    def m5_tape(self, x: torch.Tensor, layer: int):
+        """dmad_m5_tape (test hook): block `layer` (1..4) -> (pooled post-ReLU map [B,C,T] float32, decisions [B,C,T] uint8 = arg | on << 2)
+        as the launch of m5_vjp produces them."""
+        xw = self._wave(x)
+        B = xw.shape[0]
+        if layer not in (1, 2, 3, 4):
+            raise DmadError('layer must be 1..4, not %r' % (layer,))
+        c, t = self.m5_maps[layer - 1] if self.has_m5 else (1, 1)       # before load_m5 the call itself refuses (DMAD_ERR_STATE)
+        pooled = torch.empty((B, c, t), device=xw.device, dtype=torch.float32)
+        dec = torch.empty((B, c, t), device=xw.device, dtype=torch.uint8)
+        check(self.lib.dmad_m5_tape(self._h, _ptr(xw), B, int(layer), _ptr(pooled), _ptr(dec), _stream()))
+        return pooled, dec
+
+    def m5_query_logits(self, x: torch.Tensor, repeats: int, sampler: int = 0, t_star: int = 0, c_a: float = 0.0, c_b: float = 0.0,
+                        c_eps=None, c_div=None, c_sig=None, seed: int = 0, sample0: int = 0):
+        """dmad_m5_query_logits: query_logits with M5 in the place of mel dB -> classifier; (log-probabilities [repeats*B, m5_classes],
+        decisions int32 [repeats*B]); row r*B+b is clip b."""
+        return self._query(self.lib.dmad_m5_query_logits, self._m5_width(), x, repeats, sampler, t_star, c_a, c_b, c_eps, c_div, c_sig, seed, sample0)
+
+    def m5_defense_query_logits(self, x: torch.Tensor, repeats: int, defense: dict):
+        """dmad_m5_defense_query_logits: defense_query_logits with M5 in the place of mel dB -> classifier (`defense` as there)."""
+        return self._defense_query(self.lib.dmad_m5_defense_query_logits, self._m5_width(), x, repeats, defense)
+
+    # ------------------------------------------------------------------ Philox draws, timing and profiling hooks
+    def _philox(self, fn, seed, sample0, stream, B):
+        out = torch.empty((B, self.L), dtype=torch.float32, device=self.device)
+        check(fn(self._h, int(seed), int(sample0), int(stream), int(B), _ptr(out), _stream()))
+        return out
+
     def philox_uniform(self, seed: int, sample0: int, stream: int, B: int) -> torch.Tensor:
         """dmad_philox_uniform: [B, L], row b the uniforms ((word >> 8) + 0.5) * 2^-24 of key (seed, sample0 + b, stream)."""
-        out = torch.empty((B, self.L), dtype=torch.float32, device=self.device)
-        check(self.lib.dmad_philox_uniform(self._h, int(seed), int(sample0), int(stream), int(B), _ptr(out), _stream()))
-        return out
+        return self._philox(self.lib.dmad_philox_uniform, seed, sample0, stream, B)
+
+    def philox_normal(self, seed: int, sample0: int, stream: int, B: int) -> torch.Tensor:
+        return self._philox(self.lib.dmad_philox_normal, seed, sample0, stream, B)
 
     def philox_raw(self, seed: int, sample: int, stream: int, nblocks: int) -> torch.Tensor:
         out = torch.empty(nblocks * 4, dtype=torch.int32, device=self.device)
         check(self.lib.dmad_philox_raw(self._h, int(seed), int(sample), int(stream), int(nblocks), _ptr(out), _stream()))
-        return out
-
-    def philox_normal(self, seed: int, sample0: int, stream: int, B: int) -> torch.Tensor:
-        out = torch.empty((B, self.L), dtype=torch.float32, device=self.device)
-        check(self.lib.dmad_philox_normal(self._h, int(seed), int(sample0), int(stream), int(B), _ptr(out), _stream()))
         return out
 
     def time_layer(self, layer: int, B: int, iters: int) -> float:
@@ -1265,20 +1256,27 @@ class Engine:
     def profile_layers(self, max_launches: int):
         check(self.lib.dmad_profile_layers(self._h, int(max_launches)))
 
+    def _profile(self, fn):
+        ms, n = C.c_float(0), C.c_int32(0)
+        check(fn(self._h, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
     def profile_read(self):
         """-> (summed ms, launches) of the bracketed wn_layer_bf16 launches."""
-        ms, n = C.c_float(0), C.c_int32(0)
-        check(self.lib.dmad_profile_read(self._h, C.byref(ms), C.byref(n)))
-        return float(ms.value), int(n.value)
+        return self._profile(self.lib.dmad_profile_read)
 
     def profile_read_final(self):
         """-> (summed ms, launches) of the bracketed wn_final launches; call before profile_read()."""
-        ms, n = C.c_float(0), C.c_int32(0)
-        check(self.lib.dmad_profile_read_final(self._h, C.byref(ms), C.byref(n)))
-        return float(ms.value), int(n.value)
+        return self._profile(self.lib.dmad_profile_read_final)
 
     def device_bytes(self) -> int:
         return int(self.lib.dmad_device_bytes(self._h))
+
+
+# ---------------------------------------------------------------------- standalone op hooks (no engine: test / measurement)
+def _op(export: str, *args):
+    """one call of an engine-less export on the current stream"""
+    check(getattr(_lib.load(), export)(*args, _stream()))
 
 
 def conv_h16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1, groups: int = 1, relu: bool = False,
@@ -1286,7 +1284,6 @@ def conv_h16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = No
     """dmad_conv_h16 — the f16 conv-GEMM family as a standalone op (test hook).  x: f16 NHWC [B,H,H,Cx] (CUDA), x2: optional second
     map [B,H,H,C2] whose channels follow x's (dense convs only); w: f16 [groups, taps, M, K] (taps 9 or 1, K per group = (Cx + C2) /
     groups); bias fp32 [groups*M]; res: optional f16 [B,Ho,Ho,groups*M].  Returns (out32 | None, out16 | None), NHWC."""
-    lib = _lib.load()
     assert x.is_cuda and x.dtype == torch.float16 and w.is_cuda and w.dtype == torch.float16 and x.dim() == 4 and w.dim() == 4
     x, w = x.contiguous(), w.contiguous()
     B, H, W_, cx = x.shape
@@ -1304,13 +1301,11 @@ def conv_h16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = No
     Ho = (H - 1) // stride + 1
     out32 = torch.empty((B, Ho, Ho, groups * M), device=x.device, dtype=torch.float32) if want32 else None
     out16 = torch.empty((B, Ho, Ho, groups * M), device=x.device, dtype=torch.float16) if want16 else None
-    if bias is not None:
-        bias = bias.detach().contiguous().float()
     if res is not None:
         assert res.dtype == torch.float16 and tuple(res.shape) == (B, Ho, Ho, groups * M)
         res = res.contiguous()
-    check(lib.dmad_conv_h16(_ptr(x), _ptr(x2), int(ksplit), _ptr(w), _ptr(bias), _ptr(res), B, H, M, K, taps, int(stride), int(groups),
-                            1 if relu else 0, _ptr(out32), _ptr(out16), _stream()))
+    _op('dmad_conv_h16', _ptr(x), _ptr(x2), int(ksplit), _ptr(w), _ptr(_f32(bias)), _ptr(res), B, H, M, K, taps, int(stride), int(groups),
+        1 if relu else 0, _ptr(out32), _ptr(out16))
     return out32, out16
 
 
@@ -1318,7 +1313,6 @@ def conv_h16_up2(x_half: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Ten
     """dmad_conv_h16_up2 — nearest x2 upsampling + 3x3 conv in one launch (test hook of GemmH16Args::up2).  x_half: f16 NHWC
     [B,H/2,H/2,K]; w: f16 [1,9,M,K]; res: optional f16 [B,H,H,M].  Returns (out32, out16, stats | None); raises DmadError when the shape
     is not served by the fusing form."""
-    lib = _lib.load()
     assert x_half.is_cuda and x_half.dtype == torch.float16 and w.dtype == torch.float16 and w.shape[0] == 1 and w.shape[1] == 9
     x_half, w = x_half.contiguous(), w.contiguous()
     B, Hh, _, K = x_half.shape
@@ -1327,23 +1321,20 @@ def conv_h16_up2(x_half: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Ten
     out32 = torch.empty((B, H, H, M), device=x_half.device, dtype=torch.float32)
     out16 = torch.empty((B, H, H, M), device=x_half.device, dtype=torch.float16)
     stats = torch.zeros((B * H * H // 64, M // 4, 2), device=x_half.device, dtype=torch.float32) if want_stats else None
-    if bias is not None:
-        bias = bias.detach().contiguous().float()
     if res is not None:
         assert res.dtype == torch.float16 and tuple(res.shape) == (B, H, H, M)
         res = res.contiguous()
-    check(lib.dmad_conv_h16_up2(_ptr(x_half), _ptr(w), _ptr(bias), _ptr(res), B, H, M, K, _ptr(out32), _ptr(out16), _ptr(stats), _stream()))
+    _op('dmad_conv_h16_up2', _ptr(x_half), _ptr(w), _ptr(_f32(bias)), _ptr(res), B, H, M, K, _ptr(out32), _ptr(out16), _ptr(stats))
     return out32, out16, stats
 
 
 def split_f16(x: torch.Tensor) -> torch.Tensor:
     """dmad_split_f16: the split-f16 storage form (hi / lo f16 pairs in the bytes of the floats) of an fp32 CUDA tensor whose last dimension is a
     multiple of 4; returned as a float32 tensor of the same shape (its bits are NOT floats)."""
-    lib = _lib.load()
     assert x.is_cuda and x.dtype == torch.float32 and x.shape[-1] % 4 == 0
     x = x.contiguous()
     y = torch.empty_like(x)
-    check(lib.dmad_split_f16(_ptr(x), x.numel(), _ptr(y), _stream()))
+    _op('dmad_split_f16', _ptr(x), x.numel(), _ptr(y))
     return y
 
 
@@ -1353,7 +1344,6 @@ def conv_x3(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = Non
     """dmad_conv_x3 — the split-f16 conv GEMM as a standalone op (test hook).  x: fp32 NHWC [B,H,H,Cx], x2: optional second map whose
     channels follow x's (dense only); w: fp32 [taps, M, K] (dense) or [groups, taps, M, K]; bias fp32 [groups*M]; res fp32
     [B,Ho,Ho,groups*M] (res_split: handed to the kernel in the split format).  Operands are converted with split_f16 here."""
-    lib = _lib.load()
     assert x.is_cuda and x.dtype == torch.float32 and w.is_cuda and w.dtype == torch.float32 and x.dim() == 4 and w.dim() in (3, 4)
     if w.dim() == 3:
         w = w[None]
@@ -1369,20 +1359,17 @@ def conv_x3(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = Non
         assert cx == groups * K
     Ho = (H - 1) // stride + 1
     out = torch.empty((B, Ho, Ho, groups * M), device=x.device, dtype=torch.float32)
-    if bias is not None:
-        bias = bias.detach().contiguous().float()
     if res is not None:
         assert tuple(res.shape) == (B, Ho, Ho, groups * M) and res.dtype == torch.float32
         res = split_f16(res) if res_split else res.contiguous()
-    check(lib.dmad_conv_x3(_ptr(xs), _ptr(x2s), int(ksplit), _ptr(ws), _ptr(bias), _ptr(res), B, H, M, K, taps, int(stride), int(groups),
-                           1 if relu else 0, 1 if out_split else 0, 1 if res_split else 0, _ptr(out), _stream()))
+    _op('dmad_conv_x3', _ptr(xs), _ptr(x2s), int(ksplit), _ptr(ws), _ptr(_f32(bias)), _ptr(res), B, H, M, K, taps, int(stride), int(groups),
+        1 if relu else 0, 1 if out_split else 0, 1 if res_split else 0, _ptr(out))
     return out
 
 
 def conv_h16_stats(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1, res: Optional[torch.Tensor] = None):
     """dmad_conv_h16_stats: dense f16 conv (x [B,H,H,K] f16, w [1,taps,M,K] f16) -> (out16 [B,Ho,Ho,M] f16, stats [B*Ho*Ho/blk, M/4, 2] fp32):
     the GroupNorm statistics the producing GEMM's epilogue leaves for groupnorm16_apply (blk = 64 pixels, 16 on 4x4 maps)."""
-    lib = _lib.load()
     assert x.is_cuda and x.dtype == torch.float16 and w.dtype == torch.float16 and w.shape[0] == 1
     x, w = x.contiguous(), w.contiguous()
     B, H, _, K = x.shape
@@ -1392,11 +1379,9 @@ def conv_h16_stats(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor
     blk = 64 if Ho * Ho >= 64 else 16
     out16 = torch.empty((B, Ho, Ho, M), device=x.device, dtype=torch.float16)
     stats = torch.zeros((B * Ho * Ho // blk, M // 4, 2), device=x.device, dtype=torch.float32)
-    if bias is not None:
-        bias = bias.detach().contiguous().float()
     if res is not None:
         res = res.contiguous()
-    check(lib.dmad_conv_h16_stats(_ptr(x), _ptr(w), _ptr(bias), _ptr(res), B, H, M, K, taps, int(stride), _ptr(out16), _ptr(stats), _stream()))
+    _op('dmad_conv_h16_stats', _ptr(x), _ptr(w), _ptr(_f32(bias)), _ptr(res), B, H, M, K, taps, int(stride), _ptr(out16), _ptr(stats))
     return out16, stats
 
 
@@ -1404,23 +1389,15 @@ def groupnorm16_apply(x: torch.Tensor, st: torch.Tensor, gamma: torch.Tensor, be
                       x2: Optional[torch.Tensor] = None, st2: Optional[torch.Tensor] = None, out32: bool = False):
     """dmad_groupnorm16_apply: one-pass GroupNorm32 (+ scale-shift, + SiLU) of the f16 map x [B,HW,c1] (| x2 [B,HW,C-c1]) from the
     statistics slabs of conv_h16_stats.  Returns y [B,HW,C] (f16, or fp32 with out32)."""
-    lib = _lib.load()
     x, st = x.contiguous(), st.contiguous()
     B, HW, c1 = x.shape
     C = c1 + (x2.shape[2] if x2 is not None else 0)
     y = torch.empty((B, HW, C), device=x.device, dtype=torch.float32 if out32 else torch.float16)
     if x2 is not None:
         x2, st2 = x2.contiguous(), st2.contiguous()
-    gamma, beta = gamma.detach().contiguous().float(), beta.detach().contiguous().float()
-    if ss is not None:
-        ss = ss.detach().contiguous().float()
-    check(lib.dmad_groupnorm16_apply(_ptr(x), _ptr(st), _ptr(x2), _ptr(st2), int(c1 if x2 is not None else 0), _ptr(gamma), _ptr(beta), _ptr(ss),
-                                     1 if silu else 0, B, HW, C, None if out32 else _ptr(y), _ptr(y) if out32 else None, _stream()))
+    _op('dmad_groupnorm16_apply', _ptr(x), _ptr(st), _ptr(x2), _ptr(st2), int(c1 if x2 is not None else 0), _ptr(_f32(gamma)), _ptr(_f32(beta)),
+        _ptr(_f32(ss)), 1 if silu else 0, B, HW, C, None if out32 else _ptr(y), _ptr(y) if out32 else None)
     return y
-
-
-def _f32(t):
-    return None if t is None else t.detach().contiguous().float()
 
 
 def conv_f32(x: torch.Tensor, w: torch.Tensor, shift: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None, stride: int = 1,
@@ -1430,7 +1407,6 @@ def conv_f32(x: torch.Tensor, w: torch.Tensor, shift: Optional[torch.Tensor] = N
     channels follow x's), or [B,K] rows (the plain GEMM of the Linear layers); w fp32 [groups, taps, M, K] (or [taps, M, K]); scale /
     shift [groups*M]; res like the output; slab: optional fp32 split-K workspace, n_ref the row count the split count is derived from.
     Returns (out, choice) with choice = dict(bm, narrow, two, splits): what the launcher chose."""
-    lib = _lib.load()
     assert x.is_cuda and x.dtype == torch.float32 and w.is_cuda and w.dtype == torch.float32 and x.dim() in (2, 4) and w.dim() in (3, 4)
     if w.dim() == 3:
         w = w[None]
@@ -1457,9 +1433,8 @@ def conv_f32(x: torch.Tensor, w: torch.Tensor, shift: Optional[torch.Tensor] = N
     if res is not None:
         assert tuple(res.shape) == oshape
     choice = (C.c_int32 * 4)()
-    check(lib.dmad_conv_f32(_ptr(x), _ptr(x2c), int(ksplit), _ptr(w), _ptr(scale), _ptr(shift), _ptr(res), B, H, M, K, taps, int(stride),
-                            int(groups), 1 if relu else 0, _ptr(slab), slab.numel() if slab is not None else 0, int(n_ref), _ptr(out), choice,
-                            _stream()))
+    _op('dmad_conv_f32', _ptr(x), _ptr(x2c), int(ksplit), _ptr(w), _ptr(scale), _ptr(shift), _ptr(res), B, H, M, K, taps, int(stride),
+        int(groups), 1 if relu else 0, _ptr(slab), slab.numel() if slab is not None else 0, int(n_ref), _ptr(out), choice)
     return out, dict(bm=choice[0], narrow=choice[1], two=choice[2], splits=choice[3])
 
 
@@ -1469,7 +1444,6 @@ def conv_f32_vjp(g_y: torch.Tensor, w: torch.Tensor, H: int, form: int = 0, stri
     ResNeXt29, 3 VGG19_bn's dense 3x3 with its BN scale).  g_y fp32 [B,Ho,Ho,groups*M] (ldt channels with a padded 1x1 image), w [groups, taps, M, K] in the forward layout, H the
     forward conv's input resolution.  Returns (g_x, wT, gm | None, work | None): the gradient, the packed weight image as the pack kernel
     wrote it, the masked gradient, and the dilated / pre-sum work map."""
-    lib = _lib.load()
     assert g_y.is_cuda and g_y.dtype == torch.float32 and w.dtype == torch.float32 and g_y.dim() == 4 and w.dim() == 4
     g_y, w = g_y.contiguous(), w.contiguous()
     _, taps, M, K = w.shape
@@ -1496,22 +1470,20 @@ def conv_f32_vjp(g_y: torch.Tensor, w: torch.Tensor, H: int, form: int = 0, stri
         assert tuple(acc.shape) == tuple(g_x.shape)
     if mask_y is not None:
         assert tuple(mask_y.shape) == tuple(g_y.shape)
-    check(lib.dmad_conv_f32_vjp(_ptr(g_y), _ptr(w), _ptr(scale), _ptr(mask_y), _ptr(acc), B, int(H), M, K, taps, int(stride), int(groups),
-                                int(form), int(ldt), _ptr(wT), _ptr(gm), _ptr(work), _ptr(g_x), _stream()))
+    _op('dmad_conv_f32_vjp', _ptr(g_y), _ptr(w), _ptr(scale), _ptr(mask_y), _ptr(acc), B, int(H), M, K, taps, int(stride), int(groups),
+        int(form), int(ldt), _ptr(wT), _ptr(gm), _ptr(work), _ptr(g_x))
     return g_x, wT, gm, work
 
 
 def groupnorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, silu: bool = False, ss: Optional[torch.Tensor] = None,
                   x2: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dmad_groupnorm_f32: GroupNorm32 (+ scale-shift, + SiLU) of the fp32 map x [B,HW,c1] (| x2 [B,HW,C-c1]) -> y [B,HW,C] (test hook)."""
-    lib = _lib.load()
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
     x, x2 = x.contiguous(), (None if x2 is None else x2.contiguous())
     B, HW, c1 = x.shape
     Cn = c1 + (x2.shape[2] if x2 is not None else 0)
     y = torch.empty((B, HW, Cn), device=x.device, dtype=torch.float32)
-    check(lib.dmad_groupnorm_f32(_ptr(x), _ptr(x2), int(c1), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(_f32(ss)), 1 if silu else 0, B, HW, Cn,
-                                 _ptr(y), _stream()))
+    _op('dmad_groupnorm_f32', _ptr(x), _ptr(x2), int(c1), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(_f32(ss)), 1 if silu else 0, B, HW, Cn, _ptr(y))
     return y
 
 
@@ -1520,7 +1492,6 @@ def groupnorm_bwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, gy: 
                   add2: Optional[torch.Tensor] = None):
     """dmad_groupnorm_bwd: the gradient of groupnorm_f32 with respect to its input -> (gx [B,HW,c1], gx2 [B,HW,C-c1] | None), add / add2
     ([B,HW,C]) summed in (test hook)."""
-    lib = _lib.load()
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
     x, x2, gy = x.contiguous(), (None if x2 is None else x2.contiguous()), gy.contiguous()
     B, HW, c1 = x.shape
@@ -1529,68 +1500,64 @@ def groupnorm_bwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, gy: 
     gx = torch.empty_like(x)
     gx2 = torch.empty_like(x2) if x2 is not None else None
     gamma, beta, ss, add, add2 = _f32(gamma), _f32(beta), _f32(ss), _f32(add), _f32(add2)
-    check(lib.dmad_groupnorm_bwd(_ptr(x), _ptr(x2), int(c1), _ptr(gamma), _ptr(beta), _ptr(ss), 1 if silu else 0, _ptr(gy), _ptr(add),
-                                 _ptr(add2), B, HW, Cn, _ptr(gx), _ptr(gx2), _stream()))
+    _op('dmad_groupnorm_bwd', _ptr(x), _ptr(x2), int(c1), _ptr(gamma), _ptr(beta), _ptr(ss), 1 if silu else 0, _ptr(gy), _ptr(add),
+        _ptr(add2), B, HW, Cn, _ptr(gx), _ptr(gx2))
     return gx, gx2
 
 
 def qkv_attention_f32(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     """dmad_qkv_attention_f32: qkv fp32 [B,T,heads*192] (head-major q | k | v) -> out [B,T,heads*64] (test hook)."""
-    lib = _lib.load()
     assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3 and qkv.shape[2] == heads * 192
     qkv = qkv.contiguous()
     B, T, _ = qkv.shape
     out = torch.empty((B, T, heads * 64), device=qkv.device, dtype=torch.float32)
-    check(lib.dmad_qkv_attention_f32(_ptr(qkv), B, T, int(heads), _ptr(out), _stream()))
+    _op('dmad_qkv_attention_f32', _ptr(qkv), B, T, int(heads), _ptr(out))
     return out
 
 
 def qkv_attention_bwd(qkv: torch.Tensor, go: torch.Tensor, heads: int) -> torch.Tensor:
     """dmad_qkv_attention_bwd: the gradient of qkv_attention_f32 -> gqkv [B,T,heads*192] (dq | dk | dv per head) (test hook)."""
-    lib = _lib.load()
     assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3 and qkv.shape[2] == heads * 192
     qkv, go = qkv.contiguous(), go.contiguous()
     B, T, _ = qkv.shape
     assert tuple(go.shape) == (B, T, heads * 64) and go.dtype == torch.float32
     gqkv = torch.empty_like(qkv)
-    check(lib.dmad_qkv_attention_bwd(_ptr(qkv), _ptr(go), B, T, int(heads), _ptr(gqkv), _stream()))
+    _op('dmad_qkv_attention_bwd', _ptr(qkv), _ptr(go), B, T, int(heads), _ptr(gqkv))
     return gqkv
 
 
 def rx_head_bwd(g_logits: torch.Tensor, W: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """dmad_rx_head_bwd: g_logits [B,ncls], W [ncls,C], y [B,HW,C] -> gz [B,HW,C] (FC, average pool and the last ReLU backward) (test hook)."""
-    lib = _lib.load()
     g_logits, W, y = _f32(g_logits), _f32(W), _f32(y)
     B, HW, Cn = y.shape
     assert tuple(g_logits.shape) == (B, W.shape[0]) and W.shape[1] == Cn and y.is_cuda
     gz = torch.empty_like(y)
-    check(lib.dmad_rx_head_bwd(_ptr(g_logits), _ptr(W), _ptr(y), B, int(W.shape[0]), HW, Cn, _ptr(gz), _stream()))
+    _op('dmad_rx_head_bwd', _ptr(g_logits), _ptr(W), _ptr(y), B, int(W.shape[0]), HW, Cn, _ptr(gz))
     return gz
 
 
 def vgg_pool_relu_bwd(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """dmad_vgg_pool_relu_bwd: g [B,H/2,H/2,C], y [B,H,H,C] (the saved post-ReLU map) -> gpre [B,H,H,C] (2x2 max-pool and the ReLU in front
     of it, backward) (test hook)."""
-    lib = _lib.load()
     g, y = _f32(g), _f32(y)
     B, H, _, Cn = y.shape
     assert y.is_cuda and y.shape[2] == H and tuple(g.shape) == (B, H // 2, H // 2, Cn)
     gpre = torch.empty_like(y)
-    check(lib.dmad_vgg_pool_relu_bwd(_ptr(g), _ptr(y), B, H, Cn, _ptr(gpre), _stream()))
+    _op('dmad_vgg_pool_relu_bwd', _ptr(g), _ptr(y), B, H, Cn, _ptr(gpre))
     return gpre
 
 
 def rx_conv1_bwd(g: torch.Tensor, a: torch.Tensor, w: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     """dmad_rx_conv1_bwd: g, a [B,32,32,64], w [64,9], scale [64] -> gspec [B,32,32] (conv1's ReLU, BN and 1 <- 64 conv backward) (test hook)."""
-    lib = _lib.load()
     g, a, w, scale = _f32(g), _f32(a), _f32(w), _f32(scale)
     B = g.shape[0]
     assert tuple(g.shape) == (B, 32, 32, 64) and tuple(a.shape) == (B, 32, 32, 64) and tuple(w.shape) == (64, 9) and tuple(scale.shape) == (64,)
     gspec = torch.empty((B, 32, 32), device=g.device, dtype=torch.float32)
-    check(lib.dmad_rx_conv1_bwd(_ptr(g), _ptr(a), _ptr(w), _ptr(scale), B, _ptr(gspec), _stream()))
+    _op('dmad_rx_conv1_bwd', _ptr(g), _ptr(a), _ptr(w), _ptr(scale), B, _ptr(gspec))
     return gspec
 
 
+# ---------------------------------------------------------------------- which engine a module binds to
 def bind_classifier(state_dict, loader_name: str, engine: Optional[Engine] = None) -> Engine:
     """Engine that holds exactly `state_dict` as its classifier: `engine` (refused if it holds another one), else the
     shared engine, else — when the shared engine already serves a different classifier — an engine of this module's own
