@@ -13,7 +13,7 @@ namespace dmad {
 void launch_cvjp_transpose(const float* src, int rows, int cols, long lds, const float* scale, float* dst, int ldd, hipStream_t s);
 // the grouped 3x3 conv's backward image: src [g][tap][m][k] (G x G per group, 8 groups) -> dst[g][8 - tap][k][m] * scale[g * G + m]
 void launch_cvjp_pack_grouped(const float* src, const float* scale, float* dst, int G, hipStream_t s);
-// the dense 3x3 conv's backward image (VGG19_bn): src [tap][M][K] -> dst[8 - tap][k][m] * scale[m]
+// the dense 3x3 conv's backward image (VGG19_bn, WideResNet): src [tap][M][K] -> dst[8 - tap][k][m] * scale[m] (scale null: the plain image)
 void launch_cvjp_pack_dense(const float* src, const float* scale, float* dst, int M, int K, hipStream_t s);
 // 2x2 max-pool and the ReLU in front of it, backward: y [B][H][H][C] the saved post-ReLU map (the pool's input), g [B][H/2][H/2][C] ->
 // gpre [B][H][H][C], the gradient at the ReLU's input.  Each window's g goes to its maximum, the first in scan order (top-left, top-right,

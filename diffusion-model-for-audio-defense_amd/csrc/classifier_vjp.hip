@@ -39,7 +39,8 @@ __global__ void cvjp_pack_dense_kernel(const float* __restrict__ src, const floa
     const int m = (int)(i % M);
     const long r = i / M;
     const int k = (int)(r % K), t = (int)(r / K);
-    dst[i] = src[((long)(8 - t) * M + m) * K + k] * scale[m];
+    const float v = src[((long)(8 - t) * M + m) * K + k];
+    dst[i] = scale ? v * scale[m] : v;
 }
 
 // one float4 of channels of one pooled pixel: the window's first maximum in scan order takes g if it is > 0 (torch's max_pool2d keeps

@@ -20,6 +20,7 @@
 #include "wave_defense.h"
 #include "m5.h"
 #include "masking.h"
+#include "wrn.h"
 #include "gemm_f32.h"
 #include "gemm_h16.h"
 #include "wn_bf16.h"
@@ -240,7 +241,7 @@ struct dmad_engine {
     float *act0 = nullptr, *act1 = nullptr, *logits = nullptr, *slab = nullptr;
     long slab_floats = 0;
     // ResNeXt29 8x64d (models/resnext.py): 9 bottlenecks, every conv with its folded eval-BatchNorm scale/shift
-    int cls_kind = 0;                      // 0 = VGG19_bn, 1 = ResNeXt29
+    int cls_kind = 0;                      // 0 = VGG19_bn, 1 = ResNeXt29, 2 = WideResNet-28-10
     struct RxConv { float *w = nullptr, *scale = nullptr, *shift = nullptr; h16_t* wh = nullptr; float* wx = nullptr; float* wT = nullptr; };   // wh: f16 image with the BN scale folded in (16-bit tier); wx: split-f16 image (middle tier); wT: transposed (3x3: tap-flipped) image with the BN scale folded in (classifier VJP)
     struct RxBlock { RxConv reduce, conv, expand, shortc; bool has_short = false; int cin = 0, cout = 0, D = 0, stride = 1; };
     RxBlock rx[9];
@@ -268,6 +269,24 @@ struct dmad_engine {
     float* vconvwT[16] = {nullptr};
     float* vfcwT[2] = {nullptr};
     VggTape vg_tape;
+    // WideResNet-28-10 (models/wideresnet.py): 12 pre-activation blocks; w1 / w2: the 3x3 GEMM images [tap][cout][cin], ws the
+    // 1x1 shortcut [cout][cin] of a stage's first block; s1 / b1: the folded bn1 (on the residual stream), s2 / b2: the folded bn2 (conv1's
+    // epilogue); w1T / w2T / wsT: the backward images (conv1's with bn2's scale folded in), packed on the first VJP reservation
+    struct WrnBlock {
+        int cin = 0, cout = 0, stride = 1;
+        float *s1 = nullptr, *b1 = nullptr, *w1 = nullptr, *s2 = nullptr, *b2 = nullptr, *w2 = nullptr, *ws = nullptr;
+        float *w1T = nullptr, *w2T = nullptr, *wsT = nullptr;
+    };
+    WrnBlock wrn[12];
+    float *wrn_stem = nullptr, *wrn_bns = nullptr, *wrn_bnb = nullptr, *wrn_fcw = nullptr, *wrn_fcb = nullptr;
+    float* wrn_fcws = nullptr;              // fc.w with the final bn's scale folded into its columns: the head backward's image
+    float *wrnX = nullptr, *wrnY = nullptr, *wrnO = nullptr, *wrnH = nullptr, *wrnS = nullptr, *wrnP = nullptr;   // NHWC work maps ([maxB] x 32 x 32 x 160) and the pooled vector
+    // WideResNet VJP workspace (dmad_reserve_wrn_vjp): the tape of the fp32 forward — o and h of blocks 0..11, then the final post-ReLU
+    // map, 25 slots of [wrnvjpB] spectrograms — and the gradient work maps
+    struct WrnTape { float* o[12] = {}; float* h[12] = {}; float* f = nullptr; };
+    int wrnvjpB = 0, wrnvjp_lastB = 0;
+    float *wrnvjp_tape = nullptr, *wrnvjp_work = nullptr;
+    WrnTape wrn_tape;
     // mel front-end VJP (dmad_mel_db_vjp): transposed filterbank [kMelLd][32] and DFT [2048][kDftKT] images, gradient maps of
     // melvjpB clips per pass (allocated on the first call)
     int melvjpB = 0;
@@ -767,6 +786,114 @@ int finalize_resnext(dmad_engine* e) {
         if (int r = gemm_h16_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, f16 conv GEMM) failed: %d", r);
     }
     if (e->rx_x3) if (int r = gemm_x3_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, split-f16 tier) failed: %d", r);
+    return 0;
+}
+
+// WideResNet-28-10 (models/wideresnet.py): names wrn.conv1.w [16,1,3,3]; per block i = 4 * stage + k: wrn.b<i>.bn1.{scale,
+// shift} [cin], .conv1.w [cout,cin,3,3] with .conv1.{scale,shift} [cout] (the folded bn2), .conv2.w [cout,cout,3,3], .short.w [cout,cin]
+// where cin != cout; wrn.bn.{scale,shift} [640], wrn.fc.w [classes,640], wrn.fc.b.  Every shape is checked (DMAD_ERR_SHAPE) before
+// anything is uploaded.  The fp32 images serve every engine precision.
+constexpr size_t kWrnMap = 163840;       // floats per spectrogram of the largest map: 32 x 32 x 160
+int finalize_wrn(dmad_engine* e) {
+    const int widths[4] = {16, 160, 320, 640}, nc = e->cfg.num_classes;
+    auto wget = [&](const std::string& name, std::initializer_list<int64_t> shape, const HostW** out) -> int {
+        auto it = e->hw.find(name);
+        if (it == e->hw.end()) return fail(DMAD_ERR_STATE, "weight '%s' was not loaded", name.c_str());
+        if (it->second.shape != std::vector<int64_t>(shape)) {
+            std::string have, want;
+            for (int64_t d : it->second.shape) have += (have.empty() ? "" : ",") + std::to_string(d);
+            for (int64_t d : shape) want += (want.empty() ? "" : ",") + std::to_string(d);
+            return fail(DMAD_ERR_SHAPE, "WideResNet-28-10: weight '%s' is [%s], expected [%s]", name.c_str(), have.c_str(), want.c_str());
+        }
+        *out = &it->second;
+        return 0;
+    };
+    struct Src { const HostW *s1, *b1, *w1, *s2, *b2, *w2, *ws; };
+    Src src[12];
+    const HostW *stem, *bns, *bnb, *fcw, *fcb;
+    CHK(wget("wrn.conv1.w", {16, 1, 3, 3}, &stem));
+    for (int i = 0; i < 12; ++i) {
+        dmad_engine::WrnBlock& b = e->wrn[i];
+        const int st = i / 4, k = i % 4;
+        b.cin = k == 0 ? widths[st] : widths[st + 1];
+        b.cout = widths[st + 1];
+        b.stride = (k == 0 && st > 0) ? 2 : 1;
+        const std::string base = "wrn.b" + std::to_string(i);
+        CHK(wget(base + ".bn1.scale", {b.cin}, &src[i].s1));
+        CHK(wget(base + ".bn1.shift", {b.cin}, &src[i].b1));
+        CHK(wget(base + ".conv1.w", {b.cout, b.cin, 3, 3}, &src[i].w1));
+        CHK(wget(base + ".conv1.scale", {b.cout}, &src[i].s2));
+        CHK(wget(base + ".conv1.shift", {b.cout}, &src[i].b2));
+        CHK(wget(base + ".conv2.w", {b.cout, b.cout, 3, 3}, &src[i].w2));
+        src[i].ws = nullptr;
+        if (b.cin != b.cout) CHK(wget(base + ".short.w", {b.cout, b.cin}, &src[i].ws));
+    }
+    CHK(wget("wrn.bn.scale", {640}, &bns));
+    CHK(wget("wrn.bn.shift", {640}, &bnb));
+    CHK(wget("wrn.fc.w", {nc, 640}, &fcw));
+    CHK(wget("wrn.fc.b", {nc}, &fcb));
+    auto image = [&](const std::vector<float>& cw, int M, int K, float** dst) -> int {      // [M][K][3][3] -> [tap][M][K]
+        std::vector<float> A((size_t)9 * M * K);
+        for (int co = 0; co < M; ++co)
+            for (int ci = 0; ci < K; ++ci)
+                for (int t = 0; t < 9; ++t) A[((size_t)t * M + co) * K + ci] = cw[((size_t)co * K + ci) * 9 + t];
+        return e->upload(dst, A);
+    };
+    CHK(e->upload(&e->wrn_stem, stem->v));
+    for (int i = 0; i < 12; ++i) {
+        dmad_engine::WrnBlock& b = e->wrn[i];
+        CHK(e->upload(&b.s1, src[i].s1->v)); CHK(e->upload(&b.b1, src[i].b1->v));
+        CHK(image(src[i].w1->v, b.cout, b.cin, &b.w1));
+        CHK(e->upload(&b.s2, src[i].s2->v)); CHK(e->upload(&b.b2, src[i].b2->v));
+        CHK(image(src[i].w2->v, b.cout, b.cout, &b.w2));
+        if (src[i].ws) CHK(e->upload(&b.ws, src[i].ws->v));
+    }
+    CHK(e->upload(&e->wrn_bns, bns->v)); CHK(e->upload(&e->wrn_bnb, bnb->v));
+    CHK(e->upload(&e->wrn_fcw, fcw->v)); CHK(e->upload(&e->wrn_fcb, fcb->v));
+    std::vector<float> ws((size_t)nc * 640);                  // the head backward's image: fc.w[k][c] * bn.scale[c], rounded once
+    for (int k = 0; k < nc; ++k)
+        for (int c = 0; c < 640; ++c) ws[(size_t)k * 640 + c] = (float)((double)fcw->v[(size_t)k * 640 + c] * (double)bns->v[c]);
+    CHK(e->upload(&e->wrn_fcws, ws));
+    const size_t B = (size_t)e->maxB;
+    CHK(e->alloc(&e->wrnX, B * kWrnMap)); CHK(e->alloc(&e->wrnY, B * kWrnMap)); CHK(e->alloc(&e->wrnO, B * kWrnMap));
+    CHK(e->alloc(&e->wrnH, B * kWrnMap)); CHK(e->alloc(&e->wrnS, B * kWrnMap));         // the shortcut's map: 32 x 32 x 160 in block 0
+    CHK(e->alloc(&e->wrnP, B * 640));
+    return 0;
+}
+
+// WideResNet.forward on NHWC fp32 maps: the stem kernel, then per block the pre-activation o = relu(bn1(x)) (wrn.hip), conv1 with bn2 and
+// the ReLU in its epilogue, the shortcut (the raw x, or in a stage's first block the 1x1 conv of the ACTIVATED o) and conv2 with the
+// shortcut as its residual; the final pre-activation, the 8 x 8 average pool and the FC.  Every GEMM gets the split-K slab and the row
+// count of a max_batch launch, so a sample's logits do not depend on its batch.  tape != nullptr (the VJP; B <= wrnvjpB): o, h and the
+// final map go to the tape's slots instead of the work maps (same launches, same n_ref, same bits)
+int classify_wrn(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, const dmad_engine::WrnTape* tape = nullptr) {
+    float *X = e->wrnX, *Y = e->wrnY;
+    launch_wrn_stem(spec, e->wrn_stem, X, B, s);
+    int H = 32;
+    for (int i = 0; i < 12; ++i) {
+        const dmad_engine::WrnBlock& b = e->wrn[i];
+        float* O = tape ? tape->o[i] : e->wrnO;
+        float* Hm = tape ? tape->h[i] : e->wrnH;
+        const int Ho = (H - 1) / b.stride + 1;
+        const long nref_out = (long)e->maxB * Ho * Ho;
+        launch_wrn_preact(X, b.s1, b.b1, O, (long)B * H * H, b.cin, s);
+        launch_gemm_f32(nhwc_conv_args(b.w1, b.s2, b.b2, O, Hm, b.cout, b.cin, 9, B, H, b.stride, nullptr, 1), s, e->slab, e->slab_floats, nref_out);
+        const float* res = X;
+        if (b.ws) {
+            launch_gemm_f32(nhwc_conv_args(b.ws, nullptr, nullptr, O, e->wrnS, b.cout, b.cin, 1, B, H, b.stride, nullptr), s, e->slab, e->slab_floats,
+                            nref_out);
+            res = e->wrnS;
+        }
+        launch_gemm_f32(nhwc_conv_args(b.w2, nullptr, nullptr, Hm, Y, b.cout, b.cout, 9, B, Ho, 1, res), s, e->slab, e->slab_floats, nref_out);
+        std::swap(X, Y);
+        H = Ho;
+    }
+    float* F = tape ? tape->f : e->wrnO;
+    launch_wrn_preact(X, e->wrn_bns, e->wrn_bnb, F, (long)B * 64, 640, s);
+    launch_avgpool_nhwc(F, e->wrnP, B, 64, 640, s);
+    launch_gemm_f32(plain_gemm(e->wrn_fcw, e->wrnP, logits, nullptr, e->wrn_fcb, e->cfg.num_classes, 640, B, e->cfg.num_classes, 640, 0), s, e->slab,
+                    e->slab_floats, (long)e->maxB);
+    LASTCHK();
     return 0;
 }
 
@@ -1554,15 +1681,17 @@ void rx_pack_wT(const float* w, const float* scale, float* wT, int M, int K, int
 // gradient's channels per group = the conv's input channels, K: the conv's output channels per group, padded for a 1x1 image with ldt > M),
 // no split-K.  Stride 2: the grouped 3x3 runs at Hin = 2 Ho on the zero-dilated gradient (work: [B][Hin][Hin][groups * K]); the 1x1
 // shortcut runs at Ho (work: [B][Ho][Ho][M]) and is scattered into the even pixels of gx.  res (optional, gx's shape; not with the
-// stride-2 1x1) is added in the GEMM's epilogue.
+// stride-2 1x1) is added in the GEMM's epilogue.  slab (optional; dense convs): the split-K workspace with n_ref = max_batch x the GEMM's
+// pixels, as the forward passes them (WideResNet); without it the launch is ResNeXt29's, bit for bit.
 int rx_conv_dgrad(const float* wT, const float* g, float* gx, int M, int K, int taps, int groups, int B, int Ho, int stride, float* work,
-                  const float* res, hipStream_t s) {
+                  const float* res, hipStream_t s, float* slab = nullptr, long slab_floats = 0, int maxB = 0) {
     const bool dil_in = stride == 2 && taps == 9, dil_out = stride == 2 && taps == 1;
     if (dil_in) launch_dilate2x_nhwc(g, work, B, Ho, groups * K, s);
     const int H = dil_in ? 2 * Ho : Ho;
     const GemmF32Args a = nhwc_conv_args(wT, nullptr, nullptr, dil_in ? work : g, dil_out ? work : gx, M, K, taps, B, H, 1, dil_out ? nullptr : res, 0, groups,
                                          groups * K, groups * M);
-    if (launch_gemm_f32(a, s) != 0) return fail(DMAD_ERR_STATE, "classifier VJP: no GEMM for M = %d, K = %d, taps = %d", M, K, taps);
+    if (launch_gemm_f32(a, s, slab, slab_floats, (long)maxB * H * H) != 0)
+        return fail(DMAD_ERR_STATE, "classifier VJP: no GEMM for M = %d, K = %d, taps = %d", M, K, taps);
     if (dil_out) launch_dilate2x_nhwc(work, gx, B, Ho, M, s);
     return 0;
 }
@@ -1604,7 +1733,7 @@ int rx_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits,
 
 int classify_vjp(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
     CHK(need_classifier(e));
-    if (e->cls_kind != 1) return fail(DMAD_ERR_STATE, "the classifier VJP serves ResNeXt29 only: this engine holds VGG19_bn");
+    if (e->cls_kind != 1) return fail(DMAD_ERR_STATE, "the classifier VJP serves ResNeXt29 only: this engine holds %s", e->cls_kind == 2 ? "WideResNet-28-10 (dmad_wrn_vjp)" : "VGG19_bn");
     if (!e->rxvjpB) return fail(DMAD_ERR_STATE, "no classifier VJP workspace: call dmad_reserve_classifier_vjp first");
     CHK(need_batch(e, B));
     const int nc = e->cfg.num_classes;
@@ -1719,6 +1848,7 @@ int classify(dmad_engine* e, const float* spec, int B, float* logits, hipStream_
     CHK(need_classifier(e)); CHK(need_batch(e, B));
     if (e->cls_kind == 1) return (h16 == 1 && e->rx_h16) ? classify_resnext_h16(e, spec, B, logits, s)
                                  : (h16 == 2 && e->rx_x3) ? classify_resnext_x3(e, spec, B, logits, s) : classify_resnext(e, spec, B, logits, s);
+    if (e->cls_kind == 2) return classify_wrn(e, spec, B, logits, s);      // every tier falls to fp32, as for VGG19_bn
     return classify_vgg(e, spec, B, logits, s);
 }
 
@@ -1782,7 +1912,7 @@ int vgg_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits
 
 int need_vgg(const dmad_engine* e) {
     CHK(need_classifier(e));
-    return e->cls_kind == 0 ? 0 : fail(DMAD_ERR_STATE, "the VGG19_bn VJP serves VGG19_bn only: this engine holds ResNeXt29 (dmad_classify_vjp)");
+    return e->cls_kind == 0 ? 0 : fail(DMAD_ERR_STATE, "the VGG19_bn VJP serves VGG19_bn only: this engine holds %s", e->cls_kind == 2 ? "WideResNet-28-10 (dmad_wrn_vjp)" : "ResNeXt29 (dmad_classify_vjp)");
 }
 
 int vgg_vjp(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
@@ -1795,6 +1925,76 @@ int vgg_vjp(dmad_engine* e, const float* spec, int B, const float* g_logits, flo
         return vgg_vjp_pass(e, spec + b0 * 1024, bb, g_logits + b0 * nc, g_spec + b0 * 1024, logits ? logits + b0 * nc : e->logits, s);
     }));
     if (B <= e->vgvjpB) e->vgvjp_lastB = B;
+    return 0;
+}
+
+// (H, C) of the WideResNet tape's slot `index`: o / h of block index / 2, then the final map; floats per spectrogram = H * H * C
+void wrn_tape_map(const dmad_engine* e, int index, int* H, int* C) {
+    if (index >= 24) { *H = 8; *C = 640; return; }
+    const int i = index / 2, Hin = i < 4 ? 32 : i < 8 ? (i == 4 ? 32 : 16) : (i == 8 ? 16 : 8);
+    const dmad_engine::WrnBlock& b = e->wrn[i];
+    if (index & 1) { *H = Hin / b.stride; *C = b.cout; }
+    else { *H = Hin; *C = b.cin; }
+}
+// floats per spectrogram of the gradient work maps of wrn_vjp_pass: the block out / in gradients, g_h, its zero-dilation (stage 2's first
+// block: 32 x 32 x 320), g_o, the shortcut's gradient at the output resolution (16 x 16 x 160 at most) and at the input resolution
+const size_t kWrnWork[7] = {kWrnMap, kWrnMap, kWrnMap, 2 * kWrnMap, kWrnMap, kWrnMap / 4, kWrnMap};
+
+// g_spec = (d logits / d spec)^T g_logits of classify_wrn; logits: the forward it recomputes (B <= wrnvjpB)
+int wrn_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
+    const dmad_engine::WrnTape& tp = e->wrn_tape;
+    CHK(classify_wrn(e, spec, B, logits, s, &tp));
+    float* G[7];
+    G[0] = e->wrnvjp_work;
+    for (int k = 1; k < 7; ++k) G[k] = G[k - 1] + kWrnWork[k - 1] * e->wrnvjpB;
+    float *cur = G[0], *nxt = G[1], *gh = G[2], *gD = G[3], *go = G[4], *gS = G[5], *gSd = G[6];
+    // head: FC^T (on the image that carries the final bn's scale), the 8 x 8 average pool and the last ReLU's mask: the gradient at block 11's output
+    launch_rx_head_bwd(g_logits, e->wrn_fcws, tp.f, cur, B, e->cfg.num_classes, 64, 640, s);
+    int H = 8;
+    for (int i = 11; i >= 0; --i) {
+        const dmad_engine::WrnBlock& b = e->wrn[i];
+        const int Ho = H, Hin = Ho * b.stride;
+        CHK(rx_conv_dgrad(b.w2T, cur, gh, b.cout, b.cout, 9, 1, B, Ho, 1, nullptr, nullptr, s, e->slab, e->slab_floats, e->maxB));       // conv2
+        launch_relu_mask(gh, tp.h[i], gh, (long)B * Ho * Ho * b.cout, s);                                                                // relu2 (bn2's scale is in w1T)
+        const float* gsc = nullptr;
+        if (b.wsT) {                                                                                                                     // the 1x1 shortcut of the activated input
+            float* out = b.stride == 2 ? gSd : gS;
+            CHK(rx_conv_dgrad(b.wsT, cur, out, b.cin, b.cout, 1, 1, B, Ho, b.stride, gS, nullptr, s, e->slab, e->slab_floats, e->maxB));
+            gsc = out;
+        }
+        CHK(rx_conv_dgrad(b.w1T, gh, go, b.cin, b.cout, 9, 1, B, Ho, b.stride, gD, gsc, s, e->slab, e->slab_floats, e->maxB));            // conv1 (stride) + the shortcut's
+        launch_wrn_preact_bwd(go, tp.o[i], b.s1, b.wsT ? nullptr : cur, nxt, (long)B * Hin * Hin, b.cin, s);                             // relu1, bn1, + the identity shortcut
+        std::swap(cur, nxt);
+        H = Hin;
+    }
+    launch_wrn_stem_bwd(cur, e->wrn_stem, g_spec, B, s);
+    LASTCHK();
+    return 0;
+}
+
+int need_wrn(const dmad_engine* e) {
+    CHK(need_classifier(e));
+    return e->cls_kind == 2 ? 0 : fail(DMAD_ERR_STATE, "the WideResNet VJP serves WideResNet-28-10 only: this engine holds %s",
+                                       e->cls_kind == 1 ? "ResNeXt29 (dmad_classify_vjp)" : "VGG19_bn (dmad_vgg_vjp)");
+}
+
+int wrn_vjp(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
+    CHK(need_wrn(e));
+    if (!e->wrnvjpB) return fail(DMAD_ERR_STATE, "no WideResNet VJP workspace: call dmad_reserve_wrn_vjp first");
+    CHK(need_batch(e, B));
+    const int nc = e->cfg.num_classes;
+    e->wrnvjp_lastB = 0;
+    CHK(for_passes(B, e->wrnvjpB, [&](int64_t b0, int bb) {
+        return wrn_vjp_pass(e, spec + b0 * 1024, bb, g_logits + b0 * nc, g_spec + b0 * 1024, logits ? logits + b0 * nc : e->logits, s);
+    }));
+    if (B <= e->wrnvjpB) e->wrnvjp_lastB = B;
+    return 0;
+}
+
+// the exact-vote loops refuse a WideResNet engine: no recheck bound has been measured for this classifier
+int need_vote_bound(const dmad_engine* e) {
+    if (e->cls_final && e->cls_kind == 2 && e->mode == DMAD_MODE_EXACT_VOTES)
+        return fail(DMAD_ERR_STATE, "no recheck bound has been measured for WideResNet-28-10: the exact-vote loops refuse it (DMAD_MODE_FAST and DMAD_MODE_FP32 serve it)");
     return 0;
 }
 
@@ -2105,6 +2305,12 @@ int dmad_finalize_weights(dmad_engine* e) {
     } else if (e->cfg.with_classifier && !e->cls_final && e->hw.count("rx.conv1.w")) {
         CHK(finalize_resnext(e));
         e->cls_final = true; e->cls_kind = 1; did = true;
+    } else if (e->cfg.with_classifier && !e->cls_final && e->hw.count("wrn.conv1.w")) {
+        if (int r = finalize_wrn(e)) {       // a refused set leaves nothing behind, like a refused M5 set
+            for (auto it = e->hw.begin(); it != e->hw.end();) it = it->first.compare(0, 4, "wrn.") == 0 ? e->hw.erase(it) : std::next(it);
+            return r;
+        }
+        e->cls_final = true; e->cls_kind = 2; did = true;
     }
     if (!e->un_final && e->hw.count("un.time_embed.0.weight")) {
         if (!e->slab) {                     // engines created without a classifier have no split-K workspace yet
@@ -2469,14 +2675,26 @@ int dmad_conv_f32_vjp(const float* g_y, const float* w, const float* scale, cons
                       int32_t M, int32_t K, int32_t taps, int32_t stride, int32_t groups, int32_t form, int32_t ldt, float* wT, float* gm,
                       float* work, float* g_x, dmad_stream s) {
     if (!g_y || !w || !wT || !g_x) return fail(DMAD_ERR_INVALID, "null argument");
-    if (B < 1 || H < 1 || M < 16 || K < 4 || (M % 16) || (K % 4) || (stride != 1 && stride != 2) || (taps != 1 && taps != 9) || form < 0 || form > 3)
-        return fail(DMAD_ERR_INVALID, "bad geometry (M a multiple of 16, K of 4, taps 1 or 9, stride 1 or 2, form 0 - 3)");
+    if (B < 1 || H < 1 || M < 16 || K < 4 || (M % 16) || (K % 4) || (stride != 1 && stride != 2) || (taps != 1 && taps != 9) || form < 0 || form > 4)
+        return fail(DMAD_ERR_INVALID, "bad geometry (M a multiple of 16, K of 4, taps 1 or 9, stride 1 or 2, form 0 - 4)");
     if (stride == 2 && (H & 1)) return fail(DMAD_ERR_INVALID, "a stride-2 gradient is dilated to an even map: H = %d", H);
     if ((stride == 2 || form == 1) && !work) return fail(DMAD_ERR_INVALID, "this form needs the work map");
     if (int r = gemm_f32_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, fp32 narrow tile) failed: %d", r);
     const hipStream_t st = (hipStream_t)s;
     const int Ho = form == 1 ? 2 * H : (H - 1) / stride + 1;
-    if (form == 3) {                             // VGG19_bn's form
+    if (form == 4) {                             // WideResNet's form: a dense 3x3 / 1x1 at stride 1 or 2, scale optional
+        if (groups != 1 || ldt || (taps == 1 && stride == 2 && acc))
+            return fail(DMAD_ERR_INVALID, "WideResNet's form: dense, no padded pitch, no acc with the stride-2 1x1");
+        const float* g = g_y;
+        if (mask_y) {
+            if (!gm) return fail(DMAD_ERR_INVALID, "the ReLU mask needs its output map");
+            launch_relu_mask(g_y, mask_y, gm, (long)B * Ho * Ho * M, st);
+            g = gm;
+        }
+        if (taps == 9) launch_cvjp_pack_dense(w, scale, wT, M, K, st);
+        else launch_cvjp_transpose(w, M, K, K, scale, wT, M, st);
+        CHK(rx_conv_dgrad(wT, g, g_x, K, M, taps, 1, B, Ho, stride, work, acc, st));
+    } else if (form == 3) {                      // VGG19_bn's form
         if (taps != 9 || stride != 1 || groups != 1 || !scale || ldt || acc || (K % 16))
             return fail(DMAD_ERR_INVALID, "VGG19_bn's form: a dense 3x3 with stride 1, a scale, K a multiple of 16, no acc and no padded pitch");
         const float* g = g_y;
@@ -2713,7 +2931,7 @@ int dmad_reserve_classifier_vjp(dmad_engine* e, int32_t max_batch) {
     if (!e) return fail(DMAD_ERR_INVALID, "null engine");
     if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
     CHK(need_classifier(e));
-    if (e->cls_kind != 1) return fail(DMAD_ERR_STATE, "the classifier VJP serves ResNeXt29 only: this engine holds VGG19_bn");
+    if (e->cls_kind != 1) return fail(DMAD_ERR_STATE, "the classifier VJP serves ResNeXt29 only: this engine holds %s", e->cls_kind == 2 ? "WideResNet-28-10 (dmad_wrn_vjp)" : "VGG19_bn");
     const int vB = max_batch < e->maxB ? max_batch : e->maxB;
     if (vB <= e->rxvjpB) return 0;
     // tape slots in floats per spectrogram: conv1's output, then per bottleneck T1 (input resolution), T2 and Y (output resolution)
@@ -2829,6 +3047,98 @@ int dmad_vgg_pool_relu_bwd(const float* g, const float* y, int32_t B, int32_t H,
     if (!g || !y || !gpre) return fail(DMAD_ERR_INVALID, "null argument");
     if (B < 1 || H < 2 || (H & 1) || C < 4 || (C & 3)) return fail(DMAD_ERR_INVALID, "bad geometry (H even, C a multiple of 4)");
     launch_vgg_pool_relu_bwd(g, y, gpre, B, H, C, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_reserve_wrn_vjp(dmad_engine* e, int32_t max_batch) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
+    if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
+    CHK(need_wrn(e));
+    const int vB = max_batch < e->maxB ? max_batch : e->maxB;
+    if (vB <= e->wrnvjpB) return 0;
+    if (e->wrnvjpB) {                       // a larger reservation replaces the present one
+        e->release(&e->wrnvjp_tape); e->release(&e->wrnvjp_work);
+        e->wrnvjpB = e->wrnvjp_lastB = 0;
+    }
+    // the backward images, packed on the device from the resident fp32 images, each one once: the 3x3 convs tap-flipped and transposed
+    // (conv1's with bn2's scale folded in, conv2's plain), the 1x1 shortcuts transposed
+    for (int i = 0; i < 12; ++i) {
+        dmad_engine::WrnBlock& b = e->wrn[i];
+        if (!b.w1T) {
+            CHK(e->alloc(&b.w1T, (size_t)9 * b.cin * b.cout));
+            launch_cvjp_pack_dense(b.w1, b.s2, b.w1T, b.cout, b.cin, nullptr);
+        }
+        if (!b.w2T) {
+            CHK(e->alloc(&b.w2T, (size_t)9 * b.cout * b.cout));
+            launch_cvjp_pack_dense(b.w2, nullptr, b.w2T, b.cout, b.cout, nullptr);
+        }
+        if (b.ws && !b.wsT) {
+            CHK(e->alloc(&b.wsT, (size_t)b.cin * b.cout));                // [cout][cin] -> [cin][cout]
+            launch_cvjp_transpose(b.ws, b.cout, b.cin, b.cin, nullptr, b.wsT, b.cout, nullptr);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    size_t tape = 0, off[25], work = 0;
+    for (int k = 0; k < 25; ++k) { int H, C; wrn_tape_map(e, k, &H, &C); off[k] = tape; tape += (size_t)H * H * C; }
+    for (size_t w : kWrnWork) work += w;
+    CHK(e->alloc(&e->wrnvjp_tape, (size_t)vB * tape));
+    if (int r = e->alloc(&e->wrnvjp_work, (size_t)vB * work)) {           // no half reservation stays behind
+        e->release(&e->wrnvjp_tape);
+        return r;
+    }
+    for (int k = 0; k < 24; ++k) ((k & 1) ? e->wrn_tape.h : e->wrn_tape.o)[k / 2] = e->wrnvjp_tape + off[k] * vB;
+    e->wrn_tape.f = e->wrnvjp_tape + off[24] * vB;
+    HIPCHK(hipDeviceSynchronize());
+    e->wrnvjpB = vB;
+    return 0;
+}
+
+int dmad_wrn_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s) {
+    if (!e || !spec || !g_logits || !g_spec) return fail(DMAD_ERR_INVALID, "null argument");
+    return wrn_vjp(e, spec, B, g_logits, g_spec, logits, (hipStream_t)s);
+}
+
+int dmad_wrn_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s) {
+    if (!e || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(need_wrn(e));
+    if (index < 0 || index > 24) return fail(DMAD_ERR_INVALID, "tape map %d outside [0, 24]", index);
+    if (B < 1 || B > e->wrnvjp_lastB) return fail(DMAD_ERR_STATE, "the tape holds %d rows of a one-pass dmad_wrn_vjp call, not %d", e->wrnvjp_lastB, B);
+    int H, C;
+    wrn_tape_map(e, index, &H, &C);
+    const float* src = index == 24 ? e->wrn_tape.f : (index & 1) ? e->wrn_tape.h[index / 2] : e->wrn_tape.o[index / 2];
+    HIPCHK(hipMemcpyAsync(out, src, (size_t)B * H * H * C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)s));
+    return 0;
+}
+
+int dmad_wrn_preact(const float* x, const float* scale, const float* shift, int64_t n_px, int32_t C, float* out, dmad_stream s) {
+    if (!x || !scale || !shift || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    if (n_px < 1 || C < 4 || (C & 3)) return fail(DMAD_ERR_INVALID, "bad geometry (C a multiple of 4)");
+    launch_wrn_preact(x, scale, shift, out, (long)n_px, C, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_wrn_preact_bwd(const float* g, const float* o, const float* scale, const float* res, int64_t n_px, int32_t C, float* gx, dmad_stream s) {
+    if (!g || !o || !scale || !gx) return fail(DMAD_ERR_INVALID, "null argument");
+    if (n_px < 1 || C < 4 || (C & 3)) return fail(DMAD_ERR_INVALID, "bad geometry (C a multiple of 4)");
+    launch_wrn_preact_bwd(g, o, scale, res, gx, (long)n_px, C, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_wrn_stem(const float* spec, const float* w, int32_t B, float* out, dmad_stream s) {
+    if (!spec || !w || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
+    launch_wrn_stem(spec, w, out, B, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_wrn_stem_bwd(const float* g, const float* w, int32_t B, float* gspec, dmad_stream s) {
+    if (!g || !w || !gspec) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
+    launch_wrn_stem_bwd(g, w, gspec, B, (hipStream_t)s);
     LASTCHK();
     return 0;
 }
@@ -2982,7 +3292,7 @@ int dmad_eval_samples(dmad_engine* e, const float* clip, float sigma, float sqrt
     if (!e || !clip || !idx || (!logits_out && !x0_out)) return fail(DMAD_ERR_INVALID, "null argument");
     if (n < 0) return fail(DMAD_ERR_INVALID, "n < 0");
     CHK(need_path(e, path));
-    if (logits_out) CHK(need_with_classifier(e));
+    if (logits_out) { CHK(need_with_classifier(e)); CHK(need_vote_bound(e)); }
     const WaveJob job{clip, delta, sigma, sqrt_alpha_bar_star, t, c_a, c_b, seed, sample0, nullptr};
     CHK(for_passes(n, path == PATH_DEFAULT ? e->maxB : e->maxB32, [&](int64_t done, int B) {
         return wave_rows(e, job, 0, (const long long*)idx + done, B, path, x0_out ? x0_out + done * e->L : e->x0,
@@ -2998,6 +3308,7 @@ int dmad_smooth_votes(dmad_engine* e, const float* clip, float sigma, float sqrt
     if (!e || !clip) return fail(DMAD_ERR_INVALID, "null argument");
     if (n < 0 || batch < 1 || batch > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d] or n < 0", batch, e->maxB);
     if (e->cfg.with_classifier && !counts) return fail(DMAD_ERR_INVALID, "counts must not be null");
+    CHK(need_vote_bound(e));
     hipStream_t st = (hipStream_t)s;
     const int L = e->L, C = e->cfg.num_classes;
     const WaveJob job{clip, delta, sigma, sqrt_alpha_bar_star, t, c_a, c_b, seed, sample0, x0_out};
@@ -3110,6 +3421,7 @@ int dmad_spec_smooth_votes(dmad_engine* e, const float* clip, float sigma, int32
                            int32_t batch, uint64_t seed, uint64_t sample0, int64_t* counts, float* logits_out, float* spec_out, dmad_stream s) {
     if (!e || !clip || !counts || !c_a || !c_b || !c_1 || !c_2 || !c_sig) return fail(DMAD_ERR_INVALID, "null argument");
     if (!e->cfg.with_classifier || !e->cls_final) return fail(DMAD_ERR_STATE, "the spec-domain vote loop needs the mel front-end and a finalised classifier");
+    CHK(need_vote_bound(e));
     CHK(need_unet(e));
     if (n < 0 || batch < 1 || batch > e->maxB) return fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d] or n < 0", batch, e->maxB);
     if (t_star < 0) return fail(DMAD_ERR_INVALID, "t_star %d < 0", t_star);
@@ -3141,6 +3453,7 @@ int dmad_spec_eval_samples(dmad_engine* e, const float* clip, float sigma, int32
                            const int64_t* idx, int64_t n, int32_t tier, float* logits_out, float* spec_out, dmad_stream s) {
     if (!e || !clip || !idx || !c_a || !c_b || !c_1 || !c_2 || !c_sig || (!logits_out && !spec_out)) return fail(DMAD_ERR_INVALID, "null argument");
     if (!e->cfg.with_classifier || !e->cls_final) return fail(DMAD_ERR_STATE, "the spec-domain chain needs the mel front-end and a finalised classifier");
+    CHK(need_vote_bound(e));
     CHK(need_unet(e));
     if (n < 0 || t_star < 0 || !(mel_hi > mel_lo)) return fail(DMAD_ERR_INVALID, "bad argument");
     if (tier != 0 && tier != 1 && tier != 2) return fail(DMAD_ERR_INVALID, "unknown UNet tier %d (0 exact fp32, 1 16-bit, 2 split-f16)", tier);

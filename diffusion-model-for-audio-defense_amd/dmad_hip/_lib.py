@@ -104,6 +104,13 @@ _SIGNATURES = {
     'dmad_reserve_vgg_vjp': (C.c_int, [_P, C.c_int32]),
     'dmad_vgg_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     'dmad_vgg_vjp_tape': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_reserve_wrn_vjp': (C.c_int, [_P, C.c_int32]),
+    'dmad_wrn_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    'dmad_wrn_vjp_tape': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_wrn_preact': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P, _P]),
+    'dmad_wrn_preact_bwd': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P]),
+    'dmad_wrn_stem': (C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    'dmad_wrn_stem_bwd': (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     'dmad_vpsde_purify': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64,
                                     C.c_int32, _P, _P, _P]),
     'dmad_vpsde_purify_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P, _P, _P, _P]),

@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import DmadConfig, DmadError, check
+from .synth import WRN_BLOCKS, WRN_WIDTHS  # noqa: F401  (WideResNet-28-10's geometry, stated once with the stand-in)
 
 BF16, FP32, EXACT = 0, 1, 2                       # enum dmad_precision
 MODE_FAST, MODE_EXACT_VOTES, MODE_FP32 = 0, 1, 2  # enum dmad_mode (EXACT engines)
@@ -63,6 +64,19 @@ TAIL_Z = 5.4
 VGG19_CFG = [64, 64, 'M', 128, 128, 'M', 256, 256, 256, 256, 'M', 512, 512, 512, 512, 'M', 512, 512, 512, 512, 'M']
 # (H, C) of VGG19_bn's 16 post-ReLU conv maps on a 32 x 32 spectrogram: the conv slots of the VJP's tape (vgg_vjp_tape)
 VGG_TAPE_MAPS = ((32, 64),) * 2 + ((16, 128),) * 2 + ((8, 256),) * 4 + ((4, 512),) * 4 + ((2, 512),) * 4
+# WideResNet-28-10: (cin, cout, stride) of its 12 pre-activation blocks, and (H, C) of the 25 post-ReLU maps of the VJP's tape
+# (wrn_vjp_tape): o = relu(bn1(x)) and h = relu(bn2(conv1(o))) of blocks 0..11, then the final map; 2 310 144 floats per spectrogram
+
+
+def _wrn_tape_maps():
+    maps, H = [], 32
+    for cin, cout, stride in WRN_BLOCKS:
+        maps += [(H, cin), (H // stride, cout)]
+        H //= stride
+    return tuple(maps) + ((8, 640),)
+
+
+WRN_TAPE_MAPS = _wrn_tape_maps()
 M5_CHANNELS = (32, 32, 64, 64)                     # output channels of M5's four conv blocks (n_channel = 32)
 # the WaveNet geometry an engine is created with unless the caller names another one
 DEFAULT_WAVENET = dict(res_channels=256, skip_channels=256, num_res_layers=36, dilation_cycle=12,
@@ -224,6 +238,35 @@ def fold_resnext29_state_dict(sd: Dict[str, object], eps: float = 1e-5) -> Dict[
     return {k: _as_np(v) for k, v in out.items()}
 
 
+def fold_wideresnet_state_dict(sd: Dict[str, object], eps: float = 1e-5, dtype=np.float32) -> Dict[str, np.ndarray]:
+    """models/wideresnet.py WideResNet(depth=28, widen_factor=10, in_channels=1) state dict -> the `wrn.*` arrays of include/dmad.h: each
+    block's bn1 (the pre-activation on the residual stream), bn2 (conv1's epilogue) and the final bn folded to scale / shift in float64
+    and rounded once; shortcut weights as [cout, cin]; block i = 4 * stage + k.  Any other geometry is refused (DmadError).  dtype: what the float64 folds are
+    rounded to (np.float64: the arrays before the rounding, for the tests)."""
+    def shape(k):
+        return tuple(int(d) for d in sd[k].shape) if k in sd else None
+
+    if shape('conv1.weight') != (16, 1, 3, 3):
+        raise DmadError('only WideResNet-28-10 with 1 input channel is built natively: conv1.weight is %s, not (16, 1, 3, 3)' % (shape('conv1.weight'),))
+    if shape('fc.weight') is None or shape('fc.weight')[1:] != (640,) or 'block1.layer.4.conv1.weight' in sd or 'block1.layer.3.conv1.weight' not in sd:
+        raise DmadError('only WideResNet-28-10 is built natively: four blocks per stage and a 640-wide head (fc.weight is %s)' % (shape('fc.weight'),))
+    out = {'wrn.conv1.w': _f64(sd['conv1.weight'])}
+    for i, (cin, cout, _) in enumerate(WRN_BLOCKS):
+        src, dst = 'block%d.layer.%d.' % (i // 4 + 1, i % 4), 'wrn.b%d.' % i
+        if shape(src + 'conv1.weight') != (cout, cin, 3, 3) or shape(src + 'conv2.weight') != (cout, cout, 3, 3):
+            raise DmadError('only WideResNet-28-10 is built natively: %sconv1.weight is %s, not %s' % (src, shape(src + 'conv1.weight'), (cout, cin, 3, 3)))
+        out[dst + 'bn1.scale'], out[dst + 'bn1.shift'] = _fold_bn(sd, src + 'bn1', eps)
+        out[dst + 'conv1.w'] = _f64(sd[src + 'conv1.weight'])
+        out[dst + 'conv1.scale'], out[dst + 'conv1.shift'] = _fold_bn(sd, src + 'bn2', eps)
+        out[dst + 'conv2.w'] = _f64(sd[src + 'conv2.weight'])
+        if cin != cout:
+            out[dst + 'short.w'] = _f64(sd[src + 'convShortcut.weight']).reshape(cout, cin)
+    out['wrn.bn.scale'], out['wrn.bn.shift'] = _fold_bn(sd, 'bn1', eps)
+    out['wrn.fc.w'] = _f64(sd['fc.weight'])
+    out['wrn.fc.b'] = _f64(sd['fc.bias'])
+    return {k: np.ascontiguousarray(v, dtype=dtype) for k, v in out.items()}
+
+
 def fold_m5_state_dict(sd: Dict[str, object], stride: int = 16, eps: float = 1e-5) -> Dict[str, np.ndarray]:
     """M5Net.M5 state dict -> the `m5.*` arrays of include/dmad.h: the conv weights as they are, each eval-BatchNorm folded (in float64)
     into s = gamma / sqrt(var + eps) and shift = beta + (bias - mean) * s, fc1, and conv1's stride (the one geometry field no tensor
@@ -276,7 +319,7 @@ class Engine:
         self.has_unet = False
         self.has_m5 = False
         self.m5_owner, self.m5_classes, self.m5_maps = None, 0, ()
-        self.vjp_batch = self.unet_vjp_batch = self.classifier_vjp_batch = self.vgg_vjp_batch = 0     # rows per pass the VJP workspaces are reserved for
+        self.vjp_batch = self.unet_vjp_batch = self.classifier_vjp_batch = self.vgg_vjp_batch = self.wrn_vjp_batch = 0     # rows per pass the VJP workspaces are reserved for
         # which weights are resident (state_fingerprint): a module that binds to an engine holding OTHER weights must
         # not silently run them
         self.wavenet_owner = self.classifier_owner = self.unet_owner = None
@@ -355,6 +398,15 @@ class Engine:
             self.floor1 = max(self.floor1, self._committed_margin1())
             if self.recheck_margin < self.floor1:
                 self.set_recheck_margin(self.floor1, calibrated=True)
+
+    def load_wideresnet28_10(self, state_dict):
+        """models/wideresnet.py WideResNet-28-10 state dict -> engine (names prefixed 'wrn.').  No recheck bound has been measured for this
+        classifier: on an EXACT engine the vote loops refuse it in the exact-vote mode (DmadError with the library's reason)."""
+        if self.has_classifier:
+            raise DmadError('classifier weights are already loaded into this engine')
+        self._load(fold_wideresnet_state_dict(state_dict))
+        self.has_classifier = True
+        self.classifier_owner, self.classifier_kind = state_fingerprint(state_dict), 'wideresnet28_10'
 
     def load_m5(self, state_dict, stride: int = 16):
         """M5Net.M5 state dict -> engine (names prefixed 'm5.'); a part of its own beside the spectrogram classifier.  stride: conv1's."""
@@ -724,6 +776,27 @@ class Engine:
         check(self.lib.dmad_vgg_vjp_tape(self._h, int(index), int(B), _ptr(out), _stream()))
         return out
 
+    def reserve_wrn_vjp(self, max_batch: int):
+        """dmad_reserve_wrn_vjp: the workspace of wrn_vjp (the WideResNet forward's tape of 25 post-ReLU maps, the gradient maps and, once,
+        the backward weight images) for up to max_batch spectrograms per pass (capped at max_batch; a larger reservation replaces a
+        smaller one).  WideResNet engines of every precision; DmadError otherwise."""
+        self._reserve('wrn_vjp', max_batch, min(int(max_batch), self.max_batch))
+
+    def wrn_vjp(self, spec: torch.Tensor, g_logits: torch.Tensor, want_logits: bool = False):
+        """g_spec = (d logits / d spec)^T g_logits for logits = WideResNet-28-10(spec) on the fp32 tier ([B,1,32,32] or [B,32,32] ->
+        [B,32,32]).  want_logits: also return the logits, bit-identical to classify_tier(spec, 0).  Reserves on demand like vgg_vjp."""
+        return self._logits_vjp(self.lib.dmad_wrn_vjp, spec, g_logits, want_logits, None if self.wrn_vjp_batch else self.reserve_wrn_vjp)
+
+    def wrn_vjp_tape(self, index: int, B: int) -> torch.Tensor:
+        """dmad_wrn_vjp_tape: map `index` (0..24, WRN_TAPE_MAPS) of the last wrn_vjp call's tape, rows [0, B), NHWC [B,H,H,C] (test hook;
+        that call must have run as one pass)."""
+        if not 0 <= int(index) < len(WRN_TAPE_MAPS):
+            raise DmadError('tape map %d outside [0, %d]' % (index, len(WRN_TAPE_MAPS) - 1))
+        H, Cn = WRN_TAPE_MAPS[index]
+        out = torch.empty((int(B), H, H, Cn), device='cuda', dtype=torch.float32)
+        check(self.lib.dmad_wrn_vjp_tape(self._h, int(index), int(B), _ptr(out), _stream()))
+        return out
+
     # ------------------------------------------------------------------ the vote loops and their exact-vote mode (EXACT engines)
     def vote(self, logits: torch.Tensor, counts: torch.Tensor):
         lg = logits.detach().contiguous().float()
@@ -822,7 +895,10 @@ class Engine:
 
     def _committed_margin1(self) -> float:
         """the committed tier-1 bound for this engine's operand format and resident classifier kind"""
-        table = DEFAULT_RECHECK_MARGIN_RESNEXT29 if getattr(self, 'classifier_kind', None) == 'resnext29' else DEFAULT_RECHECK_MARGIN
+        kind = getattr(self, 'classifier_kind', None)
+        if kind == 'wideresnet28_10':
+            raise DmadError('no recheck bound has been measured for WideResNet-28-10: it has no committed margin')
+        table = DEFAULT_RECHECK_MARGIN_RESNEXT29 if kind == 'resnext29' else DEFAULT_RECHECK_MARGIN
         return table[self.half_type]
 
     def set_recheck_margin2(self, tau2: float, calibrated: bool = False):
@@ -1441,7 +1517,7 @@ def conv_f32(x: torch.Tensor, w: torch.Tensor, shift: Optional[torch.Tensor] = N
 def conv_f32_vjp(g_y: torch.Tensor, w: torch.Tensor, H: int, form: int = 0, stride: int = 1, groups: int = 1,
                  scale: Optional[torch.Tensor] = None, mask_y: Optional[torch.Tensor] = None, acc: Optional[torch.Tensor] = None, ldt: int = 0):
     """dmad_conv_f32_vjp — the data gradient of an NHWC conv (test hook; forms of include/dmad.h: 0 UNet conv, 1 UNet Upsample, 2
-    ResNeXt29, 3 VGG19_bn's dense 3x3 with its BN scale).  g_y fp32 [B,Ho,Ho,groups*M] (ldt channels with a padded 1x1 image), w [groups, taps, M, K] in the forward layout, H the
+    ResNeXt29, 3 VGG19_bn's dense 3x3 with its BN scale, 4 WideResNet's dense 3x3 / 1x1 at stride 1 or 2 with an optional scale).  g_y fp32 [B,Ho,Ho,groups*M] (ldt channels with a padded 1x1 image), w [groups, taps, M, K] in the forward layout, H the
     forward conv's input resolution.  Returns (g_x, wT, gm | None, work | None): the gradient, the packed weight image as the pack kernel
     wrote it, the masked gradient, and the dilated / pre-sum work map."""
     assert g_y.is_cuda and g_y.dtype == torch.float32 and w.dtype == torch.float32 and g_y.dim() == 4 and w.dim() == 4
@@ -1545,6 +1621,49 @@ def vgg_pool_relu_bwd(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     gpre = torch.empty_like(y)
     _op('dmad_vgg_pool_relu_bwd', _ptr(g), _ptr(y), B, H, Cn, _ptr(gpre))
     return gpre
+
+
+def wrn_preact(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
+    """dmad_wrn_preact: x [..., C] (NHWC), scale / shift [C] -> max(scale * x + shift, 0) (WideResNet's pre-activation) (test hook)."""
+    x, scale, shift = _f32(x), _f32(scale), _f32(shift)
+    Cn = x.shape[-1]
+    assert x.is_cuda and tuple(scale.shape) == (Cn,) and tuple(shift.shape) == (Cn,)
+    out = torch.empty_like(x)
+    _op('dmad_wrn_preact', _ptr(x), _ptr(scale), _ptr(shift), x.numel() // Cn, Cn, _ptr(out))
+    return out
+
+
+def wrn_preact_bwd(g: torch.Tensor, o: torch.Tensor, scale: torch.Tensor, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dmad_wrn_preact_bwd: g, o (the saved post-ReLU map), res (optional) [..., C], scale [C] -> res + (o > 0) * scale * g (test hook)."""
+    g, o, scale = _f32(g), _f32(o), _f32(scale)
+    Cn = g.shape[-1]
+    assert g.is_cuda and o.shape == g.shape and tuple(scale.shape) == (Cn,)
+    if res is not None:
+        res = _f32(res)
+        assert res.shape == g.shape
+    gx = torch.empty_like(g)
+    _op('dmad_wrn_preact_bwd', _ptr(g), _ptr(o), _ptr(scale), _ptr(res), g.numel() // Cn, Cn, _ptr(gx))
+    return gx
+
+
+def wrn_stem(spec: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """dmad_wrn_stem: spec [B,32,32], w [16,9] -> [B,32,32,16] (the 1 -> 16 3x3 conv, no BN, no ReLU) (test hook)."""
+    spec, w = _f32(spec), _f32(w)
+    B = spec.shape[0]
+    assert spec.is_cuda and tuple(spec.shape) == (B, 32, 32) and tuple(w.shape) == (16, 9)
+    out = torch.empty((B, 32, 32, 16), device=spec.device, dtype=torch.float32)
+    _op('dmad_wrn_stem', _ptr(spec), _ptr(w), B, _ptr(out))
+    return out
+
+
+def wrn_stem_bwd(g: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """dmad_wrn_stem_bwd: g [B,32,32,16], w [16,9] -> gspec [B,32,32] (the stem conv's backward) (test hook)."""
+    g, w = _f32(g), _f32(w)
+    B = g.shape[0]
+    assert g.is_cuda and tuple(g.shape) == (B, 32, 32, 16) and tuple(w.shape) == (16, 9)
+    gspec = torch.empty((B, 32, 32), device=g.device, dtype=torch.float32)
+    _op('dmad_wrn_stem_bwd', _ptr(g), _ptr(w), B, _ptr(gspec))
+    return gspec
 
 
 def rx_conv1_bwd(g: torch.Tensor, a: torch.Tensor, w: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:

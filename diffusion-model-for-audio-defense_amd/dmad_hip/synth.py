@@ -116,11 +116,16 @@ def vgg19_bn_state_dict(seed: int = 4321, num_classes: int = 10, in_channels: in
     return sd
 
 
-def _load_calibration(sd, name):
+def _load_calibration(sd, name, golden=False):
     """Overwrites entries of `sd` with the committed calibration data dmad_hip/data/<name> (BatchNorm running statistics, and for
-    ResNeXt29 the centred / scaled head): tests/golden/make_vgg_calib.py, tests/golden/make_classifier_calib.py."""
+    ResNeXt29 the centred / scaled head): tests/golden/make_vgg_calib.py, tests/golden/make_classifier_calib.py.  golden: the file
+    lies with the test fixtures, tests/golden/<name> of the repository (WideResNet: tests/golden/make_wrn_calib.py)."""
     import os
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', name)
+    here = os.path.dirname(os.path.abspath(__file__))
+    path = os.path.join(os.path.dirname(os.path.dirname(here)), 'tests', 'golden', name) if golden else os.path.join(here, 'data', name)
+    if not os.path.exists(path):
+        raise FileNotFoundError('%s is missing: the calibrated stand-in needs the repository\'s committed calibration data (calibrated=False '
+                                'gives the uncalibrated weights)' % path)
     with np.load(path) as z:
         for k in z.files:
             assert sd[k].shape == z[k].shape, k
@@ -214,6 +219,69 @@ def resnext29_state_dict(seed: int = 2929, num_classes: int = 10, in_channels: i
     sd['classifier.bias'] = _f32(rng.standard_normal(num_classes) * 0.1)
     if calibrated and seed == 2929 and num_classes == 10 and in_channels == 1:
         _load_calibration(sd, 'resnext29_calib_seed2929.npz')
+    return sd
+
+
+# WideResNet-28-10: the stem's and the three stages' widths, and (cin, cout, stride) of its 12 pre-activation blocks (block i = 4 * stage + k)
+# -- the one statement of the geometry: the engine's loader and the tests' float64 walk import it
+WRN_WIDTHS = (16, 160, 320, 640)
+WRN_BLOCKS = tuple((WRN_WIDTHS[st] if k == 0 else WRN_WIDTHS[st + 1], WRN_WIDTHS[st + 1], 2 if (k == 0 and st > 0) else 1)
+                   for st in range(3) for k in range(4))
+WRN_SEED = 2810
+
+
+def wideresnet28_10_state_dict(seed: int = WRN_SEED, num_classes: int = 10, in_channels: int = 1, calibrated: bool = True):
+    """fp32 numpy state dict for models/wideresnet.py WideResNet(depth=28, widen_factor=10, dropRate=0, num_classes=10, in_channels=1):
+    36.5 M parameters under the reference's keys (conv1, block{1,2,3}.layer.{k}.{bn1,conv1,bn2,conv2,convShortcut}, bn1, fc).  Conv
+    weights use the fan-out init of the reference's constructor.  The stem has no BatchNorm, so block 0's bn1 is the first one a dB image
+    meets: its statistics are sized for inputs around -20 dB +- 12, like the VGG's and the ResNeXt's first BN.  The residual stream is never
+    normalised (every BN sits in a branch or in front of the head), so conv2's branch is damped through bn2's gamma and the later bn1
+    statistics follow the stream's growth: the stack stays O(1).
+
+    With `calibrated` (and seed 2810) the BatchNorm running statistics and a centred, scaled head come from the committed data file
+    tests/golden/wideresnet28_10_calib_seed2810.npz of the repository (a test fixture: the stand-in serves the tests and the timing
+    tool; one calibration pass over spectrograms in the mel front-end's dB range, tests/golden/make_wrn_calib.py), so that several classes are predicted with top-2 margins of order one and every one of the 25 ReLU
+    maps is alive on a fraction of its units that is neither 0 nor 1."""
+    rng = np.random.default_rng(seed)
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+
+    def conv(name, cout, cin, k):
+        w = rng.standard_normal((cout, cin, k, k)) * np.sqrt(2.0 / (cout * k * k))      # fan_out mode
+        sd[name + '.weight'] = _f32(w)
+        return w
+
+    def bn(name, c, gamma=(0.6, 1.4), mean=None, var=None):
+        sd[name + '.weight'] = _f32(rng.uniform(*gamma, size=c))
+        sd[name + '.bias'] = _f32(rng.standard_normal(c) * 0.1)
+        sd[name + '.running_mean'] = _f32(rng.standard_normal(c) * 0.2 if mean is None else mean)
+        sd[name + '.running_var'] = _f32(rng.uniform(0.5, 1.5, size=c) if var is None else var)
+        sd[name + '.num_batches_tracked'] = np.asarray(1000, dtype=np.int64)
+
+    w = conv('conv1', WRN_WIDTHS[0], in_channels, 3)
+    wsum = w.reshape(WRN_WIDTHS[0], -1).sum(1)
+    wl2 = np.sqrt((w.reshape(WRN_WIDTHS[0], -1) ** 2).sum(1))
+    stream = 1.0                                       # the residual stream's variance, in units of its value behind block 0
+    for i, (cin, cout, _) in enumerate(WRN_BLOCKS):
+        st, k = divmod(i, 4)
+        p = 'block%d.layer.%d.' % (st + 1, k)
+        if st == 0 and k == 0:
+            bn(p + 'bn1', cin, mean=wsum * (-20.0), var=(wl2 * 12.0) ** 2 + 1.0)
+        else:
+            bn(p + 'bn1', cin, var=rng.uniform(0.5, 1.5, size=cin) * stream)
+        conv(p + 'conv1', cout, cin, 3)
+        # a conv's output variance under this init is ~ fan_in / fan_out of its (half-alive) input's second moment
+        bn(p + 'bn2', cout, gamma=(0.3, 0.7), var=rng.uniform(0.5, 1.5, size=cout) * (1.0 * cin / cout))
+        conv(p + 'conv2', cout, cout, 3)
+        if cin != cout:
+            conv(p + 'convShortcut', cout, cin, 1)
+            stream = 1.0
+        else:
+            stream += 0.25
+    bn('bn1', WRN_WIDTHS[3], var=rng.uniform(0.5, 1.5, size=WRN_WIDTHS[3]) * stream)
+    sd['fc.weight'] = _f32(rng.standard_normal((num_classes, WRN_WIDTHS[3])) * np.sqrt(2.0 / WRN_WIDTHS[3]))
+    sd['fc.bias'] = _f32(rng.standard_normal(num_classes) * 0.1)
+    if calibrated and seed == WRN_SEED and num_classes == 10 and in_channels == 1:
+        _load_calibration(sd, 'wideresnet28_10_calib_seed%d.npz' % seed, golden=True)
     return sd
 
 

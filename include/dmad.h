@@ -29,7 +29,7 @@ enum dmad_status {
     DMAD_ERR_INVALID = -1,      /* bad argument / unsupported configuration */
     DMAD_ERR_STATE = -2,        /* weights not finalised, batch larger than max_batch, ... */
     DMAD_ERR_HIP = -3,          /* a HIP runtime call failed */
-    DMAD_ERR_SHAPE = -4         /* a weight set whose geometry no kernel serves (the M5 part); the message names the field */
+    DMAD_ERR_SHAPE = -4         /* a weight set whose geometry no kernel serves (the M5 part, WideResNet); the message names the field */
 };
 
 enum dmad_precision {
@@ -103,6 +103,12 @@ const char* dmad_last_warning(void);
  * or, instead of the vgg.* set, ResNeXt29 8x64d (models/resnext.py:23-142; bottleneck i = 3 * stage + k, i = 0..8):
  *   rx.conv1.w[64,1,3,3]  rx.b{i}.reduce.w[D,cin]  rx.b{i}.conv.w[D,D/8,3,3]  rx.b{i}.expand.w[cout,D]
  *   rx.b{i}.short.w[cout,cin] (where cin != cout), each with .scale[M] .shift[M];  rx.fc.w[classes,1024] rx.fc.b
+ * or WideResNet-28-10 (models/wideresnet.py; block i = 4 * stage + k, i = 0..11; widths 16 / 160 / 320 / 640), recognised by wrn.conv1.w:
+ *   wrn.conv1.w[16,1,3,3]  wrn.b{i}.bn1.scale[cin] .bn1.shift[cin] (the pre-activation on the residual stream)
+ *   wrn.b{i}.conv1.w[cout,cin,3,3] .conv1.scale[cout] .conv1.shift[cout] (the folded bn2)  wrn.b{i}.conv2.w[cout,cout,3,3]
+ *   wrn.b{i}.short.w[cout,cin] (where cin != cout)  wrn.bn.scale[640] wrn.bn.shift[640]  wrn.fc.w[classes,640] wrn.fc.b
+ *   every shape is checked: DMAD_ERR_SHAPE for any other geometry, and the refused set is dropped.
+ * An engine holds one spectrogram classifier.
  * dmad_finalize_weights() packs whichever complete set (WaveNet, classifier) has been loaded and is not
  * packed yet into the MFMA/LDS layouts and uploads it; it may be called once per set. */
 int dmad_load_weight(dmad_engine* e, const char* name, const float* host, const int64_t* shape, int32_t ndim);
@@ -362,6 +368,33 @@ int dmad_masking_step(dmad_engine* e, const float* x, float* delta, const float*
 int dmad_reserve_vgg_vjp(dmad_engine* e, int32_t max_batch);
 int dmad_vgg_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s);
 int dmad_vgg_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s);
+
+/* The same trio for WideResNet-28-10 (models/wideresnet.py).  DESIGN §21.  The forward (dmad_classify and every surface behind it) runs
+ * on the fp32 tier whatever the tier asked for; its split counts follow from the layer and max_batch, so a sample's logits do not depend
+ * on its batch.  No recheck bound has been measured for this classifier: dmad_smooth_votes, dmad_eval_samples, dmad_spec_smooth_votes and
+ * dmad_spec_eval_samples return DMAD_ERR_STATE for it in DMAD_MODE_EXACT_VOTES (DMAD_MODE_FAST and DMAD_MODE_FP32 serve it;
+ * dmad_eval_samples only when it is asked for logits: a call for purified waveforms alone never reaches the classifier).
+ *
+ * dmad_reserve_wrn_vjp reserves, for up to max_batch spectrograms per pass: the TAPE of the fp32 forward — the 25 post-ReLU maps in forward
+ * order, o = relu(bn1(x)) and h = relu(bn2(conv1(o))) of blocks 0..11 and the final map, 2 310 144 floats (9.2 MB) per spectrogram —,
+ * seven gradient work maps (1 187 840 floats, 4.8 MB per spectrogram) and, on the first reservation, the backward images: every 3x3
+ * tap-flipped with m / k swapped (conv1's with bn2's scale folded in: wT[8 - tap][k][m] = w[tap][m][k] * scale[m]; conv2's plain), the
+ * three 1x1 shortcuts transposed (36.5 M floats, as large as the forward images).  Capped at the engine's max_batch; a larger reservation
+ * replaces a smaller one, a smaller one keeps the present.  Counted by dmad_device_bytes.
+ *
+ * dmad_wrn_vjp:  g_spec = (d logits / d spec)^T g_logits on the fp32 tier, shapes as dmad_vgg_vjp.  logits: optional (NULL), bit-identical
+ * to dmad_classify_tier(.., 0, ..).  Every engine precision.  B in [1, max_batch], in passes of the reservation's size.  The backward:
+ * dmad_rx_head_bwd's kernel on fc.w with the final bn's scale folded into its columns; per block, in reverse, conv2's data gradient, the
+ * ReLU mask of h, the shortcut's 1x1 at the output resolution (scattered into the even pixels at stride 2), conv1's data gradient (at
+ * stride 2 on the zero-dilated gradient) with the shortcut's as its residual, then dmad_wrn_preact_bwd; the stem's backward last.  No
+ * atomics; every GEMM gets the forward's slab and max_batch * H * H reference rows, so g_spec does not depend on B, on the row's place or
+ * on the reservation's size.  DMAD_ERR_STATE without a reservation, before the weights are finalised, or for another classifier.
+ *
+ * dmad_wrn_vjp_tape (test hook): map `index` (0..24: o / h of block index / 2, then the final map; NHWC) of the last call's tape, rows
+ * [0, B); valid when that call ran as one pass and B <= its B, DMAD_ERR_STATE otherwise. */
+int dmad_reserve_wrn_vjp(dmad_engine* e, int32_t max_batch);
+int dmad_wrn_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s);
+int dmad_wrn_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s);
 
 /* The reverse VP-SDE purifier of the reference's adaptive-attack driver (adaptive_attack_eval.py --defense Diffusion ->
  * diffusion_models/diffwave_sde.py RevDiffWave.audio_editing_sample: torchsde.sdeint_adjoint(RevVPSDE, method='euler', dt = 1/T)).
@@ -772,6 +805,9 @@ int dmad_conv_x3(const float* x, const float* x2, int32_t ksplit, const float* w
  *           scattered into the even pixels of g_x.  acc: the GEMM's residual (not with the stride-2 1x1).
  *   form 3  VGG19_bn's dense 3x3 convs (stride 1, one group, K % 16 == 0) with the eval-mode BN scale [M] folded into the image: wT
  *           [8 - tap][k][m] = w[tap][m][k] * scale[m]; mask_y (optional, g_y's shape) as in form 2; no acc, no ldt.
+ *   form 4  WideResNet's dense convs: the 3x3 (image as form 3, scale optional) or the 1x1 (wT [K][M]) at stride 1 or 2.  Stride 2: the 3x3
+ *           runs on the zero-dilated gradient (work [B][H][H][M]); the 1x1 runs at Ho (work [B][Ho][Ho][K]) and is scattered into the even
+ *           pixels of g_x.  acc: the GEMM's residual (not with the stride-2 1x1); mask_y as in form 2; no ldt.
  * M % 16 == 0, K % 4 == 0; H even with stride 2.  wT, gm and work are left as the kernels wrote them (the tests read them). */
 int dmad_conv_f32(const float* x, const float* x2, int32_t ksplit, const float* w, const float* scale, const float* shift, const float* res,
                   int32_t B, int32_t H, int32_t M, int32_t K, int32_t taps, int32_t stride, int32_t groups, int32_t relu, float* slab,
@@ -800,6 +836,15 @@ int dmad_rx_conv1_bwd(const float* g, const float* a, const float* w, const floa
  * [B][H][H][C], every element written once: a window's g at its first maximum in scan order (top-left, top-right, bottom-left,
  * bottom-right) where that maximum is > 0, zero elsewhere.  H even, C % 4 == 0. */
 int dmad_vgg_pool_relu_bwd(const float* g, const float* y, int32_t B, int32_t H, int32_t C, float* gpre, dmad_stream s);
+/* WideResNet's small kernels (csrc/wrn.hip), NHWC maps of n_px pixels x C channels (C % 4 == 0).  dmad_wrn_preact: out = max(scale[c] * x +
+ * shift[c], 0).  dmad_wrn_preact_bwd: gx = (res ? res : 0) + (o > 0 ? scale[c] * g : 0), o the saved post-ReLU map (-0.0 and negatives
+ * give 0), res optional.  dmad_wrn_stem: spec [B][32][32] -> out [B][32][32][16], the 1 -> 16 3x3 conv (w [16][9], zero padding, no BN, no
+ * ReLU).  dmad_wrn_stem_bwd: gspec [B][32][32] = sum over taps (ky, kx ascending) and c ascending of w[c][ky][kx] * g at (y + 1 - ky,
+ * x + 1 - kx), g [B][32][32][16]. */
+int dmad_wrn_preact(const float* x, const float* scale, const float* shift, int64_t n_px, int32_t C, float* out, dmad_stream s);
+int dmad_wrn_preact_bwd(const float* g, const float* o, const float* scale, const float* res, int64_t n_px, int32_t C, float* gx, dmad_stream s);
+int dmad_wrn_stem(const float* spec, const float* w, int32_t B, float* out, dmad_stream s);
+int dmad_wrn_stem_bwd(const float* g, const float* w, int32_t B, float* gspec, dmad_stream s);
 
 /* Bytes of device memory held by the engine. */
 int64_t dmad_device_bytes(const dmad_engine* e);
