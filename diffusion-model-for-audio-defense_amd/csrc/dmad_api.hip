@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <map>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -254,21 +255,16 @@ struct dmad_engine {
     bool rx_h16 = false;
     bool rx_x3 = false;                    // exact-vote engines: ResNeXt29's split-f16 tier (every conv as three f16 MFMAs per product: fp32-grade), tier 1 of the exact-vote loop
     h16_t *rxX16 = nullptr, *rxY16 = nullptr, *rxT1h = nullptr, *rxT2h = nullptr, *rxS16 = nullptr;
-    // ResNeXt29 VJP workspace (dmad_reserve_classifier_vjp): the tape of the fp32 forward — conv1's output and per bottleneck
-    // its post-ReLU T1 / T2 and block output Y — [rxvjpB] spectrograms per slot, and six gradient work maps of 32 x 32 x 1024 floats
-    struct RxTape { float* c1 = nullptr; float* t1[9] = {}; float* t2[9] = {}; float* y[9] = {}; };
-    int rxvjpB = 0;
-    float *rxvjp_tape = nullptr, *rxvjp_work = nullptr;
-    RxTape rx_tape;
-    // VGG19_bn VJP workspace (dmad_reserve_vgg_vjp): the tape of the fp32 forward — the 16 post-ReLU conv maps and the two
-    // post-ReLU FC vectors — [vgvjpB] spectrograms per slot, two gradient ping-pong maps of 32 x 32 x 64 floats per spectrogram and the
-    // backward weight images: convs 1 - 15 tap-flipped and transposed with the BN scale folded in, classifier.0 / .3 transposed
-    struct VggTape { float* c[16] = {}; float* f[2] = {}; };
-    int vgvjpB = 0, vgvjp_lastB = 0;       // lastB: rows of the last pass when the last call ran as one pass (dmad_vgg_vjp_tape), else 0
-    float *vgvjp_tape = nullptr, *vgvjp_work = nullptr;
+    // Classifier VJP workspace (dmad_reserve_classifier_vjp / _vgg_vjp / _wrn_vjp; an engine holds one classifier, so
+    // one workspace serves all three): the tape of the fp32 forward — the slots of cls_tape_layout in forward order, [cvjpB] spectrograms
+    // each — and the network's gradient work maps (kRxWork / kVggWork / kWrnWork)
+    struct TapeSlot { float* p = nullptr; size_t floats = 0; };    // floats per spectrogram
+    int cvjpB = 0, cvjp_lastB = 0;         // lastB: rows of the last pass when the last call ran as one pass (dmad_*_vjp_tape), else 0
+    float *cvjp_tape = nullptr, *cvjp_work = nullptr;
+    std::vector<TapeSlot> cvjp_slot;
+    // VGG19_bn's backward weight images: convs 1 - 15 tap-flipped and transposed with the BN scale folded in, classifier.0 / .3 transposed
     float* vconvwT[16] = {nullptr};
     float* vfcwT[2] = {nullptr};
-    VggTape vg_tape;
     // WideResNet-28-10 (models/wideresnet.py): 12 pre-activation blocks; w1 / w2: the 3x3 GEMM images [tap][cout][cin], ws the
     // 1x1 shortcut [cout][cin] of a stage's first block; s1 / b1: the folded bn1 (on the residual stream), s2 / b2: the folded bn2 (conv1's
     // epilogue); w1T / w2T / wsT: the backward images (conv1's with bn2's scale folded in), packed on the first VJP reservation
@@ -281,12 +277,6 @@ struct dmad_engine {
     float *wrn_stem = nullptr, *wrn_bns = nullptr, *wrn_bnb = nullptr, *wrn_fcw = nullptr, *wrn_fcb = nullptr;
     float* wrn_fcws = nullptr;              // fc.w with the final bn's scale folded into its columns: the head backward's image
     float *wrnX = nullptr, *wrnY = nullptr, *wrnO = nullptr, *wrnH = nullptr, *wrnS = nullptr, *wrnP = nullptr;   // NHWC work maps ([maxB] x 32 x 32 x 160) and the pooled vector
-    // WideResNet VJP workspace (dmad_reserve_wrn_vjp): the tape of the fp32 forward — o and h of blocks 0..11, then the final post-ReLU
-    // map, 25 slots of [wrnvjpB] spectrograms — and the gradient work maps
-    struct WrnTape { float* o[12] = {}; float* h[12] = {}; float* f = nullptr; };
-    int wrnvjpB = 0, wrnvjp_lastB = 0;
-    float *wrnvjp_tape = nullptr, *wrnvjp_work = nullptr;
-    WrnTape wrn_tape;
     // mel front-end VJP (dmad_mel_db_vjp): transposed filterbank [kMelLd][32] and DFT [2048][kDftKT] images, gradient maps of
     // melvjpB clips per pass (allocated on the first call)
     int melvjpB = 0;
@@ -411,6 +401,16 @@ int need_classifier(const dmad_engine* e) {      // ... and its weights finalise
     if (int r = need_with_classifier(e)) return r;
     return e->cls_final ? 0 : fail(DMAD_ERR_STATE, "classifier weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
 }
+// the classifiers by cls_kind: the network, the name its VJP goes by in the refusals, its VJP export and its reservation export
+const struct { const char *net, *vjp_of, *vjp, *reserve; } kCls[3] = {
+    {"VGG19_bn", "VGG19_bn", "dmad_vgg_vjp", "dmad_reserve_vgg_vjp"},
+    {"ResNeXt29", "classifier", "dmad_classify_vjp", "dmad_reserve_classifier_vjp"},
+    {"WideResNet-28-10", "WideResNet", "dmad_wrn_vjp", "dmad_reserve_wrn_vjp"}};
+int need_kind(const dmad_engine* e, int kind) {  // the finalised classifier is the one whose VJP, reservation or tape is asked for
+    CHK(need_classifier(e));
+    return e->cls_kind == kind ? 0 : fail(DMAD_ERR_STATE, "the %s VJP serves %s only: this engine holds %s (%s)", kCls[kind].vjp_of, kCls[kind].net,
+                                          kCls[e->cls_kind].net, kCls[e->cls_kind].vjp);
+}
 int need_m5(const dmad_engine* e) { return e->m5_final ? 0 : fail(DMAD_ERR_STATE, "M5 weights are not finalised (dmad_load_weight + dmad_finalize_weights)"); }
 int need_batch(const dmad_engine* e, int B) { return B >= 1 && B <= e->maxB ? 0 : fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB); }
 int need_path(const dmad_engine* e, int path) {  // a WaveNet path the caller names (dmad_wavenet_eps_path / dmad_eval_samples)
@@ -422,6 +422,46 @@ int need_path(const dmad_engine* e, int path) {  // a WaveNet path the caller na
 template <class Fn>
 int for_passes(int64_t total, int64_t cap, Fn fn) {
     for (int64_t off = 0; off < total; off += cap) CHK(fn(off, (int)(total - off < cap ? total - off : cap)));
+    return 0;
+}
+
+// ---- VJP reservations (dmad_reserve_*_vjp)
+// A backward weight image, allocated and packed once.  Its own pointer is its guard: a reservation that failed part of the way (out of
+// memory) keeps the images it had packed, and the next call packs exactly the missing ones
+template <class Fn>
+int pack_once(dmad_engine* e, float** image, size_t floats, Fn pack) {
+    if (*image) return 0;
+    CHK(e->alloc(image, floats));
+    pack();
+    return 0;
+}
+
+// One reservation of min(max_batch, e->*cap) clips per pass; e->*size is the present one.  need(): the export's preconditions in its own
+// order; bufs(): the buffers that scale with the pass size; pack(): the backward images that are still missing (pack_once); lay(vB):
+// allocates bufs() for vB clips and lays them out.  A smaller request returns 0 and touches nothing; a larger one releases the present
+// buffers first, and if anything then fails every one of them is released again: no half reservation stays behind, e->*size stays 0
+template <class Need, class Bufs, class Pack, class Lay>
+int reserve_vjp(dmad_engine* e, int max_batch, int dmad_engine::*cap, int dmad_engine::*size, Need need, Bufs bufs, Pack pack, Lay lay) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
+    if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
+    CHK(need());
+    const int vB = max_batch < e->*cap ? max_batch : e->*cap;
+    if (vB <= e->*size) return 0;
+    const std::vector<float**> held = bufs();
+    for (float** p : held) e->release(p);
+    e->*size = 0;
+    auto fill = [&]() -> int {
+        CHK(pack());
+        HIPCHK(hipGetLastError());
+        CHK(lay(vB));
+        HIPCHK(hipDeviceSynchronize());
+        return 0;
+    };
+    if (int r = fill()) {
+        for (float** p : held) e->release(p);
+        return r;
+    }
+    e->*size = vB;
     return 0;
 }
 
@@ -454,6 +494,15 @@ GemmF32Args nhwc_conv_args(const float* A, const float* scale, const float* shif
     g.A = A; g.X = X; g.C = C; g.scale = scale; g.shift = shift; g.M = M; g.K = K; g.taps = taps; g.ldc = ldc < 0 ? M : ldc; g.relu = relu;
     g.N = (long)B * Ho * Ho; g.mode = 2; g.H = H; g.W = H; g.Cin = K; g.ldx = ldx < 0 ? K : ldx; g.stride = stride; g.groups = groups; g.res = res;
     return g;
+}
+
+// a dense 3x3 conv's weights [M][K][3][3] as its GEMM image [tap][M][K]
+std::vector<float> conv3_image(const std::vector<float>& cw, int M, int K) {
+    std::vector<float> A((size_t)9 * M * K);
+    for (int co = 0; co < M; ++co)
+        for (int ci = 0; ci < K; ++ci)
+            for (int t = 0; t < 9; ++t) A[((size_t)t * M + co) * K + ci] = cw[((size_t)co * K + ci) * 9 + t];
+    return A;
 }
 
 int upload_h16(dmad_engine* e, const std::vector<float>& A, h16_t** wh) {
@@ -668,16 +717,8 @@ int finalize_classifier(dmad_engine* e) {
         snprintf(nm, sizeof nm, "vgg.conv%d.w", li);
         w = e->get(nm, {v, cin, 3, 3});
         if (!w) return DMAD_ERR_STATE;
-        const std::vector<float>& cw = w->v;
-        if (li == 0) {
-            CHK(e->upload(&e->vconv1w, cw));
-        } else {
-            std::vector<float> A((size_t)9 * v * cin);
-            for (int co = 0; co < v; ++co)
-                for (int ci = 0; ci < cin; ++ci)
-                    for (int t = 0; t < 9; ++t) A[((size_t)t * v + co) * cin + ci] = cw[((size_t)co * cin + ci) * 9 + t];
-            CHK(e->upload(&e->vconvw[li], A));
-        }
+        if (li == 0) CHK(e->upload(&e->vconv1w, w->v));
+        else CHK(e->upload(&e->vconvw[li], conv3_image(w->v, v, cin)));
         snprintf(nm, sizeof nm, "vgg.conv%d.scale", li);
         w = e->get(nm, {v}); if (!w) return DMAD_ERR_STATE;
         CHK(e->upload(&e->vscale[li], w->v));
@@ -832,20 +873,13 @@ int finalize_wrn(dmad_engine* e) {
     CHK(wget("wrn.bn.shift", {640}, &bnb));
     CHK(wget("wrn.fc.w", {nc, 640}, &fcw));
     CHK(wget("wrn.fc.b", {nc}, &fcb));
-    auto image = [&](const std::vector<float>& cw, int M, int K, float** dst) -> int {      // [M][K][3][3] -> [tap][M][K]
-        std::vector<float> A((size_t)9 * M * K);
-        for (int co = 0; co < M; ++co)
-            for (int ci = 0; ci < K; ++ci)
-                for (int t = 0; t < 9; ++t) A[((size_t)t * M + co) * K + ci] = cw[((size_t)co * K + ci) * 9 + t];
-        return e->upload(dst, A);
-    };
     CHK(e->upload(&e->wrn_stem, stem->v));
     for (int i = 0; i < 12; ++i) {
         dmad_engine::WrnBlock& b = e->wrn[i];
         CHK(e->upload(&b.s1, src[i].s1->v)); CHK(e->upload(&b.b1, src[i].b1->v));
-        CHK(image(src[i].w1->v, b.cout, b.cin, &b.w1));
+        CHK(e->upload(&b.w1, conv3_image(src[i].w1->v, b.cout, b.cin)));
         CHK(e->upload(&b.s2, src[i].s2->v)); CHK(e->upload(&b.b2, src[i].b2->v));
-        CHK(image(src[i].w2->v, b.cout, b.cout, &b.w2));
+        CHK(e->upload(&b.w2, conv3_image(src[i].w2->v, b.cout, b.cout)));
         if (src[i].ws) CHK(e->upload(&b.ws, src[i].ws->v));
     }
     CHK(e->upload(&e->wrn_bns, bns->v)); CHK(e->upload(&e->wrn_bnb, bnb->v));
@@ -864,16 +898,16 @@ int finalize_wrn(dmad_engine* e) {
 // WideResNet.forward on NHWC fp32 maps: the stem kernel, then per block the pre-activation o = relu(bn1(x)) (wrn.hip), conv1 with bn2 and
 // the ReLU in its epilogue, the shortcut (the raw x, or in a stage's first block the 1x1 conv of the ACTIVATED o) and conv2 with the
 // shortcut as its residual; the final pre-activation, the 8 x 8 average pool and the FC.  Every GEMM gets the split-K slab and the row
-// count of a max_batch launch, so a sample's logits do not depend on its batch.  tape != nullptr (the VJP; B <= wrnvjpB): o, h and the
-// final map go to the tape's slots instead of the work maps (same launches, same n_ref, same bits)
-int classify_wrn(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, const dmad_engine::WrnTape* tape = nullptr) {
+// count of a max_batch launch, so a sample's logits do not depend on its batch.  tape != nullptr (the VJP; B <= cvjpB): o and h of block i go
+// to the tape's slots 2 i and 2 i + 1 and the final map to slot 24 instead of the work maps (same launches, same n_ref, same bits)
+int classify_wrn(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, const dmad_engine::TapeSlot* tape = nullptr) {
     float *X = e->wrnX, *Y = e->wrnY;
     launch_wrn_stem(spec, e->wrn_stem, X, B, s);
     int H = 32;
     for (int i = 0; i < 12; ++i) {
         const dmad_engine::WrnBlock& b = e->wrn[i];
-        float* O = tape ? tape->o[i] : e->wrnO;
-        float* Hm = tape ? tape->h[i] : e->wrnH;
+        float* O = tape ? tape[2 * i].p : e->wrnO;
+        float* Hm = tape ? tape[2 * i + 1].p : e->wrnH;
         const int Ho = (H - 1) / b.stride + 1;
         const long nref_out = (long)e->maxB * Ho * Ho;
         launch_wrn_preact(X, b.s1, b.b1, O, (long)B * H * H, b.cin, s);
@@ -888,7 +922,7 @@ int classify_wrn(dmad_engine* e, const float* spec, int B, float* logits, hipStr
         std::swap(X, Y);
         H = Ho;
     }
-    float* F = tape ? tape->f : e->wrnO;
+    float* F = tape ? tape[24].p : e->wrnO;
     launch_wrn_preact(X, e->wrn_bns, e->wrn_bnb, F, (long)B * 64, 640, s);
     launch_avgpool_nhwc(F, e->wrnP, B, 64, 640, s);
     launch_gemm_f32(plain_gemm(e->wrn_fcw, e->wrnP, logits, nullptr, e->wrn_fcb, e->cfg.num_classes, 640, B, e->cfg.num_classes, 640, 0), s, e->slab,
@@ -980,17 +1014,18 @@ int classify_resnext_h16(dmad_engine* e, const float* spec, int B, float* logits
     return 0;
 }
 
-// CifarResNeXt.forward (models/resnext.py:133-142) on NHWC fp32 maps.  tape != nullptr (the classifier VJP; B <= rxvjpB): conv1's
-// output and every bottleneck's T1 / T2 / block output are written to the tape's slots instead of the work maps (same launches, same bits)
-int classify_resnext(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, const dmad_engine::RxTape* tape = nullptr) {
-    float *X = tape ? tape->c1 : e->rxX, *Y = e->rxY;
+// CifarResNeXt.forward (models/resnext.py:133-142) on NHWC fp32 maps.  tape != nullptr (the classifier VJP; B <= cvjpB): conv1's
+// output goes to the tape's slot 0 and bottleneck i's T1 / T2 / block output to slots 3 i + 1 / + 2 / + 3 instead of the work maps (same
+// launches, same bits)
+int classify_resnext(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, const dmad_engine::TapeSlot* tape = nullptr) {
+    float *X = tape ? tape[0].p : e->rxX, *Y = e->rxY;
     launch_vgg_conv1(spec, e->rxconv1.w, e->rxconv1.scale, e->rxconv1.shift, X, B, s);      // 1 -> 64, 3x3, BN, ReLU
     int H = 32;
     for (int i = 0; i < 9; ++i) {
         const dmad_engine::RxBlock& b = e->rx[i];
-        float* T1 = tape ? tape->t1[i] : e->rxT1;
-        float* T2 = tape ? tape->t2[i] : e->rxT2;
-        if (tape) Y = tape->y[i];
+        float* T1 = tape ? tape[3 * i + 1].p : e->rxT1;
+        float* T2 = tape ? tape[3 * i + 2].p : e->rxT2;
+        if (tape) Y = tape[3 * i + 3].p;
         const int Ho = (H - 1) / b.stride + 1;
         const long Nin = (long)B * H * H, Nout = (long)B * Ho * Ho, nref_in = (long)e->maxB * H * H, nref_out = (long)e->maxB * Ho * Ho;
         // conv_reduce + bn_reduce + ReLU (1x1)
@@ -1033,10 +1068,7 @@ inline bool un_attn_at(int ds) { return ds == 2 || ds == 4; }
 
 int un_conv3(dmad_engine* e, const std::string& name, int cout, int cin, float** w, float** b, h16_t** wh = nullptr, float** wx = nullptr) {
     const HostW* h = e->get(name + ".weight", {cout, cin, 3, 3}); if (!h) return DMAD_ERR_STATE;
-    std::vector<float> A((size_t)9 * cout * cin);
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int t = 0; t < 9; ++t) A[((size_t)t * cout + co) * cin + ci] = h->v[((size_t)co * cin + ci) * 9 + t];
+    const std::vector<float> A = conv3_image(h->v, cout, cin);
     CHK(e->upload(w, A));
     if (wh && e->un_h16) CHK(upload_h16(e, A, wh));
     if (wx && e->un_x3) CHK(upload_split(e, A, wx));
@@ -1660,10 +1692,41 @@ int mel_db(dmad_engine* e, const float* x, int B, float* spec, hipStream_t s, in
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Classifier-side vector-Jacobian products: the ResNeXt29 input VJP on its fp32 tier and the mel front-end VJP.
-// Both recompute their forward; every GEMM runs without split-K and every small kernel reduces in a fixed order, so the
-// gradients are bit-reproducible and do not depend on the batch.
+// Classifier-side vector-Jacobian products: the input VJPs of ResNeXt29, VGG19_bn (§18) and WideResNet-28-10 (§21) on
+// their fp32 forwards — one pass function per network, one tape layout, driver and tape reader for all three (cls_vjp, cls_vjp_tape) —
+// the mel front-end VJP (§14) and the masking loss on its maps (§20); the VGG19_bn forward and the classifier dispatch sit here too.
+// Every VJP recomputes its forward.  ResNeXt29's and the mel VJP's GEMMs run without split-K, VGG19_bn's and WideResNet's with the split
+// count of a max_batch launch, and every small kernel reduces in a fixed order: the gradients are bit-reproducible and do not depend on
+// the batch.
 // ---------------------------------------------------------------------------------------------------------------
+// floats per spectrogram of the tape's slots, in forward order.  ResNeXt29, 28 slots: conv1's output, then per bottleneck its post-ReLU T1
+// (input resolution), T2 and block output Y (output resolution)
+std::vector<size_t> rx_tape_layout(const dmad_engine* e) {
+    std::vector<size_t> f{(size_t)1024 * 64};
+    size_t H = 32, Hi;
+    for (const auto& b : e->rx) { Hi = H; H = (H - 1) / b.stride + 1; f.insert(f.end(), {Hi * Hi * b.D, H * H * b.D, H * H * b.cout}); }
+    return f;
+}
+// VGG19_bn, 18 slots: the 16 post-ReLU conv maps, then the two post-ReLU FC vectors (311 296 floats in all)
+std::vector<size_t> vgg_tape_layout() {
+    std::vector<size_t> f;
+    size_t H = 32;
+    for (int v : kVggCfg) { if (v < 0) H >>= 1; else f.push_back(H * H * v); }
+    f.insert(f.end(), {4096, 4096});
+    return f;
+}
+// WideResNet, 25 slots: o (input resolution) and h (output resolution) of blocks 0..11, then the final post-ReLU map
+std::vector<size_t> wrn_tape_layout(const dmad_engine* e) {
+    std::vector<size_t> f;
+    size_t H = 32;
+    for (const auto& b : e->wrn) { f.push_back(H * H * b.cin); H = (H - 1) / b.stride + 1; f.push_back(H * H * b.cout); }
+    f.push_back(H * H * 640);
+    return f;
+}
+// the engine's classifier: the slots' offsets, the tape's size (dmad_reserve_*_vjp) and the reader's bounds (dmad_*_vjp_tape) follow from this list
+std::vector<size_t> cls_tape_layout(const dmad_engine* e) {
+    return e->cls_kind == 1 ? rx_tape_layout(e) : e->cls_kind == 2 ? wrn_tape_layout(e) : vgg_tape_layout();
+}
 constexpr int kDftKT = 2064;             // K of the DFT^T GEMM: the 2050 re / im rows padded to a multiple of 16
 
 // floats per spectrogram of the six gradient work maps of rx_vjp_pass: block in / out gradients (32 x 32 x 256 at most), g_T2, its
@@ -1696,26 +1759,26 @@ int rx_conv_dgrad(const float* wT, const float* g, float* gx, int M, int K, int 
     return 0;
 }
 
-// g_spec = (d logits / d spec)^T g_logits of classify_resnext; logits: the forward it recomputes (B <= rxvjpB)
+// g_spec = (d logits / d spec)^T g_logits of classify_resnext; logits: the forward it recomputes (B <= cvjpB)
 int rx_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
-    const dmad_engine::RxTape& tp = e->rx_tape;
-    CHK(classify_resnext(e, spec, B, logits, s, &tp));
+    const dmad_engine::TapeSlot* tp = e->cvjp_slot.data();          // slot 0: conv1's output, 3 i + 1 / + 2 / + 3: T1 / T2 / Y of bottleneck i
+    CHK(classify_resnext(e, spec, B, logits, s, tp));
     float* G[6];
-    G[0] = e->rxvjp_work;
-    for (int k = 1; k < 6; ++k) G[k] = G[k - 1] + kRxWork[k - 1] * e->rxvjpB;
-    float *gT = G[2], *gD = G[3], *gU = G[4], *gS = G[5], *gSd = G[5] + 65536l * e->rxvjpB;
+    G[0] = e->cvjp_work;
+    for (int k = 1; k < 6; ++k) G[k] = G[k - 1] + kRxWork[k - 1] * e->cvjpB;
+    float *gT = G[2], *gD = G[3], *gU = G[4], *gS = G[5], *gSd = G[5] + 65536l * e->cvjpB;
     // head: FC, 8 x 8 average pool and the last block's ReLU in one kernel
-    launch_rx_head_bwd(g_logits, e->rxfcw, tp.y[8], G[0], B, e->cfg.num_classes, 64, 1024, s);
+    launch_rx_head_bwd(g_logits, e->rxfcw, tp[27].p, G[0], B, e->cfg.num_classes, 64, 1024, s);
     float *cur = G[0], *nxt = G[1];
     int H = 8;
     for (int i = 8; i >= 0; --i) {
         const dmad_engine::RxBlock& b = e->rx[i];
         const int Ho = H, Hin = Ho * b.stride, Gc = b.D / 8;
-        if (i < 8) launch_relu_mask(cur, tp.y[i], cur, (long)B * Ho * Ho * b.cout, s);     // the block output's ReLU
+        if (i < 8) launch_relu_mask(cur, tp[3 * i + 3].p, cur, (long)B * Ho * Ho * b.cout, s);     // the block output's ReLU
         CHK(rx_conv_dgrad(b.expand.wT, cur, gT, b.D, b.cout, 1, 1, B, Ho, 1, nullptr, nullptr, s));     // conv_expand (1x1) + bn_expand
-        launch_relu_mask(gT, tp.t2[i], gT, (long)B * Ho * Ho * b.D, s);
+        launch_relu_mask(gT, tp[3 * i + 2].p, gT, (long)B * Ho * Ho * b.D, s);
         CHK(rx_conv_dgrad(b.conv.wT, gT, gU, Gc, Gc, 9, 8, B, Ho, b.stride, gD, nullptr, s));          // grouped 3x3 (stride) + bn
-        launch_relu_mask(gU, tp.t1[i], gU, (long)B * Hin * Hin * b.D, s);
+        launch_relu_mask(gU, tp[3 * i + 1].p, gU, (long)B * Hin * Hin * b.D, s);
         const float* res = cur;                                                              // identity shortcut
         if (b.has_short) {                                                                   // 1x1 (stride) + bn at the output resolution,
             float* gsc = b.stride == 2 ? gSd : gS;                                           // scattered into the even pixels
@@ -1726,20 +1789,9 @@ int rx_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits,
         std::swap(cur, nxt);
         H = Hin;
     }
-    launch_rx_conv1_bwd(cur, tp.c1, e->rxconv1.w, e->rxconv1.scale, g_spec, B, s);            // conv1's ReLU, bn and 1 <- 64 3x3 conv
+    launch_rx_conv1_bwd(cur, tp[0].p, e->rxconv1.w, e->rxconv1.scale, g_spec, B, s);            // conv1's ReLU, bn and 1 <- 64 3x3 conv
     LASTCHK();
     return 0;
-}
-
-int classify_vjp(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
-    CHK(need_classifier(e));
-    if (e->cls_kind != 1) return fail(DMAD_ERR_STATE, "the classifier VJP serves ResNeXt29 only: this engine holds %s", e->cls_kind == 2 ? "WideResNet-28-10 (dmad_wrn_vjp)" : "VGG19_bn");
-    if (!e->rxvjpB) return fail(DMAD_ERR_STATE, "no classifier VJP workspace: call dmad_reserve_classifier_vjp first");
-    CHK(need_batch(e, B));
-    const int nc = e->cfg.num_classes;
-    return for_passes(B, e->rxvjpB, [&](int64_t b0, int bb) {
-        return rx_vjp_pass(e, spec + b0 * 1024, bb, g_logits + b0 * nc, g_spec + b0 * 1024, logits ? logits + b0 * nc : e->logits, s);
-    });
 }
 
 // first call: the transposed filterbank / DFT images and the gradient maps of up to 64 clips per pass
@@ -1811,17 +1863,17 @@ int masking(dmad_engine* e, const float* delta, int B, const float* theta, const
 // h16 = 1: the classifier's 16-bit tier where one is resident (ResNeXt29 on engines with a 16-bit side) — the fast mode's; 2: its
 // split-f16 tier (exact-vote engines) — tier 1 of the exact-vote loops; every other caller (dmad_classify, the recheck tiers) gets the
 // fp32 matrix cores
-// VGG19_bn on the fp32 matrix cores.  tape (the VJP's forward): every conv writes its post-ReLU map and the first two Linear layers
-// their post-ReLU vectors into the tape's slots in place of act0 / act1 — the same launches with the same n_ref, so the same bits —
+// VGG19_bn on the fp32 matrix cores.  tape (the VJP's forward): conv li writes its post-ReLU map into the tape's slot li and the first two Linear
+// layers their post-ReLU vectors into slots 16 and 17 in place of act0 / act1 — the same launches with the same n_ref, so the same bits —
 // and only the pooled maps pass through act0
-int classify_vgg(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, const dmad_engine::VggTape* tape = nullptr) {
+int classify_vgg(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, const dmad_engine::TapeSlot* tape = nullptr) {
     auto spare = [&](const float* in) { return in == e->act0 ? e->act1 : e->act0; };      // the work map `in` does not occupy
-    float* cur = tape ? tape->c[0] : e->act0;
+    float* cur = tape ? tape[0].p : e->act0;
     launch_vgg_conv1(spec, e->vconv1w, e->vscale[0], e->vshift[0], cur, B, s);
     int H = 32, cin = 64, li = 1;
     for (int i = 1; i < kVggCfgLen; ++i) {
         const int v = kVggCfg[i];
-        float* nxt = (tape && v > 0) ? tape->c[li] : spare(cur);
+        float* nxt = (tape && v > 0) ? tape[li].p : spare(cur);
         if (v < 0) {
             launch_maxpool2_nhwc(cur, nxt, B, H, H, cin, s);
             H >>= 1;
@@ -1835,7 +1887,7 @@ int classify_vgg(dmad_engine* e, const float* spec, int B, float* logits, hipStr
     }
     const int fin[3] = {512, 4096, 4096}, fout[3] = {4096, 4096, e->cfg.num_classes};
     for (int j = 0; j < 3; ++j) {
-        float* dst = (j == 2) ? logits : tape ? tape->f[j] : spare(cur);
+        float* dst = (j == 2) ? logits : tape ? tape[16 + j].p : spare(cur);
         launch_gemm_f32(plain_gemm(e->vfcw[j], cur, dst, nullptr, e->vfcb[j], fout[j], fin[j], B, fout[j], fin[j], j < 2), s, e->slab,
                         e->slab_floats, (long)e->maxB);
         cur = dst;
@@ -1852,16 +1904,6 @@ int classify(dmad_engine* e, const float* spec, int B, float* logits, hipStream_
     return classify_vgg(e, spec, B, logits, s);
 }
 
-// floats per spectrogram of the VGG19_bn tape's slots: the 16 post-ReLU conv maps, then the two post-ReLU FC vectors (311 296 in all)
-size_t vgg_tape_floats(int index) {
-    if (index >= 16) return 4096;
-    int H = 32, li = 0;
-    for (int i = 0; i < kVggCfgLen; ++i) {
-        if (kVggCfg[i] < 0) { H >>= 1; continue; }
-        if (li++ == index) return (size_t)H * H * kVggCfg[i];
-    }
-    return 0;
-}
 constexpr size_t kVggWork = 65536;       // floats per spectrogram of one gradient ping-pong map: 32 x 32 x 64, the largest map
 
 // The data gradient of a dense VGG19_bn 3x3 conv on its packed image (launch_cvjp_pack_dense): g [B][H][H][M] -> gx [B][H][H][K], the
@@ -1873,20 +1915,20 @@ int vgg_conv_dgrad(const float* wT, const float* g, float* gx, int M, int K, int
     return 0;
 }
 
-// g_spec = (d logits / d spec)^T g_logits of classify_vgg; logits: the forward it recomputes (B <= vgvjpB)
+// g_spec = (d logits / d spec)^T g_logits of classify_vgg; logits: the forward it recomputes (B <= cvjpB)
 int vgg_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
-    const dmad_engine::VggTape& tp = e->vg_tape;
-    CHK(classify_vgg(e, spec, B, logits, s, &tp));
-    float *cur = e->vgvjp_work, *nxt = e->vgvjp_work + kVggWork * e->vgvjpB;
+    const dmad_engine::TapeSlot* tp = e->cvjp_slot.data();          // slots 0..15: the conv maps, 16 / 17: the FC vectors
+    CHK(classify_vgg(e, spec, B, logits, s, tp));
+    float *cur = e->cvjp_work, *nxt = e->cvjp_work + kVggWork * e->cvjpB;
     auto rows = [&](const float* wT, const float* g, float* out, int M, int K) -> int {      // out [B][M] = g [B][K] wT[M][K]^T
         if (launch_gemm_f32(plain_gemm(wT, g, out, nullptr, nullptr, M, K, B, M, K, 0), s, e->slab, e->slab_floats, (long)e->maxB) != 0)
             return fail(DMAD_ERR_STATE, "VGG19_bn VJP: no GEMM for M = %d, K = %d", M, K);
         return 0;
     };
     // classifier.6 (num_classes reduction elements, k ascending) with classifier.4's ReLU, then classifier.3 / .0 on their transposed images
-    launch_rx_head_bwd(g_logits, e->vfcw[2], tp.f[1], cur, B, e->cfg.num_classes, 1, 4096, s);
+    launch_rx_head_bwd(g_logits, e->vfcw[2], tp[17].p, cur, B, e->cfg.num_classes, 1, 4096, s);
     CHK(rows(e->vfcwT[1], cur, nxt, 4096, 4096));
-    launch_relu_mask(nxt, tp.f[0], nxt, (long)B * 4096, s);
+    launch_relu_mask(nxt, tp[16].p, nxt, (long)B * 4096, s);
     CHK(rows(e->vfcwT[0], nxt, cur, 512, 4096));                                             // the gradient at the last pool's output
     int H = 1, li = 16;
     bool masked = false;                 // cur is the gradient at a ReLU's input (after a pool) / at its output (after a conv)
@@ -1894,68 +1936,42 @@ int vgg_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits
         const int v = kVggCfg[i];
         if (v < 0) {                     // the pool and the ReLU of conv li - 1 in front of it
             H <<= 1;
-            launch_vgg_pool_relu_bwd(cur, tp.c[li - 1], nxt, B, H, kVggCfg[i - 1], s);
+            launch_vgg_pool_relu_bwd(cur, tp[li - 1].p, nxt, B, H, kVggCfg[i - 1], s);
             masked = true;
         } else {                         // conv li - 1 (its input: conv li - 2's map, or a pooled one) with its BN scale
             --li;
-            if (!masked) launch_relu_mask(cur, tp.c[li], cur, (long)B * H * H * v, s);
+            if (!masked) launch_relu_mask(cur, tp[li].p, cur, (long)B * H * H * v, s);
             const int cin = kVggCfg[i - 1] > 0 ? kVggCfg[i - 1] : kVggCfg[i - 2];
             CHK(vgg_conv_dgrad(e->vconvwT[li], cur, nxt, v, cin, B, H, e->slab, e->slab_floats, (long)e->maxB * H * H, s));
             masked = false;
         }
         std::swap(cur, nxt);
     }
-    launch_rx_conv1_bwd(cur, tp.c[0], e->vconv1w, e->vscale[0], g_spec, B, s);               // conv 0's ReLU, bn and 1 <- 64 3x3 conv
+    launch_rx_conv1_bwd(cur, tp[0].p, e->vconv1w, e->vscale[0], g_spec, B, s);               // conv 0's ReLU, bn and 1 <- 64 3x3 conv
     LASTCHK();
     return 0;
 }
 
-int need_vgg(const dmad_engine* e) {
-    CHK(need_classifier(e));
-    return e->cls_kind == 0 ? 0 : fail(DMAD_ERR_STATE, "the VGG19_bn VJP serves VGG19_bn only: this engine holds %s", e->cls_kind == 2 ? "WideResNet-28-10 (dmad_wrn_vjp)" : "ResNeXt29 (dmad_classify_vjp)");
-}
-
-int vgg_vjp(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
-    CHK(need_vgg(e));
-    if (!e->vgvjpB) return fail(DMAD_ERR_STATE, "no VGG19_bn VJP workspace: call dmad_reserve_vgg_vjp first");
-    CHK(need_batch(e, B));
-    const int nc = e->cfg.num_classes;
-    e->vgvjp_lastB = 0;
-    CHK(for_passes(B, e->vgvjpB, [&](int64_t b0, int bb) {
-        return vgg_vjp_pass(e, spec + b0 * 1024, bb, g_logits + b0 * nc, g_spec + b0 * 1024, logits ? logits + b0 * nc : e->logits, s);
-    }));
-    if (B <= e->vgvjpB) e->vgvjp_lastB = B;
-    return 0;
-}
-
-// (H, C) of the WideResNet tape's slot `index`: o / h of block index / 2, then the final map; floats per spectrogram = H * H * C
-void wrn_tape_map(const dmad_engine* e, int index, int* H, int* C) {
-    if (index >= 24) { *H = 8; *C = 640; return; }
-    const int i = index / 2, Hin = i < 4 ? 32 : i < 8 ? (i == 4 ? 32 : 16) : (i == 8 ? 16 : 8);
-    const dmad_engine::WrnBlock& b = e->wrn[i];
-    if (index & 1) { *H = Hin / b.stride; *C = b.cout; }
-    else { *H = Hin; *C = b.cin; }
-}
 // floats per spectrogram of the gradient work maps of wrn_vjp_pass: the block out / in gradients, g_h, its zero-dilation (stage 2's first
 // block: 32 x 32 x 320), g_o, the shortcut's gradient at the output resolution (16 x 16 x 160 at most) and at the input resolution
 const size_t kWrnWork[7] = {kWrnMap, kWrnMap, kWrnMap, 2 * kWrnMap, kWrnMap, kWrnMap / 4, kWrnMap};
 
-// g_spec = (d logits / d spec)^T g_logits of classify_wrn; logits: the forward it recomputes (B <= wrnvjpB)
+// g_spec = (d logits / d spec)^T g_logits of classify_wrn; logits: the forward it recomputes (B <= cvjpB)
 int wrn_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
-    const dmad_engine::WrnTape& tp = e->wrn_tape;
-    CHK(classify_wrn(e, spec, B, logits, s, &tp));
+    const dmad_engine::TapeSlot* tp = e->cvjp_slot.data();          // slots 2 i / 2 i + 1: o / h of block i, 24: the final map
+    CHK(classify_wrn(e, spec, B, logits, s, tp));
     float* G[7];
-    G[0] = e->wrnvjp_work;
-    for (int k = 1; k < 7; ++k) G[k] = G[k - 1] + kWrnWork[k - 1] * e->wrnvjpB;
+    G[0] = e->cvjp_work;
+    for (int k = 1; k < 7; ++k) G[k] = G[k - 1] + kWrnWork[k - 1] * e->cvjpB;
     float *cur = G[0], *nxt = G[1], *gh = G[2], *gD = G[3], *go = G[4], *gS = G[5], *gSd = G[6];
     // head: FC^T (on the image that carries the final bn's scale), the 8 x 8 average pool and the last ReLU's mask: the gradient at block 11's output
-    launch_rx_head_bwd(g_logits, e->wrn_fcws, tp.f, cur, B, e->cfg.num_classes, 64, 640, s);
+    launch_rx_head_bwd(g_logits, e->wrn_fcws, tp[24].p, cur, B, e->cfg.num_classes, 64, 640, s);
     int H = 8;
     for (int i = 11; i >= 0; --i) {
         const dmad_engine::WrnBlock& b = e->wrn[i];
         const int Ho = H, Hin = Ho * b.stride;
         CHK(rx_conv_dgrad(b.w2T, cur, gh, b.cout, b.cout, 9, 1, B, Ho, 1, nullptr, nullptr, s, e->slab, e->slab_floats, e->maxB));       // conv2
-        launch_relu_mask(gh, tp.h[i], gh, (long)B * Ho * Ho * b.cout, s);                                                                // relu2 (bn2's scale is in w1T)
+        launch_relu_mask(gh, tp[2 * i + 1].p, gh, (long)B * Ho * Ho * b.cout, s);                                                                // relu2 (bn2's scale is in w1T)
         const float* gsc = nullptr;
         if (b.wsT) {                                                                                                                     // the 1x1 shortcut of the activated input
             float* out = b.stride == 2 ? gSd : gS;
@@ -1963,7 +1979,7 @@ int wrn_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits
             gsc = out;
         }
         CHK(rx_conv_dgrad(b.w1T, gh, go, b.cin, b.cout, 9, 1, B, Ho, b.stride, gD, gsc, s, e->slab, e->slab_floats, e->maxB));            // conv1 (stride) + the shortcut's
-        launch_wrn_preact_bwd(go, tp.o[i], b.s1, b.wsT ? nullptr : cur, nxt, (long)B * Hin * Hin, b.cin, s);                             // relu1, bn1, + the identity shortcut
+        launch_wrn_preact_bwd(go, tp[2 * i].p, b.s1, b.wsT ? nullptr : cur, nxt, (long)B * Hin * Hin, b.cin, s);                             // relu1, bn1, + the identity shortcut
         std::swap(cur, nxt);
         H = Hin;
     }
@@ -1972,23 +1988,56 @@ int wrn_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits
     return 0;
 }
 
-int need_wrn(const dmad_engine* e) {
-    CHK(need_classifier(e));
-    return e->cls_kind == 2 ? 0 : fail(DMAD_ERR_STATE, "the WideResNet VJP serves WideResNet-28-10 only: this engine holds %s",
-                                       e->cls_kind == 1 ? "ResNeXt29 (dmad_classify_vjp)" : "VGG19_bn (dmad_vgg_vjp)");
-}
-
-int wrn_vjp(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
-    CHK(need_wrn(e));
-    if (!e->wrnvjpB) return fail(DMAD_ERR_STATE, "no WideResNet VJP workspace: call dmad_reserve_wrn_vjp first");
+// dmad_classify_vjp / dmad_vgg_vjp / dmad_wrn_vjp: the VJP of classifier `kind` in passes of the reservation; lastB remembers a one-pass call
+// for the tape reader
+int cls_vjp(dmad_engine* e, int kind, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
+    if (!e || !spec || !g_logits || !g_spec) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(need_kind(e, kind));
+    if (!e->cvjpB) return fail(DMAD_ERR_STATE, "no %s VJP workspace: call %s first", kCls[kind].vjp_of, kCls[kind].reserve);
     CHK(need_batch(e, B));
     const int nc = e->cfg.num_classes;
-    e->wrnvjp_lastB = 0;
-    CHK(for_passes(B, e->wrnvjpB, [&](int64_t b0, int bb) {
-        return wrn_vjp_pass(e, spec + b0 * 1024, bb, g_logits + b0 * nc, g_spec + b0 * 1024, logits ? logits + b0 * nc : e->logits, s);
+    const auto pass = kind == 1 ? rx_vjp_pass : kind == 2 ? wrn_vjp_pass : vgg_vjp_pass;
+    e->cvjp_lastB = 0;
+    CHK(for_passes(B, e->cvjpB, [&](int64_t b0, int bb) {
+        return pass(e, spec + b0 * 1024, bb, g_logits + b0 * nc, g_spec + b0 * 1024, logits ? logits + b0 * nc : e->logits, s);
     }));
-    if (B <= e->wrnvjpB) e->wrnvjp_lastB = B;
+    if (B <= e->cvjpB) e->cvjp_lastB = B;
     return 0;
+}
+
+// dmad_vgg_vjp_tape / dmad_wrn_vjp_tape: slot `index` of the tape a one-pass call left, B rows
+int cls_vjp_tape(dmad_engine* e, int kind, int index, int B, float* out, hipStream_t s) {
+    if (!e || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(need_kind(e, kind));
+    const int slots = (int)cls_tape_layout(e).size();
+    if (index < 0 || index >= slots) return fail(DMAD_ERR_INVALID, "tape map %d outside [0, %d]", index, slots - 1);
+    if (B < 1 || B > e->cvjp_lastB) return fail(DMAD_ERR_STATE, "the tape holds %d rows of a one-pass %s call, not %d", e->cvjp_lastB, kCls[kind].vjp, B);
+    const dmad_engine::TapeSlot& t = e->cvjp_slot[index];
+    HIPCHK(hipMemcpyAsync(out, t.p, (size_t)B * t.floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// the reservation of classifier `kind`'s VJP: its tape and `work` floats of gradient maps per spectrogram; pack(): its backward images
+template <class Pack>
+int reserve_cls_vjp(dmad_engine* e, int max_batch, int kind, size_t work, Pack pack) {
+    return reserve_vjp(
+        e, max_batch, &dmad_engine::maxB, &dmad_engine::cvjpB, [&] { return need_kind(e, kind); },
+        [&] { return std::vector<float**>{&e->cvjp_tape, &e->cvjp_work}; },
+        [&]() -> int {
+            e->cvjp_lastB = 0;               // the tape a reader could ask for is gone
+            e->cvjp_slot.clear();
+            return pack();
+        },
+        [&](int vB) -> int {
+            const std::vector<size_t> lay = cls_tape_layout(e);
+            size_t tape = 0;
+            for (size_t f : lay) tape += f;
+            CHK(e->alloc(&e->cvjp_tape, (size_t)vB * tape));
+            CHK(e->alloc(&e->cvjp_work, (size_t)vB * work));
+            float* at = e->cvjp_tape;
+            for (size_t f : lay) { e->cvjp_slot.push_back({at, f}); at += f * vB; }
+            return 0;
+        });
 }
 
 // the exact-vote loops refuse a WideResNet engine: no recheck bound has been measured for this classifier
@@ -2828,31 +2877,32 @@ int dmad_spec_recheck_stats2(dmad_engine* e, int64_t* samples, int64_t* rechecke
 }
 
 int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
-    if (!e->f32) return fail(DMAD_ERR_STATE, "the WaveNet VJP runs on the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights");
-    CHK(need_wavenet(e));
-    const int vB = max_batch < e->maxB32 ? max_batch : e->maxB32;
-    if (vB <= e->vjpB) return 0;
-    const size_t LP = e->LP, NL = e->NL;
-    if (e->vjpB) {                          // a larger reservation replaces the present one
-        e->release(&e->vjp_save); e->release(&e->vjp_gH); e->release(&e->vjp_G); e->release(&e->vjp_gg); e->release(&e->vjp_g2);
-        e->vjpB = 0;
-    }
-    if (!e->vjp_wdilT) {
-        CHK(e->alloc(&e->vjp_wdilT, NL * 3 * 256 * 512)); CHK(e->alloc(&e->vjp_wgT, NL * 2 * 256 * 256)); CHK(e->alloc(&e->vjp_wf0T, 256 * 256));
-        launch_vjp_pack(e->wdil, e->wrs, e->wf0, e->vjp_wdilT, e->vjp_wgT, e->vjp_wf0T, e->NL, nullptr);
-        HIPCHK(hipGetLastError());
-    }
-    // zeroed: the padding rows of the saved streams and of the gradient maps are read as the convs' zero padding and never written
-    CHK(e->alloc(&e->vjp_save, NL * vB * LP * kC, true));
-    CHK(e->alloc(&e->vjp_gH, (size_t)vB * LP * 512, true));
-    CHK(e->alloc(&e->vjp_G, 3 * (size_t)vB * LP * kC, true));
-    CHK(e->alloc(&e->vjp_gg, (size_t)vB * e->L * kC));
-    CHK(e->alloc(&e->vjp_g2, 2 * (size_t)vB * e->L));
-    HIPCHK(hipDeviceSynchronize());
-    e->vjpB = vB;
-    return 0;
+    return reserve_vjp(
+        e, max_batch, &dmad_engine::maxB32, &dmad_engine::vjpB,
+        [&]() -> int {
+            if (!e->f32) return fail(DMAD_ERR_STATE, "the WaveNet VJP runs on the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights");
+            return need_wavenet(e);
+        },
+        [&] { return std::vector<float**>{&e->vjp_save, &e->vjp_gH, &e->vjp_G, &e->vjp_gg, &e->vjp_g2}; },
+        [&]() -> int {                      // one kernel packs all three images: it runs again while any of them was missing
+            const size_t NL = e->NL;
+            const bool missing = !e->vjp_wdilT || !e->vjp_wgT || !e->vjp_wf0T;
+            CHK(pack_once(e, &e->vjp_wdilT, NL * 3 * 256 * 512, [] {}));
+            CHK(pack_once(e, &e->vjp_wgT, NL * 2 * 256 * 256, [] {}));
+            CHK(pack_once(e, &e->vjp_wf0T, 256 * 256, [] {}));
+            if (missing) launch_vjp_pack(e->wdil, e->wrs, e->wf0, e->vjp_wdilT, e->vjp_wgT, e->vjp_wf0T, e->NL, nullptr);
+            return 0;
+        },
+        [&](int vB) -> int {
+            const size_t LP = e->LP, NL = e->NL;
+            // zeroed: the padding rows of the saved streams and of the gradient maps are read as the convs' zero padding and never written
+            CHK(e->alloc(&e->vjp_save, NL * vB * LP * kC, true));
+            CHK(e->alloc(&e->vjp_gH, (size_t)vB * LP * 512, true));
+            CHK(e->alloc(&e->vjp_G, 3 * (size_t)vB * LP * kC, true));
+            CHK(e->alloc(&e->vjp_gg, (size_t)vB * e->L * kC));
+            CHK(e->alloc(&e->vjp_g2, 2 * (size_t)vB * e->L));
+            return 0;
+        });
 }
 
 int dmad_wavenet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps, dmad_stream s) {
@@ -2861,65 +2911,58 @@ int dmad_wavenet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B,
 }
 
 int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
-    CHK(need_unet(e));
-    if (!e->f32) return fail(DMAD_ERR_STATE, "the UNet VJP runs on the exact-fp32 UNet tier: it needs a DMAD_FP32 or DMAD_EXACT engine");
-    const int vB = max_batch < e->maxB32 ? max_batch : e->maxB32;
-    if (vB <= e->unvjpB) return 0;
-    // tape slots and saved-map gradients, in floats per spectrogram
-    std::vector<size_t> out_off, t2_off, qkv_off, ghs_off;
-    size_t tape = 0, ghs = 0;
-    for (const auto& o : e->un_ops) {
-        const size_t px = (size_t)o.H * o.H, opx = o.kind == 3 ? px / 4 : o.kind == 4 ? px * 4 : px;
-        t2_off.push_back(o.kind == 1 ? tape : SIZE_MAX); if (o.kind == 1) tape += px * o.cout;
-        qkv_off.push_back(o.kind == 2 ? tape : SIZE_MAX); if (o.kind == 2) tape += px * 3 * o.cin;
-        out_off.push_back(tape); tape += opx * o.cout;
-    }
-    for (size_t i = 0; i < e->un_hs_ch.size(); ++i) { ghs_off.push_back(ghs); ghs += (size_t)e->un_hs_hw[i] * e->un_hs_ch[i]; }
-    const size_t W = (size_t)1024 * 384;
-    if (e->unvjpB) {                        // a larger reservation replaces the present one
-        e->release(&e->unvjp_tape); e->release(&e->unvjp_ghs); e->release(&e->unvjp_work); e->release(&e->unvjp_g2);
-        e->unvjpB = 0;
-    }
-    if (!e->unvjp_zero) {                   // transposed weight images, packed on the device from the resident fp32 images
-        CHK(e->alloc(&e->unvjp_zero, kUnMC, true));
-        auto pack = [&](dmad_engine::UnOp& o) -> int {
-            const long ci = o.cin, co = o.cout;
-            if (o.kind == 0) {              // [co][9] -> [9][co], taps flipped (the 128 -> 1 conv's image)
-                CHK(e->alloc(&o.w1T, 9 * co)); launch_unvjp_pack(o.w1, o.w1T, 9, (int)co, 1, 1, 9, 0, 1, nullptr);
-            } else if (o.kind == 2) {       // qkv [3C][C] -> [C][3C], proj_out [C][C] -> transposed
-                CHK(e->alloc(&o.w1T, 3 * ci * ci)); un_pack_wT(o.w1, o.w1T, 1, ci, 3 * ci, nullptr);
-                CHK(e->alloc(&o.w2T, ci * ci)); un_pack_wT(o.w2, o.w2T, 1, ci, ci, nullptr);
-            } else {                        // 3x3 [tap][co][ci] -> [8 - tap][ci][co]
-                CHK(e->alloc(&o.w1T, 9 * ci * co)); un_pack_wT(o.w1, o.w1T, 9, ci, co, nullptr);
-                if (o.kind == 1) {
-                    CHK(e->alloc(&o.w2T, 9 * co * co)); un_pack_wT(o.w2, o.w2T, 9, co, co, nullptr);
-                    if (ci != co) { CHK(e->alloc(&o.skwT, ci * co)); un_pack_wT(o.skw, o.skwT, 1, ci, co, nullptr); }
+    return reserve_vjp(
+        e, max_batch, &dmad_engine::maxB32, &dmad_engine::unvjpB,
+        [&]() -> int {
+            CHK(need_unet(e));
+            return e->f32 ? 0 : fail(DMAD_ERR_STATE, "the UNet VJP runs on the exact-fp32 UNet tier: it needs a DMAD_FP32 or DMAD_EXACT engine");
+        },
+        [&] { return std::vector<float**>{&e->unvjp_tape, &e->unvjp_ghs, &e->unvjp_work, &e->unvjp_g2}; },
+        [&]() -> int {                      // transposed weight images, packed on the device from the resident fp32 images
+            if (!e->unvjp_zero) CHK(e->alloc(&e->unvjp_zero, kUnMC, true));
+            for (auto& o : e->un_ops) {
+                const long ci = o.cin, co = o.cout;
+                if (o.kind == 0) {          // [co][9] -> [9][co], taps flipped (the 128 -> 1 conv's image)
+                    CHK(pack_once(e, &o.w1T, 9 * co, [&] { launch_unvjp_pack(o.w1, o.w1T, 9, (int)co, 1, 1, 9, 0, 1, nullptr); }));
+                } else if (o.kind == 2) {   // qkv [3C][C] -> [C][3C], proj_out [C][C] -> transposed
+                    CHK(pack_once(e, &o.w1T, 3 * ci * ci, [&] { un_pack_wT(o.w1, o.w1T, 1, ci, 3 * ci, nullptr); }));
+                    CHK(pack_once(e, &o.w2T, ci * ci, [&] { un_pack_wT(o.w2, o.w2T, 1, ci, ci, nullptr); }));
+                } else {                    // 3x3 [tap][co][ci] -> [8 - tap][ci][co]
+                    CHK(pack_once(e, &o.w1T, 9 * ci * co, [&] { un_pack_wT(o.w1, o.w1T, 9, ci, co, nullptr); }));
+                    if (o.kind == 1) CHK(pack_once(e, &o.w2T, 9 * co * co, [&] { un_pack_wT(o.w2, o.w2T, 9, co, co, nullptr); }));
+                    if (o.kind == 1 && ci != co) CHK(pack_once(e, &o.skwT, ci * co, [&] { un_pack_wT(o.skw, o.skwT, 1, ci, co, nullptr); }));
                 }
             }
+            CHK(pack_once(e, &e->un_outT, 9 * kUnMC, [&] { launch_unvjp_pack(e->un_outw, e->un_outT, kUnMC, 9, 1, 1, kUnMC, 0, 2, nullptr); }));   // [9][128] -> [128][9], flipped
+            HIPCHK(hipGetLastError());
+            if (int r = unvjp_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, attention backward) failed: %d", r);
             return 0;
-        };
-        for (auto& o : e->un_ops) CHK(pack(o));
-        CHK(e->alloc(&e->un_outT, 9 * kUnMC)); launch_unvjp_pack(e->un_outw, e->un_outT, kUnMC, 9, 1, 1, kUnMC, 0, 2, nullptr);   // [9][128] -> [128][9], flipped
-        HIPCHK(hipGetLastError());
-        if (int r = unvjp_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, attention backward) failed: %d", r);
-    }
-    CHK(e->alloc(&e->unvjp_tape, (size_t)vB * tape));
-    CHK(e->alloc(&e->unvjp_ghs, (size_t)vB * ghs));
-    CHK(e->alloc(&e->unvjp_work, 6 * (size_t)vB * W));
-    CHK(e->alloc(&e->unvjp_g2, 2 * (size_t)vB * 1024));
-    auto at = [&](size_t off) { return off == SIZE_MAX ? nullptr : e->unvjp_tape + off * vB; };
-    e->un_tape = dmad_engine::UnTape{};
-    for (size_t k = 0; k < out_off.size(); ++k) {
-        e->un_tape.out.push_back(at(out_off[k])); e->un_tape.t2.push_back(at(t2_off[k])); e->un_tape.qkv.push_back(at(qkv_off[k]));
-        if (e->un_ops[k].save >= 0) e->un_tape.hs.push_back(e->un_tape.out[k]);
-    }
-    e->unvjp_ghs_at.clear();
-    for (size_t off : ghs_off) e->unvjp_ghs_at.push_back(e->unvjp_ghs + off * vB);
-    HIPCHK(hipDeviceSynchronize());
-    e->unvjpB = vB;
-    return 0;
+        },
+        [&](int vB) -> int {
+            // tape slots and saved-map gradients, in floats per spectrogram
+            std::vector<size_t> out_off, t2_off, qkv_off, ghs_off;
+            size_t tape = 0, ghs = 0;
+            for (const auto& o : e->un_ops) {
+                const size_t px = (size_t)o.H * o.H, opx = o.kind == 3 ? px / 4 : o.kind == 4 ? px * 4 : px;
+                t2_off.push_back(o.kind == 1 ? tape : SIZE_MAX); if (o.kind == 1) tape += px * o.cout;
+                qkv_off.push_back(o.kind == 2 ? tape : SIZE_MAX); if (o.kind == 2) tape += px * 3 * o.cin;
+                out_off.push_back(tape); tape += opx * o.cout;
+            }
+            for (size_t i = 0; i < e->un_hs_ch.size(); ++i) { ghs_off.push_back(ghs); ghs += (size_t)e->un_hs_hw[i] * e->un_hs_ch[i]; }
+            CHK(e->alloc(&e->unvjp_tape, (size_t)vB * tape));
+            CHK(e->alloc(&e->unvjp_ghs, (size_t)vB * ghs));
+            CHK(e->alloc(&e->unvjp_work, 6 * (size_t)vB * 1024 * 384));
+            CHK(e->alloc(&e->unvjp_g2, 2 * (size_t)vB * 1024));
+            auto at = [&](size_t off) { return off == SIZE_MAX ? nullptr : e->unvjp_tape + off * vB; };
+            e->un_tape = dmad_engine::UnTape{};
+            for (size_t k = 0; k < out_off.size(); ++k) {
+                e->un_tape.out.push_back(at(out_off[k])); e->un_tape.t2.push_back(at(t2_off[k])); e->un_tape.qkv.push_back(at(qkv_off[k]));
+                if (e->un_ops[k].save >= 0) e->un_tape.hs.push_back(e->un_tape.out[k]);
+            }
+            e->unvjp_ghs_at.clear();
+            for (size_t off : ghs_off) e->unvjp_ghs_at.push_back(e->unvjp_ghs + off * vB);
+            return 0;
+        });
 }
 
 int dmad_unet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps, dmad_stream s) {
@@ -2928,120 +2971,48 @@ int dmad_unet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, co
 }
 
 int dmad_reserve_classifier_vjp(dmad_engine* e, int32_t max_batch) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
-    CHK(need_classifier(e));
-    if (e->cls_kind != 1) return fail(DMAD_ERR_STATE, "the classifier VJP serves ResNeXt29 only: this engine holds %s", e->cls_kind == 2 ? "WideResNet-28-10 (dmad_wrn_vjp)" : "VGG19_bn");
-    const int vB = max_batch < e->maxB ? max_batch : e->maxB;
-    if (vB <= e->rxvjpB) return 0;
-    // tape slots in floats per spectrogram: conv1's output, then per bottleneck T1 (input resolution), T2 and Y (output resolution)
-    size_t c1_off = 0, tape = (size_t)1024 * 64, t1_off[9], t2_off[9], y_off[9];
-    int H = 32;
-    for (int i = 0; i < 9; ++i) {
-        const dmad_engine::RxBlock& b = e->rx[i];
-        const size_t Ho = (size_t)(H - 1) / b.stride + 1;
-        t1_off[i] = tape; tape += (size_t)H * H * b.D;
-        t2_off[i] = tape; tape += Ho * Ho * b.D;
-        y_off[i] = tape; tape += Ho * Ho * b.cout;
-        H = (int)Ho;
-    }
-    size_t work = 0;
-    for (size_t w : kRxWork) work += w;
-    if (e->rxvjpB) {                        // a larger reservation replaces the present one
-        e->release(&e->rxvjp_tape); e->release(&e->rxvjp_work);
-        e->rxvjpB = 0;
-    }
-    if (!e->rx[0].reduce.wT) {              // transposed images with the BN scale folded in, packed on the device from the fp32 images
-        for (int i = 0; i < 9; ++i) {
-            dmad_engine::RxBlock& b = e->rx[i];
+    // transposed images with the BN scale folded in, packed on the device from the fp32 images: reduce [D][cin] -> [cin][D], the grouped 3x3
+    // [g][tap][m][k] -> [g][8 - tap][k][m], expand [cout][D] -> [D][cout], the shortcut [cout][cin] -> [cin][cout]
+    return reserve_cls_vjp(e, max_batch, 1, std::accumulate(std::begin(kRxWork), std::end(kRxWork), (size_t)0), [&]() -> int {
+        for (dmad_engine::RxBlock& b : e->rx) {
             const int G = b.D / 8;
-            CHK(e->alloc(&b.reduce.wT, (size_t)b.cin * b.D));            // [D][cin] -> [cin][D]
-            rx_pack_wT(b.reduce.w, b.reduce.scale, b.reduce.wT, b.D, b.cin, 1, b.D, nullptr);
-            CHK(e->alloc(&b.conv.wT, (size_t)8 * 9 * G * G));            // [g][tap][m][k] -> [g][8 - tap][k][m]
-            rx_pack_wT(b.conv.w, b.conv.scale, b.conv.wT, G, G, 9, 0, nullptr);
-            CHK(e->alloc(&b.expand.wT, (size_t)b.D * b.cout));           // [cout][D] -> [D][cout]
-            rx_pack_wT(b.expand.w, b.expand.scale, b.expand.wT, b.cout, b.D, 1, b.cout, nullptr);
-            if (b.has_short) {                                           // [cout][cin] -> [cin][cout]
-                CHK(e->alloc(&b.shortc.wT, (size_t)b.cin * b.cout));
-                rx_pack_wT(b.shortc.w, b.shortc.scale, b.shortc.wT, b.cout, b.cin, 1, b.cout, nullptr);
-            }
+            CHK(pack_once(e, &b.reduce.wT, (size_t)b.cin * b.D, [&] { rx_pack_wT(b.reduce.w, b.reduce.scale, b.reduce.wT, b.D, b.cin, 1, b.D, nullptr); }));
+            CHK(pack_once(e, &b.conv.wT, (size_t)8 * 9 * G * G, [&] { rx_pack_wT(b.conv.w, b.conv.scale, b.conv.wT, G, G, 9, 0, nullptr); }));
+            CHK(pack_once(e, &b.expand.wT, (size_t)b.D * b.cout, [&] { rx_pack_wT(b.expand.w, b.expand.scale, b.expand.wT, b.cout, b.D, 1, b.cout, nullptr); }));
+            if (b.has_short)
+                CHK(pack_once(e, &b.shortc.wT, (size_t)b.cin * b.cout, [&] { rx_pack_wT(b.shortc.w, b.shortc.scale, b.shortc.wT, b.cout, b.cin, 1, b.cout, nullptr); }));
         }
-        HIPCHK(hipGetLastError());
-    }
-    CHK(e->alloc(&e->rxvjp_tape, (size_t)vB * tape));
-    CHK(e->alloc(&e->rxvjp_work, (size_t)vB * work));
-    auto at = [&](size_t off) { return e->rxvjp_tape + off * vB; };
-    e->rx_tape.c1 = at(c1_off);
-    for (int i = 0; i < 9; ++i) { e->rx_tape.t1[i] = at(t1_off[i]); e->rx_tape.t2[i] = at(t2_off[i]); e->rx_tape.y[i] = at(y_off[i]); }
-    HIPCHK(hipDeviceSynchronize());
-    e->rxvjpB = vB;
-    return 0;
+        return 0;
+    });
 }
 
 int dmad_classify_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s) {
-    if (!e || !spec || !g_logits || !g_spec) return fail(DMAD_ERR_INVALID, "null argument");
-    return classify_vjp(e, spec, B, g_logits, g_spec, logits, (hipStream_t)s);
+    return cls_vjp(e, 1, spec, B, g_logits, g_spec, logits, (hipStream_t)s);
 }
 
 int dmad_reserve_vgg_vjp(dmad_engine* e, int32_t max_batch) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
-    CHK(need_vgg(e));
-    const int vB = max_batch < e->maxB ? max_batch : e->maxB;
-    if (vB <= e->vgvjpB) return 0;
-    if (e->vgvjpB) {                        // a larger reservation replaces the present one
-        e->release(&e->vgvjp_tape); e->release(&e->vgvjp_work);
-        e->vgvjpB = e->vgvjp_lastB = 0;
-    }
-    // the backward images, packed on the device from the resident fp32 images — each one once: a call that failed part of the way
-    // (out of memory) leaves the images it had packed in place, and the next call allocates only the missing ones
-    int cin = 64, li = 1;
-    for (int i = 1; i < kVggCfgLen; ++i) {
-        const int v = kVggCfg[i];
-        if (v < 0) continue;
-        if (!e->vconvwT[li]) {
-            CHK(e->alloc(&e->vconvwT[li], (size_t)9 * cin * v));          // [tap][v][cin] -> [8 - tap][cin][v] * scale[v]
-            launch_cvjp_pack_dense(e->vconvw[li], e->vscale[li], e->vconvwT[li], v, cin, nullptr);
+    return reserve_cls_vjp(e, max_batch, 0, 2 * kVggWork, [&]() -> int {
+        int cin = 64, li = 1;
+        for (int i = 1; i < kVggCfgLen; ++i) {
+            const int v = kVggCfg[i];
+            if (v < 0) continue;
+            // [tap][v][cin] -> [8 - tap][cin][v] * scale[v]
+            CHK(pack_once(e, &e->vconvwT[li], (size_t)9 * cin * v, [&] { launch_cvjp_pack_dense(e->vconvw[li], e->vscale[li], e->vconvwT[li], v, cin, nullptr); }));
+            cin = v;
+            ++li;
         }
-        cin = v;
-        ++li;
-    }
-    if (!e->vfcwT[1]) {
-        CHK(e->alloc(&e->vfcwT[1], (size_t)4096 * 4096));                 // classifier.3 [4096][4096] -> transposed
-        launch_cvjp_transpose(e->vfcw[1], 4096, 4096, 4096, nullptr, e->vfcwT[1], 4096, nullptr);
-    }
-    if (!e->vfcwT[0]) {
-        CHK(e->alloc(&e->vfcwT[0], (size_t)512 * 4096));                  // classifier.0 [4096][512] -> [512][4096]
-        launch_cvjp_transpose(e->vfcw[0], 4096, 512, 512, nullptr, e->vfcwT[0], 4096, nullptr);
-    }
-    HIPCHK(hipGetLastError());
-    size_t tape = 0, off[18];
-    for (int k = 0; k < 18; ++k) { off[k] = tape; tape += vgg_tape_floats(k); }
-    CHK(e->alloc(&e->vgvjp_tape, (size_t)vB * tape));
-    if (int r = e->alloc(&e->vgvjp_work, (size_t)vB * 2 * kVggWork)) {    // no half reservation stays behind
-        e->release(&e->vgvjp_tape);
-        return r;
-    }
-    for (int k = 0; k < 18; ++k) (k < 16 ? e->vg_tape.c[k] : e->vg_tape.f[k - 16]) = e->vgvjp_tape + off[k] * vB;
-    HIPCHK(hipDeviceSynchronize());
-    e->vgvjpB = vB;
-    return 0;
+        // classifier.3 [4096][4096] -> transposed, classifier.0 [4096][512] -> [512][4096]
+        CHK(pack_once(e, &e->vfcwT[1], (size_t)4096 * 4096, [&] { launch_cvjp_transpose(e->vfcw[1], 4096, 4096, 4096, nullptr, e->vfcwT[1], 4096, nullptr); }));
+        CHK(pack_once(e, &e->vfcwT[0], (size_t)512 * 4096, [&] { launch_cvjp_transpose(e->vfcw[0], 4096, 512, 512, nullptr, e->vfcwT[0], 4096, nullptr); }));
+        return 0;
+    });
 }
 
 int dmad_vgg_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s) {
-    if (!e || !spec || !g_logits || !g_spec) return fail(DMAD_ERR_INVALID, "null argument");
-    return vgg_vjp(e, spec, B, g_logits, g_spec, logits, (hipStream_t)s);
+    return cls_vjp(e, 0, spec, B, g_logits, g_spec, logits, (hipStream_t)s);
 }
 
-int dmad_vgg_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s) {
-    if (!e || !out) return fail(DMAD_ERR_INVALID, "null argument");
-    CHK(need_vgg(e));
-    if (index < 0 || index > 17) return fail(DMAD_ERR_INVALID, "tape map %d outside [0, 17]", index);
-    if (B < 1 || B > e->vgvjp_lastB) return fail(DMAD_ERR_STATE, "the tape holds %d rows of a one-pass dmad_vgg_vjp call, not %d", e->vgvjp_lastB, B);
-    const float* src = index < 16 ? e->vg_tape.c[index] : e->vg_tape.f[index - 16];
-    HIPCHK(hipMemcpyAsync(out, src, (size_t)B * vgg_tape_floats(index) * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)s));
-    return 0;
-}
+int dmad_vgg_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s) { return cls_vjp_tape(e, 0, index, B, out, (hipStream_t)s); }
 
 int dmad_vgg_pool_relu_bwd(const float* g, const float* y, int32_t B, int32_t H, int32_t C, float* gpre, dmad_stream s) {
     if (!g || !y || !gpre) return fail(DMAD_ERR_INVALID, "null argument");
@@ -3052,64 +3023,22 @@ int dmad_vgg_pool_relu_bwd(const float* g, const float* y, int32_t B, int32_t H,
 }
 
 int dmad_reserve_wrn_vjp(dmad_engine* e, int32_t max_batch) {
-    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
-    if (max_batch < 1) return fail(DMAD_ERR_INVALID, "max_batch %d < 1", max_batch);
-    CHK(need_wrn(e));
-    const int vB = max_batch < e->maxB ? max_batch : e->maxB;
-    if (vB <= e->wrnvjpB) return 0;
-    if (e->wrnvjpB) {                       // a larger reservation replaces the present one
-        e->release(&e->wrnvjp_tape); e->release(&e->wrnvjp_work);
-        e->wrnvjpB = e->wrnvjp_lastB = 0;
-    }
-    // the backward images, packed on the device from the resident fp32 images, each one once: the 3x3 convs tap-flipped and transposed
-    // (conv1's with bn2's scale folded in, conv2's plain), the 1x1 shortcuts transposed
-    for (int i = 0; i < 12; ++i) {
-        dmad_engine::WrnBlock& b = e->wrn[i];
-        if (!b.w1T) {
-            CHK(e->alloc(&b.w1T, (size_t)9 * b.cin * b.cout));
-            launch_cvjp_pack_dense(b.w1, b.s2, b.w1T, b.cout, b.cin, nullptr);
+    // the 3x3 convs tap-flipped and transposed (conv1's with bn2's scale folded in, conv2's plain), the 1x1 shortcuts [cout][cin] -> [cin][cout]
+    return reserve_cls_vjp(e, max_batch, 2, std::accumulate(std::begin(kWrnWork), std::end(kWrnWork), (size_t)0), [&]() -> int {
+        for (dmad_engine::WrnBlock& b : e->wrn) {
+            CHK(pack_once(e, &b.w1T, (size_t)9 * b.cin * b.cout, [&] { launch_cvjp_pack_dense(b.w1, b.s2, b.w1T, b.cout, b.cin, nullptr); }));
+            CHK(pack_once(e, &b.w2T, (size_t)9 * b.cout * b.cout, [&] { launch_cvjp_pack_dense(b.w2, nullptr, b.w2T, b.cout, b.cout, nullptr); }));
+            if (b.ws) CHK(pack_once(e, &b.wsT, (size_t)b.cin * b.cout, [&] { launch_cvjp_transpose(b.ws, b.cout, b.cin, b.cin, nullptr, b.wsT, b.cout, nullptr); }));
         }
-        if (!b.w2T) {
-            CHK(e->alloc(&b.w2T, (size_t)9 * b.cout * b.cout));
-            launch_cvjp_pack_dense(b.w2, nullptr, b.w2T, b.cout, b.cout, nullptr);
-        }
-        if (b.ws && !b.wsT) {
-            CHK(e->alloc(&b.wsT, (size_t)b.cin * b.cout));                // [cout][cin] -> [cin][cout]
-            launch_cvjp_transpose(b.ws, b.cout, b.cin, b.cin, nullptr, b.wsT, b.cout, nullptr);
-        }
-    }
-    HIPCHK(hipGetLastError());
-    size_t tape = 0, off[25], work = 0;
-    for (int k = 0; k < 25; ++k) { int H, C; wrn_tape_map(e, k, &H, &C); off[k] = tape; tape += (size_t)H * H * C; }
-    for (size_t w : kWrnWork) work += w;
-    CHK(e->alloc(&e->wrnvjp_tape, (size_t)vB * tape));
-    if (int r = e->alloc(&e->wrnvjp_work, (size_t)vB * work)) {           // no half reservation stays behind
-        e->release(&e->wrnvjp_tape);
-        return r;
-    }
-    for (int k = 0; k < 24; ++k) ((k & 1) ? e->wrn_tape.h : e->wrn_tape.o)[k / 2] = e->wrnvjp_tape + off[k] * vB;
-    e->wrn_tape.f = e->wrnvjp_tape + off[24] * vB;
-    HIPCHK(hipDeviceSynchronize());
-    e->wrnvjpB = vB;
-    return 0;
+        return 0;
+    });
 }
 
 int dmad_wrn_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s) {
-    if (!e || !spec || !g_logits || !g_spec) return fail(DMAD_ERR_INVALID, "null argument");
-    return wrn_vjp(e, spec, B, g_logits, g_spec, logits, (hipStream_t)s);
+    return cls_vjp(e, 2, spec, B, g_logits, g_spec, logits, (hipStream_t)s);
 }
 
-int dmad_wrn_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s) {
-    if (!e || !out) return fail(DMAD_ERR_INVALID, "null argument");
-    CHK(need_wrn(e));
-    if (index < 0 || index > 24) return fail(DMAD_ERR_INVALID, "tape map %d outside [0, 24]", index);
-    if (B < 1 || B > e->wrnvjp_lastB) return fail(DMAD_ERR_STATE, "the tape holds %d rows of a one-pass dmad_wrn_vjp call, not %d", e->wrnvjp_lastB, B);
-    int H, C;
-    wrn_tape_map(e, index, &H, &C);
-    const float* src = index == 24 ? e->wrn_tape.f : (index & 1) ? e->wrn_tape.h[index / 2] : e->wrn_tape.o[index / 2];
-    HIPCHK(hipMemcpyAsync(out, src, (size_t)B * H * H * C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)s));
-    return 0;
-}
+int dmad_wrn_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s) { return cls_vjp_tape(e, 2, index, B, out, (hipStream_t)s); }
 
 int dmad_wrn_preact(const float* x, const float* scale, const float* shift, int64_t n_px, int32_t C, float* out, dmad_stream s) {
     if (!x || !scale || !shift || !out) return fail(DMAD_ERR_INVALID, "null argument");

@@ -244,6 +244,8 @@ int dmad_wavenet_eps_path(dmad_engine* e, const float* x_t, int32_t t, int32_t B
  * fp32 pass size (max_batch of a DMAD_FP32 engine, recheck_batch of a DMAD_EXACT one).  A larger reservation replaces a smaller one;
  * a smaller one keeps the present.  Counted by dmad_device_bytes.  This is the only allocation of the VJP: the data path below
  * allocates nothing.  DMAD_ERR_STATE for a DMAD_BF16 engine (it holds no fp32 weights) or before dmad_finalize_weights.
+ * A failed reservation (out of memory) leaves no partial workspace behind: the pass-sized buffers it had allocated are released, the
+ * packed weight images stay, and the next call packs only the missing ones.
  *
  * dmad_wavenet_eps_vjp:  g_x = (d eps / d x_t)^T g_eps  for eps = WaveNet((x_t, t * ones)) on the exact-fp32 path.
  * x_t, g_eps, g_x: device fp32 [B][clip_len].  eps: optional (NULL) device fp32 [B][clip_len], bit-identical to
@@ -269,6 +271,8 @@ int dmad_wavenet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B,
  * the present.  Counted by dmad_device_bytes.  This is the only allocation of the VJP: the data path below allocates nothing.
  * DMAD_ERR_STATE before the UNet weights are finalised, or for a DMAD_BF16 engine (the exact-fp32 UNet tier is a product path of
  * DMAD_FP32 and DMAD_EXACT engines only).
+ * A failed reservation (out of memory) leaves no partial workspace behind: the pass-sized buffers it had allocated are released, the
+ * packed weight images stay, and the next call packs only the missing ones.
  *
  * dmad_unet_eps_vjp:  g_x = (d eps / d x_t)^T g_eps  for eps = UNetModel(x_t, t * ones) on the exact-fp32 tier.  x_t, g_eps, g_x:
  * device fp32 [B][32][32].  eps: optional (NULL) device fp32 [B][32][32], bit-identical to dmad_unet_eps_tier(.., tier = 0, ..).  The input
@@ -293,6 +297,8 @@ int dmad_unet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, co
  * max_batch.  A larger reservation replaces a smaller one; a smaller one keeps the present.  Counted by dmad_device_bytes.
  * DMAD_ERR_STATE before the classifier weights are finalised, or for an engine that holds VGG19_bn (its pair is dmad_reserve_vgg_vjp /
  * dmad_vgg_vjp below).
+ * A failed reservation (out of memory) leaves no partial workspace behind: the pass-sized buffers it had allocated are released, the
+ * packed weight images stay, and the next call packs only the missing ones.
  *
  * dmad_classify_vjp:  g_spec = (d logits / d spec)^T g_logits  for logits = CifarResNeXt(spec) (models/resnext.py:133-142) on the fp32
  * tier.  spec, g_spec: device fp32 [B][32][32]; g_logits: device fp32 [B][num_classes].  logits: optional (NULL) device fp32

@@ -210,6 +210,23 @@ def test_determinism_and_batch_independence(eng):
         assert torch.equal(eng.mel_db_vjp(w[j:j + 1], gs[j:j + 1]), m1[j:j + 1])
 
 
+def test_two_passes_equal_one_pass(sd):
+    """B = 2 on a reservation of 1 (two passes of one row) and on a reservation of 2 (one pass): the same bits.  Its own engine: a
+    reservation cannot shrink."""
+    from dmad_hip import engine as E
+    e = E.Engine(max_batch=2, precision=E.FP32, with_wavenet=False)
+    e.load_resnext29(sd)
+    x = specs(2, 6).cuda()
+    g = torch.randn(2, 10, generator=torch.Generator().manual_seed(6)).cuda()
+    e.reserve_classifier_vjp(1)
+    g1, l1 = e.classify_vjp(x, g, want_logits=True)
+    e.reserve_classifier_vjp(2)
+    g2, l2 = e.classify_vjp(x, g, want_logits=True)
+    assert torch.equal(g1, g2) and torch.equal(l1, l2)
+    assert bool(torch.isfinite(g1).all()) and float(g1.abs().max()) > 0
+    e.close()
+
+
 def test_finite_difference(eng):
     x = specs(2, 6).cuda()
     g = torch.randn(2, 10, generator=torch.Generator().manual_seed(6)).cuda()
