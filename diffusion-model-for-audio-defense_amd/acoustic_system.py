@@ -54,8 +54,9 @@ class AcousticSystem(torch.nn.Module):
             if not (is_m5(cls) and eng.has_m5 and not cls.training and self.defense_type == 'wave'):
                 return None, 0
             return self._wave_sampler(eng, defend)                    # the same samplers; query() calls the engine's m5_* pair for them
-        if not eng.has_classifier:
-            return None, 0
+        from audio_models.RCNN_KWS.model import is_kws
+        if is_kws(cls) or not eng.has_classifier:                     # a KWSModel's `engine` is not a spectrogram-classifier binding, and
+            return None, 0                                            # KWS has no one-call query export: query() loops over forward()
         mel = isinstance(tr, MelSpectrogramDB) and tr.engine is eng
         if not mel:
             mel = [getattr(t, '_dmad_stage', None) for t in getattr(tr, 'transforms', [])] == ['mel_power', 'power_to_db']

@@ -20,6 +20,7 @@
 #include "elementwise.h"
 #include "wave_defense.h"
 #include "m5.h"
+#include "kws.h"
 #include "masking.h"
 #include "wrn.h"
 #include "gemm_f32.h"
@@ -341,6 +342,11 @@ struct dmad_engine {
     float* m5_buf = nullptr;
     M5Weights m5w;
     M5Geom m5g;
+    // Attention-CRNN keyword spotter (kws.h): a part of its own, exact fp32 on every precision.  One buffer of weight
+    // images; the row length T is an argument of every call, so the LDS layout is worked out per call
+    bool kws_final = false;
+    float* kws_buf = nullptr;
+    KwsWeights kwsw;
 
     template <typename T>
     int alloc(T** p, size_t n, bool zero = false) {
@@ -411,6 +417,7 @@ int need_kind(const dmad_engine* e, int kind) {  // the finalised classifier is 
     return e->cls_kind == kind ? 0 : fail(DMAD_ERR_STATE, "the %s VJP serves %s only: this engine holds %s (%s)", kCls[kind].vjp_of, kCls[kind].net,
                                           kCls[e->cls_kind].net, kCls[e->cls_kind].vjp);
 }
+int need_kws(const dmad_engine* e) { return e->kws_final ? 0 : fail(DMAD_ERR_STATE, "KWS weights are not finalised (dmad_load_weight + dmad_finalize_weights)"); }
 int need_m5(const dmad_engine* e) { return e->m5_final ? 0 : fail(DMAD_ERR_STATE, "M5 weights are not finalised (dmad_load_weight + dmad_finalize_weights)"); }
 int need_batch(const dmad_engine* e, int B) { return B >= 1 && B <= e->maxB ? 0 : fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB); }
 int need_path(const dmad_engine* e, int path) {  // a WaveNet path the caller names (dmad_wavenet_eps_path / dmad_eval_samples)
@@ -2159,6 +2166,95 @@ int finalize_m5(dmad_engine* e) {
     return 0;
 }
 
+// KWS: checks the geometry against what kws.hip serves and packs the weight images of both directions into one buffer
+int finalize_kws(dmad_engine* e) {
+    auto find = [&](const char* name) -> const HostW* {
+        auto it = e->hw.find(name);
+        if (it == e->hw.end()) { fail(DMAD_ERR_STATE, "weight '%s' was not loaded", name); return nullptr; }
+        return &it->second;
+    };
+    auto is = [](const HostW* w, std::initializer_list<int64_t> shape) { return w->shape == std::vector<int64_t>(shape); };
+    const char* P = "kws.CRNN_model.";
+    const HostW* dw = find("kws.CRNN_model.sepconv.0.weight");
+    const HostW* pw = find("kws.CRNN_model.sepconv.1.weight");
+    const HostW* hh = find("kws.CRNN_model.gru.weight_hh_l0");
+    const HostW* uw = find("kws.apply_attn.U.weight");
+    const HostW* st = find("kws.stride");
+    const HostW* ks = find("kws.kernel_size");
+    if (!dw || !pw || !hh || !uw || !st || !ks) return DMAD_ERR_STATE;
+    if (dw->shape.size() != 3 || pw->shape.size() != 3) return fail(DMAD_ERR_SHAPE, "KWS: sepconv weights must be Conv1d weights [out][in / groups][k]");
+    if (dw->shape[0] != kKwsIn || dw->shape[1] != 1) return fail(DMAD_ERR_SHAPE, "KWS: in_size = %lld is not supported (only %d, depthwise)", (long long)dw->shape[0], kKwsIn);
+    if (st->v.size() != 2 || st->v[0] != 8.f || st->v[1] != 2.f)
+        return fail(DMAD_ERR_SHAPE, "KWS: stride = (%g, %g) is not supported (only (8, 2))", st->v.size() > 0 ? st->v[0] : 0.f, st->v.size() > 1 ? st->v[1] : 0.f);
+    if (ks->v.size() != 2 || ks->v[0] != 20.f || ks->v[1] != (float)kKwsK || dw->shape[2] != kKwsK || !is(pw, {pw->shape[0], kKwsIn, 1}))
+        return fail(DMAD_ERR_SHAPE, "KWS: kernel_size = (%g, %g) is not supported (only (20, %d): a 5-tap depthwise conv, one pointwise group)",
+                    ks->v.size() > 0 ? ks->v[0] : 0.f, ks->v.size() > 1 ? ks->v[1] : 0.f, kKwsK);
+    if (pw->shape[0] != kKwsH || !is(hh, {kKwsG, kKwsH}))
+        return fail(DMAD_ERR_SHAPE, "KWS: hidden_size = %lld is not supported (only %d)", (long long)pw->shape[0], kKwsH);
+    if (!e->hw.count("kws.CRNN_model.gru.weight_ih_l1") || e->hw.count("kws.CRNN_model.gru.weight_ih_l2"))
+        return fail(DMAD_ERR_SHAPE, "KWS: gru_num_layers is not supported (only 2)");
+    if (!e->hw.count("kws.CRNN_model.gru.weight_ih_l0_reverse")) return fail(DMAD_ERR_SHAPE, "KWS: num_dirs = 1 is not supported (only a bidirectional GRU)");
+    if (!is(uw, {kKwsOut, 2 * kKwsH})) return fail(DMAD_ERR_SHAPE, "KWS: num_classes = %lld is not supported (only %d)", uw->shape.empty() ? 0ll : (long long)uw->shape[0], kKwsOut);
+    std::vector<float> img;
+    size_t off[24];
+    int n = 0;
+    auto put = [&](size_t count) { off[n++] = img.size(); img.resize(img.size() + ((count + 3) & ~(size_t)3), 0.f); return img.data() + off[n - 1]; };
+    auto copy = [&](const std::string& name, std::initializer_list<int64_t> shape) -> int {
+        const HostW* w = e->get(name, shape);
+        if (!w) return DMAD_ERR_SHAPE;
+        memcpy(put(w->v.size()), w->v.data(), w->v.size() * sizeof(float));
+        return 0;
+    };
+    // rows x cols -> cols x rows
+    auto transposed = [&](const float* src, int rows, int cols) {
+        float* t = put((size_t)rows * cols);
+        for (int r = 0; r < rows; ++r) for (int c = 0; c < cols; ++c) t[(size_t)c * rows + r] = src[(size_t)r * cols + c];
+    };
+    CHK(copy(std::string(P) + "sepconv.0.weight", {kKwsIn, 1, kKwsK}));
+    CHK(copy(std::string(P) + "sepconv.0.bias", {kKwsIn}));
+    transposed(pw->v.data(), kKwsH, kKwsIn);
+    CHK(copy(std::string(P) + "sepconv.1.weight", {kKwsH, kKwsIn, 1}));
+    CHK(copy(std::string(P) + "sepconv.1.bias", {kKwsH}));
+    for (int l = 0; l < 2; ++l) {                          // the two directions of a layer side by side: row = direction * 192 + gate row
+        const int K = l ? 2 * kKwsH : kKwsH;
+        std::vector<float> cat[4];
+        const char* kind[4] = {"weight_ih", "bias_ih", "weight_hh", "bias_hh"};
+        for (int k = 0; k < 4; ++k)
+            for (int d = 0; d < 2; ++d) {
+                char name[96];
+                snprintf(name, sizeof name, "%sgru.%s_l%d%s", P, kind[k], l, d ? "_reverse" : "");
+                const HostW* w = k == 0 ? e->get(name, {kKwsG, K}) : k == 2 ? e->get(name, {kKwsG, kKwsH}) : e->get(name, {kKwsG});
+                if (!w) return DMAD_ERR_SHAPE;
+                cat[k].insert(cat[k].end(), w->v.begin(), w->v.end());
+            }
+        transposed(cat[0].data(), 2 * kKwsG, K);
+        memcpy(put(cat[0].size()), cat[0].data(), cat[0].size() * sizeof(float));
+        memcpy(put(cat[1].size()), cat[1].data(), cat[1].size() * sizeof(float));
+        transposed(cat[2].data(), 2 * kKwsG, kKwsH);
+        memcpy(put(cat[2].size()), cat[2].data(), cat[2].size() * sizeof(float));
+        memcpy(put(cat[3].size()), cat[3].data(), cat[3].size() * sizeof(float));
+    }
+    const HostW* wx = e->get("kws.attn_layer.Wx_b.weight", {2 * kKwsH, 2 * kKwsH});
+    if (!wx) return DMAD_ERR_SHAPE;
+    transposed(wx->v.data(), 2 * kKwsH, 2 * kKwsH);
+    CHK(copy("kws.attn_layer.Wx_b.weight", {2 * kKwsH, 2 * kKwsH}));
+    CHK(copy("kws.attn_layer.Wx_b.bias", {2 * kKwsH}));
+    CHK(copy("kws.attn_layer.Vt.weight", {1, 2 * kKwsH}));
+    CHK(copy("kws.apply_attn.U.weight", {kKwsOut, 2 * kKwsH}));
+    CHK(e->upload(&e->kws_buf, img));
+    const float* d = e->kws_buf;
+    KwsWeights& W = e->kwsw;
+    n = 0;
+    W.dw = d + off[n++]; W.dwb = d + off[n++]; W.pwT = d + off[n++]; W.pw = d + off[n++]; W.pwb = d + off[n++];
+    for (int l = 0; l < 2; ++l) {
+        W.wihT[l] = d + off[n++]; W.wih[l] = d + off[n++]; W.bih[l] = d + off[n++];
+        W.whhT[l] = d + off[n++]; W.whh[l] = d + off[n++]; W.bhh[l] = d + off[n++];
+    }
+    W.wxT = d + off[n++]; W.wx = d + off[n++]; W.wxb = d + off[n++]; W.vt = d + off[n++]; W.u = d + off[n++];
+    if (int r = kws_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, KWS) failed: %d", r);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2375,6 +2471,13 @@ int dmad_finalize_weights(dmad_engine* e) {
             return r;
         }
         e->m5_final = true; did = true;
+    }
+    if (!e->kws_final && e->hw.count("kws.CRNN_model.sepconv.0.weight")) {
+        if (int r = finalize_kws(e)) {       // a refused set leaves nothing behind, like a refused M5 set
+            for (auto it = e->hw.begin(); it != e->hw.end();) it = it->first.compare(0, 4, "kws.") == 0 ? e->hw.erase(it) : std::next(it);
+            return r;
+        }
+        e->kws_final = true; did = true;
     }
     if (!did) return fail(DMAD_ERR_STATE, "nothing to finalise: no complete weight set was loaded");
     e->hw.clear();
@@ -3592,9 +3695,39 @@ int m5_launch(dmad_engine* e, const float* x, int B, float* logp, int32_t* cls, 
     return 0;
 }
 
+// the host-side checks of the three KWS exports, then the one launch they share
+int kws_launch(dmad_engine* e, const char* who, const float* spec, int B, int T, float* logp, int32_t* cls, const float* g_logp, float* g_spec,
+               int stage, float* tape, hipStream_t st) {
+    if (B < 1) return fail(DMAD_ERR_INVALID, "%s: B must be >= 1", who);
+    CHK(need_kws(e));
+    KwsGeom g;
+    if (const char* m = kws_geometry(T, &g)) return fail(DMAD_ERR_SHAPE, "%s: %s (T = %d)", who, m, T);
+    launch_kws(e->kwsw, g, spec, B, logp, cls, g_logp, g_spec, stage, tape, st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+// ---- KWS (audio_models/RCNN_KWS/model.py:93-114): forward, input VJP and the tape hook
+
+int dmad_kws_logits(dmad_engine* e, const float* spec, int32_t B, int32_t T, float* logp, int32_t* decisions, dmad_stream s) {
+    if (!e || !spec || !logp) return fail(DMAD_ERR_INVALID, "dmad_kws_logits: null argument");
+    return kws_launch(e, "dmad_kws_logits", spec, B, T, logp, decisions, nullptr, nullptr, -1, nullptr, (hipStream_t)s);
+}
+
+int dmad_kws_vjp(dmad_engine* e, const float* spec, int32_t B, int32_t T, const float* g_logp, float* g_spec, float* logp, dmad_stream s) {
+    if (!e || !spec || !g_logp || !g_spec) return fail(DMAD_ERR_INVALID, "dmad_kws_vjp: null argument");
+    return kws_launch(e, "dmad_kws_vjp", spec, B, T, logp, nullptr, g_logp, g_spec, -1, nullptr, (hipStream_t)s);
+}
+
+int dmad_kws_tape(dmad_engine* e, const float* spec, int32_t B, int32_t T, int32_t stage, float* out, dmad_stream s) {
+    if (!e || !spec || !out) return fail(DMAD_ERR_INVALID, "dmad_kws_tape: null argument");
+    if (stage < 0 || stage > 3) return fail(DMAD_ERR_INVALID, "dmad_kws_tape: stage must be in 0..3");
+    return kws_launch(e, "dmad_kws_tape", spec, B, T, nullptr, nullptr, nullptr, nullptr, stage, out, (hipStream_t)s);
+}
 
 // adaptive_attack_eval.py:190-201 (AcousticSystem with a Time / FreqDomainDefense as its defender) behind the query layout of
 // dmad_query_logits

@@ -376,3 +376,28 @@ class WaveIIRHIP(torch.autograd.Function):
         x, = ctx.saved_tensors
         g = ctx.engine.wave_iir_vjp(x, g_y.contiguous(), ctx.b, ctx.a, ctx.lo, ctx.hi)
         return g.view(x.shape).to(x.dtype), None, None, None, None, None
+
+
+class KWSHIP(torch.autograd.Function):
+    """log-probabilities = KWSModel(spec [B,1,32,T]) on the engine (kws_logits), differentiable in `spec` through the engine's VJP
+    (dmad_kws_vjp, which recomputes the forward and walks back through time in the same launch).  Saves only the input; nothing is
+    reserved.  No weight gradients.  First-order only: create_graph=True raises."""
+
+    @staticmethod
+    def forward(ctx, spec, engine):
+        _require_cuda(spec)
+        ctx.engine = engine
+        ctx.save_for_backward(spec)
+        return engine.kws_logits(spec)
+
+    @staticmethod
+    def backward(ctx, g_logp):
+        _first_order_only('KWS')
+        spec, = ctx.saved_tensors
+        g = ctx.engine.kws_vjp(spec, g_logp.contiguous())
+        return g.view(spec.shape).to(spec.dtype), None
+
+
+def kws_hip(engine, spec: torch.Tensor) -> torch.Tensor:
+    """log-probabilities = KWSModel(spec [B,1,32,T] or [B,32,T]) on the engine, differentiable in `spec` (KWSHIP)."""
+    return KWSHIP.apply(spec, engine)

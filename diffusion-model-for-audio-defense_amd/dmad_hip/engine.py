@@ -77,6 +77,8 @@ def _wrn_tape_maps():
 
 
 WRN_TAPE_MAPS = _wrn_tape_maps()
+KWS_BINS, KWS_CLASSES = 32, 4                      # mel bins and classes of the attention-CRNN keyword spotter (csrc/kws.h)
+KWS_MAX_T = 644                                    # kKwsMaxT: the longest row dmad_kws_* serve (40 GRU steps)
 M5_CHANNELS = (32, 32, 64, 64)                     # output channels of M5's four conv blocks (n_channel = 32)
 # the WaveNet geometry an engine is created with unless the caller names another one
 DEFAULT_WAVENET = dict(res_channels=256, skip_channels=256, num_res_layers=36, dilation_cycle=12,
@@ -267,6 +269,11 @@ def fold_wideresnet_state_dict(sd: Dict[str, object], eps: float = 1e-5, dtype=n
     return {k: np.ascontiguousarray(v, dtype=dtype) for k, v in out.items()}
 
 
+def kws_steps(T: int) -> int:
+    """GRU steps of a T-frame spectrogram: Conv1d(k=5, stride 2) then Conv1d(k=1, stride 8)"""
+    return ((T - 5) // 2) // 8 + 1 if T >= 5 else 0
+
+
 def fold_m5_state_dict(sd: Dict[str, object], stride: int = 16, eps: float = 1e-5) -> Dict[str, np.ndarray]:
     """M5Net.M5 state dict -> the `m5.*` arrays of include/dmad.h: the conv weights as they are, each eval-BatchNorm folded (in float64)
     into s = gamma / sqrt(var + eps) and shift = beta + (bias - mean) * s, fc1, and conv1's stride (the one geometry field no tensor
@@ -319,6 +326,7 @@ class Engine:
         self.has_unet = False
         self.has_m5 = False
         self.m5_owner, self.m5_classes, self.m5_maps = None, 0, ()
+        self.has_kws, self.kws_owner = False, None
         self.vjp_batch = self.unet_vjp_batch = self.classifier_vjp_batch = self.vgg_vjp_batch = self.wrn_vjp_batch = 0     # rows per pass the VJP workspaces are reserved for
         # which weights are resident (state_fingerprint): a module that binds to an engine holding OTHER weights must
         # not silently run them
@@ -422,8 +430,20 @@ class Engine:
             t = t // 4 - 2
         self.m5_maps = tuple(maps)
 
+    def load_kws(self, state_dict, kernel_size=(20, 5), stride=(8, 2)):
+        """RCNN_KWS.model.KWSModel state dict -> engine (its 24 tensors under 'kws.' + key, and the constructor's kernel_size / stride,
+        which no tensor shows); a part of its own beside the spectrogram classifier and M5."""
+        if self.has_kws:
+            raise DmadError('KWS weights are already loaded into this engine')
+        arrays = {'kws.' + k: _as_np(v) for k, v in state_dict.items()}
+        arrays['kws.kernel_size'] = np.array(kernel_size, dtype=np.float32)
+        arrays['kws.stride'] = np.array(stride, dtype=np.float32)
+        self._load(arrays)
+        self.has_kws = True
+        self.kws_owner = state_fingerprint(state_dict)
+
     def bind(self, part: str, state_dict, loader) -> None:
-        """Make `state_dict` the resident weights of `part` ('wavenet' / 'classifier' / 'unet' / 'm5'): upload them if the
+        """Make `state_dict` the resident weights of `part` ('wavenet' / 'classifier' / 'unet' / 'm5' / 'kws'): upload them if the
         part is empty, accept them if they ARE the resident ones, refuse anything else (an engine holds one weight set per
         part for its lifetime; use get_engine(fresh=True) / Engine(...) for a second model)."""
         owner = getattr(self, part + '_owner')
@@ -1306,6 +1326,54 @@ class Engine:
         """dmad_m5_defense_query_logits: defense_query_logits with M5 in the place of mel dB -> classifier (`defense` as there)."""
         return self._defense_query(self.lib.dmad_m5_defense_query_logits, self._m5_width(), x, repeats, defense)
 
+    # ------------------------------------------------------------------ KWS (dmad_kws_*): dB mel spectrogram in, log-probabilities out
+    @staticmethod
+    def _kws_spec(x: torch.Tensor) -> torch.Tensor:
+        """[B,1,32,T] or [B,32,T] -> contiguous fp32 [B,32,T]; T is an argument of every call, and the library checks it"""
+        _on_gpu(x)
+        x = x.detach()
+        if x.dim() == 4:
+            assert x.shape[1] == 1, 'expected [B,1,%d,T]' % KWS_BINS
+            x = x[:, 0]
+        assert x.dim() == 3 and x.shape[1] == KWS_BINS, 'expected [B,%d,T], got %s' % (KWS_BINS, tuple(x.shape))
+        return x.contiguous().float()
+
+    def kws_logits(self, spec: torch.Tensor, want_decisions: bool = False):
+        """dmad_kws_logits: spec [B,1,32,T] or [B,32,T] -> log-probabilities [B,4] (and, want_decisions, their int32 arg-max).  One launch
+        whatever B is, like m5_logits: no workspace that max_batch would size, and a row's bits do not depend on the batch."""
+        xs = self._kws_spec(spec)
+        B, T = xs.shape[0], xs.shape[2]
+        out = torch.empty((B, KWS_CLASSES), device=xs.device, dtype=torch.float32)
+        dec = torch.empty((B,), device=xs.device, dtype=torch.int32) if want_decisions else None
+        check(self.lib.dmad_kws_logits(self._h, _ptr(xs), B, T, _ptr(out), _ptr(dec), _stream()))
+        return (out, dec) if want_decisions else out
+
+    def kws_vjp(self, spec: torch.Tensor, g: torch.Tensor, want_logits: bool = False):
+        """dmad_kws_vjp: g_spec [B,32,T] = (d logp / d spec)^T g for logp = KWSModel(spec), g [B,4]; exact zeros at the frames no GRU
+        step reads.  want_logits: also the log-probabilities, bit-identical to kws_logits(spec).  The forward is recomputed inside the
+        call; nothing is saved or reserved."""
+        xs = self._kws_spec(spec)
+        B, T = xs.shape[0], xs.shape[2]
+        if not g.is_cuda or tuple(g.shape) != (B, KWS_CLASSES):
+            raise DmadError('g must be a CUDA tensor [%d, %d], not %s' % (B, KWS_CLASSES, tuple(g.shape)))
+        gl = _f32(g)
+        gs = torch.empty_like(xs)
+        lp = torch.empty((B, KWS_CLASSES), device=xs.device, dtype=torch.float32) if want_logits else None
+        check(self.lib.dmad_kws_vjp(self._h, _ptr(xs), B, T, _ptr(gl), _ptr(gs), _ptr(lp), _stream()))
+        return (gs, lp) if want_logits else gs
+
+    def kws_tape(self, spec: torch.Tensor, stage: int) -> torch.Tensor:
+        """dmad_kws_tape (test hook), as the launch of kws_vjp produces them: stage 0 the sepconv output [B,T2,64], 1 / 2 the output of GRU
+        layer 0 / 1 [B,T2,128] (forward direction first), 3 the attention scores [B,T2]."""
+        xs = self._kws_spec(spec)
+        B, T = xs.shape[0], xs.shape[2]
+        if stage not in (0, 1, 2, 3):
+            raise DmadError('stage must be 0..3, not %r' % (stage,))
+        t2 = max(kws_steps(T), 1)              # a T the library refuses still needs a buffer to pass
+        out = torch.empty((B, t2) + ((64,), (128,), (128,), ())[stage], device=xs.device, dtype=torch.float32)
+        check(self.lib.dmad_kws_tape(self._h, _ptr(xs), B, T, int(stage), _ptr(out), _stream()))
+        return out
+
     # ------------------------------------------------------------------ Philox draws, timing and profiling hooks
     def _philox(self, fn, seed, sample0, stream, B):
         out = torch.empty((B, self.L), dtype=torch.float32, device=self.device)
@@ -1699,6 +1767,16 @@ def bind_m5(state_dict, stride: int = 16, engine: Optional[Engine] = None) -> En
     if engine is None and eng.has_m5 and eng.m5_owner != state_fingerprint(state_dict):
         eng = Engine(dict(eng.wavenet_geometry), max_batch=eng.max_batch, precision=eng.precision)
     eng.bind('m5', state_dict, lambda sd: eng.load_m5(sd, stride))
+    return eng
+
+
+def bind_kws(state_dict, kernel_size=(20, 5), stride=(8, 2), engine: Optional[Engine] = None) -> Engine:
+    """Engine that holds exactly `state_dict` as its KWS part, chosen as bind_m5 chooses: `engine` (refused if it holds another KWS
+    model), else the shared engine, else -- when the shared engine already serves a different one -- an engine of this module's own."""
+    eng = engine if engine is not None else get_engine()
+    if engine is None and eng.has_kws and eng.kws_owner != state_fingerprint(state_dict):
+        eng = Engine(dict(eng.wavenet_geometry), max_batch=eng.max_batch, precision=eng.precision)
+    eng.bind('kws', state_dict, lambda sd: eng.load_kws(sd, kernel_size, stride))
     return eng
 
 

@@ -725,6 +725,40 @@ int dmad_m5_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repe
 int dmad_m5_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, const dmad_wave_defense* d, float* logits,
                                  int32_t* decisions, dmad_stream s);
 
+/* ---- KWS, the attention-CRNN keyword spotter (audio_models/RCNN_KWS/model.py:66-114 KWSModel): a part of its own beside the WaveNet,
+ * the spectrogram classifier, the UNet and M5.  A dB mel spectrogram [B][32][T] in, 4 log-probabilities out: depthwise
+ * Conv1d(32,32,5,stride 2) -> pointwise Conv1d(32,64,1,stride 8) -> 2-layer bidirectional GRU(64), h0 = 0 -> additive attention over
+ * time -> bias-free Linear -> log_softmax.  Its mel front-end is not on the engine.
+ *
+ * Weights (dmad_load_weight): the 24 tensors of the module's state dict in their own shapes, each under "kws." + its key
+ *   kws.CRNN_model.sepconv.0.weight [32][1][5]  .0.bias [32]  .1.weight [64][32][1]  .1.bias [64]
+ *   kws.CRNN_model.gru.weight_ih_l<l><sfx> [192][64 or 128]  weight_hh_l<l><sfx> [192][64]  bias_ih_l<l><sfx> / bias_hh_l<l><sfx> [192],
+ *     l = 0, 1 and <sfx> = "" or "_reverse" (torch's gate order r, z, n)
+ *   kws.attn_layer.Wx_b.weight [128][128]  .bias [128]   kws.attn_layer.Vt.weight [1][128]   kws.apply_attn.U.weight [4][128]
+ * and two arrays for what no tensor shows:  kws.kernel_size [2] = (20, 5)   kws.stride [2] = (8, 2)   (as floats).
+ * dmad_finalize_weights packs them.  Supported: in_size 32, hidden_size 64, kernel_size (20, 5), stride (8, 2), 2 GRU layers, 2
+ * directions, 4 classes; anything else is DMAD_ERR_SHAPE with a message that names the field.  KWS is exact fp32 on every engine
+ * precision.  One workgroup serves one row and keeps its activations in LDS: NO workspace in device memory, nothing reserved at
+ * finalisation, no call allocates.  Every sum runs in a fixed order inside the row's workgroup, so a row's bits do not depend on B, on
+ * its row index or on the call.  Any B >= 1 (no max_batch limit); 5 <= T <= 644 (40 GRU steps: what the LDS of one CU holds), any
+ * other T is DMAD_ERR_SHAPE; rows need no more than 4-byte alignment.  All three calls return DMAD_ERR_STATE before the KWS weights
+ * are finalised.  Both checks are made on the host, before any launch.
+ *
+ * dmad_kws_logits (KWSModel.forward with hidden = None):  spec device fp32 [B][32][T] -> logp [B][4]; decisions: optional int32 [B],
+ * the arg-max (the first maximum wins).
+ *
+ * dmad_kws_vjp (what loss.backward() runs through KWSModel.forward):  g_spec = (d logp / d spec)^T g_logp, [B][32][T], for g_logp
+ * [B][4].  The forward is recomputed in the same launch.  Every element of g_spec is written: step j of the GRU reads frames
+ * 16 j .. 16 j + 4 only, and every other frame gets an exact 0.  logp: optional, bit-identical to dmad_kws_logits.  First order only,
+ * no weight gradients.
+ *
+ * dmad_kws_tape (test hook), written by the launch dmad_kws_vjp makes, T2 = ((T - 5) / 2) / 8 + 1 steps:  stage 0 the sepconv output
+ * [B][T2][64]; stages 1 and 2 the output of GRU layer 0 and 1, [B][T2][128], forward direction first; stage 3 the attention scores
+ * e, [B][T2]. */
+int dmad_kws_logits(dmad_engine* e, const float* spec, int32_t B, int32_t T, float* logp, int32_t* decisions, dmad_stream s);
+int dmad_kws_vjp(dmad_engine* e, const float* spec, int32_t B, int32_t T, const float* g_logp, float* g_spec, float* logp, dmad_stream s);
+int dmad_kws_tape(dmad_engine* e, const float* spec, int32_t B, int32_t T, int32_t stage, float* out, dmad_stream s);
+
 /* counts[argmax_c logits[b][c]] += 1 (first maximum wins) — certified_robust.py:59-65. */
 int dmad_vote(dmad_engine* e, const float* logits, int32_t B, int64_t* counts, dmad_stream s);
 
