@@ -9,7 +9,11 @@ ONE C-ABI call — dmad_query_logits for defense_type 'wave' (repeat -> DDPM pur
 dmad_defense_query_logits for a baseline waveform defense (TimeDomainDefense / FreqDomainDefense on backend 'hip'),
 dmad_spec_query_logits for 'spec' (repeat -> mel dB -> spec-domain purifier -> classifier -> arg-max).  With transform None and an
 M5 that use_engine() put on the engine the 'wave' chains are dmad_m5_query_logits / dmad_m5_defense_query_logits (the same rows and
-Philox keys, M5 in the place of mel dB -> classifier).  Otherwise it loops over forward()."""
+Philox keys, M5 in the place of mel dB -> classifier).  A KWSModel that use_engine() put on the engine behind the keyword spotter's own mel front-end
+on that engine (dmad_hip.transforms.KWSMelSpectrogramDB, or the shims' MelSpectrogram(sample_rate=16000, n_mels=32) + AmplitudeToDB pair)
+is the third family: forward() itself is one call there (kws_wave_logits, or autograd.KWSWaveHIP on the gradient branch with grad_backend
+'hip'), and the 'wave' chains are dmad_kws_query_logits / dmad_kws_defense_query_logits, which need clips of the engine's clip_len (without
+a defender any length runs, as kws_wave_logits on the repeated rows).  Otherwise it loops over forward()."""
 import torch
 
 
@@ -35,6 +39,13 @@ class AcousticSystem(torch.nn.Module):
         x = self._rescale(x)
         use_defender = defend == True and self.defender is not None   # noqa: E712 (reference semantics)
         output = self.defender(x) if (use_defender and self.defense_type == 'wave') else x
+        eng = self._kws_engine() if output.is_cuda and not (use_defender and self.defense_type == 'spec') else None
+        if eng is not None:                                           # KWSModel behind its own front-end, both on one engine: one call
+            if not (torch.is_grad_enabled() and output.requires_grad):
+                return eng.kws_wave_logits(output)
+            if self.classifier.grad_backend == 'hip' and getattr(self.transform, 'grad_backend', 'hip') == 'hip':
+                from dmad_hip.autograd import kws_wave_hip
+                return kws_wave_hip(eng, output)
         if self.transform is not None:
             output = self.transform(output)
         if use_defender and self.defense_type == 'spec':
@@ -42,8 +53,30 @@ class AcousticSystem(torch.nn.Module):
         return self.classifier(output)
 
     # ------------------------------------------------------------------------------------------------------------
-    def _engine_chain(self, defend):
-        """The engine that can run this system as one dmad_query_logits call, with the sampler id, or (None, 0)."""
+    @staticmethod
+    def _stages(tr):
+        """the `_dmad_stage` names of a Compose (`.transforms`) or an nn.Sequential, and the stages themselves"""
+        ts = getattr(tr, 'transforms', None)
+        if ts is None and isinstance(tr, torch.nn.Sequential):
+            ts = list(tr.children())
+        ts = list(ts or [])
+        return [getattr(t, '_dmad_stage', None) for t in ts], ts
+
+    def _kws_engine(self):
+        """The engine of a KWSModel in eval mode whose transform is the keyword spotter's mel front-end on the same engine, or None."""
+        from audio_models.RCNN_KWS.model import is_kws
+        cls, tr = self.classifier, self.transform
+        eng = getattr(cls, 'engine', None) if 'engine' in getattr(cls, '__dict__', {}) else None
+        if eng is None or tr is None or not is_kws(cls) or cls.training:
+            return None
+        if getattr(tr, '_dmad_stage', None) == 'kws_mel_db':          # dmad_hip.transforms.KWSMelSpectrogramDB
+            return eng if tr.engine is eng else None
+        names, ts = self._stages(tr)
+        return eng if names == ['kws_mel_power', 'power_to_db'] and getattr(ts[0], 'engine', None) is eng else None
+
+    def _engine_chain(self, defend, L=None):
+        """The engine that can run this system as one dmad_query_logits call, with the sampler id, or (None, 0).  L: the clip length of
+        the query, which the KWS chains with a defender need to be the engine's."""
         from dmad_hip.transforms import MelSpectrogramDB
         cls, tr, den = self.classifier, self.transform, self.defender
         eng = getattr(cls, 'engine', None) if 'engine' in getattr(cls, '__dict__', {}) else None
@@ -55,8 +88,13 @@ class AcousticSystem(torch.nn.Module):
                 return None, 0
             return self._wave_sampler(eng, defend)                    # the same samplers; query() calls the engine's m5_* pair for them
         from audio_models.RCNN_KWS.model import is_kws
-        if is_kws(cls) or not eng.has_classifier:                     # a KWSModel's `engine` is not a spectrogram-classifier binding, and
-            return None, 0                                            # KWS has no one-call query export: query() loops over forward()
+        if is_kws(cls):                                               # a KWSModel's `engine` is not a spectrogram-classifier binding:
+            if self._kws_engine() is not eng or self.defense_type != 'wave':      # only behind its own front-end is it a one-call chain
+                return None, 0
+            eng, sampler = self._wave_sampler(eng, defend)
+            return (None, 0) if (sampler and L != eng.L) else (eng, sampler)      # the purifier and the defenses run at clip_len only
+        if not eng.has_classifier:
+            return None, 0
         mel = isinstance(tr, MelSpectrogramDB) and tr.engine is eng
         if not mel:
             mel = [getattr(t, '_dmad_stage', None) for t in getattr(tr, 'transforms', [])] == ['mel_power', 'power_to_db']
@@ -92,10 +130,14 @@ class AcousticSystem(torch.nn.Module):
         the reference's order."""
         x = self._rescale(x)
         B = x.shape[0]
-        eng, sampler = self._engine_chain(defend)
+        eng, sampler = self._engine_chain(defend, x.shape[-1])
         if eng is not None and x.is_cuda:
-            # a chain without a transform is an M5 on the engine: the same rows and keys, M5 in the place of mel dB -> classifier
-            pre = 'm5_' if self.transform is None else ''
+            # a chain without a transform is an M5 on the engine: the same rows and keys, M5 in the place of mel dB -> classifier;
+            # a chain that _kws_engine() recognises is a KWSModel behind its own mel front-end in that place
+            pre = 'm5_' if self.transform is None else ('kws_' if self._kws_engine() is eng else '')
+            if pre == 'kws_' and sampler == 0:                        # no purifier, no defense: the rows at any length, in one call
+                logits, dec = eng.kws_wave_logits(x.repeat(repeats, 1, 1), want_decisions=True)
+                return logits.view(repeats, B, -1), dec.view(repeats, B).long()
             if sampler == 1:
                 den = self.defender
                 ts, c_a, c_b, c_eps, c_div, c_sig = den.purify_coefficients()

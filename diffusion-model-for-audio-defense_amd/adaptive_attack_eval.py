@@ -227,14 +227,16 @@ def attacker_factory(args, AS_MODEL, log=print):
     return make_attacker
 
 
-def evaluate(args, AS_MODEL, classifier, make_attacker, log=print):
-    """The evaluation loop both attack drivers share (reference l.234-370): clean, purified-clean and attacked accuracy over the test folder.
+def evaluate(args, AS_MODEL, classifier, make_attacker, log=print, test_dataset=None):
+    """The evaluation loop the attack drivers share (reference l.234-370): clean, purified-clean and attacked accuracy over the test folder
+    (`test_dataset`: another dataset of {'samples', 'target'} items, as kws_adaptive_attack_eval.py passes).
     `make_attacker()` is called after the model lines are logged and returns an object with generate(x=, y=, targeted=) -> (x_adv, success),
     success a list per clip or the (stage 1, stage 2) pair of AudioAttack."""
     from datasets.sc_dataset import SC09Dataset
     from transforms import FixAudioLength, LoadAudio
     AS_MODEL.eval()
-    test_dataset = SC09Dataset(folder=args.data_path, transform=_Compose([LoadAudio(), FixAudioLength()]), num_per_class=args.num_per_class)
+    if test_dataset is None:
+        test_dataset = SC09Dataset(folder=args.data_path, transform=_Compose([LoadAudio(), FixAudioLength()]), num_per_class=args.num_per_class)
     test_dataloader = DataLoader(test_dataset, batch_size=args.batch_size, sampler=None, shuffle=False, pin_memory=True,
                                  num_workers=args.dataload_workers_nums)
     log('classifier model: {}'.format(classifier._get_name()))

@@ -21,6 +21,7 @@
 #include "wave_defense.h"
 #include "m5.h"
 #include "kws.h"
+#include "kws_mel.h"
 #include "masking.h"
 #include "wrn.h"
 #include "gemm_f32.h"
@@ -347,6 +348,11 @@ struct dmad_engine {
     bool kws_final = false;
     float* kws_buf = nullptr;
     KwsWeights kwsw;
+    // Mel front-end of the keyword spotter (kws_mel.h): constants built at first use on any engine, and the scratch of the
+    // two wave exports -- dB spectrogram and its gradient of kKwsWaveRows (512) rows at the longest T, of which only the read frames are used
+    KwsMelConst kmel;
+    float* kws_spec = nullptr;
+    float* kws_gspec = nullptr;
 
     template <typename T>
     int alloc(T** p, size_t n, bool zero = false) {
@@ -418,6 +424,17 @@ int need_kind(const dmad_engine* e, int kind) {  // the finalised classifier is 
                                           kCls[e->cls_kind].net, kCls[e->cls_kind].vjp);
 }
 int need_kws(const dmad_engine* e) { return e->kws_final ? 0 : fail(DMAD_ERR_STATE, "KWS weights are not finalised (dmad_load_weight + dmad_finalize_weights)"); }
+int need_kws_mel(dmad_engine* e) {          // the constants of kws_mel.h, float64 on the host and rounded once
+    if (e->kmel.af) return 0;
+    KwsMelHost h;
+    if (const char* m = kws_mel_host_constants(&h)) return fail(DMAD_ERR_STATE, "KWS mel constants: %s", m);
+    float *af = nullptr, *ab = nullptr, *fb = nullptr, *w0 = nullptr, *w1 = nullptr;
+    int32_t *m0 = nullptr, *lo = nullptr, *hi = nullptr;
+    CHK(e->upload(&ab, h.ab)); CHK(e->upload(&fb, h.fb)); CHK(e->upload(&w0, h.w0)); CHK(e->upload(&w1, h.w1));
+    CHK(e->upload(&m0, h.m0)); CHK(e->upload(&lo, h.lo)); CHK(e->upload(&hi, h.hi)); CHK(e->upload(&af, h.af));
+    e->kmel = KwsMelConst{af, ab, fb, w0, w1, m0, lo, hi};       // af last: it is the guard
+    return 0;
+}
 int need_m5(const dmad_engine* e) { return e->m5_final ? 0 : fail(DMAD_ERR_STATE, "M5 weights are not finalised (dmad_load_weight + dmad_finalize_weights)"); }
 int need_batch(const dmad_engine* e, int B) { return B >= 1 && B <= e->maxB ? 0 : fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB); }
 int need_path(const dmad_engine* e, int path) {  // a WaveNet path the caller names (dmad_wavenet_eps_path / dmad_eval_samples)
@@ -3707,9 +3724,120 @@ int kws_launch(dmad_engine* e, const char* who, const float* spec, int B, int T,
     return 0;
 }
 
+constexpr int kKwsWaveRows = 512;           // rows of one pass of the wave exports: what the engine-owned spectrogram scratch holds (two
+                                            // rounds of one-workgroup-per-row kws_kernel launches over the CUs; 64 rows left three quarters idle)
+constexpr int kKwsWaveMinL = kMelHop * (kKwsMinT - 1), kKwsWaveMaxL = kMelHop * kKwsMaxT - 1;      // T = 1 + L / 200 in 5 .. kKwsMaxT
+
+// the host-side checks of the three mel exports
+int kws_mel_args(dmad_engine* e, const char* who, int B, int L) {
+    if (B < 1) return fail(DMAD_ERR_INVALID, "%s: B must be >= 1", who);
+    if (L < kMelMinL) return fail(DMAD_ERR_SHAPE, "%s: L = %d is below %d: the reflect padding mirrors %d samples", who, L, kMelMinL, kMelHop);
+    return need_kws_mel(e);
+}
+
+// ... and of the wave and query exports: finalised weights, T inside what kws.hip serves, the constants and the scratch
+int kws_wave_args(dmad_engine* e, const char* who, int B, int L, KwsGeom* g) {
+    if (B < 1) return fail(DMAD_ERR_INVALID, "%s: B must be >= 1", who);
+    CHK(need_kws(e));
+    if (L < kKwsWaveMinL || L > kKwsWaveMaxL)
+        return fail(DMAD_ERR_SHAPE, "%s: L = %d is outside %d .. %d (T = 1 + L / %d frames must lie in %d .. %d)", who, L, kKwsWaveMinL, kKwsWaveMaxL,
+                    kMelHop, kKwsMinT, kKwsMaxT);
+    if (const char* m = kws_geometry(1 + L / kMelHop, g)) return fail(DMAD_ERR_SHAPE, "%s: %s (L = %d)", who, m, L);
+    CHK(need_kws_mel(e));
+    if (!e->kws_spec) CHK(e->alloc(&e->kws_spec, (size_t)kKwsWaveRows * kKwsIn * kKwsMaxT));
+    if (!e->kws_gspec) CHK(e->alloc(&e->kws_gspec, (size_t)kKwsWaveRows * kKwsIn * kKwsMaxT));
+    return 0;
+}
+
+// waveforms x [B][L] -> the read frames of mel dB -> kws_kernel, in passes of kKwsWaveRows rows (rows are independent: the pass size
+// cannot change a bit).  With g_logp also the waveform gradient: the KWS VJP, then the mel VJP on the read frames
+int kws_wave_rows(dmad_engine* e, const KwsGeom& g, const float* x, int B, int L, float* logp, int32_t* cls, const float* g_logp, float* g_x,
+                  hipStream_t st) {
+    return for_passes(B, kKwsWaveRows, [&](int64_t r0, int nb) -> int {
+        const float* xr = x + r0 * L;
+        launch_kws_mel(e->kmel, xr, nb, L, g.T2, e->kws_spec, 1, st);
+        launch_kws(e->kwsw, g, e->kws_spec, nb, logp ? logp + r0 * kKwsOut : nullptr, cls ? cls + r0 : nullptr,
+                   g_logp ? g_logp + r0 * kKwsOut : nullptr, g_logp ? e->kws_gspec : nullptr, -1, nullptr, st);
+        if (g_logp) launch_kws_mel_vjp(e->kmel, xr, e->kws_gspec, nb, L, g.T2, g_x + r0 * L, nullptr, st);
+        HIPCHK(hipGetLastError());
+        return 0;
+    });
+}
+
 }  // namespace
 
 extern "C" {
+
+// ---- the KWS mel front-end (kws_adaptive_attack_eval.py: MelSpectrogram(sample_rate=16000, n_mels=32), AmplitudeToDB('power'))
+
+int dmad_kws_mel_power(dmad_engine* e, const float* x, int32_t B, int32_t L, float* out, dmad_stream s) {
+    if (!e || !x || !out) return fail(DMAD_ERR_INVALID, "dmad_kws_mel_power: null argument");
+    CHK(kws_mel_args(e, "dmad_kws_mel_power", B, L));
+    launch_kws_mel(e->kmel, x, B, L, 0, out, 0, (hipStream_t)s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int dmad_kws_mel_db(dmad_engine* e, const float* x, int32_t B, int32_t L, float* out, dmad_stream s) {
+    if (!e || !x || !out) return fail(DMAD_ERR_INVALID, "dmad_kws_mel_db: null argument");
+    CHK(kws_mel_args(e, "dmad_kws_mel_db", B, L));
+    launch_kws_mel(e->kmel, x, B, L, 0, out, 1, (hipStream_t)s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int dmad_kws_mel_db_vjp(dmad_engine* e, const float* x, int32_t B, int32_t L, const float* g_spec, float* g_x, float* spec, dmad_stream s) {
+    if (!e || !x || !g_spec || !g_x) return fail(DMAD_ERR_INVALID, "dmad_kws_mel_db_vjp: null argument");
+    CHK(kws_mel_args(e, "dmad_kws_mel_db_vjp", B, L));
+    launch_kws_mel_vjp(e->kmel, x, g_spec, B, L, 0, g_x, spec, (hipStream_t)s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int dmad_kws_wave_logits(dmad_engine* e, const float* x, int32_t B, int32_t L, float* logp, int32_t* decisions, dmad_stream s) {
+    if (!e || !x || !logp) return fail(DMAD_ERR_INVALID, "dmad_kws_wave_logits: null argument");
+    KwsGeom g;
+    CHK(kws_wave_args(e, "dmad_kws_wave_logits", B, L, &g));
+    return kws_wave_rows(e, g, x, B, L, logp, decisions, nullptr, nullptr, (hipStream_t)s);
+}
+
+int dmad_kws_wave_vjp(dmad_engine* e, const float* x, int32_t B, int32_t L, const float* g_logp, float* g_x, float* logp, dmad_stream s) {
+    if (!e || !x || !g_logp || !g_x) return fail(DMAD_ERR_INVALID, "dmad_kws_wave_vjp: null argument");
+    KwsGeom g;
+    CHK(kws_wave_args(e, "dmad_kws_wave_vjp", B, L, &g));
+    return kws_wave_rows(e, g, x, B, L, logp, nullptr, g_logp, g_x, (hipStream_t)s);
+}
+
+int dmad_kws_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, int32_t sampler, int32_t t_star, float c_a, float c_b,
+                          const float* c_eps, const float* c_div, const float* c_sig, uint64_t seed, uint64_t sample0, float* logits,
+                          int32_t* decisions, dmad_stream s) {
+    CHK(query_args(e, x, logits, B, repeats, sampler, t_star, c_eps, c_div, c_sig));
+    KwsGeom g;
+    CHK(kws_wave_args(e, "dmad_kws_query_logits", B, e->L, &g));
+    if (sampler) CHK(need_wavenet(e));
+    hipStream_t st = (hipStream_t)s;
+    // the arg-max comes out of the KWS launch itself, so query_loop's vote is not asked for
+    return query_loop(e, x, B, repeats, logits, nullptr, st, [&](int nb, int64_t r0, float* lg) -> int {
+        const float* pur;
+        CHK(run_query_sampler(e, sampler, t_star, c_a, c_b, c_eps, c_div, c_sig, seed, sample0, r0, nb, st, &pur));
+        return kws_wave_rows(e, g, pur, nb, e->L, lg, decisions ? decisions + r0 : nullptr, nullptr, nullptr, st);
+    }, kKwsOut);
+}
+
+int dmad_kws_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, const dmad_wave_defense* d, float* logits,
+                                  int32_t* decisions, dmad_stream s) {
+    if (!e || !x || !logits || !d) return fail(DMAD_ERR_INVALID, "dmad_kws_defense_query_logits: null argument");
+    if (B < 1 || repeats < 1) return fail(DMAD_ERR_INVALID, "dmad_kws_defense_query_logits: B and repeats must be >= 1");
+    IirPlan plan;
+    if (const char* m = wave_defense_check(d, e->L, &plan)) return fail(DMAD_ERR_INVALID, "dmad_kws_defense_query_logits: %s", m);
+    KwsGeom g;
+    CHK(kws_wave_args(e, "dmad_kws_defense_query_logits", B, e->L, &g));
+    hipStream_t st = (hipStream_t)s;
+    return query_loop(e, x, B, repeats, logits, nullptr, st, [&](int nb, int64_t r0, float* lg) -> int {
+        CHK(run_wave_defense(e, d, plan, nb, st));
+        return kws_wave_rows(e, g, e->x0, nb, e->L, lg, decisions ? decisions + r0 : nullptr, nullptr, nullptr, st);
+    }, kKwsOut);
+}
 
 // ---- KWS (audio_models/RCNN_KWS/model.py:93-114): forward, input VJP and the tape hook
 

@@ -85,6 +85,8 @@ __device__ inline float relu_nan(float t) { return t < 0.f ? 0.f : t; }
 __device__ inline float max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
 __device__ inline float clamp_min_nan(float t, float lo) { return t < lo ? lo : t; }
 __device__ inline float clamp_nan(float t, float lo, float hi) { return t < lo ? lo : (t > hi ? hi : t); }
+// AmplitudeToDB(stype='power') of one value: the function of dmad_power_to_db and of the KWS mel front-end (kws_mel.hip)
+__device__ inline float power_db(float p) { return __fmul_rn(10.f, (float)log10((double)clamp_min_nan(p, 1e-10f))); }
 
 __device__ inline float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ inline float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }

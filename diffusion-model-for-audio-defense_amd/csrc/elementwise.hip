@@ -710,7 +710,7 @@ void launch_mel_db(const float* M, float* spec, int B, int to_db, hipStream_t s)
 // AmplitudeToDB(stype='power') on its own: y = 10 * log10(max(x, 1e-10))
 __global__ void power_to_db_kernel(const float* __restrict__ x, float* __restrict__ y, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) y[i] = __fmul_rn(10.f, (float)log10((double)clamp_min_nan(x[i], 1e-10f)));
+    if (i < n) y[i] = power_db(x[i]);
 }
 void launch_power_to_db(const float* x, float* y, long n, hipStream_t s) {
     hipLaunchKernelGGL(power_to_db_kernel, dim3(nblk(n, 256)), dim3(256), 0, s, x, y, n);

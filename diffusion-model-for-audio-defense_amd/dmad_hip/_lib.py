@@ -152,6 +152,14 @@ _SIGNATURES = {
     'dmad_kws_logits': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     'dmad_kws_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     'dmad_kws_tape': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_kws_mel_power': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_kws_mel_db': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_kws_mel_db_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    'dmad_kws_wave_logits': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    'dmad_kws_wave_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    'dmad_kws_query_logits': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P,
+                                        C.c_uint64, C.c_uint64, _P, _P, _P]),
+    'dmad_kws_defense_query_logits': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(DmadWaveDefense), _P, _P, _P]),
     'dmad_m5_query_logits': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P,
                                        C.c_uint64, C.c_uint64, _P, _P, _P]),
     'dmad_m5_defense_query_logits': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(DmadWaveDefense), _P, _P, _P]),

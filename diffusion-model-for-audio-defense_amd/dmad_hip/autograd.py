@@ -8,6 +8,7 @@ caller's CUDA tensors, fed with the same folded weights the engine packs:
 
     wavenet_eps   WaveNet_Speech_Commands.forward   DiffWave_Unconditional/WaveNet.py:75-97,120-135,164-172; util.py:68-93
     mel_db        MelSpectrogram + AmplitudeToDB    certified_robustness_eval.py:85-87 (torchaudio 0.11 semantics)
+    kws_mel_db    MelSpectrogram + AmplitudeToDB    kws_adaptive_attack_eval.py:74-76 (n_fft 400, hop 200, reflect padding, htk scale; any L, any device)
 
 (the classifiers' own nn layers are their restatement: models/vgg.py:48-52, models/resnext.py:47-62,133-142).
 Scope: gradients only.  Nothing here runs when no gradient is requested — inference calls go to libdmad_hip.so and fail loudly
@@ -27,6 +28,10 @@ ResNeXtHIP and MelDBHIP are the native alternatives for the last two stages of e
 'hip', MelSpectrogramDB(..., grad_backend='hip')): the classifier's forward is the engine's fp32 ResNeXt29 tier and its backward the
 engine's ResNeXt29 VJP (dmad_classify_vjp, tape re-written on the device); the mel front-end's backward recomputes the forward and
 walks dB, filterbank, |.|^2, DFT and overlap-add in reverse (dmad_mel_db_vjp).  Neither computes weight gradients.
+
+KWSMelDBHIP and KWSWaveHIP are the native alternatives for the keyword spotter's front-end and for the front-end with KWSModel behind it
+(KWSMelSpectrogramDB(..., grad_backend='hip'); AcousticSystem.forward of a KWSModel behind its own front-end): dmad_kws_mel_db_vjp, and
+dmad_kws_wave_vjp, which computes only the spectrogram frames the model reads.
 """
 import math
 
@@ -401,3 +406,83 @@ class KWSHIP(torch.autograd.Function):
 def kws_hip(engine, spec: torch.Tensor) -> torch.Tensor:
     """log-probabilities = KWSModel(spec [B,1,32,T] or [B,32,T]) on the engine, differentiable in `spec` (KWSHIP)."""
     return KWSHIP.apply(spec, engine)
+
+
+_KWS_MEL_CACHE = {}
+
+
+def kws_mel_filterbank() -> np.ndarray:
+    """The htk filterbank of torchaudio MelSpectrogram(sample_rate=16000, n_mels=32) in float64, [32][201]: 34 points equally spaced in
+    mel = 2595 log10(1 + f / 700) between 0 and 8000 Hz, bins at linspace(0, 8000, 201), max(0, min(down, up)), no norm."""
+    mel = np.linspace(0.0, 2595.0 * np.log10(1.0 + 8000.0 / 700.0), 34)
+    pts = 700.0 * (10.0 ** (mel / 2595.0) - 1.0)
+    freqs = np.linspace(0.0, 8000.0, 201)
+    down = (freqs[None, :] - pts[:-2, None]) / (pts[1:-1, None] - pts[:-2, None])
+    up = (pts[2:, None] - freqs[None, :]) / (pts[2:, None] - pts[1:-1, None])
+    return np.maximum(0.0, np.minimum(down, up))
+
+
+def kws_mel_db(x: torch.Tensor) -> torch.Tensor:
+    """[B,1,L] -> [B,1,32,1 + L // 200] dB mel spectrogram of the keyword spotter's front-end (torchaudio MelSpectrogram(16000,
+    n_mels=32) then AmplitudeToDB('power')), differentiable in x, in x's dtype and on x's device: the restatement in torch ops that the
+    CPU path and the grad_backend = 'torch' branch run (the engine's kernels are dmad_kws_mel_*)."""
+    key = (str(x.device), x.dtype)
+    if key not in _KWS_MEL_CACHE:
+        _KWS_MEL_CACHE[key] = (torch.hann_window(400, periodic=True, dtype=torch.float64).to(x.device, x.dtype),
+                               torch.from_numpy(kws_mel_filterbank()).to(x.device, x.dtype))
+    win, fb = _KWS_MEL_CACHE[key]
+    spec = torch.stft(x[:, 0], n_fft=400, hop_length=200, win_length=400, window=win, center=True, pad_mode='reflect',
+                      normalized=False, onesided=True, return_complex=True)
+    power = spec.real ** 2 + spec.imag ** 2                                        # [B, 201, T]
+    mel = torch.matmul(fb, power)                                                  # [B, 32, T]
+    return (10.0 * torch.log10(torch.clamp(mel, min=1e-10))).unsqueeze(1)
+
+
+class KWSMelDBHIP(torch.autograd.Function):
+    """[B,1,L] -> [B,1,32,T] dB mel spectrogram of the keyword spotter's front-end on the engine (kws_mel_db), differentiable in `x`
+    through the engine's VJP (dmad_kws_mel_db_vjp, which recomputes the forward).  Saves only the input.  First-order only:
+    create_graph=True raises."""
+
+    @staticmethod
+    def forward(ctx, x, engine):
+        _require_cuda(x)
+        ctx.engine = engine
+        ctx.save_for_backward(x)
+        return engine.kws_mel_db(x).unsqueeze(1)
+
+    @staticmethod
+    def backward(ctx, g_spec):
+        _first_order_only('KWS mel')
+        x, = ctx.saved_tensors
+        g = ctx.engine.kws_mel_db_vjp(x, g_spec.contiguous())
+        return g.view(x.shape).to(x.dtype), None
+
+
+def kws_mel_db_hip(engine, x: torch.Tensor) -> torch.Tensor:
+    """[B,1,L] -> [B,1,32,T] on the engine, differentiable in x (KWSMelDBHIP)."""
+    return KWSMelDBHIP.apply(x, engine)
+
+
+class KWSWaveHIP(torch.autograd.Function):
+    """log-probabilities = KWSModel(kws_mel_db(x [B,1,L])) on the engine in one call (kws_wave_logits: only the frames the model reads
+    are computed), differentiable in `x` through dmad_kws_wave_vjp (the KWS VJP, then the mel VJP on the read frames).  Saves only the
+    input; nothing is reserved.  No weight gradients.  First-order only: create_graph=True raises."""
+
+    @staticmethod
+    def forward(ctx, x, engine):
+        _require_cuda(x)
+        ctx.engine = engine
+        ctx.save_for_backward(x)
+        return engine.kws_wave_logits(x)
+
+    @staticmethod
+    def backward(ctx, g_logp):
+        _first_order_only('KWS wave')
+        x, = ctx.saved_tensors
+        g = ctx.engine.kws_wave_vjp(x, g_logp.contiguous())
+        return g.view(x.shape).to(x.dtype), None
+
+
+def kws_wave_hip(engine, x: torch.Tensor) -> torch.Tensor:
+    """log-probabilities = KWSModel(kws_mel_db(x)) on the engine, differentiable in `x` (KWSWaveHIP)."""
+    return KWSWaveHIP.apply(x, engine)

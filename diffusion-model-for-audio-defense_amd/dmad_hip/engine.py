@@ -274,6 +274,11 @@ def kws_steps(T: int) -> int:
     return ((T - 5) // 2) // 8 + 1 if T >= 5 else 0
 
 
+def kws_frames(L: int) -> int:
+    """spectrogram frames of an L-sample clip behind the KWS mel front-end (hop 200, center=True)"""
+    return 1 + int(L) // 200
+
+
 def fold_m5_state_dict(sd: Dict[str, object], stride: int = 16, eps: float = 1e-5) -> Dict[str, np.ndarray]:
     """M5Net.M5 state dict -> the `m5.*` arrays of include/dmad.h: the conv weights as they are, each eval-BatchNorm folded (in float64)
     into s = gamma / sqrt(var + eps) and shift = beta + (bias - mean) * s, fc1, and conv1's stride (the one geometry field no tensor
@@ -1373,6 +1378,81 @@ class Engine:
         out = torch.empty((B, t2) + ((64,), (128,), (128,), ())[stage], device=xs.device, dtype=torch.float32)
         check(self.lib.dmad_kws_tape(self._h, _ptr(xs), B, T, int(stage), _ptr(out), _stream()))
         return out
+
+    # ------------------------------------------------------------------ the KWS mel front-end (dmad_kws_mel_*, dmad_kws_wave_*): any clip length
+    @staticmethod
+    def _kws_wave(x: torch.Tensor) -> torch.Tensor:
+        """[B,1,L] or [B,L] -> contiguous fp32 [B,L]; L is an argument of every call, and the library checks it"""
+        _on_gpu(x)
+        x = x.detach()
+        if x.dim() == 3:
+            assert x.shape[1] == 1, 'expected [B,1,L]'
+            x = x[:, 0]
+        assert x.dim() == 2, 'expected [B,L], got %s' % (tuple(x.shape),)
+        return x.contiguous().float()
+
+    def _kws_mel(self, fn, x):
+        xw = self._kws_wave(x)
+        B, L = xw.shape
+        out = torch.empty((B, KWS_BINS, kws_frames(L)), device=xw.device, dtype=torch.float32)
+        check(fn(self._h, _ptr(xw), B, L, _ptr(out), _stream()))
+        return out
+
+    def kws_mel_power(self, x: torch.Tensor) -> torch.Tensor:
+        """dmad_kws_mel_power: x [B,1,L] or [B,L] -> mel power [B,32,T], T = 1 + L // 200 (torchaudio MelSpectrogram(16000, n_mels=32)).
+        One launch whatever B and L are."""
+        return self._kws_mel(self.lib.dmad_kws_mel_power, x)
+
+    def kws_mel_db(self, x: torch.Tensor) -> torch.Tensor:
+        """dmad_kws_mel_db: kws_mel_power followed by AmplitudeToDB('power'), in the same launch."""
+        return self._kws_mel(self.lib.dmad_kws_mel_db, x)
+
+    def kws_mel_db_vjp(self, x: torch.Tensor, g_spec: torch.Tensor, want_spec: bool = False):
+        """dmad_kws_mel_db_vjp: g_x [B,L] = (d kws_mel_db / d x)^T g_spec for g_spec [B,32,T] (or [B,1,32,T]).  want_spec: also the dB
+        spectrogram, bit-identical to kws_mel_db(x).  The forward is recomputed inside the one launch; nothing is saved or reserved."""
+        xw = self._kws_wave(x)
+        B, L = xw.shape
+        T = kws_frames(L)
+        if not g_spec.is_cuda or g_spec.numel() != B * KWS_BINS * T or g_spec.shape[-1] != T:
+            raise DmadError('g_spec must be a CUDA tensor [%d, %d, %d], not %s' % (B, KWS_BINS, T, tuple(g_spec.shape)))
+        gs = _f32(g_spec)
+        gx = torch.empty_like(xw)
+        spec = torch.empty((B, KWS_BINS, T), device=xw.device, dtype=torch.float32) if want_spec else None
+        check(self.lib.dmad_kws_mel_db_vjp(self._h, _ptr(xw), B, L, _ptr(gs), _ptr(gx), _ptr(spec), _stream()))
+        return (gx, spec) if want_spec else gx
+
+    def kws_wave_logits(self, x: torch.Tensor, want_decisions: bool = False):
+        """dmad_kws_wave_logits: x [B,1,L] or [B,L] -> log-probabilities [B,4] of KWSModel behind its mel front-end, bit-identical to
+        kws_logits(kws_mel_db(x)); only the spectrogram frames the model reads are computed.  One library call whatever B is."""
+        xw = self._kws_wave(x)
+        B, L = xw.shape
+        out = torch.empty((B, KWS_CLASSES), device=xw.device, dtype=torch.float32)
+        dec = torch.empty((B,), device=xw.device, dtype=torch.int32) if want_decisions else None
+        check(self.lib.dmad_kws_wave_logits(self._h, _ptr(xw), B, L, _ptr(out), _ptr(dec), _stream()))
+        return (out, dec) if want_decisions else out
+
+    def kws_wave_vjp(self, x: torch.Tensor, g: torch.Tensor, want_logits: bool = False):
+        """dmad_kws_wave_vjp: g_x [B,L] = (d logp / d x)^T g for logp = KWSModel(kws_mel_db(x)), g [B,4]; bit-identical to
+        kws_mel_db_vjp(x, kws_vjp(kws_mel_db(x), g)).  want_logits: also the log-probabilities, bit-identical to kws_wave_logits(x)."""
+        xw = self._kws_wave(x)
+        B, L = xw.shape
+        if not g.is_cuda or tuple(g.shape) != (B, KWS_CLASSES):
+            raise DmadError('g must be a CUDA tensor [%d, %d], not %s' % (B, KWS_CLASSES, tuple(g.shape)))
+        gl = _f32(g)
+        gx = torch.empty_like(xw)
+        lp = torch.empty((B, KWS_CLASSES), device=xw.device, dtype=torch.float32) if want_logits else None
+        check(self.lib.dmad_kws_wave_vjp(self._h, _ptr(xw), B, L, _ptr(gl), _ptr(gx), _ptr(lp), _stream()))
+        return (gx, lp) if want_logits else gx
+
+    def kws_query_logits(self, x: torch.Tensor, repeats: int, sampler: int = 0, t_star: int = 0, c_a: float = 0.0, c_b: float = 0.0,
+                         c_eps=None, c_div=None, c_sig=None, seed: int = 0, sample0: int = 0):
+        """dmad_kws_query_logits: query_logits with mel dB -> KWSModel in the place of mel dB -> classifier; x [B,1,clip_len] ->
+        (log-probabilities [repeats*B, 4], decisions int32 [repeats*B]); row r*B+b is clip b."""
+        return self._query(self.lib.dmad_kws_query_logits, KWS_CLASSES, x, repeats, sampler, t_star, c_a, c_b, c_eps, c_div, c_sig, seed, sample0)
+
+    def kws_defense_query_logits(self, x: torch.Tensor, repeats: int, defense: dict):
+        """dmad_kws_defense_query_logits: defense_query_logits with mel dB -> KWSModel behind the defense (`defense` as there)."""
+        return self._defense_query(self.lib.dmad_kws_defense_query_logits, KWS_CLASSES, x, repeats, defense)
 
     # ------------------------------------------------------------------ Philox draws, timing and profiling hooks
     def _philox(self, fn, seed, sample0, stream, B):

@@ -759,6 +759,43 @@ int dmad_kws_logits(dmad_engine* e, const float* spec, int32_t B, int32_t T, flo
 int dmad_kws_vjp(dmad_engine* e, const float* spec, int32_t B, int32_t T, const float* g_logp, float* g_spec, float* logp, dmad_stream s);
 int dmad_kws_tape(dmad_engine* e, const float* spec, int32_t B, int32_t T, int32_t stage, float* out, dmad_stream s);
 
+/* ---- The keyword spotter's mel front-end (kws_adaptive_attack_eval.py:74-76: torchaudio MelSpectrogram(sample_rate=16000, n_mels=32)
+ * then AmplitudeToDB(stype='power')) for clips of ANY length L, an argument of every call: n_fft = win_length = 400,
+ * hop 200, periodic Hann, center=True with reflect padding of 200 samples, 201 one-sided bins, power 2, htk mel scale without norm
+ * between 0 and 8000 Hz, 10 log10(max(., 1e-10)).  T = 1 + L / 200 frames.  Exact fp32 on every engine; its constants are built at
+ * the first call (no with_classifier, no weights) and dmad_device_bytes counts them.  Nothing is sized by max_batch: any B >= 1.  A
+ * frame's bits depend on its own 400 samples only -- not on B, the row, the call, nor on which frames are computed beside it.
+ * Refusals are made on the host before any launch and name L: DMAD_ERR_SHAPE for L < 201 (the reflect padding mirrors 200 samples)
+ * in the three mel calls, and for L outside 800 .. 128 799 (T outside 5 .. 644) in the wave and query calls, which return
+ * DMAD_ERR_STATE before the KWS weights are finalised.
+ *
+ * dmad_kws_mel_power (MelSpectrogram(sample_rate=16000, n_mels=32)(x), l.74):  x device fp32 [B][L] -> out [B][32][T], one launch.
+ * dmad_kws_mel_db (Wave2Spect(x), l.76: ... then AmplitudeToDB('power')):  the same in dB.
+ *
+ * dmad_kws_mel_db_vjp (what loss.backward() runs through Wave2Spect):  g_x [B][L] = (d spec / d x)^T g_spec for g_spec [B][32][T], one
+ * launch that recomputes the forward; no atomics, every element of g_x is written (the buffer need not be cleared), and the order of
+ * every sum is fixed (frames ascending, direct before reflected).  spec: optional, bit-identical to dmad_kws_mel_db. */
+int dmad_kws_mel_power(dmad_engine* e, const float* x, int32_t B, int32_t L, float* out, dmad_stream s);
+int dmad_kws_mel_db(dmad_engine* e, const float* x, int32_t B, int32_t L, float* out, dmad_stream s);
+int dmad_kws_mel_db_vjp(dmad_engine* e, const float* x, int32_t B, int32_t L, const float* g_spec, float* g_x, float* spec, dmad_stream s);
+/* dmad_kws_wave_logits (AS_MODEL(waveforms, False), l.230: Classifier(Wave2Spect(x))):  x [B][L] -> logp [B][4] (decisions: optional
+ * int32 [B]), bit-identical to dmad_kws_logits on dmad_kws_mel_db.  Only the frames KWSModel reads, 16 j .. 16 j + 4 per GRU step j,
+ * are computed; the spectrogram lives in an engine-owned scratch of 512 rows (42 MB, and as much for its gradient), allocated at the
+ * first call, and B is walked in passes of 512 rows (the pass size cannot change a bit). */
+int dmad_kws_wave_logits(dmad_engine* e, const float* x, int32_t B, int32_t L, float* logp, int32_t* decisions, dmad_stream s);
+/* dmad_kws_wave_vjp (loss.backward() of white_box_attack.py through AS_MODEL without a defender, l.103, 250):  g_x [B][L] =
+ * (d logp / d x)^T g_logp: the KWS VJP, then the mel VJP on the read frames; bit-identical to dmad_kws_mel_db_vjp on dmad_kws_vjp.
+ * logp: optional, bit-identical to dmad_kws_wave_logits. */
+int dmad_kws_wave_vjp(dmad_engine* e, const float* x, int32_t B, int32_t L, const float* g_logp, float* g_x, float* logp, dmad_stream s);
+/* dmad_m5_query_logits with  mel dB -> KWSModel  in the place of M5 (kws_adaptive_attack_eval.py:186-204: FAKEBOB / SirenAttack
+ * queries of AS_MODEL with the DiffWave defender, l.109-111); L is the engine's clip_len. */
+int dmad_kws_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, int32_t sampler, int32_t t_star, float c_a, float c_b,
+                          const float* c_eps, const float* c_div, const float* c_sig, uint64_t seed, uint64_t sample0, float* logits,
+                          int32_t* decisions, dmad_stream s);
+/* dmad_m5_defense_query_logits the same way (kws_adaptive_attack_eval.py:117-136 with a Time / FreqDomainDefense as the defender). */
+int dmad_kws_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, const dmad_wave_defense* d, float* logits,
+                                  int32_t* decisions, dmad_stream s);
+
 /* counts[argmax_c logits[b][c]] += 1 (first maximum wins) — certified_robust.py:59-65. */
 int dmad_vote(dmad_engine* e, const float* logits, int32_t B, int64_t* counts, dmad_stream s);
 
