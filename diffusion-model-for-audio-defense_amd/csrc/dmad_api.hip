@@ -2813,6 +2813,60 @@ int dmad_groupnorm16_apply(const uint16_t* x, const float* st, const uint16_t* x
     return 0;
 }
 
+int dmad_qkv_attention_h16(const uint16_t* qkv16, int32_t B, int32_t T, int32_t heads, uint16_t* out16, dmad_stream s) {
+    if (!qkv16 || !out16) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || B > 65535 || heads < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
+    if (int rc = launch_qkv_attention_h16(qkv16, out16, B, T, heads, (hipStream_t)s))
+        return fail(rc > 0 ? DMAD_ERR_HIP : DMAD_ERR_INVALID, "f16 attention (T = %d): %s", T, rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported map size");
+    LASTCHK();
+    return 0;
+}
+
+int dmad_groupnorm16(const uint16_t* x16, const uint16_t* x2_16, int32_t c1, const float* gamma, const float* beta, const float* ss,
+                     int32_t silu, int32_t B, int32_t HW, int32_t C, uint16_t* y16, float* y32, dmad_stream s) {
+    if (!x16 || !gamma || !beta || (!y16 == !y32)) return fail(DMAD_ERR_INVALID, "null argument (exactly one of y16 / y32)");
+    if (launch_groupnorm_nhwc(nullptr, gamma, beta, ss, silu, y32, B, HW, C, (hipStream_t)s, nullptr, x2_16 ? c1 : 0, y16, x16, x2_16))
+        return fail(DMAD_ERR_INVALID, "no two-pass f16 GroupNorm for a %d-pixel x %d-channel map (c1 = %d)", HW, C, c1);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_conv1ch_3x3(const float* in, const float* w, const float* bias, int32_t B, int32_t Cout, float* out32, uint16_t* out16, float* stats,
+                     dmad_stream s) {
+    if (!in || !w || !bias || (!out32 && !out16)) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || Cout < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
+    if (launch_conv1ch_3x3(in, w, bias, out32, B, Cout, (hipStream_t)s, out16, stats))
+        return fail(DMAD_ERR_INVALID, "no 1-channel 3x3 conv for %d output channels%s", Cout, stats ? " with statistics (Cout <= 128, a multiple of 4)" : " (Cout <= 128)");
+    LASTCHK();
+    return 0;
+}
+
+int dmad_conv3x3_c128_to1(const float* in, const float* w, const float* bias, int32_t B, const float* g_in, float alpha, float gamma,
+                          float* out, dmad_stream s) {
+    if (!in || !w || !bias || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || g_in == out) return fail(DMAD_ERR_INVALID, "bad geometry (g_in and out are two buffers)");
+    launch_conv3x3_c128_to1(in, w, bias, out, B, (hipStream_t)s, g_in, alpha, gamma);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_conv3x3_c128_to1_h16(const uint16_t* in16, const float* w, const float* bias, int32_t B, float* out, dmad_stream s) {
+    if (!in16 || !w || !bias || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
+    launch_conv3x3_c128_to1_h16(in16, w, bias, out, B, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_upsample2x(const void* in, int32_t B, int32_t H, int32_t C, int32_t is_f16, void* out, dmad_stream s) {
+    if (!in || !out || in == out) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || H < 1 || C < 1 || (C % (is_f16 ? 8 : 4))) return fail(DMAD_ERR_INVALID, "bad geometry (C a multiple of %d)", is_f16 ? 8 : 4);
+    if (is_f16) launch_upsample2x_nhwc_h16((const h16_t*)in, (h16_t*)out, B, H, H, C, (hipStream_t)s);
+    else launch_upsample2x_nhwc((const float*)in, (float*)out, B, H, H, C, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
 int dmad_conv_f32(const float* x, const float* x2, int32_t ksplit, const float* w, const float* scale, const float* shift, const float* res,
                   int32_t B, int32_t H, int32_t M, int32_t K, int32_t taps, int32_t stride, int32_t groups, int32_t relu, float* slab,
                   int64_t slab_floats, int64_t n_ref, float* out, int32_t* choice, dmad_stream s) {
@@ -2898,9 +2952,9 @@ int dmad_conv_f32_vjp(const float* g_y, const float* w, const float* scale, cons
 }
 
 int dmad_groupnorm_f32(const float* x, const float* x2, int32_t c1, const float* gamma, const float* beta, const float* ss, int32_t silu,
-                       int32_t B, int32_t HW, int32_t C, float* y, dmad_stream s) {
+                       int32_t B, int32_t HW, int32_t C, int32_t split, float* y, dmad_stream s) {
     if (!x || !gamma || !beta || !y) return fail(DMAD_ERR_INVALID, "null argument");
-    if (launch_groupnorm_nhwc(x, gamma, beta, ss, silu, y, B, HW, C, (hipStream_t)s, x2, x2 ? c1 : 0))
+    if (launch_groupnorm_nhwc(x, gamma, beta, ss, silu, y, B, HW, C, (hipStream_t)s, x2, x2 ? c1 : 0, nullptr, nullptr, nullptr, split ? 1 : 0))
         return fail(DMAD_ERR_INVALID, "no fp32 GroupNorm for a %d-pixel x %d-channel map (c1 = %d)", HW, C, c1);
     LASTCHK();
     return 0;
@@ -2916,10 +2970,10 @@ int dmad_groupnorm_bwd(const float* x, const float* x2, int32_t c1, const float*
     return 0;
 }
 
-int dmad_qkv_attention_f32(const float* qkv, int32_t B, int32_t T, int32_t heads, float* out, dmad_stream s) {
+int dmad_qkv_attention_f32(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t split, float* out, dmad_stream s) {
     if (!qkv || !out) return fail(DMAD_ERR_INVALID, "null argument");
     if (B < 1 || heads < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
-    if (int rc = launch_qkv_attention(qkv, out, B, T, heads, (hipStream_t)s))
+    if (int rc = launch_qkv_attention(qkv, out, B, T, heads, (hipStream_t)s, nullptr, split ? 1 : 0))
         return fail(rc > 0 ? DMAD_ERR_HIP : DMAD_ERR_INVALID, "attention (T = %d): %s", T, rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported map size");
     LASTCHK();
     return 0;

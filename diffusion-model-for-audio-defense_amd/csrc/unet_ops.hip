@@ -79,8 +79,10 @@ __global__ void __launch_bounds__(256) conv3x3_c128_to1_kernel(const float* __re
 }
 
 // The same conv on an f16 map (the 16-bit tier's last layer), on the matrix cores: per pixel the nine taps' dot products with its OWN
-// 128 channels — a 16 x 16 x 32 MFMA chain with the taps as rows (9 of 16) and 16 pixels as columns, the weights split into f16
-// hi + lo parts so that they keep fp32 precision — go to LDS, and an output pixel is the sum of nine neighbours' partials.  Every
+// 128 channels — a 16 x 16 x 32 MFMA chain with the taps as rows (9 of 16) and 16 pixels as columns, the weights in the split format of
+// dmad_common.h (hi = f16(w), lo = f16((w - hi) * 2^11): 22 significant bits for |w| down to ~6e-5, the scaled lo stays a normal f16
+// where an unscaled w - hi is a subnormal from |w| ~ 1e-3 down), the hi and the lo products in accumulators of their own, joined as
+// acc_hi + acc_lo * 2^-11 — go to LDS, and an output pixel is the sum of nine neighbours' partials.  Every
 // input byte is read once (the direct form above re-reads each row nine times through L2: 675 us per 2048 spectrograms; this 1).
 // One workgroup per image: 4 waves x 16 pixels per step, 16 steps, then 4 outputs per thread.
 __global__ void __launch_bounds__(256) conv3x3_c128_to1_h16_kernel(const h16_t* __restrict__ in, const float* __restrict__ w,
@@ -94,9 +96,10 @@ __global__ void __launch_bounds__(256) conv3x3_c128_to1_h16_kernel(const h16_t* 
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const float wf = r16 < 9 ? w[r16 * 128 + kk * 32 + q * 8 + r] : 0.f;
-            const _Float16 h = (_Float16)wf;
+            _Float16 h, l;
+            split1(wf, h, l);                              // lo carries (w - hi) * 2^11: 11 more bits down to |w| ~ 2^-25, not an f16 subnormal
             ah[kk][r] = h;
-            al[kk][r] = (_Float16)(wf - (float)h);
+            al[kk][r] = l;
         }
     const h16_t* img = in + b * 1024 * 128;
     for (int it = 0; it < 16; ++it) {
@@ -104,12 +107,14 @@ __global__ void __launch_bounds__(256) conv3x3_c128_to1_h16_kernel(const h16_t* 
         f16x8 x[4];
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) x[kk] = *(const f16x8*)(img + px * 128 + kk * 32 + q * 8);
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f}, acl = acc;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[kk], x[kk], acc, 0, 0, 0);
+            acl = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[kk], x[kk], acl, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[kk], x[kk], acc, 0, 0, 0);
         }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = __builtin_fmaf(acl[r], kSplitInv, acc[r]);
         if (q < 2) {                                       // lane (q, r16): taps 4 q .. 4 q + 3 of pixel r16
 #pragma unroll
             for (int r = 0; r < 4; ++r) P[px * 9 + q * 4 + r] = acc[r];

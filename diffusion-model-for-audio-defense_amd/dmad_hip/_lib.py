@@ -73,13 +73,19 @@ _SIGNATURES = {
                                C.c_int32, _P, _P]),
     'dmad_conv_h16_stats': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     'dmad_groupnorm16_apply': (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    'dmad_qkv_attention_h16': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_groupnorm16': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    'dmad_conv1ch_3x3': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    'dmad_conv3x3_c128_to1': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_float, C.c_float, _P, _P]),
+    'dmad_conv3x3_c128_to1_h16': (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
+    'dmad_upsample2x': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_conv_f32': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, _P]),
     'dmad_conv_f32_vjp': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, _P, _P, _P, _P, _P]),
-    'dmad_groupnorm_f32': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_groupnorm_f32': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_groupnorm_bwd': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
-    'dmad_qkv_attention_f32': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_qkv_attention_f32': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_qkv_attention_bwd': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_rx_head_bwd': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_rx_conv1_bwd': (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P]),

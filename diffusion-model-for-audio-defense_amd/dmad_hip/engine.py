@@ -1624,6 +1624,73 @@ def groupnorm16_apply(x: torch.Tensor, st: torch.Tensor, gamma: torch.Tensor, be
     return y
 
 
+def groupnorm16(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, silu: bool = True, ss: Optional[torch.Tensor] = None,
+                x2: Optional[torch.Tensor] = None, out32: bool = False) -> torch.Tensor:
+    """dmad_groupnorm16: the two-pass GroupNorm32 (+ scale-shift, + SiLU) of the f16 map x [B,HW,c1] (| x2 [B,HW,C-c1]) — the form the 16-bit
+    tier falls back to without a statistics slab.  Returns y [B,HW,C] (f16, or fp32 with out32) (test hook)."""
+    assert x.is_cuda and x.dtype == torch.float16 and x.dim() == 3 and (x2 is None or x2.dtype == torch.float16)
+    x, x2 = x.contiguous(), (None if x2 is None else x2.contiguous())
+    B, HW, c1 = x.shape
+    C = c1 + (x2.shape[2] if x2 is not None else 0)
+    y = torch.empty((B, HW, C), device=x.device, dtype=torch.float32 if out32 else torch.float16)
+    _op('dmad_groupnorm16', _ptr(x), _ptr(x2), int(c1 if x2 is not None else 0), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(_f32(ss)),
+        1 if silu else 0, B, HW, C, None if out32 else _ptr(y), _ptr(y) if out32 else None)
+    return y
+
+
+def qkv_attention_h16(qkv: torch.Tensor, heads: int) -> torch.Tensor:
+    """dmad_qkv_attention_h16: qkv f16 [B,T,heads*192] (head-major q | k | v) -> out f16 [B,T,heads*64] (test hook)."""
+    assert qkv.is_cuda and qkv.dtype == torch.float16 and qkv.dim() == 3 and qkv.shape[2] == heads * 192
+    qkv = qkv.contiguous()
+    B, T, _ = qkv.shape
+    out = torch.empty((B, T, heads * 64), device=qkv.device, dtype=torch.float16)
+    _op('dmad_qkv_attention_h16', _ptr(qkv), B, T, int(heads), _ptr(out))
+    return out
+
+
+def conv1ch_3x3(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, want32: bool = True, want16: bool = True, want_stats: bool = False):
+    """dmad_conv1ch_3x3: the UNet's first layer, x fp32 [B,32,32], w [Cout,9] (or [Cout,3,3]), bias [Cout] -> (out32 | None, out16 | None,
+    stats | None): [B,1024,Cout] fp32 / f16 and the GroupNorm statistics slab [B*16, Cout/4, 2] of the f16-rounded outputs (test hook)."""
+    x, w, bias = _f32(x), _f32(w), _f32(bias)
+    assert x.is_cuda and x.dim() == 3 and tuple(x.shape[1:]) == (32, 32)
+    B, Cout = x.shape[0], w.shape[0]
+    assert w.numel() == Cout * 9 and bias.numel() == Cout
+    out32 = torch.empty((B, 1024, Cout), device=x.device, dtype=torch.float32) if want32 else None
+    out16 = torch.empty((B, 1024, Cout), device=x.device, dtype=torch.float16) if want16 else None
+    stats = torch.full((B * 16, max(Cout // 4, 1), 2), float('nan'), device=x.device, dtype=torch.float32) if want_stats else None
+    _op('dmad_conv1ch_3x3', _ptr(x), _ptr(w), _ptr(bias), B, Cout, _ptr(out32), _ptr(out16), _ptr(stats))
+    return out32, out16, stats
+
+
+def conv3x3_c128_to1(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, g_in: Optional[torch.Tensor] = None, alpha: float = 1.0,
+                     gamma: float = 0.0) -> torch.Tensor:
+    """dmad_conv3x3_c128_to1 / _h16: the UNet's last layer, x [B,1024,128] (fp32, or f16: the 16-bit tier's MFMA form), w fp32 [9,128]
+    (tap-major), bias [1] -> out fp32 [B,1024]; with g_in [B,1024] (fp32 form only): alpha * g_in - gamma * conv (test hook)."""
+    assert x.is_cuda and x.dim() == 3 and tuple(x.shape[1:]) == (1024, 128) and x.dtype in (torch.float32, torch.float16)
+    x, w, bias = x.contiguous(), _f32(w), _f32(bias)
+    assert w.numel() == 9 * 128 and bias.numel() == 1
+    B = x.shape[0]
+    out = torch.empty((B, 1024), device=x.device, dtype=torch.float32)
+    if x.dtype == torch.float16:
+        assert g_in is None
+        _op('dmad_conv3x3_c128_to1_h16', _ptr(x), _ptr(w), _ptr(bias), B, _ptr(out))
+    else:
+        g_in = _f32(g_in)
+        assert g_in is None or tuple(g_in.shape) == (B, 1024)
+        _op('dmad_conv3x3_c128_to1', _ptr(x), _ptr(w), _ptr(bias), B, _ptr(g_in), float(alpha), float(gamma), _ptr(out))
+    return out
+
+
+def upsample2x(x: torch.Tensor) -> torch.Tensor:
+    """dmad_upsample2x: nearest-neighbour x2 of an NHWC map x [B,H,H,C] (fp32 or f16) -> [B,2H,2H,C] (test hook)."""
+    assert x.is_cuda and x.dim() == 4 and x.shape[1] == x.shape[2] and x.dtype in (torch.float32, torch.float16)
+    x = x.contiguous()
+    B, H, _, Cn = x.shape
+    out = torch.empty((B, 2 * H, 2 * H, Cn), device=x.device, dtype=x.dtype)
+    _op('dmad_upsample2x', _ptr(x), B, H, Cn, 1 if x.dtype == torch.float16 else 0, _ptr(out))
+    return out
+
+
 def conv_f32(x: torch.Tensor, w: torch.Tensor, shift: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None, stride: int = 1,
              groups: int = 1, relu: bool = False, res: Optional[torch.Tensor] = None, x2: Optional[torch.Tensor] = None,
              slab: Optional[torch.Tensor] = None, n_ref: int = 0):
@@ -1700,14 +1767,16 @@ def conv_f32_vjp(g_y: torch.Tensor, w: torch.Tensor, H: int, form: int = 0, stri
 
 
 def groupnorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, silu: bool = False, ss: Optional[torch.Tensor] = None,
-                  x2: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """dmad_groupnorm_f32: GroupNorm32 (+ scale-shift, + SiLU) of the fp32 map x [B,HW,c1] (| x2 [B,HW,C-c1]) -> y [B,HW,C] (test hook)."""
+                  x2: Optional[torch.Tensor] = None, split: bool = False) -> torch.Tensor:
+    """dmad_groupnorm_f32: GroupNorm32 (+ scale-shift, + SiLU) of the fp32 map x [B,HW,c1] (| x2 [B,HW,C-c1]) -> y [B,HW,C] (test hook).
+    split: y in the split-f16 storage form (as split_f16 returns it: its bits are NOT floats)."""
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
     x, x2 = x.contiguous(), (None if x2 is None else x2.contiguous())
     B, HW, c1 = x.shape
     Cn = c1 + (x2.shape[2] if x2 is not None else 0)
     y = torch.empty((B, HW, Cn), device=x.device, dtype=torch.float32)
-    _op('dmad_groupnorm_f32', _ptr(x), _ptr(x2), int(c1), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(_f32(ss)), 1 if silu else 0, B, HW, Cn, _ptr(y))
+    _op('dmad_groupnorm_f32', _ptr(x), _ptr(x2), int(c1), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(_f32(ss)), 1 if silu else 0, B, HW, Cn,
+        1 if split else 0, _ptr(y))
     return y
 
 
@@ -1729,13 +1798,14 @@ def groupnorm_bwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, gy: 
     return gx, gx2
 
 
-def qkv_attention_f32(qkv: torch.Tensor, heads: int) -> torch.Tensor:
-    """dmad_qkv_attention_f32: qkv fp32 [B,T,heads*192] (head-major q | k | v) -> out [B,T,heads*64] (test hook)."""
+def qkv_attention_f32(qkv: torch.Tensor, heads: int, split: bool = False) -> torch.Tensor:
+    """dmad_qkv_attention_f32: qkv fp32 [B,T,heads*192] (head-major q | k | v) -> out [B,T,heads*64] (test hook).  split: out in the
+    split-f16 storage form (as split_f16 returns it: its bits are NOT floats)."""
     assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3 and qkv.shape[2] == heads * 192
     qkv = qkv.contiguous()
     B, T, _ = qkv.shape
     out = torch.empty((B, T, heads * 64), device=qkv.device, dtype=torch.float32)
-    _op('dmad_qkv_attention_f32', _ptr(qkv), B, T, int(heads), _ptr(out))
+    _op('dmad_qkv_attention_f32', _ptr(qkv), B, T, int(heads), 1 if split else 0, _ptr(out))
     return out
 
 

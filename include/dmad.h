@@ -845,6 +845,34 @@ int dmad_groupnorm16_apply(const uint16_t* x, const float* st, const uint16_t* x
                            const float* beta, const float* ss, int32_t silu, int32_t B, int32_t HW, int32_t C, uint16_t* y16, float* y32,
                            dmad_stream s);
 
+/* Test hooks of what sits between the GEMMs of the UNet's 16-bit tier (csrc/unet_ops.hip), standalone (no engine state is read).  Each
+ * calls the launcher the engine path calls; a shape the launcher does not serve is DMAD_ERR_INVALID.
+ *
+ * dmad_qkv_attention_h16: QKVAttention on f16 maps — qkv16 [B][T][heads * 192] with the head-major split (head h: q, k, v = 64 channels
+ *   each from h * 192), out16 [B][T][heads * 64]; both products on the f16 matrix cores, fp32 scores / softmax / accumulation.  T = 16, 64
+ *   or 256.
+ * dmad_groupnorm16: the two-pass GroupNorm32 (+ scale-shift, + SiLU) of an f16 map x16 [B][HW][c1] (| x2_16 [B][HW][C - c1]; NULL: one
+ *   map) — the form the tier falls back to when a statistics slab is missing; y16 (f16) or y32 (fp32) [B][HW][C], exactly one of them.
+ *   C % 128 == 0, C <= 512, c1 % 4 == 0.
+ * dmad_conv1ch_3x3: the first layer, 1 -> Cout 3x3 conv with zero padding and bias on 32 x 32 maps: in [B][32][32], w [Cout][9], out32 /
+ *   out16 [B][1024][Cout] (at least one), stats (optional) the GroupNorm statistics slab [B * 16][Cout / 4][2] of the f16-rounded outputs
+ *   (64-pixel blocks = pairs of image rows).  Cout <= 128; with stats Cout % 4 == 0.
+ * dmad_conv3x3_c128_to1: the last layer, 128 -> 1 3x3 conv with zero padding and bias: in [B][1024][128], w [9][128] (tap-major), bias
+ *   [1], out [B][1024].  g_in != NULL ([B][1024], not out): out = alpha * g_in - gamma * (that conv), each product and the difference
+ *   rounded once (the adjoint update of a reverse VP-SDE step).
+ * dmad_conv3x3_c128_to1_h16: the same conv on an f16 map in16 [B][1024][128] with fp32 weights (the 16-bit tier's last layer).
+ * dmad_upsample2x: nearest-neighbour x2 of an NHWC map in [B][H][H][C] -> out [B][2H][2H][C], fp32 (C % 4 == 0) or, with is_f16, f16
+ *   (C % 8 == 0). */
+int dmad_qkv_attention_h16(const uint16_t* qkv16, int32_t B, int32_t T, int32_t heads, uint16_t* out16, dmad_stream s);
+int dmad_groupnorm16(const uint16_t* x16, const uint16_t* x2_16, int32_t c1, const float* gamma, const float* beta, const float* ss,
+                     int32_t silu, int32_t B, int32_t HW, int32_t C, uint16_t* y16, float* y32, dmad_stream s);
+int dmad_conv1ch_3x3(const float* in, const float* w, const float* bias, int32_t B, int32_t Cout, float* out32, uint16_t* out16, float* stats,
+                     dmad_stream s);
+int dmad_conv3x3_c128_to1(const float* in, const float* w, const float* bias, int32_t B, const float* g_in, float alpha, float gamma,
+                          float* out, dmad_stream s);
+int dmad_conv3x3_c128_to1_h16(const uint16_t* in16, const float* w, const float* bias, int32_t B, float* out, dmad_stream s);
+int dmad_upsample2x(const void* in, int32_t B, int32_t H, int32_t C, int32_t is_f16, void* out, dmad_stream s);
+
 /* Test hooks of the split-f16 conv GEMM (csrc/gemm_f32.hip, gemm_x3_kernel in its NHWC form: the kernel behind the UNet's middle tier),
  * standalone.  dmad_split_f16: y = the split-f16 storage form of the n fp32 values x (n % 4 == 0; hi = f16(v), lo = f16((v - hi) 2^11), four
  * values per 16-byte chunk: the bytes of four floats; x == y allowed).  dmad_conv_x3: NHWC convolution of split-format operands — x
@@ -894,15 +922,17 @@ int dmad_conv_f32_vjp(const float* g_y, const float* w, const float* scale, cons
                       float* work, float* g_x, dmad_stream s);
 /* GroupNorm32 in fp32 and its backward (csrc/unet_ops.hip, csrc/unet_vjp.hip):  y = SiLU?(GN(cat(x, x2)) * gamma + beta [* (1 + ss[c]) +
  * ss[C + c]]) over [B][HW][C], x holding c1 channels and x2 the rest (x2 NULL: one map).  Forward: C % 128 == 0, C <= 512, c1 % 4 == 0, maps
- * up to 32 x 32 x 384 (16 float4s per thread).  Backward: C % 32 == 0, any 0 < c1 < C; gx / gx2 = the gradient's two parts (+ add + add2, [B][HW][C]). */
+ * up to 32 x 32 x 384 (16 float4s per thread); split: y is written in the split-f16 storage format of dmad_split_f16 (the operand form of
+ * the split-f16 middle tier).  Backward: C % 32 == 0, any 0 < c1 < C; gx / gx2 = the gradient's two parts (+ add + add2, [B][HW][C]). */
 int dmad_groupnorm_f32(const float* x, const float* x2, int32_t c1, const float* gamma, const float* beta, const float* ss, int32_t silu,
-                       int32_t B, int32_t HW, int32_t C, float* y, dmad_stream s);
+                       int32_t B, int32_t HW, int32_t C, int32_t split, float* y, dmad_stream s);
 int dmad_groupnorm_bwd(const float* x, const float* x2, int32_t c1, const float* gamma, const float* beta, const float* ss, int32_t silu,
                        const float* gy, const float* add, const float* add2, int32_t B, int32_t HW, int32_t C, float* gx, float* gx2,
                        dmad_stream s);
 /* QKVAttention in fp32 and its backward: qkv [B][T][heads * 192] with the head-major split (head h: q, k, v = 64 channels each from h * 192),
- * out / go [B][T][heads * 64], gqkv like qkv.  T = 16, 64 or 256; any other T is DMAD_ERR_INVALID. */
-int dmad_qkv_attention_f32(const float* qkv, int32_t B, int32_t T, int32_t heads, float* out, dmad_stream s);
+ * out / go [B][T][heads * 64], gqkv like qkv.  T = 16, 64 or 256; any other T is DMAD_ERR_INVALID.  split: out is written in the split-f16
+ * storage format of dmad_split_f16. */
+int dmad_qkv_attention_f32(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t split, float* out, dmad_stream s);
 int dmad_qkv_attention_bwd(const float* qkv, const float* go, int32_t B, int32_t T, int32_t heads, float* gqkv, dmad_stream s);
 /* The two ends of ResNeXt29's backward walk.  dmad_rx_head_bwd: gz [B][HW][C] = (y > 0) * (W^T g_logits)[c] / HW — FC [ncls][C], average
  * pool and the last ReLU.  dmad_rx_conv1_bwd: gspec [B][32][32] = the 1 <- 64 3x3 conv (w [64][9], BN scale [64]) of (a > 0) * g, both
