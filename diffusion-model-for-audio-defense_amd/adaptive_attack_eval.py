@@ -16,8 +16,8 @@ DS, LPF, BPF: baseline_defense_eval.py).
 Additions to the reference's flags:
   * `--classifier_path`: the classifier checkpoint; its default is the path the reference hard-codes (it overrides
     `--classifier_model` / `--classifier_type`, which are kept for compatibility and otherwise unused, as in the reference);
-  * `--grad_backend {hip,torch}` (default hip): the gradient of the classifier (ResNeXt29, VGG19_bn, WideResNet-28-10 or M5) and of the mel
-    front-end — the engine's vector-Jacobian products, or the torch layers (DESIGN §14, §18, §19, §21).  An M5 checkpoint (`M5Net.M5`) classifies the raw
+  * `--grad_backend {hip,torch}` (default hip): the gradient of the classifier (ResNeXt29, VGG19_bn, WideResNet-28-10, DenseNet-BC-100-12 or M5) and of the mel
+    front-end — the engine's vector-Jacobian products, or the torch layers (DESIGN §14, §18, §19, §21, §24).  An M5 checkpoint (`M5Net.M5`) classifies the raw
     waveform: the system is AcousticSystem(classifier, transform=None, ...) as in the reference, and `--defense Diffusion-Spec` is refused;
   * `--score_grad`: passed to the SDE purifiers (default: their module defaults, 'none' for RevDiffWave, 'hip' for
     RevImprovedDiffusion).
@@ -92,7 +92,7 @@ def build_parser():
     parser.add_argument('--eot_defense_size', type=int, default=1)
     parser.add_argument('--verbose', type=int, default=1)
     parser.add_argument('--grad_backend', choices=['hip', 'torch'], default='hip',
-                        help='gradient of the classifier (ResNeXt29, VGG19_bn, WideResNet-28-10, M5) and of the mel front-end: the engine VJPs or the torch layers')
+                        help='gradient of the classifier (ResNeXt29, VGG19_bn, WideResNet-28-10, DenseNet-BC-100-12, M5) and of the mel front-end: the engine VJPs or the torch layers')
     # device arguments
     parser.add_argument("--dataload_workers_nums", type=int, default=8, help='number of workers for dataloader')
     parser.add_argument("--batch_size", type=int, default=20, help='batch size')
@@ -199,7 +199,7 @@ def build_front(args, classifier=None):
         return classifier, None
     if hasattr(classifier, 'bind_engine') and 'engine' not in classifier.__dict__:
         classifier.bind_engine()
-    if 'torch' in getattr(classifier, 'GRAD_BACKENDS', ()) and 'hip' in classifier.GRAD_BACKENDS:    # ResNeXt29, VGG19_bn and WideResNet-28-10
+    if 'torch' in getattr(classifier, 'GRAD_BACKENDS', ()) and 'hip' in classifier.GRAD_BACKENDS:    # ResNeXt29, VGG19_bn, WideResNet-28-10 and DenseNet-BC-100-12
         classifier.grad_backend = args.grad_backend
     return classifier, MelSpectrogramDB(classifier.__dict__.get('engine'), grad_backend=args.grad_backend)
 

@@ -24,6 +24,7 @@
 #include "kws_mel.h"
 #include "masking.h"
 #include "wrn.h"
+#include "densenet.h"
 #include "gemm_f32.h"
 #include "gemm_h16.h"
 #include "wn_bf16.h"
@@ -244,7 +245,7 @@ struct dmad_engine {
     float *act0 = nullptr, *act1 = nullptr, *logits = nullptr, *slab = nullptr;
     long slab_floats = 0;
     // ResNeXt29 8x64d (models/resnext.py): 9 bottlenecks, every conv with its folded eval-BatchNorm scale/shift
-    int cls_kind = 0;                      // 0 = VGG19_bn, 1 = ResNeXt29, 2 = WideResNet-28-10
+    int cls_kind = 0;                      // 0 = VGG19_bn, 1 = ResNeXt29, 2 = WideResNet-28-10, 3 = DenseNet-BC-100-12
     struct RxConv { float *w = nullptr, *scale = nullptr, *shift = nullptr; h16_t* wh = nullptr; float* wx = nullptr; float* wT = nullptr; };   // wh: f16 image with the BN scale folded in (16-bit tier); wx: split-f16 image (middle tier); wT: transposed (3x3: tap-flipped) image with the BN scale folded in (classifier VJP)
     struct RxBlock { RxConv reduce, conv, expand, shortc; bool has_short = false; int cin = 0, cout = 0, D = 0, stride = 1; };
     RxBlock rx[9];
@@ -279,6 +280,15 @@ struct dmad_engine {
     float *wrn_stem = nullptr, *wrn_bns = nullptr, *wrn_bnb = nullptr, *wrn_fcw = nullptr, *wrn_fcb = nullptr;
     float* wrn_fcws = nullptr;              // fc.w with the final bn's scale folded into its columns: the head backward's image
     float *wrnX = nullptr, *wrnY = nullptr, *wrnO = nullptr, *wrnH = nullptr, *wrnS = nullptr, *wrnP = nullptr;   // NHWC work maps ([maxB] x 32 x 32 x 160) and the pooled vector
+    // DenseNet-BC-100-12 (models/densenet.py): 48 bottleneck layers (16 per dense block), two transitions.  A layer: s1 / b1 the
+    // folded bn1 [cin], w1 the 1x1 image [48][K4] (K4 = cin rounded up to 4, zero columns), s2 / b2 the folded bn2 [48], w2 the 3x3 image
+    // [16][9 * 48] (rows 12..15 zero); w1T [cin][48] and w2T [48][9 * 12] (tap-flipped) the backward images.  All built on the host.
+    struct DnLayer { int cin = 0, blk = 0; float *s1 = nullptr, *b1 = nullptr, *w1 = nullptr, *s2 = nullptr, *b2 = nullptr, *w2 = nullptr, *w1T = nullptr, *w2T = nullptr; };
+    struct DnTrans { int cin = 0, cout = 0; float *s = nullptr, *b = nullptr, *w = nullptr, *wT = nullptr; };      // w [cout][cin4], wT [cin][cout4]
+    DnLayer dn[48];
+    DnTrans dnT[2];
+    float *dn_stem = nullptr, *dn_bns = nullptr, *dn_bnb = nullptr, *dn_fcw = nullptr, *dn_fcb = nullptr, *dn_fcws = nullptr;
+    float *dnS[3] = {nullptr, nullptr, nullptr}, *dnH = nullptr, *dnTm = nullptr;      // [maxB] streams (kDnPitch), the h map 32 x 32 x 48 and a transition's conv output 32 x 32 x 108
     // mel front-end VJP (dmad_mel_db_vjp): transposed filterbank [kMelLd][32] and DFT [2048][kDftKT] images, gradient maps of
     // melvjpB clips per pass (allocated on the first call)
     int melvjpB = 0;
@@ -414,10 +424,11 @@ int need_classifier(const dmad_engine* e) {      // ... and its weights finalise
     return e->cls_final ? 0 : fail(DMAD_ERR_STATE, "classifier weights are not finalised (dmad_load_weight + dmad_finalize_weights)");
 }
 // the classifiers by cls_kind: the network, the name its VJP goes by in the refusals, its VJP export and its reservation export
-const struct { const char *net, *vjp_of, *vjp, *reserve; } kCls[3] = {
+const struct { const char *net, *vjp_of, *vjp, *reserve; } kCls[4] = {
     {"VGG19_bn", "VGG19_bn", "dmad_vgg_vjp", "dmad_reserve_vgg_vjp"},
     {"ResNeXt29", "classifier", "dmad_classify_vjp", "dmad_reserve_classifier_vjp"},
-    {"WideResNet-28-10", "WideResNet", "dmad_wrn_vjp", "dmad_reserve_wrn_vjp"}};
+    {"WideResNet-28-10", "WideResNet", "dmad_wrn_vjp", "dmad_reserve_wrn_vjp"},
+    {"DenseNet-BC-100-12", "DenseNet", "dmad_dn_vjp", "dmad_reserve_dn_vjp"}};
 int need_kind(const dmad_engine* e, int kind) {  // the finalised classifier is the one whose VJP, reservation or tape is asked for
     CHK(need_classifier(e));
     return e->cls_kind == kind ? 0 : fail(DMAD_ERR_STATE, "the %s VJP serves %s only: this engine holds %s (%s)", kCls[kind].vjp_of, kCls[kind].net,
@@ -854,6 +865,20 @@ int finalize_resnext(dmad_engine* e) {
     return 0;
 }
 
+// a loaded weight with its shape checked: DMAD_ERR_SHAPE names the network, the weight and both shapes (WideResNet, DenseNet)
+int get_shaped(dmad_engine* e, const char* net, const std::string& name, std::initializer_list<int64_t> shape, const HostW** out) {
+    auto it = e->hw.find(name);
+    if (it == e->hw.end()) return fail(DMAD_ERR_STATE, "weight '%s' was not loaded", name.c_str());
+    if (it->second.shape != std::vector<int64_t>(shape)) {
+        std::string have, want;
+        for (int64_t d : it->second.shape) have += (have.empty() ? "" : ",") + std::to_string(d);
+        for (int64_t d : shape) want += (want.empty() ? "" : ",") + std::to_string(d);
+        return fail(DMAD_ERR_SHAPE, "%s: weight '%s' is [%s], expected [%s]", net, name.c_str(), have.c_str(), want.c_str());
+    }
+    *out = &it->second;
+    return 0;
+}
+
 // WideResNet-28-10 (models/wideresnet.py): names wrn.conv1.w [16,1,3,3]; per block i = 4 * stage + k: wrn.b<i>.bn1.{scale,
 // shift} [cin], .conv1.w [cout,cin,3,3] with .conv1.{scale,shift} [cout] (the folded bn2), .conv2.w [cout,cout,3,3], .short.w [cout,cin]
 // where cin != cout; wrn.bn.{scale,shift} [640], wrn.fc.w [classes,640], wrn.fc.b.  Every shape is checked (DMAD_ERR_SHAPE) before
@@ -861,18 +886,7 @@ int finalize_resnext(dmad_engine* e) {
 constexpr size_t kWrnMap = 163840;       // floats per spectrogram of the largest map: 32 x 32 x 160
 int finalize_wrn(dmad_engine* e) {
     const int widths[4] = {16, 160, 320, 640}, nc = e->cfg.num_classes;
-    auto wget = [&](const std::string& name, std::initializer_list<int64_t> shape, const HostW** out) -> int {
-        auto it = e->hw.find(name);
-        if (it == e->hw.end()) return fail(DMAD_ERR_STATE, "weight '%s' was not loaded", name.c_str());
-        if (it->second.shape != std::vector<int64_t>(shape)) {
-            std::string have, want;
-            for (int64_t d : it->second.shape) have += (have.empty() ? "" : ",") + std::to_string(d);
-            for (int64_t d : shape) want += (want.empty() ? "" : ",") + std::to_string(d);
-            return fail(DMAD_ERR_SHAPE, "WideResNet-28-10: weight '%s' is [%s], expected [%s]", name.c_str(), have.c_str(), want.c_str());
-        }
-        *out = &it->second;
-        return 0;
-    };
+    auto wget = [&](const std::string& name, std::initializer_list<int64_t> shape, const HostW** out) { return get_shaped(e, "WideResNet-28-10", name, shape, out); };
     struct Src { const HostW *s1, *b1, *w1, *s2, *b2, *w2, *ws; };
     Src src[12];
     const HostW *stem, *bns, *bnb, *fcw, *fcb;
@@ -951,6 +965,133 @@ int classify_wrn(dmad_engine* e, const float* spec, int B, float* logits, hipStr
     launch_avgpool_nhwc(F, e->wrnP, B, 64, 640, s);
     launch_gemm_f32(plain_gemm(e->wrn_fcw, e->wrnP, logits, nullptr, e->wrn_fcb, e->cfg.num_classes, 640, B, e->cfg.num_classes, 640, 0), s, e->slab,
                     e->slab_floats, (long)e->maxB);
+    LASTCHK();
+    return 0;
+}
+
+// DenseNet-BC-100-12 (models/densenet.py): names dn.conv1.w [24,1,3,3]; per layer l = 16 * block + i: dn.l<l>.bn1.{scale,shift}
+// [cin], .conv1.w [48,cin] with .conv1.{scale,shift} [48] (the folded bn2), .conv2.w [12,48,3,3]; per transition j: dn.t<j>.bn.{scale,shift}
+// [cin], .conv.w [cout,cin]; dn.bn.{scale,shift} [342], dn.fc.w [classes,342], dn.fc.b.  Every shape is checked (DMAD_ERR_SHAPE) before
+// anything is uploaded.  One stream per resolution: logical widths kDnWidth at the pitches kDnPitch (multiples of 8: every row, every
+// layer's slice and every float2 / float4 access is aligned); a block starts with kDnC0 channels.
+constexpr int kDnH[3] = {32, 16, 8}, kDnC0[3] = {24, 108, 150}, kDnWidth[3] = {216, 300, 342}, kDnPitch[3] = {216, 304, 344};
+inline int up4(int k) { return (k + 3) & ~3; }
+int finalize_dn(dmad_engine* e) {
+    const int nc = e->cfg.num_classes;
+    auto wget = [&](const std::string& name, std::initializer_list<int64_t> shape, const HostW** out) { return get_shaped(e, "DenseNet-BC-100-12", name, shape, out); };
+    struct Src { const HostW *s1, *b1, *w1, *s2, *b2, *w2; };
+    Src src[48];
+    const HostW *ts[2], *tb[2], *tw[2], *stem, *bns, *bnb, *fcw, *fcb;
+    CHK(wget("dn.conv1.w", {24, 1, 3, 3}, &stem));
+    for (int l = 0; l < 48; ++l) {
+        dmad_engine::DnLayer& L = e->dn[l];
+        L.blk = l / 16;
+        L.cin = kDnC0[L.blk] + 12 * (l % 16);
+        const std::string base = "dn.l" + std::to_string(l);
+        CHK(wget(base + ".bn1.scale", {L.cin}, &src[l].s1));
+        CHK(wget(base + ".bn1.shift", {L.cin}, &src[l].b1));
+        CHK(wget(base + ".conv1.w", {48, L.cin}, &src[l].w1));
+        CHK(wget(base + ".conv1.scale", {48}, &src[l].s2));
+        CHK(wget(base + ".conv1.shift", {48}, &src[l].b2));
+        CHK(wget(base + ".conv2.w", {12, 48, 3, 3}, &src[l].w2));
+    }
+    for (int j = 0; j < 2; ++j) {
+        dmad_engine::DnTrans& T = e->dnT[j];
+        T.cin = kDnWidth[j]; T.cout = kDnC0[j + 1];
+        const std::string base = "dn.t" + std::to_string(j);
+        CHK(wget(base + ".bn.scale", {T.cin}, &ts[j]));
+        CHK(wget(base + ".bn.shift", {T.cin}, &tb[j]));
+        CHK(wget(base + ".conv.w", {T.cout, T.cin}, &tw[j]));
+    }
+    CHK(wget("dn.bn.scale", {342}, &bns));
+    CHK(wget("dn.bn.shift", {342}, &bnb));
+    CHK(wget("dn.fc.w", {nc, 342}, &fcw));
+    CHK(wget("dn.fc.b", {nc}, &fcb));
+    // [M][K] -> [M][up4(K)] with zero columns (T = false) or its transpose [K][up4(M)] (T = true): the 1x1 images, forward and backward
+    auto pw_image = [&](const std::vector<float>& w, int M, int K, bool T, float** dst) -> int {
+        const int R = T ? K : M, Cn = T ? M : K, C4 = up4(Cn);
+        std::vector<float> A((size_t)R * C4, 0.f);
+        for (int r = 0; r < R; ++r)
+            for (int c = 0; c < Cn; ++c) A[(size_t)r * C4 + c] = T ? w[(size_t)c * K + r] : w[(size_t)r * K + c];
+        return e->upload(dst, A);
+    };
+    CHK(e->upload(&e->dn_stem, stem->v));
+    for (int l = 0; l < 48; ++l) {
+        dmad_engine::DnLayer& L = e->dn[l];
+        CHK(e->upload(&L.s1, src[l].s1->v)); CHK(e->upload(&L.b1, src[l].b1->v));
+        CHK(pw_image(src[l].w1->v, 48, L.cin, false, &L.w1));
+        CHK(pw_image(src[l].w1->v, 48, L.cin, true, &L.w1T));
+        CHK(e->upload(&L.s2, src[l].s2->v)); CHK(e->upload(&L.b2, src[l].b2->v));
+        const std::vector<float>& w2 = src[l].w2->v;                       // [12][48][3][3]
+        std::vector<float> A((size_t)16 * 432, 0.f), AT((size_t)48 * 108);
+        for (int j = 0; j < 12; ++j)
+            for (int c = 0; c < 48; ++c)
+                for (int t = 0; t < 9; ++t) {
+                    const float v = w2[((size_t)j * 48 + c) * 9 + t];
+                    A[(size_t)j * 432 + t * 48 + c] = v;
+                    AT[(size_t)c * 108 + (8 - t) * 12 + j] = v;
+                }
+        CHK(e->upload(&L.w2, A)); CHK(e->upload(&L.w2T, AT));
+    }
+    for (int j = 0; j < 2; ++j) {
+        dmad_engine::DnTrans& T = e->dnT[j];
+        CHK(e->upload(&T.s, ts[j]->v)); CHK(e->upload(&T.b, tb[j]->v));
+        CHK(pw_image(tw[j]->v, T.cout, T.cin, false, &T.w));
+        CHK(pw_image(tw[j]->v, T.cout, T.cin, true, &T.wT));
+    }
+    CHK(e->upload(&e->dn_bns, bns->v)); CHK(e->upload(&e->dn_bnb, bnb->v));
+    CHK(e->upload(&e->dn_fcw, fcw->v)); CHK(e->upload(&e->dn_fcb, fcb->v));
+    std::vector<float> ws((size_t)nc * 342);                  // the head backward's image: fc.w[k][c] * bn.scale[c], rounded once
+    for (int k = 0; k < nc; ++k)
+        for (int c = 0; c < 342; ++c) ws[(size_t)k * 342 + c] = (float)((double)fcw->v[(size_t)k * 342 + c] * (double)bns->v[c]);
+    CHK(e->upload(&e->dn_fcws, ws));
+    const size_t B = (size_t)e->maxB;
+    for (int k = 0; k < 3; ++k) CHK(e->alloc(&e->dnS[k], B * kDnH[k] * kDnH[k] * kDnPitch[k]));
+    CHK(e->alloc(&e->dnH, B * 1024 * 48));
+    CHK(e->alloc(&e->dnTm, B * 1024 * 108));
+    return 0;
+}
+
+DnPwArgs dn_pw_fwd(const float* A, int M, int K, const float* in, int ldi, long n_px, const float* s_in, const float* b_in, const float* s_out,
+                   const float* b_out, float* out, int ldo) {
+    DnPwArgs a{};
+    a.A = A; a.M = M; a.K = K; a.K4 = up4(K); a.in = in; a.ldi = ldi; a.n_px = n_px;
+    a.s_in = s_in; a.b_in = b_in; a.s_out = s_out; a.b_out = b_out; a.out = out; a.ldo = ldo;
+    return a;
+}
+DnPwArgs dn_pw_bwd(const float* A, int M, int K, const float* g, int ldg, long n_px, int pool, int H, const float* x, int ldx, const float* s1,
+                   const float* b1, float* out, int ldo, int add) {
+    DnPwArgs a{};
+    a.A = A; a.M = M; a.K = K; a.K4 = up4(K); a.in = g; a.ldi = ldg; a.n_px = n_px; a.pool = pool; a.H = H;
+    a.x = x; a.ldx = ldx; a.s1 = s1; a.b1 = b1; a.out = out; a.ldo = ldo; a.add = add;
+    return a;
+}
+
+// DenseNet.forward: the stem into stream 0; per layer the bottleneck kernel (bn1 + ReLU while staging, 1x1 on the MFMA, bn2 + ReLU as the
+// epilogue -> h) and the growth kernel (3x3, 12 channels into the stream's next slice): 2 launches; per transition the same 1x1 kernel
+// without epilogue and the 2x2 average pool into the next stream; the head kernel.  102 launches.  Every kernel works pixel by pixel, so
+// a sample's logits do not depend on its batch.  tape != nullptr (the VJP; B <= cvjpB): the three streams and the 48 h maps go to the
+// tape's slots instead of the work maps (same launches, same bits)
+int classify_dn(dmad_engine* e, const float* spec, int B, float* logits, hipStream_t s, const dmad_engine::TapeSlot* tape = nullptr) {
+    float* S[3];
+    for (int k = 0; k < 3; ++k) S[k] = tape ? tape[k].p : e->dnS[k];
+    launch_dn_stem(spec, e->dn_stem, S[0], kDnPitch[0], B, s);
+    for (int blk = 0; blk < 3; ++blk) {
+        const int H = kDnH[blk], ld = kDnPitch[blk];
+        const long n_px = (long)B * H * H;
+        for (int l = 16 * blk; l < 16 * blk + 16; ++l) {
+            const dmad_engine::DnLayer& L = e->dn[l];
+            float* Hm = tape ? tape[3 + l].p : e->dnH;
+            launch_dn_pw(dn_pw_fwd(L.w1, 48, L.cin, S[blk], ld, n_px, L.s1, L.b1, L.s2, L.b2, Hm, 48), false, s);
+            launch_dn_growth(L.w2, Hm, S[blk], ld, L.cin, B, H, s);
+        }
+        if (blk < 2) {
+            const dmad_engine::DnTrans& T = e->dnT[blk];
+            launch_dn_pw(dn_pw_fwd(T.w, T.cout, T.cin, S[blk], ld, n_px, T.s, T.b, nullptr, nullptr, e->dnTm, up4(T.cout)), false, s);
+            launch_dn_pool(e->dnTm, up4(T.cout), S[blk + 1], kDnPitch[blk + 1], B, H, T.cout, s);
+        }
+    }
+    launch_dn_head(S[2], kDnPitch[2], e->dn_bns, e->dn_bnb, e->dn_fcw, e->dn_fcb, logits, B, 64, 342, e->cfg.num_classes, s);
     LASTCHK();
     return 0;
 }
@@ -1747,9 +1888,17 @@ std::vector<size_t> wrn_tape_layout(const dmad_engine* e) {
     f.push_back(H * H * 640);
     return f;
 }
+// DenseNet, 51 slots: the three streams at their pitches (the inputs every pre-activation decision is recomputed from), then the 48
+// post-ReLU h maps; 322 048 + 1 032 192 floats per spectrogram
+std::vector<size_t> dn_tape_layout() {
+    std::vector<size_t> f;
+    for (int k = 0; k < 3; ++k) f.push_back((size_t)kDnH[k] * kDnH[k] * kDnPitch[k]);
+    for (int l = 0; l < 48; ++l) f.push_back((size_t)kDnH[l / 16] * kDnH[l / 16] * 48);
+    return f;
+}
 // the engine's classifier: the slots' offsets, the tape's size (dmad_reserve_*_vjp) and the reader's bounds (dmad_*_vjp_tape) follow from this list
 std::vector<size_t> cls_tape_layout(const dmad_engine* e) {
-    return e->cls_kind == 1 ? rx_tape_layout(e) : e->cls_kind == 2 ? wrn_tape_layout(e) : vgg_tape_layout();
+    return e->cls_kind == 1 ? rx_tape_layout(e) : e->cls_kind == 2 ? wrn_tape_layout(e) : e->cls_kind == 3 ? dn_tape_layout() : vgg_tape_layout();
 }
 constexpr int kDftKT = 2064;             // K of the DFT^T GEMM: the 2050 re / im rows padded to a multiple of 16
 
@@ -1925,6 +2074,7 @@ int classify(dmad_engine* e, const float* spec, int B, float* logits, hipStream_
     if (e->cls_kind == 1) return (h16 == 1 && e->rx_h16) ? classify_resnext_h16(e, spec, B, logits, s)
                                  : (h16 == 2 && e->rx_x3) ? classify_resnext_x3(e, spec, B, logits, s) : classify_resnext(e, spec, B, logits, s);
     if (e->cls_kind == 2) return classify_wrn(e, spec, B, logits, s);      // every tier falls to fp32, as for VGG19_bn
+    if (e->cls_kind == 3) return classify_dn(e, spec, B, logits, s);       // likewise
     return classify_vgg(e, spec, B, logits, s);
 }
 
@@ -2012,7 +2162,66 @@ int wrn_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits
     return 0;
 }
 
-// dmad_classify_vjp / dmad_vgg_vjp / dmad_wrn_vjp: the VJP of classifier `kind` in passes of the reservation; lastB remembers a one-pass call
+// floats per spectrogram of the gradient work maps of dn_vjp_pass: one gradient stream per resolution (the streams' pitches) and g_h
+const size_t kDnWork[4] = {(size_t)1024 * 216, (size_t)256 * 304, (size_t)64 * 344, (size_t)1024 * 48};
+
+// g_spec = (d logits / d spec)^T g_logits of classify_dn; logits: the forward it recomputes (B <= cvjpB).  The head's backward fills the
+// last gradient stream; per layer, last to first: the transposed 3x3 of the layer's own 12-channel slice (complete by then: only later
+// layers add to it) masked by h and scaled by bn2 -> g_h, then the transposed 1x1 masked by the recomputed bn1 decision and scaled by
+// bn1, ADDED into channels [0, cin) of the same gradient stream — so a channel collects its terms in layer order, last to first; a
+// transition's backward (pool, transposed 1x1, pre-activation) writes the whole previous gradient stream once.  100 launches.
+int dn_vjp_pass(dmad_engine* e, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
+    const dmad_engine::TapeSlot* tp = e->cvjp_slot.data();          // slots 0..2: the streams, 3 + l: h of layer l
+    CHK(classify_dn(e, spec, B, logits, s, tp));
+    float* G[4];
+    G[0] = e->cvjp_work;
+    for (int k = 1; k < 4; ++k) G[k] = G[k - 1] + kDnWork[k - 1] * e->cvjpB;
+    float* gh = G[3];
+    launch_dn_head_bwd(g_logits, e->dn_fcws, tp[2].p, kDnPitch[2], e->dn_bns, e->dn_bnb, G[2], kDnPitch[2], B, 64, 342, e->cfg.num_classes, s);
+    for (int blk = 2; blk >= 0; --blk) {
+        const int H = kDnH[blk], ld = kDnPitch[blk];
+        const long n_px = (long)B * H * H;
+        for (int l = 16 * blk + 15; l >= 16 * blk; --l) {
+            const dmad_engine::DnLayer& L = e->dn[l];
+            launch_dn_growth_bwd(L.w2T, G[blk], ld, L.cin, tp[3 + l].p, L.s2, gh, B, H, s);
+            launch_dn_pw(dn_pw_bwd(L.w1T, L.cin, 48, gh, 48, n_px, 0, H, tp[blk].p, ld, L.s1, L.b1, G[blk], ld, 1), true, s);
+        }
+        if (blk > 0) {
+            const dmad_engine::DnTrans& T = e->dnT[blk - 1];
+            const int Hp = kDnH[blk - 1], ldp = kDnPitch[blk - 1];
+            launch_dn_pw(dn_pw_bwd(T.wT, T.cin, T.cout, G[blk], ld, (long)B * Hp * Hp, 1, Hp, tp[blk - 1].p, ldp, T.s, T.b, G[blk - 1], ldp, 0), true, s);
+        }
+    }
+    launch_dn_stem_bwd(G[0], kDnPitch[0], e->dn_stem, g_spec, B, s);
+    LASTCHK();
+    return 0;
+}
+
+// dmad_dn_vjp_tape: post-ReLU map `index` (0..98, forward order) as the forward decided it.  An h map is copied from its slot; an o map, a
+// transition's and the final map are recomputed from the stream by dn_preact, the function the forward's staging applied
+int dn_vjp_tape(dmad_engine* e, int index, int B, float* out, hipStream_t s) {
+    if (!e || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(need_kind(e, 3));
+    if (index < 0 || index > 98) return fail(DMAD_ERR_INVALID, "tape map %d outside [0, 98]", index);
+    if (B < 1 || B > e->cvjp_lastB) return fail(DMAD_ERR_STATE, "the tape holds %d rows of a one-pass dmad_dn_vjp call, not %d", e->cvjp_lastB, B);
+    const int blk = index / 33, j = index % 33, H = kDnH[blk];
+    const long n_px = (long)B * H * H;
+    const float* S = e->cvjp_slot[blk].p;
+    if (index == 98 || j == 32) {
+        const float* sc = index == 98 ? e->dn_bns : e->dnT[blk].s;
+        const float* sh = index == 98 ? e->dn_bnb : e->dnT[blk].b;
+        launch_dn_preact_map(S, kDnPitch[blk], sc, sh, out, n_px, kDnWidth[blk], s);
+    } else if (j & 1) {
+        HIPCHK(hipMemcpyAsync(out, e->cvjp_slot[3 + 16 * blk + j / 2].p, (size_t)n_px * 48 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    } else {
+        const dmad_engine::DnLayer& L = e->dn[16 * blk + j / 2];
+        launch_dn_preact_map(S, kDnPitch[blk], L.s1, L.b1, out, n_px, L.cin, s);
+    }
+    LASTCHK();
+    return 0;
+}
+
+// dmad_classify_vjp / dmad_vgg_vjp / dmad_wrn_vjp / dmad_dn_vjp: the VJP of classifier `kind` in passes of the reservation; lastB remembers a one-pass call
 // for the tape reader
 int cls_vjp(dmad_engine* e, int kind, const float* spec, int B, const float* g_logits, float* g_spec, float* logits, hipStream_t s) {
     if (!e || !spec || !g_logits || !g_spec) return fail(DMAD_ERR_INVALID, "null argument");
@@ -2020,7 +2229,7 @@ int cls_vjp(dmad_engine* e, int kind, const float* spec, int B, const float* g_l
     if (!e->cvjpB) return fail(DMAD_ERR_STATE, "no %s VJP workspace: call %s first", kCls[kind].vjp_of, kCls[kind].reserve);
     CHK(need_batch(e, B));
     const int nc = e->cfg.num_classes;
-    const auto pass = kind == 1 ? rx_vjp_pass : kind == 2 ? wrn_vjp_pass : vgg_vjp_pass;
+    const auto pass = kind == 1 ? rx_vjp_pass : kind == 2 ? wrn_vjp_pass : kind == 3 ? dn_vjp_pass : vgg_vjp_pass;
     e->cvjp_lastB = 0;
     CHK(for_passes(B, e->cvjpB, [&](int64_t b0, int bb) {
         return pass(e, spec + b0 * 1024, bb, g_logits + b0 * nc, g_spec + b0 * 1024, logits ? logits + b0 * nc : e->logits, s);
@@ -2064,10 +2273,11 @@ int reserve_cls_vjp(dmad_engine* e, int max_batch, int kind, size_t work, Pack p
         });
 }
 
-// the exact-vote loops refuse a WideResNet engine: no recheck bound has been measured for this classifier
+// the exact-vote loops refuse a WideResNet or DenseNet engine: no recheck bound has been measured for these classifiers
 int need_vote_bound(const dmad_engine* e) {
-    if (e->cls_final && e->cls_kind == 2 && e->mode == DMAD_MODE_EXACT_VOTES)
-        return fail(DMAD_ERR_STATE, "no recheck bound has been measured for WideResNet-28-10: the exact-vote loops refuse it (DMAD_MODE_FAST and DMAD_MODE_FP32 serve it)");
+    if (e->cls_final && (e->cls_kind == 2 || e->cls_kind == 3) && e->mode == DMAD_MODE_EXACT_VOTES)
+        return fail(DMAD_ERR_STATE, "no recheck bound has been measured for %s: the exact-vote loops refuse it (DMAD_MODE_FAST and DMAD_MODE_FP32 serve it)",
+                    kCls[e->cls_kind].net);
     return 0;
 }
 
@@ -2473,6 +2683,12 @@ int dmad_finalize_weights(dmad_engine* e) {
             return r;
         }
         e->cls_final = true; e->cls_kind = 2; did = true;
+    } else if (e->cfg.with_classifier && !e->cls_final && e->hw.count("dn.conv1.w")) {
+        if (int r = finalize_dn(e)) {        // likewise
+            for (auto it = e->hw.begin(); it != e->hw.end();) it = it->first.compare(0, 3, "dn.") == 0 ? e->hw.erase(it) : std::next(it);
+            return r;
+        }
+        e->cls_final = true; e->cls_kind = 3; did = true;
     }
     if (!e->un_final && e->hw.count("un.time_embed.0.weight")) {
         if (!e->slab) {                     // engines created without a classifier have no split-K workspace yet
@@ -3242,6 +3458,111 @@ int dmad_wrn_stem_bwd(const float* g, const float* w, int32_t B, float* gspec, d
     if (!g || !w || !gspec) return fail(DMAD_ERR_INVALID, "null argument");
     if (B < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
     launch_wrn_stem_bwd(g, w, gspec, B, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_reserve_dn_vjp(dmad_engine* e, int32_t max_batch) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null engine");
+    // the backward images are built with the forward's at dmad_finalize_weights: nothing to pack
+    return reserve_cls_vjp(e, max_batch, 3, std::accumulate(std::begin(kDnWork), std::end(kDnWork), (size_t)0), [&]() -> int { return 0; });
+}
+
+int dmad_dn_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s) {
+    return cls_vjp(e, 3, spec, B, g_logits, g_spec, logits, (hipStream_t)s);
+}
+
+int dmad_dn_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s) { return dn_vjp_tape(e, index, B, out, (hipStream_t)s); }
+
+// the kernel hooks of densenet.hip: the geometry every access relies on is checked here
+int dmad_dn_pw(const float* A, int32_t M, int32_t K, const float* x, int32_t ldx, int64_t n_px, const float* s_in, const float* b_in, const float* s_out,
+               const float* b_out, float* out, int32_t ldo, dmad_stream s) {
+    if (!A || !x || !s_in || !b_in || !out || (!s_out != !b_out)) return fail(DMAD_ERR_INVALID, "null argument");
+    if (n_px < 1 || M < 1 || K < 2 || (K & 1) || (ldx & 1) || ldx < K || ldo < M) return fail(DMAD_ERR_INVALID, "bad geometry (K and the input pitch even, pitches >= widths)");
+    launch_dn_pw(dn_pw_fwd(A, M, K, x, ldx, (long)n_px, s_in, b_in, s_out, b_out, out, ldo), false, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_dn_pw_bwd(const float* A, int32_t M, int32_t K, const float* g, int32_t ldg, int64_t n_px, int32_t pool, int32_t H, const float* x, int32_t ldx,
+                   const float* s1, const float* b1, float* out, int32_t ldo, int32_t add, dmad_stream s) {
+    if (!A || !g || !x || !s1 || !b1 || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    if (n_px < 1 || M < 1 || K < 2 || (K & 1) || (ldg & 1) || ldg < K || ldx < M || ldo < M) return fail(DMAD_ERR_INVALID, "bad geometry (K and the gradient's pitch even, pitches >= widths)");
+    if (pool && (H < 2 || (H & 1) || n_px % ((int64_t)H * H))) return fail(DMAD_ERR_INVALID, "the pooled form takes whole H x H maps, H even");
+    launch_dn_pw(dn_pw_bwd(A, M, K, g, ldg, (long)n_px, pool ? 1 : 0, H, x, ldx, s1, b1, out, ldo, add ? 1 : 0), true, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dn_growth_geometry(int B, int H, int ld, int off) {
+    if (B < 1 || (H != 8 && H != 16 && H != 32) || (ld & 1) || (off & 1) || off < 0 || off + 12 > ld)
+        return fail(DMAD_ERR_INVALID, "bad geometry (H 8, 16 or 32; pitch and offset even; offset + 12 <= pitch)");
+    return 0;
+}
+
+int dmad_dn_growth(const float* A, const float* h, int32_t B, int32_t H, float* stream, int32_t ld, int32_t off, dmad_stream s) {
+    if (!A || !h || !stream) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(dn_growth_geometry(B, H, ld, off));
+    launch_dn_growth(A, h, stream, ld, off, B, H, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_dn_growth_bwd(const float* A, const float* g, int32_t ld, int32_t off, const float* h, const float* s2, int32_t B, int32_t H, float* gh,
+                       dmad_stream s) {
+    if (!A || !g || !h || !s2 || !gh) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(dn_growth_geometry(B, H, ld, off));
+    launch_dn_growth_bwd(A, g, ld, off, h, s2, gh, B, H, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_dn_stem(const float* spec, const float* w, int32_t B, float* stream, int32_t ld, dmad_stream s) {
+    if (!spec || !w || !stream) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || ld < 24 || (ld & 3)) return fail(DMAD_ERR_INVALID, "bad geometry (pitch a multiple of 4, >= 24)");
+    launch_dn_stem(spec, w, stream, ld, B, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_dn_stem_bwd(const float* g, int32_t ld, const float* w, int32_t B, float* gspec, dmad_stream s) {
+    if (!g || !w || !gspec) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || ld < 24 || (ld & 3)) return fail(DMAD_ERR_INVALID, "bad geometry (pitch a multiple of 4, >= 24)");
+    launch_dn_stem_bwd(g, ld, w, gspec, B, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_dn_pool(const float* t, int32_t ldt, int32_t B, int32_t H, int32_t C, float* out, int32_t ldo, dmad_stream s) {
+    if (!t || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || H < 2 || (H & 1) || C < 1 || ldt < C || ldo < C) return fail(DMAD_ERR_INVALID, "bad geometry (H even, pitches >= C)");
+    launch_dn_pool(t, ldt, out, ldo, B, H, C, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_dn_preact(const float* x, int32_t ldx, const float* scale, const float* shift, int64_t n_px, int32_t C, float* out, dmad_stream s) {
+    if (!x || !scale || !shift || !out) return fail(DMAD_ERR_INVALID, "null argument");
+    if (n_px < 1 || C < 1 || ldx < C) return fail(DMAD_ERR_INVALID, "bad geometry (pitch >= C)");
+    launch_dn_preact_map(x, ldx, scale, shift, out, (long)n_px, C, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_dn_head(const float* x, int32_t ldx, const float* bns, const float* bnb, const float* fcw, const float* fcb, int32_t B, int32_t HW, int32_t C,
+                 int32_t ncls, float* logits, dmad_stream s) {
+    if (!x || !bns || !bnb || !fcw || !fcb || !logits) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || HW < 1 || (HW & (HW - 1)) || C < 1 || C > 384 || ldx < C || ncls < 1) return fail(DMAD_ERR_INVALID, "bad geometry (HW a power of two, C <= 384)");
+    launch_dn_head(x, ldx, bns, bnb, fcw, fcb, logits, B, HW, C, ncls, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+int dmad_dn_head_bwd(const float* g_logits, const float* fcws, const float* x, int32_t ldx, const float* bns, const float* bnb, int32_t B, int32_t HW,
+                     int32_t C, int32_t ncls, float* g, int32_t ldg, dmad_stream s) {
+    if (!g_logits || !fcws || !x || !bns || !bnb || !g) return fail(DMAD_ERR_INVALID, "null argument");
+    if (B < 1 || HW < 1 || (HW & (HW - 1)) || C < 1 || ldx < C || ldg < C || ncls < 1) return fail(DMAD_ERR_INVALID, "bad geometry (HW a power of two, pitches >= C)");
+    launch_dn_head_bwd(g_logits, fcws, x, ldx, bns, bnb, g, ldg, B, HW, C, ncls, (hipStream_t)s);
     LASTCHK();
     return 0;
 }

@@ -113,6 +113,20 @@ _SIGNATURES = {
     'dmad_reserve_wrn_vjp': (C.c_int, [_P, C.c_int32]),
     'dmad_wrn_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     'dmad_wrn_vjp_tape': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_reserve_dn_vjp': (C.c_int, [_P, C.c_int32]),
+    'dmad_dn_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    'dmad_dn_vjp_tape': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_dn_pw': (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_int32, _P]),
+    'dmad_dn_pw_bwd': (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32,
+                                 C.c_int32, _P]),
+    'dmad_dn_growth': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P]),
+    'dmad_dn_growth_bwd': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_dn_stem': (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P]),
+    'dmad_dn_stem_bwd': (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P]),
+    'dmad_dn_pool': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    'dmad_dn_preact': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, _P]),
+    'dmad_dn_head': (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_dn_head_bwd': (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     'dmad_wrn_preact': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P, _P]),
     'dmad_wrn_preact_bwd': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P]),
     'dmad_wrn_stem': (C.c_int, [_P, _P, C.c_int32, _P, _P]),

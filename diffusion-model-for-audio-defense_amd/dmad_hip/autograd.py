@@ -208,7 +208,7 @@ def unet_eps_hip(engine, x: torch.Tensor, t: int) -> torch.Tensor:
 
 
 def _classifier_forward(ctx, spec, engine):
-    """the forward of ResNeXtHIP, VGGHIP and WRNHIP: the resident classifier's fp32 tier"""
+    """the forward of ResNeXtHIP, VGGHIP, WRNHIP and DNHIP: the resident classifier's fp32 tier"""
     _require_cuda(spec)
     logits = engine.classify_tier(spec, 0)
     ctx.engine = engine
@@ -280,6 +280,28 @@ class WRNHIP(torch.autograd.Function):
 def wrn_hip(engine, spec: torch.Tensor) -> torch.Tensor:
     """logits = WideResNet-28-10(spec [B,1,32,32]) on the engine's fp32 tier, differentiable in `spec` (WRNHIP)."""
     return WRNHIP.apply(spec, engine)
+
+
+class DNHIP(torch.autograd.Function):
+    """logits = DenseNet-BC-100-12(spec [B,1,32,32]) on the engine's fp32 tier (classify_tier(spec, 0)), differentiable in `spec` through
+    the engine's VJP.  Saves only the input; the backward re-runs the forward with its tape saved (dmad_dn_vjp).  The VJP workspace is
+    reserved on first use.  No weight gradients.  First-order only: create_graph=True raises."""
+    forward = staticmethod(_classifier_forward)
+
+    @staticmethod
+    def backward(ctx, g_logits):
+        _first_order_only('DenseNet-BC-100-12')
+        spec, = ctx.saved_tensors
+        eng, B = ctx.engine, spec.shape[0]
+        if eng.dn_vjp_batch < min(B, eng.max_batch):
+            eng.reserve_dn_vjp(B)
+        g = eng.dn_vjp(spec, g_logits.contiguous())
+        return g.view(spec.shape).to(spec.dtype), None
+
+
+def dn_hip(engine, spec: torch.Tensor) -> torch.Tensor:
+    """logits = DenseNet-BC-100-12(spec [B,1,32,32]) on the engine's fp32 tier, differentiable in `spec` (DNHIP)."""
+    return DNHIP.apply(spec, engine)
 
 
 class M5HIP(torch.autograd.Function):

@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from ._lib import DmadConfig, DmadError, check
 from .synth import WRN_BLOCKS, WRN_WIDTHS  # noqa: F401  (WideResNet-28-10's geometry, stated once with the stand-in)
+from .synth import DN_BLOCKS, DN_GROWTH, DN_LAYERS  # noqa: F401  (DenseNet-BC-100-12's, likewise)
 
 BF16, FP32, EXACT = 0, 1, 2                       # enum dmad_precision
 MODE_FAST, MODE_EXACT_VOTES, MODE_FP32 = 0, 1, 2  # enum dmad_mode (EXACT engines)
@@ -77,6 +78,20 @@ def _wrn_tape_maps():
 
 
 WRN_TAPE_MAPS = _wrn_tape_maps()
+# DenseNet-BC-100-12: (H, C) of the 99 post-ReLU maps of dn_vjp_tape in forward order: o = relu(bn1(x)) and h of a block's 16 layers, then
+# the transition's (or, behind dense3, the final) pre-activated map
+
+
+def _dn_tape_maps():
+    maps = []
+    for H, c0, width in DN_BLOCKS:
+        for i in range(DN_LAYERS):
+            maps += [(H, c0 + DN_GROWTH * i), (H, 4 * DN_GROWTH)]
+        maps.append((H, width))
+    return tuple(maps)
+
+
+DN_TAPE_MAPS = _dn_tape_maps()
 KWS_BINS, KWS_CLASSES = 32, 4                      # mel bins and classes of the attention-CRNN keyword spotter (csrc/kws.h)
 KWS_MAX_T = 644                                    # kKwsMaxT: the longest row dmad_kws_* serve (40 GRU steps)
 M5_CHANNELS = (32, 32, 64, 64)                     # output channels of M5's four conv blocks (n_channel = 32)
@@ -279,6 +294,40 @@ def kws_frames(L: int) -> int:
     return 1 + int(L) // 200
 
 
+def fold_densenet_state_dict(sd: Dict[str, object], eps: float = 1e-5, dtype=np.float32) -> Dict[str, np.ndarray]:
+    """models/densenet.py DenseNet(depth=100, growthRate=12, compressionRate=2, in_channels=1) state dict -> the `dn.*` arrays of
+    include/dmad.h: every BatchNorm folded to scale / shift in float64 and rounded once (_fold_bn); the 1x1 weights as [cout, cin]; layer
+    l = 16 * block + i.  Any other geometry is refused (DmadError).  dtype: what the float64 folds are rounded to (np.float64: the arrays
+    before the rounding, for the tests)."""
+    def shape(k):
+        return tuple(int(d) for d in sd[k].shape) if k in sd else None
+
+    if shape('conv1.weight') != (2 * DN_GROWTH, 1, 3, 3):
+        raise DmadError('only DenseNet-BC-100-12 with 1 input channel is built natively: conv1.weight is %s, not (24, 1, 3, 3)' % (shape('conv1.weight'),))
+    if shape('fc.weight') is None or shape('fc.weight')[1:] != (DN_BLOCKS[2][2],) or 'dense1.16.conv1.weight' in sd or 'dense1.15.conv2.weight' not in sd:
+        raise DmadError('only DenseNet-BC-100-12 is built natively: 16 bottleneck layers per block and a 342-wide head (fc.weight is %s)' % (shape('fc.weight'),))
+    out = {'dn.conv1.w': _f64(sd['conv1.weight'])}
+    for blk, (_, c0, width) in enumerate(DN_BLOCKS):
+        for i in range(DN_LAYERS):
+            src, dst, cin = 'dense%d.%d.' % (blk + 1, i), 'dn.l%d.' % (DN_LAYERS * blk + i), c0 + DN_GROWTH * i
+            if shape(src + 'conv1.weight') != (4 * DN_GROWTH, cin, 1, 1) or shape(src + 'conv2.weight') != (DN_GROWTH, 4 * DN_GROWTH, 3, 3):
+                raise DmadError('only DenseNet-BC-100-12 is built natively: %sconv1.weight is %s, not %s' % (src, shape(src + 'conv1.weight'), (48, cin, 1, 1)))
+            out[dst + 'bn1.scale'], out[dst + 'bn1.shift'] = _fold_bn(sd, src + 'bn1', eps)
+            out[dst + 'conv1.w'] = _f64(sd[src + 'conv1.weight']).reshape(4 * DN_GROWTH, cin)
+            out[dst + 'conv1.scale'], out[dst + 'conv1.shift'] = _fold_bn(sd, src + 'bn2', eps)
+            out[dst + 'conv2.w'] = _f64(sd[src + 'conv2.weight'])
+        if blk < 2:
+            src, dst, cout = 'trans%d.' % (blk + 1), 'dn.t%d.' % blk, DN_BLOCKS[blk + 1][1]
+            if shape(src + 'conv1.weight') != (cout, width, 1, 1):
+                raise DmadError('only DenseNet-BC-100-12 is built natively: %sconv1.weight is %s, not %s' % (src, shape(src + 'conv1.weight'), (cout, width, 1, 1)))
+            out[dst + 'bn.scale'], out[dst + 'bn.shift'] = _fold_bn(sd, src + 'bn1', eps)
+            out[dst + 'conv.w'] = _f64(sd[src + 'conv1.weight']).reshape(cout, width)
+    out['dn.bn.scale'], out['dn.bn.shift'] = _fold_bn(sd, 'bn', eps)
+    out['dn.fc.w'] = _f64(sd['fc.weight'])
+    out['dn.fc.b'] = _f64(sd['fc.bias'])
+    return {k: np.ascontiguousarray(v, dtype=dtype) for k, v in out.items()}
+
+
 def fold_m5_state_dict(sd: Dict[str, object], stride: int = 16, eps: float = 1e-5) -> Dict[str, np.ndarray]:
     """M5Net.M5 state dict -> the `m5.*` arrays of include/dmad.h: the conv weights as they are, each eval-BatchNorm folded (in float64)
     into s = gamma / sqrt(var + eps) and shift = beta + (bias - mean) * s, fc1, and conv1's stride (the one geometry field no tensor
@@ -332,7 +381,7 @@ class Engine:
         self.has_m5 = False
         self.m5_owner, self.m5_classes, self.m5_maps = None, 0, ()
         self.has_kws, self.kws_owner = False, None
-        self.vjp_batch = self.unet_vjp_batch = self.classifier_vjp_batch = self.vgg_vjp_batch = self.wrn_vjp_batch = 0     # rows per pass the VJP workspaces are reserved for
+        self.vjp_batch = self.unet_vjp_batch = self.classifier_vjp_batch = self.vgg_vjp_batch = self.wrn_vjp_batch = self.dn_vjp_batch = 0     # rows per pass the VJP workspaces are reserved for
         # which weights are resident (state_fingerprint): a module that binds to an engine holding OTHER weights must
         # not silently run them
         self.wavenet_owner = self.classifier_owner = self.unet_owner = None
@@ -420,6 +469,15 @@ class Engine:
         self._load(fold_wideresnet_state_dict(state_dict))
         self.has_classifier = True
         self.classifier_owner, self.classifier_kind = state_fingerprint(state_dict), 'wideresnet28_10'
+
+    def load_densenet_bc_100_12(self, state_dict):
+        """models/densenet.py DenseNet-BC-100-12 state dict -> engine (names prefixed 'dn.').  No recheck bound has been measured for this
+        classifier: on an EXACT engine the vote loops refuse it in the exact-vote mode (DmadError with the library's reason)."""
+        if self.has_classifier:
+            raise DmadError('classifier weights are already loaded into this engine')
+        self._load(fold_densenet_state_dict(state_dict))
+        self.has_classifier = True
+        self.classifier_owner, self.classifier_kind = state_fingerprint(state_dict), 'densenet_bc_100_12'
 
     def load_m5(self, state_dict, stride: int = 16):
         """M5Net.M5 state dict -> engine (names prefixed 'm5.'); a part of its own beside the spectrogram classifier.  stride: conv1's."""
@@ -822,6 +880,27 @@ class Engine:
         check(self.lib.dmad_wrn_vjp_tape(self._h, int(index), int(B), _ptr(out), _stream()))
         return out
 
+    def reserve_dn_vjp(self, max_batch: int):
+        """dmad_reserve_dn_vjp: the workspace of dn_vjp (the DenseNet forward's tape: the three streams and the 48 h maps; the gradient
+        streams) for up to max_batch spectrograms per pass (capped at max_batch; a larger reservation replaces a smaller one).  DenseNet
+        engines of every precision; DmadError otherwise."""
+        self._reserve('dn_vjp', max_batch, min(int(max_batch), self.max_batch))
+
+    def dn_vjp(self, spec: torch.Tensor, g_logits: torch.Tensor, want_logits: bool = False):
+        """g_spec = (d logits / d spec)^T g_logits for logits = DenseNet-BC-100-12(spec) on the fp32 tier ([B,1,32,32] or [B,32,32] ->
+        [B,32,32]).  want_logits: also return the logits, bit-identical to classify_tier(spec, 0).  Reserves on demand like vgg_vjp."""
+        return self._logits_vjp(self.lib.dmad_dn_vjp, spec, g_logits, want_logits, None if self.dn_vjp_batch else self.reserve_dn_vjp)
+
+    def dn_vjp_tape(self, index: int, B: int) -> torch.Tensor:
+        """dmad_dn_vjp_tape: post-ReLU map `index` (0..98, DN_TAPE_MAPS) of the last dn_vjp call's forward, rows [0, B), NHWC [B,H,H,C]
+        (test hook; that call must have run as one pass)."""
+        if not 0 <= int(index) < len(DN_TAPE_MAPS):
+            raise DmadError('tape map %d outside [0, %d]' % (index, len(DN_TAPE_MAPS) - 1))
+        H, Cn = DN_TAPE_MAPS[index]
+        out = torch.empty((int(B), H, H, Cn), device='cuda', dtype=torch.float32)
+        check(self.lib.dmad_dn_vjp_tape(self._h, int(index), int(B), _ptr(out), _stream()))
+        return out
+
     # ------------------------------------------------------------------ the vote loops and their exact-vote mode (EXACT engines)
     def vote(self, logits: torch.Tensor, counts: torch.Tensor):
         lg = logits.detach().contiguous().float()
@@ -923,6 +1002,8 @@ class Engine:
         kind = getattr(self, 'classifier_kind', None)
         if kind == 'wideresnet28_10':
             raise DmadError('no recheck bound has been measured for WideResNet-28-10: it has no committed margin')
+        if kind == 'densenet_bc_100_12':
+            raise DmadError('no recheck bound has been measured for DenseNet-BC-100-12: it has no committed margin')
         table = DEFAULT_RECHECK_MARGIN_RESNEXT29 if kind == 'resnext29' else DEFAULT_RECHECK_MARGIN
         return table[self.half_type]
 
@@ -1882,6 +1963,128 @@ def wrn_stem_bwd(g: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     gspec = torch.empty((B, 32, 32), device=g.device, dtype=torch.float32)
     _op('dmad_wrn_stem_bwd', _ptr(g), _ptr(w), B, _ptr(gspec))
     return gspec
+
+
+def _dn_pw_image(w: torch.Tensor) -> torch.Tensor:
+    """[M, K] -> the 1x1 kernels' image [M, K4]: K rounded up to 4 with zero columns"""
+    M, K = w.shape
+    A = torch.zeros((M, (K + 3) & ~3), device=w.device, dtype=torch.float32)
+    A[:, :K] = w
+    return A
+
+
+def dn_pw(x: torch.Tensor, w: torch.Tensor, s_in: torch.Tensor, b_in: torch.Tensor, s_out: Optional[torch.Tensor] = None,
+          b_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dmad_dn_pw: x [n_px, ldx] (a stream: only channels [0, K) are read), w [M, K], s_in / b_in [K], s_out / b_out [M] or None ->
+    [n_px, M]: epi(w @ pre(s_in, x, b_in)) (DenseNet's bottleneck / transition 1x1) (test hook)."""
+    x, w, s_in, b_in = _f32(x), _f32(w), _f32(s_in), _f32(b_in)
+    M, K = w.shape
+    assert x.is_cuda and x.dim() == 2 and x.shape[1] >= K and tuple(s_in.shape) == (K,) and tuple(b_in.shape) == (K,)
+    if s_out is not None:
+        s_out, b_out = _f32(s_out), _f32(b_out)
+    out = torch.empty((x.shape[0], M), device=x.device, dtype=torch.float32)
+    A = _dn_pw_image(w)
+    _op('dmad_dn_pw', _ptr(A), M, K, _ptr(x), x.shape[1], x.shape[0], _ptr(s_in), _ptr(b_in), _ptr(s_out), _ptr(b_out), _ptr(out), M)
+    return out
+
+
+def dn_pw_bwd(g: torch.Tensor, w: torch.Tensor, x: torch.Tensor, s1: torch.Tensor, b1: torch.Tensor, out: torch.Tensor, add: bool = True,
+              pool_H: int = 0) -> torch.Tensor:
+    """dmad_dn_pw_bwd, IN PLACE on `out`: g [n_px or n_px / 4, ldg] (channels [0, K) are read), w [K, M] in the FORWARD layout (the conv's
+    [cout = K, cin = M]), x / out [n_px, ld] streams, s1 / b1 [M] -> out[:, :M] (+)= (pre(s1, x, b1) > 0) * s1 * (g' @ w); pool_H: the
+    resolution of out's maps when g is the gradient of their 2x2 average pool (test hook)."""
+    g, w, x, s1, b1 = _f32(g), _f32(w), _f32(x), _f32(s1), _f32(b1)
+    K, M = w.shape
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 2 and x.dim() == 2 and g.dim() == 2
+    assert g.shape[1] >= K and x.shape[1] >= M and out.shape[1] >= M and x.shape[0] == out.shape[0] and tuple(s1.shape) == (M,)
+    assert g.shape[0] * (4 if pool_H else 1) == out.shape[0]
+    A = _dn_pw_image(w.t().contiguous())
+    _op('dmad_dn_pw_bwd', _ptr(A), M, K, _ptr(g), g.shape[1], out.shape[0], 1 if pool_H else 0, int(pool_H) or 2,
+        _ptr(x), x.shape[1], _ptr(s1), _ptr(b1), _ptr(out), out.shape[1], 1 if add else 0)
+    return out
+
+
+def dn_growth(h: torch.Tensor, w: torch.Tensor, stream: torch.Tensor, off: int) -> torch.Tensor:
+    """dmad_dn_growth, IN PLACE on `stream`: h [B,H,H,48], w [12,48,3,3] -> stream[..., off:off + 12] = conv3x3(h) (zero padding); every
+    other channel of stream [B,H,H,ld] is left alone (test hook)."""
+    h, w = _f32(h), _f32(w)
+    B, H = h.shape[0], h.shape[1]
+    assert stream.is_cuda and stream.dtype == torch.float32 and stream.is_contiguous() and tuple(stream.shape[:3]) == (B, H, H)
+    assert tuple(h.shape) == (B, H, H, 48) and tuple(w.shape) == (12, 48, 3, 3)
+    A = torch.zeros((16, 9, 48), device=h.device, dtype=torch.float32)
+    A[:12] = w.reshape(12, 48, 9).permute(0, 2, 1)
+    _op('dmad_dn_growth', _ptr(A), _ptr(h), B, H, _ptr(stream), stream.shape[3], int(off))
+    return stream
+
+
+def dn_growth_bwd(g: torch.Tensor, off: int, w: torch.Tensor, h: torch.Tensor, s2: torch.Tensor) -> torch.Tensor:
+    """dmad_dn_growth_bwd: g [B,H,H,ld] (the gradient stream; its slice [off, off + 12) is read), w [12,48,3,3], h [B,H,H,48], s2 [48] ->
+    gh [B,H,H,48] = (h > 0) * s2 * conv3x3^T(g slice) (test hook)."""
+    g, w, h, s2 = _f32(g), _f32(w), _f32(h), _f32(s2)
+    B, H = h.shape[0], h.shape[1]
+    assert g.is_cuda and tuple(g.shape[:3]) == (B, H, H) and tuple(h.shape) == (B, H, H, 48) and tuple(w.shape) == (12, 48, 3, 3)
+    A = w.reshape(12, 48, 9).flip(2).permute(1, 2, 0).contiguous()          # [c][8 - tap][j]
+    gh = torch.empty_like(h)
+    _op('dmad_dn_growth_bwd', _ptr(A), _ptr(g), g.shape[3], int(off), _ptr(h), _ptr(s2), B, H, _ptr(gh))
+    return gh
+
+
+def dn_stem(spec: torch.Tensor, w: torch.Tensor, stream: torch.Tensor) -> torch.Tensor:
+    """dmad_dn_stem, IN PLACE on `stream`: spec [B,32,32], w [24,9] -> stream[..., :24] of [B,32,32,ld] (test hook)."""
+    spec, w = _f32(spec), _f32(w)
+    B = spec.shape[0]
+    assert stream.is_cuda and stream.dtype == torch.float32 and stream.is_contiguous() and tuple(stream.shape[:3]) == (B, 32, 32) and tuple(w.shape) == (24, 9)
+    _op('dmad_dn_stem', _ptr(spec), _ptr(w), B, _ptr(stream), stream.shape[3])
+    return stream
+
+
+def dn_stem_bwd(g: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """dmad_dn_stem_bwd: g [B,32,32,ld] (channels [0, 24) are read), w [24,9] -> gspec [B,32,32] (test hook)."""
+    g, w = _f32(g), _f32(w)
+    B = g.shape[0]
+    assert g.is_cuda and tuple(g.shape[:3]) == (B, 32, 32) and tuple(w.shape) == (24, 9)
+    gspec = torch.empty((B, 32, 32), device=g.device, dtype=torch.float32)
+    _op('dmad_dn_stem_bwd', _ptr(g), g.shape[3], _ptr(w), B, _ptr(gspec))
+    return gspec
+
+
+def dn_pool(t: torch.Tensor, C: int, out: torch.Tensor) -> torch.Tensor:
+    """dmad_dn_pool, IN PLACE on `out`: t [B,H,H,ldt] -> out[..., :C] of [B,H/2,H/2,ldo], the 2x2 average pool of t's first C channels (test hook)."""
+    t = _f32(t)
+    B, H = t.shape[0], t.shape[1]
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape[:3]) == (B, H // 2, H // 2)
+    _op('dmad_dn_pool', _ptr(t), t.shape[3], B, H, int(C), _ptr(out), out.shape[3])
+    return out
+
+
+def dn_preact(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
+    """dmad_dn_preact: x [n_px, ldx], scale / shift [C] -> [n_px, C]: DenseNet's one pre-activation function on x's first C channels (test hook)."""
+    x, scale, shift = _f32(x), _f32(scale), _f32(shift)
+    Cn = scale.shape[0]
+    assert x.is_cuda and x.dim() == 2 and x.shape[1] >= Cn
+    out = torch.empty((x.shape[0], Cn), device=x.device, dtype=torch.float32)
+    _op('dmad_dn_preact', _ptr(x), x.shape[1], _ptr(scale), _ptr(shift), x.shape[0], Cn, _ptr(out))
+    return out
+
+
+def dn_head(x: torch.Tensor, bns: torch.Tensor, bnb: torch.Tensor, fcw: torch.Tensor, fcb: torch.Tensor) -> torch.Tensor:
+    """dmad_dn_head: x [B,HW,ldx], bns / bnb [C], fcw [ncls,C], fcb [ncls] -> logits [B,ncls] (test hook)."""
+    x, bns, bnb, fcw, fcb = _f32(x), _f32(bns), _f32(bnb), _f32(fcw), _f32(fcb)
+    B, HW, ldx = x.shape
+    ncls, Cn = fcw.shape
+    out = torch.empty((B, ncls), device=x.device, dtype=torch.float32)
+    _op('dmad_dn_head', _ptr(x), ldx, _ptr(bns), _ptr(bnb), _ptr(fcw), _ptr(fcb), B, HW, Cn, ncls, _ptr(out))
+    return out
+
+
+def dn_head_bwd(g_logits: torch.Tensor, fcws: torch.Tensor, x: torch.Tensor, bns: torch.Tensor, bnb: torch.Tensor, ldg: int) -> torch.Tensor:
+    """dmad_dn_head_bwd: g_logits [B,ncls], fcws [ncls,C], x [B,HW,ldx] -> g [B,HW,ldg] with channels [0, C) written, the rest zero (test hook)."""
+    g_logits, fcws, x, bns, bnb = _f32(g_logits), _f32(fcws), _f32(x), _f32(bns), _f32(bnb)
+    B, HW, ldx = x.shape
+    ncls, Cn = fcws.shape
+    g = torch.zeros((B, HW, int(ldg)), device=x.device, dtype=torch.float32)
+    _op('dmad_dn_head_bwd', _ptr(g_logits), _ptr(fcws), _ptr(x), ldx, _ptr(bns), _ptr(bnb), B, HW, Cn, ncls, _ptr(g), int(ldg))
+    return g
 
 
 def rx_conv1_bwd(g: torch.Tensor, a: torch.Tensor, w: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:

@@ -285,6 +285,60 @@ def wideresnet28_10_state_dict(seed: int = WRN_SEED, num_classes: int = 10, in_c
     return sd
 
 
+# DenseNet-BC-100-12: growth rate, bottleneck layers per dense block and (H, first width, last width) of its three blocks -- the one
+# statement of the geometry: the engine's loader and the tests' float64 walk import it
+DN_GROWTH, DN_LAYERS = 12, 16
+DN_BLOCKS = ((32, 24, 216), (16, 108, 300), (8, 150, 342))
+DN_SEED = 10012
+
+
+def densenet_bc_100_12_state_dict(seed: int = DN_SEED, num_classes: int = 10, in_channels: int = 1, calibrated: bool = True):
+    """fp32 numpy state dict for models/densenet.py DenseNet(depth=100, growthRate=12, compressionRate=2, num_classes=10, in_channels=1):
+    768 730 parameters under the reference's 596 keys (conv1, dense{1,2,3}.{k}.{bn1,conv1,bn2,conv2}, trans{1,2}.{bn1,conv1}, bn, fc), in
+    the module's order.  Conv weights use the fan-out init of the reference's constructor.  The stem has no BatchNorm, so the statistics
+    of the BatchNorms that read its 24 channels are sized for inputs around -20 dB +- 12.
+
+    With `calibrated` (and seed 10012) the BatchNorm running statistics and a centred, scaled head come from the committed data file
+    tests/golden/densenet_bc_100_12_calib_seed10012.npz of the repository (a test fixture: the stand-in serves the tests and the timing
+    tool; one calibration pass over spectrograms in the mel front-end's dB range, tests/golden/make_dn_calib.py), so that several classes
+    are predicted with top-2 margins of order one and every one of the 99 ReLU maps is alive on 5 - 95 % of its units."""
+    rng = np.random.default_rng(seed)
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+
+    def conv(name, cout, cin, k):
+        sd[name + '.weight'] = _f32(rng.standard_normal((cout, cin, k, k)) * np.sqrt(2.0 / (cout * k * k)))      # fan_out mode
+
+    def bn(name, c, stem=0):
+        sd[name + '.weight'] = _f32(rng.uniform(0.6, 1.4, size=c))
+        sd[name + '.bias'] = _f32(rng.standard_normal(c) * 0.3)
+        mean, var = rng.standard_normal(c) * 0.2, rng.uniform(0.5, 1.5, size=c)
+        if stem:                                       # the raw stem channels: sums of nine dB values
+            mean[:stem], var[:stem] = wsum * (-20.0), (wl2 * 12.0) ** 2 + 1.0
+        sd[name + '.running_mean'], sd[name + '.running_var'] = _f32(mean), _f32(var)
+        sd[name + '.num_batches_tracked'] = np.asarray(1000, dtype=np.int64)
+
+    conv('conv1', 2 * DN_GROWTH, in_channels, 3)
+    w = sd['conv1.weight'].astype(np.float64).reshape(2 * DN_GROWTH, -1)
+    wsum, wl2 = w.sum(1), np.sqrt((w ** 2).sum(1))
+    for blk, (_, c0, width) in enumerate(DN_BLOCKS):
+        for i in range(DN_LAYERS):
+            p = 'dense%d.%d' % (blk + 1, i)
+            bn(p + '.bn1', c0 + DN_GROWTH * i, stem=2 * DN_GROWTH if blk == 0 else 0)
+            conv(p + '.conv1', 4 * DN_GROWTH, c0 + DN_GROWTH * i, 1)
+            bn(p + '.bn2', 4 * DN_GROWTH)
+            conv(p + '.conv2', DN_GROWTH, 4 * DN_GROWTH, 3)
+        if blk < 2:
+            p = 'trans%d' % (blk + 1)
+            bn(p + '.bn1', width, stem=2 * DN_GROWTH if blk == 0 else 0)
+            conv(p + '.conv1', DN_BLOCKS[blk + 1][1], width, 1)
+    bn('bn', DN_BLOCKS[2][2])
+    sd['fc.weight'] = _f32(rng.standard_normal((num_classes, DN_BLOCKS[2][2])) * np.sqrt(2.0 / DN_BLOCKS[2][2]))
+    sd['fc.bias'] = _f32(rng.standard_normal(num_classes) * 0.1)
+    if calibrated and seed == DN_SEED and num_classes == 10 and in_channels == 1:
+        _load_calibration(sd, 'densenet_bc_100_12_calib_seed%d.npz' % seed, golden=True)
+    return sd
+
+
 UNET_CONFIG = dict(in_channels=1, model_channels=128, out_channels=1, num_res_blocks=3, attention_resolutions=(2, 4),
                    channel_mult=(1, 2, 2, 2), num_heads=4, use_scale_shift_norm=True)
 

@@ -29,7 +29,7 @@ enum dmad_status {
     DMAD_ERR_INVALID = -1,      /* bad argument / unsupported configuration */
     DMAD_ERR_STATE = -2,        /* weights not finalised, batch larger than max_batch, ... */
     DMAD_ERR_HIP = -3,          /* a HIP runtime call failed */
-    DMAD_ERR_SHAPE = -4         /* a weight set whose geometry no kernel serves (the M5 part, WideResNet); the message names the field */
+    DMAD_ERR_SHAPE = -4         /* a weight set whose geometry no kernel serves (the M5 part, WideResNet, DenseNet); the message names the field */
 };
 
 enum dmad_precision {
@@ -108,6 +108,10 @@ const char* dmad_last_warning(void);
  *   wrn.b{i}.conv1.w[cout,cin,3,3] .conv1.scale[cout] .conv1.shift[cout] (the folded bn2)  wrn.b{i}.conv2.w[cout,cout,3,3]
  *   wrn.b{i}.short.w[cout,cin] (where cin != cout)  wrn.bn.scale[640] wrn.bn.shift[640]  wrn.fc.w[classes,640] wrn.fc.b
  *   every shape is checked: DMAD_ERR_SHAPE for any other geometry, and the refused set is dropped.
+ * or DenseNet-BC-100-12 (models/densenet.py; layer l = 16 * block + i, l = 0..47, cin = {24, 108, 150}[block] + 12 i), recognised by dn.conv1.w:
+ *   dn.conv1.w[24,1,3,3]  dn.l{l}.bn1.scale[cin] .bn1.shift[cin]  dn.l{l}.conv1.w[48,cin] .conv1.scale[48] .conv1.shift[48] (the folded bn2)
+ *   dn.l{l}.conv2.w[12,48,3,3]  dn.t{j}.bn.scale[cin] .bn.shift[cin] dn.t{j}.conv.w[cout,cin] (j = 0, 1: 216 -> 108, 300 -> 150)
+ *   dn.bn.scale[342] dn.bn.shift[342]  dn.fc.w[classes,342] dn.fc.b;  checked and refused like the wrn.* set.
  * An engine holds one spectrogram classifier.
  * dmad_finalize_weights() packs whichever complete set (WaveNet, classifier) has been loaded and is not
  * packed yet into the MFMA/LDS layouts and uploads it; it may be called once per set. */
@@ -401,6 +405,31 @@ int dmad_vgg_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad
 int dmad_reserve_wrn_vjp(dmad_engine* e, int32_t max_batch);
 int dmad_wrn_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s);
 int dmad_wrn_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s);
+
+/* The same trio for DenseNet-BC-100-12 (models/densenet.py).  DESIGN §24.  The forward (dmad_classify and every surface behind it) runs on
+ * the fp32 tier whatever the tier asked for, in 102 launches of the kernels of csrc/densenet.hip; every kernel works pixel by pixel, so a
+ * sample's logits do not depend on its batch.  No recheck bound has been measured for this classifier: the four vote loops return
+ * DMAD_ERR_STATE for it in DMAD_MODE_EXACT_VOTES, as for WideResNet-28-10.
+ *
+ * dmad_reserve_dn_vjp reserves, for up to max_batch spectrograms per pass: the TAPE of the fp32 forward — the three concatenation streams
+ * at their pitches (32 x 32 x 216, 16 x 16 x 304, 8 x 8 x 344: 322 048 floats) and the 48 post-ReLU h maps (1 032 192 floats), 5.4 MB per
+ * spectrogram — and the gradient streams with g_h (371 200 floats, 1.5 MB per spectrogram).  The backward images are built with the
+ * forward's at dmad_finalize_weights.  Capped at the engine's max_batch; a larger reservation replaces a smaller one, a smaller one
+ * keeps the present.  Counted by dmad_device_bytes.
+ *
+ * dmad_dn_vjp:  g_spec = (d logits / d spec)^T g_logits on the fp32 tier, shapes as dmad_vgg_vjp.  logits: optional (NULL), bit-identical
+ * to dmad_classify_tier(.., 0, ..).  Every engine precision.  B in [1, max_batch], in passes of the reservation's size.  100 launches
+ * behind the forward's 102; no atomics; a gradient channel collects its terms in layer order, last to first; g_spec does not depend on B,
+ * on the row's place or on the reservation's size.  DMAD_ERR_STATE without a reservation, before the weights are finalised, or for
+ * another classifier.
+ *
+ * dmad_dn_vjp_tape (test hook): post-ReLU map `index` of the last call's forward, rows [0, B), NHWC [B][H][H][C] without padding: 2 k and
+ * 2 k + 1 are o = relu(bn1(x)) [24 + 12 k channels] and h [48] of layer k of dense1, 32 is trans1's o [216], 33..64 dense2, 65 trans2's o
+ * [300], 66..97 dense3, 98 the final map [342].  h maps are copied from the tape; the others are recomputed from the tape's streams with
+ * the forward's own pre-activation function.  Valid when that call ran as one pass and B <= its B, DMAD_ERR_STATE otherwise. */
+int dmad_reserve_dn_vjp(dmad_engine* e, int32_t max_batch);
+int dmad_dn_vjp(dmad_engine* e, const float* spec, int32_t B, const float* g_logits, float* g_spec, float* logits, dmad_stream s);
+int dmad_dn_vjp_tape(dmad_engine* e, int32_t index, int32_t B, float* out, dmad_stream s);
 
 /* The reverse VP-SDE purifier of the reference's adaptive-attack driver (adaptive_attack_eval.py --defense Diffusion ->
  * diffusion_models/diffwave_sde.py RevDiffWave.audio_editing_sample: torchsde.sdeint_adjoint(RevVPSDE, method='euler', dt = 1/T)).
@@ -952,6 +981,40 @@ int dmad_wrn_preact(const float* x, const float* scale, const float* shift, int6
 int dmad_wrn_preact_bwd(const float* g, const float* o, const float* scale, const float* res, int64_t n_px, int32_t C, float* gx, dmad_stream s);
 int dmad_wrn_stem(const float* spec, const float* w, int32_t B, float* out, dmad_stream s);
 int dmad_wrn_stem_bwd(const float* g, const float* w, int32_t B, float* gspec, dmad_stream s);
+/* DenseNet-BC-100-12's kernels (csrc/densenet.hip), one hook each.  pre(s, x, b) = max(fmaf(s, x, b), 0) with a NaN kept and
+ * -0.0 made +0.0: the one pre-activation function of the forward, the backward's masks and the tape reader.  Maps are NHWC with a pitch
+ * (floats per pixel) >= their width; no kernel reads or writes a channel outside the widths named here.
+ * dmad_dn_pw: out[p * ldo + m] = epi(sum over k < K ascending of A[m][k] * pre(s_in[k], x[p * ldx + k], b_in[k])), m < M, p < n_px (any
+ *   count); A [M][K4], K4 = K rounded up to 4, zero columns behind K; epi = pre(s_out[m], ., b_out[m]), or the identity when s_out and
+ *   b_out are NULL.  K and ldx even.  The bottleneck's 1x1 (M = 48) and a transition's (M = 108 / 150).
+ * dmad_dn_pw_bwd: v = pre(s1[m], x[p * ldx + m], b1[m]) > 0 ? s1[m] * sum over k < K ascending of A[m][k] * g'[p][k] : 0, m < M;
+ *   out[p * ldo + m] = add ? out[p * ldo + m] + v : v.  g'[p][k] = g[p * ldg + k], or with pool = 1 a quarter of g at the pixel of the
+ *   half-resolution map whose 2x2 window holds p (H: the resolution of p; n_px whole maps).  A [M][K4] as above.  K and ldg even.
+ * dmad_dn_growth: stream[p * ld + off + j] = sum over taps (ky, kx ascending), then c < 48 ascending, of A[j][tap * 48 + c] * h[(p + tap)
+ *   * 48 + c] with zero padding, j < 12; A [16][432], rows 12..15 zero; h [B][H][H][48], H in {8, 16, 32}; ld and off even (dense3's slices start at 150 + 12 i: no multiple of 4).
+ * dmad_dn_growth_bwd: gh[p * 48 + c] = h[p * 48 + c] > 0 ? s2[c] * sum over taps, then j < 12, of A[c][tap * 12 + j] * g[(p + tap) * ld +
+ *   off + j] : 0; A [48][108], the tap-flipped transpose A[c][tap * 12 + j] = w[j][c][8 - tap].
+ * dmad_dn_stem / _stem_bwd: the 1 -> 24 3x3 conv (w [24][9]) into channels [0, 24) of a stream, and its backward, as dmad_wrn_stem's.
+ * dmad_dn_pool: out[q * ldo + c] = 0.25 * (((tl + tr) + bl) + br) of the 2x2 window of t [B][H][H][ldt], c < C.
+ * dmad_dn_preact: out[p * C + c] = pre(scale[c], x[p * ldx + c], shift[c]).
+ * dmad_dn_head: logits[b][k] = fcb[k] + sum over c < C ascending of fcw[k][c] * mean over the HW pixels (ascending) of pre(bns[c], x, bnb[c]);
+ *   HW a power of two, C <= 384.  dmad_dn_head_bwd: g[p * ldg + c] = pre(bns[c], x[p * ldx + c], bnb[c]) > 0 ? (sum over k ascending of
+ *   fcws[k][c] * g_logits[b][k]) / HW : 0. */
+int dmad_dn_pw(const float* A, int32_t M, int32_t K, const float* x, int32_t ldx, int64_t n_px, const float* s_in, const float* b_in, const float* s_out,
+               const float* b_out, float* out, int32_t ldo, dmad_stream s);
+int dmad_dn_pw_bwd(const float* A, int32_t M, int32_t K, const float* g, int32_t ldg, int64_t n_px, int32_t pool, int32_t H, const float* x, int32_t ldx,
+                   const float* s1, const float* b1, float* out, int32_t ldo, int32_t add, dmad_stream s);
+int dmad_dn_growth(const float* A, const float* h, int32_t B, int32_t H, float* stream, int32_t ld, int32_t off, dmad_stream s);
+int dmad_dn_growth_bwd(const float* A, const float* g, int32_t ld, int32_t off, const float* h, const float* s2, int32_t B, int32_t H, float* gh,
+                       dmad_stream s);
+int dmad_dn_stem(const float* spec, const float* w, int32_t B, float* stream, int32_t ld, dmad_stream s);
+int dmad_dn_stem_bwd(const float* g, int32_t ld, const float* w, int32_t B, float* gspec, dmad_stream s);
+int dmad_dn_pool(const float* t, int32_t ldt, int32_t B, int32_t H, int32_t C, float* out, int32_t ldo, dmad_stream s);
+int dmad_dn_preact(const float* x, int32_t ldx, const float* scale, const float* shift, int64_t n_px, int32_t C, float* out, dmad_stream s);
+int dmad_dn_head(const float* x, int32_t ldx, const float* bns, const float* bnb, const float* fcw, const float* fcb, int32_t B, int32_t HW, int32_t C,
+                 int32_t ncls, float* logits, dmad_stream s);
+int dmad_dn_head_bwd(const float* g_logits, const float* fcws, const float* x, int32_t ldx, const float* bns, const float* bnb, int32_t B, int32_t HW,
+                     int32_t C, int32_t ncls, float* g, int32_t ldg, dmad_stream s);
 
 /* Bytes of device memory held by the engine. */
 int64_t dmad_device_bytes(const dmad_engine* e);
