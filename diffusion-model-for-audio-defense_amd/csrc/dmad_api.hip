@@ -1840,10 +1840,9 @@ int wavenet_vjp(dmad_engine* e, const float* x_t, int t, int B, const float* g_e
     });
 }
 
-int mel_db(dmad_engine* e, const float* x, int B, float* spec, hipStream_t s, int to_db = 1) {
-    CHK(need_with_classifier(e)); CHK(need_batch(e, B));
+// the mel front-end behind its padding: the B padded rows in e->mel_xp -> spec
+int mel_db_padded(dmad_engine* e, int B, float* spec, hipStream_t s, int to_db = 1) {
     const long rows = (long)B * 32;
-    launch_mel_pad(x, e->mel_xp, B, e->L, e->LPm, s);
     GemmF32Args g{};
     g.A = e->dftA; g.X = e->mel_xp; g.C = e->dftD; g.scale = nullptr; g.shift = nullptr;
     g.M = kDftM; g.K = 2048; g.taps = 1; g.ldc = kDftLd; g.relu = 0; g.N = rows; g.mode = 0;
@@ -1854,6 +1853,12 @@ int mel_db(dmad_engine* e, const float* x, int B, float* spec, hipStream_t s, in
     launch_mel_db(e->melM, spec, B, to_db, s);
     LASTCHK();
     return 0;
+}
+
+int mel_db(dmad_engine* e, const float* x, int B, float* spec, hipStream_t s, int to_db = 1) {
+    CHK(need_with_classifier(e)); CHK(need_batch(e, B));
+    launch_mel_pad(x, e->mel_xp, B, e->L, e->LPm, s);
+    return mel_db_padded(e, B, spec, s, to_db);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -3753,6 +3758,31 @@ int dmad_smooth_votes(dmad_engine* e, const float* clip, float sigma, float sqrt
     return vote_loop(e, e->wave_rt, recheck, e->wdil_x3 != nullptr, e->maxB32, n, batch, sample0, counts, first, rows, st);
 }
 
+int dmad_rs_smooth_votes(dmad_engine* e, const float* clip, float sigma, int64_t n, int32_t batch, uint64_t seed, uint64_t sample0,
+                         const float* delta, int64_t* counts, float* logits_out, dmad_stream s) {
+    if (!e || !clip) return fail(DMAD_ERR_INVALID, "dmad_rs_smooth_votes: null argument");
+    if (!counts) return fail(DMAD_ERR_INVALID, "dmad_rs_smooth_votes: counts must not be null");
+    if (n < 0) return fail(DMAD_ERR_INVALID, "dmad_rs_smooth_votes: n < 0");
+    CHK(need_classifier(e));
+    CHK(need_batch(e, batch));
+    if (((uintptr_t)clip | (uintptr_t)delta) & 15)
+        return fail(DMAD_ERR_INVALID, "dmad_rs_smooth_votes: clip and delta must be 16-byte aligned (they are read as float4)");
+    hipStream_t st = (hipStream_t)s;
+    const int L = e->L, C = e->cfg.num_classes;
+    // the noisy rows go straight into the mel front-end's padded layout; the classifier runs its fp32 tier whatever the engine's
+    // precision and mode (dmad_classify's tier), so every sample votes in the first pass and no recheck bound is involved
+    auto first = [&](int64_t done, int B, const float** lg) -> int {
+        float* out = logits_out ? logits_out + done * C : e->logits;
+        *lg = out;
+        launch_mel_pad_noise(clip, delta ? delta + done * L : nullptr, sigma, seed, sample0 + (uint64_t)done, e->mel_xp, B, L, e->LPm, st);
+        CHK(mel_db_padded(e, B, e->spec, st));
+        return classify(e, e->spec, B, out, st);
+    };
+    auto rows = [](const long long*, int, int) -> int { return 0; };       // never called: nothing is queued without a recheck
+    RecheckTiers none;                                                     // ... and the exact-vote statistics are not this loop's
+    return vote_loop(e, none, false, false, e->maxB, n, batch, sample0, counts, first, rows, st);
+}
+
 }  // extern "C"
 
 namespace {
@@ -4079,6 +4109,8 @@ int run_wave_defense(dmad_engine* e, const dmad_wave_defense* d, const IirPlan& 
     return 0;
 }
 
+constexpr int64_t kM5RsRowsPerLaunch = 16384;      // samples (= workgroups) per launch of dmad_m5_rs_smooth_votes
+
 int m5_launch(dmad_engine* e, const float* x, int B, float* logp, int32_t* cls, const float* g_logp, float* g_x, int layer, float* pooled,
               uint8_t* dec, hipStream_t st) {
     if ((uintptr_t)x & 15) return fail(DMAD_ERR_INVALID, "M5: x must be 16-byte aligned (the clip is read as float4)");
@@ -4269,6 +4301,25 @@ int dmad_m5_tape(dmad_engine* e, const float* x, int32_t B, int32_t layer, float
     if (B < 1 || layer < 1 || layer > 4) return fail(DMAD_ERR_INVALID, "dmad_m5_tape: B must be >= 1 and layer in 1..4");
     CHK(need_m5(e));
     return m5_launch(e, x, B, nullptr, nullptr, nullptr, nullptr, layer, pooled, decisions, (hipStream_t)s);
+}
+
+int dmad_m5_rs_smooth_votes(dmad_engine* e, const float* clip, float sigma, int64_t n, uint64_t seed, uint64_t sample0, const float* delta,
+                            int64_t* counts, float* logp_out, dmad_stream s) {
+    if (!e || !clip) return fail(DMAD_ERR_INVALID, "dmad_m5_rs_smooth_votes: null argument");
+    if (!counts) return fail(DMAD_ERR_INVALID, "dmad_m5_rs_smooth_votes: counts must not be null");
+    if (n < 0) return fail(DMAD_ERR_INVALID, "dmad_m5_rs_smooth_votes: n < 0");
+    CHK(need_m5(e));
+    if (((uintptr_t)clip | (uintptr_t)delta) & 15)
+        return fail(DMAD_ERR_INVALID, "dmad_m5_rs_smooth_votes: clip and delta must be 16-byte aligned (they are read as float4)");
+    const int64_t L = e->L, NO = e->m5g.n_out;
+    // one workgroup per sample; a launch's grid is capped, and a sample's bits depend on its index alone, not on where the cut falls
+    CHK(for_passes(n, kM5RsRowsPerLaunch, [&](int64_t done, int rows) -> int {
+        launch_m5_noisy(e->m5w, e->m5g, clip, delta ? delta + done * L : nullptr, sigma, seed, sample0 + (uint64_t)done, rows,
+                        (unsigned long long*)counts, logp_out ? logp_out + done * NO : nullptr, (hipStream_t)s);
+        return 0;
+    }));
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 int dmad_m5_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t repeats, int32_t sampler, int32_t t_star, float c_a, float c_b,

@@ -47,6 +47,10 @@ void launch_wn_init_f32(const float* x, const float* w, const float* bias, const
 void launch_scale(const float* x, float c, float* y, long n, hipStream_t s, bool split = false);
 void launch_dot256(const float* f, const float* w, float bias, float* out, long N, hipStream_t s);
 void launch_mel_pad(const float* x, float* xp, int B, int L, int LPm, hipStream_t s);
+// the padded rows of B Monte Carlo samples of one clip: clip + delta[b] (delta [B][L]), or clip + sigma * Philox normal of sample
+// sample0 + b (delta == nullptr); clip and delta 16-byte aligned, L and LPm multiples of 4
+void launch_mel_pad_noise(const float* clip, const float* delta, float sigma, uint64_t seed, uint64_t sample0, float* xp, int B, int L,
+                          int LPm, hipStream_t s);
 void launch_mel_power(const float* D, float* P, int ldd, int ldp, long rows, hipStream_t s);
 void launch_mel_db(const float* M, float* spec, int B, int to_db, hipStream_t s);
 void launch_power_to_db(const float* x, float* y, long n, hipStream_t s);

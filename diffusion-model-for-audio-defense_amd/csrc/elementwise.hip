@@ -1,42 +1,9 @@
 // Small HBM-bound kernels of the path: noise + scale (Philox), step-embedding MLP, scheduler
 // updates, fp32-mode gate/update, mel post-processing, VGG helpers, arg-max votes.
 #include "elementwise.h"
+#include "philox.h"
 
 namespace dmad {
-
-// ----------------------------------------------------------------------------------------------
-// Philox4x32-10 counter-based generator (Salmon et al. 2011).  counter = (block, sample_lo,
-// sample_hi, stream), key = (seed_lo, seed_hi): sample i's noise is a pure function of
-// (seed, i, stream) -> Monte Carlo votes do not depend on batch size or on the number of ranks.
-// ----------------------------------------------------------------------------------------------
-__host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-        const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        const uint32_t n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
-__device__ inline void philox_normal4(uint64_t seed, uint64_t sample, uint32_t stream, uint32_t block, float z[4]) {
-    uint32_t c[4] = {block, (uint32_t)sample, (uint32_t)(sample >> 32), stream};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    // Box-Muller on (0,1) uniforms with 24 random bits each
-    const float u0 = ((float)(c[0] >> 8) + 0.5f) * 5.9604644775390625e-8f;
-    const float u1 = ((float)(c[1] >> 8) + 0.5f) * 5.9604644775390625e-8f;
-    const float u2 = ((float)(c[2] >> 8) + 0.5f) * 5.9604644775390625e-8f;
-    const float u3 = ((float)(c[3] >> 8) + 0.5f) * 5.9604644775390625e-8f;
-    const float r0 = sqrtf(-2.f * logf(u0)), r1 = sqrtf(-2.f * logf(u2));
-    float s0, c0, s1, c1;
-    sincosf(6.283185307179586f * u1, &s0, &c0);
-    sincosf(6.283185307179586f * u3, &s1, &c1);
-    z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;
-}
 
 __global__ void philox_raw_kernel(uint64_t seed, uint64_t sample, uint32_t stream, uint32_t nblocks, uint32_t* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -503,6 +470,23 @@ __global__ void mel_pad_kernel(const float* __restrict__ x, float* __restrict__ 
     xp[i] = (p >= 0 && p < L) ? x[b * L + p] : 0.f;
 }
 
+// The same padded rows for the Monte Carlo samples of ONE clip (certified_robust.py:34-67 with denoiser None): row b is
+// clip + delta[b], or clip + sigma * the Philox normals of sample sample0 + b, the bits of mc_noise_scale_kernel at scale 1, written
+// straight into the padded layout, so the noisy waveforms are never stored on their own.  One thread per float4: a Philox block is
+// four consecutive samples and 1024, L and LPm are multiples of 4, so no float4 straddles a pad
+__global__ void mel_pad_noise_kernel(const float* __restrict__ clip, const float* __restrict__ delta, float sigma, uint64_t seed,
+                                     uint64_t sample0, float* __restrict__ xp, int L, int LPm, long total4) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total4) return;
+    const int per = LPm / 4;
+    const long b = i / per;
+    const int p = 4 * (int)(i - b * per) - 1024;
+    float4 o{0.f, 0.f, 0.f, 0.f};
+    if (p >= 0 && p < L)
+        o = noisy4(*(const float4*)(clip + p), delta ? delta + b * L + p : nullptr, sigma, seed, sample0 + (uint64_t)b, (uint32_t)(p >> 2));
+    *(float4*)(xp + 4 * i) = o;
+}
+
 // P[n][f] = re^2 + im^2, f < 1025 ; zero for the K padding up to ldp.  D is [n][ldd]: re at f, im at 1025 + f
 __global__ void mel_power_kernel(const float* __restrict__ D, float* __restrict__ P, int ldd, int ldp, long total) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -698,6 +682,11 @@ void launch_dot256(const float* f, const float* w, float bias, float* out, long 
 void launch_mel_pad(const float* x, float* xp, int B, int L, int LPm, hipStream_t s) {
     const long total = (long)B * LPm;
     hipLaunchKernelGGL(mel_pad_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, x, xp, L, LPm, total);
+}
+void launch_mel_pad_noise(const float* clip, const float* delta, float sigma, uint64_t seed, uint64_t sample0, float* xp, int B, int L,
+                          int LPm, hipStream_t s) {
+    const long total4 = (long)B * (LPm / 4);
+    hipLaunchKernelGGL(mel_pad_noise_kernel, dim3(nblk(total4, 256)), dim3(256), 0, s, clip, delta, sigma, seed, sample0, xp, L, LPm, total4);
 }
 void launch_mel_power(const float* D, float* P, int ldd, int ldp, long rows, hipStream_t s) {
     const long total = rows * ldp;

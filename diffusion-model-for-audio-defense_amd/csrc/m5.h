@@ -47,4 +47,11 @@ int m5_configure();                // hipFuncSetAttribute(max dynamic LDS); 0 or
 void launch_m5(const M5Weights& w, const M5Geom& g, const float* x, int B, float* logp, int32_t* cls, const float* g_logp, float* g_x,
                int tape_layer, float* pooled, uint8_t* dec, hipStream_t s);
 
+// The forward over `rows` Monte Carlo samples of ONE clip [L] (certified_robust.py:34-67 with denoiser None): workgroup b stages
+// clip + delta[b] (delta [rows][L]), or clip + sigma * the Philox normals keyed (seed, sample0 + b, stream 0) when delta is null (the
+// bits of launch_mc_noise_scale at scale 1), into LDS, so the noisy clips never exist in device memory; the rest is launch_m5's forward,
+// bit for bit.  counts [n_out] += 1 at each sample's first maximum; logp [rows][n_out] is optional.
+void launch_m5_noisy(const M5Weights& w, const M5Geom& g, const float* clip, const float* delta, float sigma, uint64_t seed, uint64_t sample0,
+                     int rows, unsigned long long* counts, float* logp, hipStream_t s);
+
 }  // namespace dmad

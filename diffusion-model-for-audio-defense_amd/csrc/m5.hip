@@ -1,5 +1,6 @@
 // M5 forward and input VJP in one launch, one workgroup per clip (m5.h).
 #include "m5.h"
+#include "philox.h"
 
 namespace dmad {
 
@@ -19,6 +20,16 @@ struct M5Params {
     int tape_layer;
     float* pooled;
     uint8_t* dec;
+    static constexpr bool kNoisy = false;
+};
+
+// The noisy-staging form (launch_m5_noisy): workgroup b evaluates Monte Carlo sample sample0 + b of the ONE clip x, forward and vote only
+struct M5NoisyParams : M5Params {
+    const float* delta;                  // [rows][L] caller's noise, or nullptr: sigma * Philox normal keyed (seed, sample0 + b)
+    float sigma;
+    uint64_t seed, sample0;
+    unsigned long long* counts;          // [n_out]: the workgroup's decision is added here
+    static constexpr bool kNoisy = true;
 };
 
 // BatchNorm (folded) -> ReLU -> the first maximum of four frames, as torch's max_pool1d scans them (a NaN wins and a later NaN replaces
@@ -108,8 +119,10 @@ __device__ __forceinline__ void conv3_back_route(const float* G, int pg, const f
     }
 }
 
-template <int K1>
-__global__ __launch_bounds__(kThreads) void m5_kernel(const M5Params p) {
+// P = M5Params: one clip per workgroup.  P = M5NoisyParams: every workgroup reads the same clip and adds its own sample's noise while
+// staging it; those branches are compile-time, so the M5Params kernel is the code it was without them
+template <int K1, class P>
+__global__ __launch_bounds__(kThreads) void m5_kernel(const P p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const M5Geom& g = p.g;
     const int tid = threadIdx.x, b = blockIdx.x, L = g.L;
@@ -121,8 +134,14 @@ __global__ __launch_bounds__(kThreads) void m5_kernel(const M5Params p) {
     const int T1 = g.T[0];
 
     // ---- the clip, padded by one 16-byte slot per 64 samples (pooled frames 64 samples apart then sit on different banks), and conv1 [k][32]
-    const float* xg = p.x + (long)b * L;
-    for (int i = 4 * tid; i < L; i += 4 * kThreads) *(float4*)(X + i + ((i >> 6) << 2)) = *(const float4*)(xg + i);
+    if constexpr (P::kNoisy) {           // clip + noise, in registers: the noisy clip exists in LDS only
+        const float* dg = p.delta ? p.delta + (long)b * L : nullptr;
+        for (int i = 4 * tid; i < L; i += 4 * kThreads)
+            *(float4*)(X + i + ((i >> 6) << 2)) = noisy4(*(const float4*)(p.x + i), dg ? dg + i : nullptr, p.sigma, p.seed, p.sample0 + (uint64_t)b, (uint32_t)(i >> 2));
+    } else {
+        const float* xg = p.x + (long)b * L;
+        for (int i = 4 * tid; i < L; i += 4 * kThreads) *(float4*)(X + i + ((i >> 6) << 2)) = *(const float4*)(xg + i);
+    }
     for (int i = 4 * tid; i < K1 * kM5Ch; i += 4 * kThreads) *(float4*)(W1 + i) = *(const float4*)(p.w.w1t + i);
     __syncthreads();
 
@@ -221,6 +240,7 @@ __global__ __launch_bounds__(kThreads) void m5_kernel(const M5Params p) {
         for (int o = 0; o < NO; ++o) sum += expf(small[64 + o] - m);
         small[128] = m + logf(sum);
         if (p.cls) p.cls[b] = best;
+        if constexpr (P::kNoisy) atomicAdd(&p.counts[best], 1ull);
     }
     __syncthreads();
     if (tid < NO) {
@@ -228,6 +248,7 @@ __global__ __launch_bounds__(kThreads) void m5_kernel(const M5Params p) {
         small[192 + tid] = lp;
         if (p.logp) p.logp[(long)b * NO + tid] = lp;
     }
+    if constexpr (P::kNoisy) return;
     if (!p.g_x) return;
     __syncthreads();
 
@@ -332,15 +353,24 @@ const char* m5_geometry(int L, int K1, int n_out, M5Geom* g) {
 }
 
 int m5_configure() {
-    if (hipError_t e = hipFuncSetAttribute((const void*)m5_kernel<80>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds)) return (int)e;
-    return (int)hipFuncSetAttribute((const void*)m5_kernel<160>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+    for (const void* k : {(const void*)m5_kernel<80, M5Params>, (const void*)m5_kernel<160, M5Params>, (const void*)m5_kernel<80, M5NoisyParams>,
+                          (const void*)m5_kernel<160, M5NoisyParams>})
+        if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds)) return (int)e;
+    return 0;
 }
 
 void launch_m5(const M5Weights& w, const M5Geom& g, const float* x, int B, float* logp, int32_t* cls, const float* g_logp, float* g_x,
                int tape_layer, float* pooled, uint8_t* dec, hipStream_t s) {
     M5Params p{w, g, x, logp, cls, g_logp, g_x, tape_layer, pooled, dec};
-    if (g.K1 == 80) hipLaunchKernelGGL(m5_kernel<80>, dim3((unsigned)B), dim3(kThreads), (size_t)g.lds_bytes, s, p);
-    else hipLaunchKernelGGL(m5_kernel<160>, dim3((unsigned)B), dim3(kThreads), (size_t)g.lds_bytes, s, p);
+    if (g.K1 == 80) hipLaunchKernelGGL((m5_kernel<80, M5Params>), dim3((unsigned)B), dim3(kThreads), (size_t)g.lds_bytes, s, p);
+    else hipLaunchKernelGGL((m5_kernel<160, M5Params>), dim3((unsigned)B), dim3(kThreads), (size_t)g.lds_bytes, s, p);
+}
+
+void launch_m5_noisy(const M5Weights& w, const M5Geom& g, const float* clip, const float* delta, float sigma, uint64_t seed, uint64_t sample0,
+                     int rows, unsigned long long* counts, float* logp, hipStream_t s) {
+    M5NoisyParams p{{w, g, clip, logp, nullptr, nullptr, nullptr, 0, nullptr, nullptr}, delta, sigma, seed, sample0, counts};
+    if (g.K1 == 80) hipLaunchKernelGGL((m5_kernel<80, M5NoisyParams>), dim3((unsigned)rows), dim3(kThreads), (size_t)g.lds_bytes, s, p);
+    else hipLaunchKernelGGL((m5_kernel<160, M5NoisyParams>), dim3((unsigned)rows), dim3(kThreads), (size_t)g.lds_bytes, s, p);
 }
 
 }  // namespace dmad

@@ -92,6 +92,7 @@ _SIGNATURES = {
     'dmad_vgg_pool_relu_bwd': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_smooth_votes': (C.c_int, [_P, _P, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_int64, C.c_int32,
                                     C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P]),
+    'dmad_rs_smooth_votes': (C.c_int, [_P, _P, C.c_float, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, _P, _P, _P, _P]),
     'dmad_set_mode': (C.c_int, [_P, C.c_int32]),
     'dmad_set_waveform_tier': (C.c_int, [_P, C.c_int32]),
     'dmad_set_recheck_margin': (C.c_int, [_P, C.c_float]),
@@ -169,6 +170,7 @@ _SIGNATURES = {
     'dmad_m5_logits': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
     'dmad_m5_vjp': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     'dmad_m5_tape': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    'dmad_m5_rs_smooth_votes': (C.c_int, [_P, _P, C.c_float, C.c_int64, C.c_uint64, C.c_uint64, _P, _P, _P, _P]),
     'dmad_kws_logits': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     'dmad_kws_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     'dmad_kws_tape': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),

@@ -930,6 +930,28 @@ class Engine:
                                          _ptr(x0), _stream()))
         return counts, logits, x0
 
+    def _noise_rows(self, delta: Optional[torch.Tensor], n: int) -> Optional[torch.Tensor]:
+        """the caller's noise of a randomized-smoothing loop as [n, L] float32 on the device"""
+        if delta is None:
+            return None
+        delta = delta.detach().reshape(n, self.L).contiguous().float()
+        assert delta.is_cuda
+        return delta if delta.data_ptr() % 16 == 0 else delta.clone()         # the kernels read 16 bytes at a time
+
+    def rs_smooth_votes(self, clip: torch.Tensor, sigma: float, n: int, batch: Optional[int] = None, seed: int = 0, sample0: int = 0,
+                        delta: Optional[torch.Tensor] = None, want_logits: bool = False, counts: Optional[torch.Tensor] = None):
+        """dmad_rs_smooth_votes: the Monte Carlo loop without a purifier (RobustCertificate with denoiser=None) in one call: clip + noise
+        -> mel dB -> the classifier's fp32 tier -> votes.  Returns (counts[int64, C] on device, logits|None), bit for bit what
+        classify(mel_db(clip + sigma * philox_normal(seed, sample0, 0, n))) and vote give."""
+        clip, batch, counts = self._vote_state(clip, batch, counts)
+        if clip.data_ptr() % 16:
+            clip = clip.clone()
+        logits = torch.empty((n, self.num_classes), device=clip.device) if want_logits else None
+        delta = self._noise_rows(delta, n)
+        check(self.lib.dmad_rs_smooth_votes(self._h, _ptr(clip), float(sigma), int(n), int(batch), int(seed), int(sample0), _ptr(delta),
+                                            _ptr(counts), _ptr(logits), _stream()))
+        return counts, logits
+
     def eval_samples(self, clip: torch.Tensor, sigma: float, sqrt_abar_star: float, t: int, c_a: float, c_b: float,
                      idx: torch.Tensor, path: int = 0, seed: int = 0, sample0: int = 0, delta: Optional[torch.Tensor] = None,
                      want_x0: bool = False):
@@ -1375,6 +1397,23 @@ class Engine:
         dec = torch.empty((B,), device=xw.device, dtype=torch.int32) if want_decisions else None
         check(self.lib.dmad_m5_logits(self._h, _ptr(xw), B, _ptr(out), _ptr(dec), _stream()))
         return (out, dec) if want_decisions else out
+
+    def m5_rs_smooth_votes(self, clip: torch.Tensor, sigma: float, n: int, seed: int = 0, sample0: int = 0,
+                           delta: Optional[torch.Tensor] = None, want_logits: bool = False, counts: Optional[torch.Tensor] = None):
+        """dmad_m5_rs_smooth_votes: the Monte Carlo loop of RobustCertificate(M5, transform=None, denoiser=None) in one call, one
+        workgroup per sample; the noisy clips exist in LDS only.  Returns (counts[int64, m5_classes] on device, log-probabilities|None),
+        bit for bit what m5_logits(clip + sigma * philox_normal(seed, sample0, 0, n)) and its first maxima give."""
+        clip = self._clip(clip)
+        if clip.data_ptr() % 16:
+            clip = clip.clone()
+        if counts is None:
+            counts = torch.zeros(self._m5_width(), dtype=torch.int64, device=clip.device)
+        assert counts.is_cuda and counts.dtype == torch.int64 and counts.numel() == self._m5_width()
+        logp = torch.empty((n, self._m5_width()), device=clip.device) if want_logits else None
+        delta = self._noise_rows(delta, n)
+        check(self.lib.dmad_m5_rs_smooth_votes(self._h, _ptr(clip), float(sigma), int(n), int(seed), int(sample0), _ptr(delta), _ptr(counts),
+                                               _ptr(logp), _stream()))
+        return counts, logp
 
     def m5_vjp(self, x: torch.Tensor, g: torch.Tensor, want_logits: bool = False):
         """dmad_m5_vjp: g_x [B,L] = (d logp / d x)^T g for logp = M5(x), g [B, m5_classes].  want_logits: also the log-probabilities,

@@ -6,7 +6,9 @@ What changes underneath:
     (dmad_smooth_votes) when denoiser / transform / classifier are this package's HIP-backed stages:
     noise, sqrt(alpha_bar*) scaling, one-shot DiffWave purification, mel-dB, VGG19_bn, arg-max and the
     per-class histogram never leave the GPU and the 10 `.item()` syncs of the reference become one
-    80-byte copy.  Other classifiers / transforms (M5, ResNeXt, user modules) are called as torch
+    80-byte copy.  Without a denoiser (the plain randomized-smoothing baseline) the loop is one call too:
+    dmad_rs_smooth_votes behind the HIP mel front-end and a HIP-backed classifier, dmad_m5_rs_smooth_votes for
+    an M5 on the engine.  Other classifiers / transforms (a default M5, user modules) are called as torch
     modules on the purified batch and only the vote count runs in HIP.
   * The N samples shard over torch.distributed ranks (one process per GPU); the per-class counts are
     summed with a single all_reduce (RCCL over xGMI on MI355X).  With device noise (Philox keyed by the
@@ -99,6 +101,48 @@ class RobustCertificate():
                 return None
         return eng if (getattr(cls, 'engine', None) is eng and eng.has_classifier and eng.has_unet) else None
 
+    def _fused_rs(self):
+        """The plain randomized-smoothing loop (denoiser=None, the driver's --defense_method randsmooth) as one engine call:
+        ('mel', engine) when the transform is the HIP mel front-end and the classifier is HIP-backed and bound to its engine (an unbound
+        one is bound to it first; if that engine serves another classifier it gets one of its own and the loop stays unfused, as in
+        _fused()), ('m5', engine) when there is no transform and the classifier is an M5 that use_engine() put on an engine.  None
+        otherwise: a user's torch module, a default M5 or any other transform keep the host loop."""
+        if self.denoiser is not None:
+            return None
+        cls, tr = self.classifier, self.transform
+        if getattr(cls, 'training', False):                 # the host loop runs (or refuses) a module in training mode as it is
+            return None
+        if tr is None:
+            from audio_models.M5.M5Net import is_m5
+            eng = getattr(cls, '__dict__', {}).get('engine')
+            return ('m5', eng) if is_m5(cls) and eng is not None and eng.has_m5 else None
+        if not hasattr(cls, 'bind_engine'):
+            return None
+        from dmad_hip.transforms import MelSpectrogramDB
+        if isinstance(tr, MelSpectrogramDB):
+            eng = tr.engine
+        else:                   # the reference's own Compose([MelSpectrogram, AmplitudeToDB]) through the opt-in shims
+            stages = getattr(tr, 'transforms', [])
+            if [getattr(t, '_dmad_stage', None) for t in stages] != ['mel_power', 'power_to_db']:
+                return None
+            eng = stages[0].engine
+        if 'engine' not in getattr(cls, '__dict__', {}):
+            from dmad_hip._lib import DmadError
+            try:
+                cls.bind_engine(eng)
+            except DmadError:                               # that engine serves another classifier: stay unfused
+                cls.bind_engine()
+        return ('mel', eng) if getattr(cls, 'engine', None) is eng and eng.has_classifier else None
+
+    @staticmethod
+    def _rs_votes(route, x, sigma, n, seed, sample0, delta, counts):
+        """n samples from global index sample0 on the route _fused_rs() gave, added to counts (None: fresh counts).  The passes are the
+        engine's max_batch, not the caller's batch_size: a sample's logits do not depend on the batch it ran in."""
+        kind, eng = route
+        if kind == 'm5':
+            return eng.m5_rs_smooth_votes(x, sigma, n, seed=seed, sample0=sample0, delta=delta, counts=counts)[0]
+        return eng.rs_smooth_votes(x, sigma, n, seed=seed, sample0=sample0, delta=delta, counts=counts)[0]
+
     @torch.no_grad()
     def forward(self, x: torch.Tensor):
         x_in = x
@@ -170,6 +214,7 @@ class RobustCertificate():
                                  'tau_spec %.4g, tau_spec2 %.3g' % (sigma, spec_args[0], c, self.calibrate_clips, r[2], r[3], r[0], r[1]))
             if exact and self.noise_source == 'device':
                 self._last = ('spec', seed, sigma, spec_args, num_sampling)
+        rs = self._fused_rs() if (not fused and spec_eng is None and x.is_cuda) else None
         if self.noise_source == 'torch_cpu':
             # The reference's stream: one CPU torch.normal draw per batch (ref l.47).  The stream is batch-split invariant,
             # so every rank draws the whole stream, keeps its own slice of each batch and feeds it to the engine batch by
@@ -184,6 +229,8 @@ class RobustCertificate():
                     if fused:
                         counts, _, _ = self.denoiser.engine.smooth_votes(x, sigma, coeffs[3], coeffs[0], coeffs[1], coeffs[2], e - a,
                                                                          seed=seed, sample0=a, delta=delta, counts=counts)
+                    elif rs is not None:
+                        counts = self._rs_votes(rs, x, sigma, e - a, seed, a, delta, counts)
                     else:
                         c = self._generic_votes(x, sigma, coeffs, a, e, seed, delta, batch_size)
                         counts = c if counts is None else counts + c
@@ -195,6 +242,8 @@ class RobustCertificate():
         elif fused and hi > lo:
             counts, _, _ = self.denoiser.engine.smooth_votes(x, sigma, coeffs[3], coeffs[0], coeffs[1], coeffs[2], hi - lo,
                                                              seed=seed, sample0=lo)
+        elif rs is not None and hi > lo:
+            counts = self._rs_votes(rs, x, sigma, hi - lo, seed, lo, None, None)
         else:
             counts = self._generic_votes(x, sigma, coeffs, lo, hi, seed, None, batch_size)
 

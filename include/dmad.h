@@ -207,6 +207,21 @@ int dmad_smooth_votes(dmad_engine* e, const float* clip, float sigma, float sqrt
                       float c_a, float c_b, int64_t n, int32_t batch, uint64_t seed, uint64_t sample0,
                       const float* delta, int64_t* counts, float* logits_out, float* x0_out, dmad_stream s);
 
+/* The same loop without a purifier, the plain randomized-smoothing baseline (certified_robust.py:34-67 with `denoiser is None`, the
+ * driver's --defense_method randsmooth):  for samples i in [sample0, sample0 + n):
+ *   x_in = clip + delta_i;  logits = classifier(mel_db(x_in));  counts[argmax logits] += 1     (the first maximum).
+ * delta_i: row i of `delta` (device fp32 [n][clip_len], the reference's CPU torch.normal draws) or, delta == NULL, sigma * the Philox
+ * normals keyed (seed, sample0 + i, stream 0, block l / 4): multiply, then add, each rounded (no FMA contraction), the bits of
+ * x + sigma * dmad_philox_normal(...).  No sqrt(alpha_bar*) scaling: the reference applies it only when a denoiser is present.
+ * The noisy rows are written straight into the mel front-end's padded layout; the noisy waveforms are not stored on their own.
+ * The classifier runs its fp32 tier (dmad_classify's) on every engine precision and in every mode, so the counts are those of a host
+ * loop over dmad_philox_normal / dmad_mel_db / dmad_classify / dmad_vote exactly, no recheck bound is involved, and WideResNet-28-10
+ * and DenseNet-BC-100-12 are served in the exact-vote mode too.  Needs with_classifier and finalised classifier weights, not a WaveNet.
+ * clip and delta 16-byte aligned.  counts: device int64[num_classes], ACCUMULATED into.  logits_out: optional [n][num_classes].
+ * 1 <= batch <= max_batch: rows per pass; the result does not depend on it. */
+int dmad_rs_smooth_votes(dmad_engine* e, const float* clip, float sigma, int64_t n, int32_t batch, uint64_t seed, uint64_t sample0,
+                         const float* delta, int64_t* counts, float* logits_out, dmad_stream s);
+
 /* DMAD_EXACT engines.  dmad_set_mode selects the dmad_mode (default DMAD_MODE_EXACT_VOTES).  dmad_set_recheck_margin sets
  * the bound tau: a sample whose 16-bit logits have (largest - second largest) < tau (or any NaN) does not vote from the 16-bit
  * logits; its global sample index is queued and the sample is re-evaluated from the SAME noise (Philox key (seed, index),
@@ -743,6 +758,15 @@ int dmad_defense_query_logits(dmad_engine* e, const float* x, int32_t B, int32_t
 int dmad_m5_logits(dmad_engine* e, const float* x, int32_t B, float* logp, int32_t* decisions, dmad_stream s);
 int dmad_m5_vjp(dmad_engine* e, const float* x, int32_t B, const float* g_logp, float* g_x, float* logp, dmad_stream s);
 int dmad_m5_tape(dmad_engine* e, const float* x, int32_t B, int32_t layer, float* pooled, uint8_t* decisions, dmad_stream s);
+
+/* dmad_rs_smooth_votes for RobustCertificate(M5, transform=None, denoiser=None) (certified_robust.py:34-67 with `denoiser is None`):
+ * sample i's input clip + delta_i, with the same delta / Philox keys and rounding, goes through M5; counts: device int64[n_output],
+ * ACCUMULATED into at each sample's first maximum; logp_out: optional [n][n_output], dmad_m5_logits of the noisy clip bit for bit.
+ * One workgroup per sample adds the noise while it copies the clip into LDS: the n noisy clips never exist in device memory.  Needs
+ * the M5 weights and nothing else; no workspace, no max_batch limit; a fixed number of samples per launch, which the result does not
+ * depend on.  clip and delta 16-byte aligned. */
+int dmad_m5_rs_smooth_votes(dmad_engine* e, const float* clip, float sigma, int64_t n, uint64_t seed, uint64_t sample0,
+                            const float* delta, int64_t* counts, float* logp_out, dmad_stream s);
 
 /* dmad_query_logits with M5 in the place of  mel dB -> classifier  (EOT.forward on AcousticSystem(M5, None, defender),
  * robustness_eval/_EOT.py:30-64): the same arguments, samplers 0 / 1 / 2, row layout and Philox keys; logits: [repeats * B][n_output]
