@@ -27,6 +27,7 @@
 #include "densenet.h"
 #include "gemm_f32.h"
 #include "gemm_h16.h"
+#include "kernel_setup.h"
 #include "wn_bf16.h"
 
 using namespace dmad;
@@ -447,6 +448,14 @@ int need_kws_mel(dmad_engine* e) {          // the constants of kws_mel.h, float
     return 0;
 }
 int need_m5(const dmad_engine* e) { return e->m5_final ? 0 : fail(DMAD_ERR_STATE, "M5 weights are not finalised (dmad_load_weight + dmad_finalize_weights)"); }
+// the kernel families of `mask` set up on the current device (kernel_setup.h); after the first call per device a table read each
+int need_kernels(unsigned mask) {
+    for (unsigned f = 1; f <= mask; f <<= 1)
+        if (mask & f)
+            if (int r = kernels_ready(f))
+                return fail(DMAD_ERR_HIP, "kernel set-up (max dynamic LDS, %s) failed: %s", kernel_family_name(f), hipGetErrorString((hipError_t)r));
+    return 0;
+}
 int need_batch(const dmad_engine* e, int B) { return B >= 1 && B <= e->maxB ? 0 : fail(DMAD_ERR_STATE, "batch %d outside [1, max_batch=%d]", B, e->maxB); }
 int need_path(const dmad_engine* e, int path) {  // a WaveNet path the caller names (dmad_wavenet_eps_path / dmad_eval_samples)
     if (path != PATH_DEFAULT && path != PATH_FP32 && path != PATH_X3) return fail(DMAD_ERR_INVALID, "unknown path %d", path);
@@ -859,9 +868,9 @@ int finalize_resnext(dmad_engine* e) {
     if (e->rx_h16) {
         CHK(e->alloc(&e->rxX16, B * 1024 * 256)); CHK(e->alloc(&e->rxY16, B * 1024 * 256)); CHK(e->alloc(&e->rxS16, B * 1024 * 256));
         CHK(e->alloc(&e->rxT1h, B * 1024 * 1024)); CHK(e->alloc(&e->rxT2h, B * 1024 * 512));
-        if (int r = gemm_h16_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, f16 conv GEMM) failed: %d", r);
+        CHK(need_kernels(KF_GEMM_H16));
     }
-    if (e->rx_x3) if (int r = gemm_x3_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, split-f16 tier) failed: %d", r);
+    if (e->rx_x3) CHK(need_kernels(KF_GEMM_X3));
     return 0;
 }
 
@@ -1356,9 +1365,9 @@ int finalize_unet(dmad_engine* e) {
         CHK(e->alloc(&e->un_uph, B * 1024 * 256));
         CHK(e->alloc(&e->un_atth, B * 256 * 256));
         CHK(e->alloc(&e->un_qkvh, B * 256 * 768));
-        if (int r = gemm_h16_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, f16 conv GEMM) failed: %d", r);
+        CHK(need_kernels(KF_GEMM_H16));
     }
-    if (e->un_x3) if (int r = gemm_x3_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, split-f16 tier) failed: %d", r);
+    if (e->un_x3) CHK(need_kernels(KF_GEMM_X3));
     CHK(e->alloc(&e->un_ss_table, (size_t)(kUnSsSteps + 1) * e->un_ss_total));
     e->un_ss_have.assign(kUnSsSteps, 0);
     e->un_t = -1;
@@ -1487,7 +1496,7 @@ GemmH16Args un_h16_args(const h16_t* A, const float* bias, const h16_t* X, float
 // GroupNorm of the 16-bit tier: the one-pass kernel when every part of the input carries its statistics slab, the two-pass ones otherwise
 int un_groupnorm16(UMap in, UMap in2, int c1, const float* gw, const float* gb, const float* ss, int silu, h16_t* y16, float* y32, int B, int HW,
                    int C, hipStream_t s) {
-    static const bool fused = []() { const char* v = getenv("DMAD_GN_FUSED"); return !(v && v[0] == '0'); }();     // A/B switch
+    static const bool fused = env_switch_on("DMAD_GN_FUSED");     // A/B switch
     if (fused && in.h && in.st && (!in2.h || in2.st) && HW >= 16 &&
         launch_groupnorm16_apply(in.h, in.st, in2.h, in2.st, c1, gw, gb, ss, silu, y16, y32, B, HW, C, s) == 0)
         return 0;
@@ -2394,8 +2403,7 @@ int finalize_m5(dmad_engine* e) {
     for (int l = 0; l < 3; ++l) { W.wf[l] = d + off[n++]; W.wb[l] = d + off[n++]; }
     for (int l = 0; l < 4; ++l) { W.scale[l] = d + off[n++]; W.shift[l] = d + off[n++]; }
     W.fcw = d + off[n++]; W.fcb = d + off[n++];
-    if (int r = m5_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, M5) failed: %d", r);
-    return 0;
+    return need_kernels(KF_M5);
 }
 
 // KWS: checks the geometry against what kws.hip serves and packs the weight images of both directions into one buffer
@@ -2483,8 +2491,7 @@ int finalize_kws(dmad_engine* e) {
         W.whhT[l] = d + off[n++]; W.whh[l] = d + off[n++]; W.bhh[l] = d + off[n++];
     }
     W.wxT = d + off[n++]; W.wx = d + off[n++]; W.wxb = d + off[n++]; W.vt = d + off[n++]; W.u = d + off[n++];
-    if (int r = kws_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, KWS) failed: %d", r);
-    return 0;
+    return need_kernels(KF_KWS);
 }
 
 }  // namespace
@@ -2530,9 +2537,9 @@ int dmad_create(const dmad_config* cfg, dmad_engine** out) {
     e->wave_rt.tau2 = 1e-3f;                // the same for the split-f16 tier (dmad_set_recheck_margin2)
     e->un_h16 = cfg->precision != DMAD_FP32;    // engines with a 16-bit side also get the UNet's f16 tier (once UNet weights are loaded)
     e->rx_h16 = cfg->precision != DMAD_FP32;    // ... and ResNeXt29's (once its weights are loaded)
-    if (const char* v = getenv("DMAD_RX_H16")) if (v[0] == '0') e->rx_h16 = false;      // A/B switch: ResNeXt29 on the fp32 matrix cores in every tier
+    if (!env_switch_on("DMAD_RX_H16")) e->rx_h16 = false;      // A/B switch: ResNeXt29 on the fp32 matrix cores in every tier
     e->rx_x3 = cfg->precision == DMAD_EXACT;    // ... and its split-f16 tier
-    if (const char* v = getenv("DMAD_RX_X3")) if (v[0] == '0') e->rx_x3 = false;        // A/B switch
+    if (!env_switch_on("DMAD_RX_X3")) e->rx_x3 = false;        // A/B switch
     e->spec_rt.tau1 = 0.13f;                // spec-domain vote loop: measured logit-difference error of the f16 UNet chain x headroom (see dmad.h)
     e->spec_rt.tau2 = 5e-4f;                // ... of the chain on the split-f16 tier (measured 2.3e-4)
     e->un_x3 = cfg->precision == DMAD_EXACT;    // exact-vote engines also hold the UNet's split-f16 middle tier
@@ -2544,7 +2551,7 @@ int dmad_create(const dmad_config* cfg, dmad_engine** out) {
     const size_t B = e->maxB, L = e->L, LP = e->LP, NL = e->NL, B32 = e->maxB32;
     int r = 0;
     do {
-        if ((r = gemm_f32_configure())) { r = fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, fp32 narrow tile) failed: %d", r); break; }
+        if ((r = need_kernels(KF_GEMM_F32))) break;
         if ((r = e->alloc(&e->xt, B * L))) break;
         if ((r = e->alloc(&e->eps, B * L))) break;
         if ((r = e->alloc(&e->x0, B * L))) break;
@@ -2553,7 +2560,7 @@ int dmad_create(const dmad_config* cfg, dmad_engine** out) {
             if ((r = e->alloc(&e->hA, B * LP * kC, true))) break;
             if ((r = e->alloc(&e->hB, B * LP * kC, true))) break;
             if ((r = e->alloc(&e->gstore, NL * B * L * kC))) break;
-            if ((r = wn_bf16_configure())) { r = fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed: %d", r); break; }
+            if ((r = need_kernels(KF_WN_LAYER | KF_WN_FINAL))) break;
         }
         if (e->f32 && wn) {
             if ((r = e->alloc(&e->hA32, B32 * LP * kC, true))) break;
@@ -2561,7 +2568,7 @@ int dmad_create(const dmad_config* cfg, dmad_engine** out) {
             if ((r = e->alloc(&e->H32, B32 * L * 512))) break;
             if ((r = e->alloc(&e->g32, B32 * L * 256))) break;
             if ((r = e->alloc(&e->skip32, B32 * L * 256))) break;
-            if (e->bf16 && (r = gemm_x3_configure())) { r = fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, split-f16 tier) failed: %d", r); break; }
+            if (e->bf16 && (r = need_kernels(KF_GEMM_X3))) break;
         }
         if (e->bf16 && e->f32) {             // recheck queue of the exact-vote mode
             e->rc_cap = 1l << 20;
@@ -2962,7 +2969,7 @@ int dmad_conv_h16(const uint16_t* x, const uint16_t* x2, int32_t ksplit, const u
                   float* out32, uint16_t* out16, dmad_stream s) {
     if (!x || !w || (!out32 && !out16)) return fail(DMAD_ERR_INVALID, "null argument");
     if (B < 1 || H < 1 || M < 1 || K < 1 || groups < 1 || (stride != 1 && stride != 2)) return fail(DMAD_ERR_INVALID, "bad geometry");
-    if (int r = gemm_h16_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, f16 conv GEMM) failed: %d", r);
+    CHK(need_kernels(KF_GEMM_H16));
     const int Ho = (H - 1) / stride + 1;
     GemmH16Args g{};
     g.A = w; g.X = x; g.C = out32; g.C16 = out16; g.shift = bias; g.res16 = res16; g.M = M; g.K = K; g.taps = taps; g.ldc = groups * M;
@@ -2977,7 +2984,7 @@ int dmad_conv_h16_up2(const uint16_t* x_half, const uint16_t* w, const float* bi
                       float* out32, uint16_t* out16, float* stats, dmad_stream s) {
     if (!x_half || !w || (!out32 && !out16)) return fail(DMAD_ERR_INVALID, "null argument");
     if (B < 1 || H < 2 || (H & 1) || M < 1 || K < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
-    if (int r = gemm_h16_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, f16 conv GEMM) failed: %d", r);
+    CHK(need_kernels(KF_GEMM_H16));
     GemmH16Args g{};
     g.A = w; g.X = x_half; g.C = out32; g.C16 = out16; g.shift = bias; g.res16 = res16; g.M = M; g.K = K; g.taps = 9; g.ldc = M;
     g.N = (long)B * H * H; g.H = H; g.W = H; g.ldx = K; g.stride = 1; g.up2 = 1;
@@ -3000,7 +3007,7 @@ int dmad_conv_x3(const float* x, const float* x2, int32_t ksplit, const float* w
                  dmad_stream s) {
     if (!x || !w || !out) return fail(DMAD_ERR_INVALID, "null argument");
     if (B < 1 || H < 1 || M < 1 || K < 1 || groups < 1 || (stride != 1 && stride != 2) || (groups > 1 && x2)) return fail(DMAD_ERR_INVALID, "bad geometry");
-    if (int r = gemm_x3_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, split-f16 tier) failed: %d", r);
+    CHK(need_kernels(KF_GEMM_X3));
     GemmF32Args g = nhwc_conv_args(w, nullptr, bias, x, out, M, K, taps, B, H, stride, res, relu, groups, x2 ? ksplit : groups * K, groups * M);
     g.x3 = 1; g.out_split = out_split; g.res_split = res_split;
     if (x2) { g.X2 = x2; g.ksplit = ksplit; g.ldx2 = K - ksplit; }
@@ -3013,7 +3020,7 @@ int dmad_conv_h16_stats(const uint16_t* x, const uint16_t* w, const float* bias,
                         int32_t taps, int32_t stride, uint16_t* out16, float* stats, dmad_stream s) {
     if (!x || !w || !out16 || !stats) return fail(DMAD_ERR_INVALID, "null argument");
     if (B < 1 || H < 1 || M < 1 || K < 1 || (stride != 1 && stride != 2)) return fail(DMAD_ERR_INVALID, "bad geometry");
-    if (int r = gemm_h16_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, f16 conv GEMM) failed: %d", r);
+    CHK(need_kernels(KF_GEMM_H16));
     const int Ho = (H - 1) / stride + 1;
     if (Ho * Ho != 16 && (Ho * Ho) % 64) return fail(DMAD_ERR_INVALID, "statistics blocks need maps of 16 or a multiple of 64 pixels");
     GemmH16Args g{};
@@ -3097,7 +3104,7 @@ int dmad_conv_f32(const float* x, const float* x2, int32_t ksplit, const float* 
     if (H == 0 && (taps != 1 || stride != 1 || groups != 1 || x2)) return fail(DMAD_ERR_INVALID, "the row form (H = 0) is a plain GEMM: one tap, one group, one input");
     if (x2 && groups > 1) return fail(DMAD_ERR_INVALID, "two-part input serves dense convs only");
     if (slab_floats < 0 || n_ref < 0 || (slab && slab_floats < 1)) return fail(DMAD_ERR_INVALID, "bad split-K workspace");
-    if (int r = gemm_f32_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, fp32 narrow tile) failed: %d", r);
+    CHK(need_kernels(KF_GEMM_F32));
     GemmF32Args g{};
     if (H == 0) {
         g = plain_gemm(w, x, out, scale, shift, M, K, B, M, K, relu);
@@ -3123,7 +3130,7 @@ int dmad_conv_f32_vjp(const float* g_y, const float* w, const float* scale, cons
         return fail(DMAD_ERR_INVALID, "bad geometry (M a multiple of 16, K of 4, taps 1 or 9, stride 1 or 2, form 0 - 4)");
     if (stride == 2 && (H & 1)) return fail(DMAD_ERR_INVALID, "a stride-2 gradient is dilated to an even map: H = %d", H);
     if ((stride == 2 || form == 1) && !work) return fail(DMAD_ERR_INVALID, "this form needs the work map");
-    if (int r = gemm_f32_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, fp32 narrow tile) failed: %d", r);
+    CHK(need_kernels(KF_GEMM_F32));
     const hipStream_t st = (hipStream_t)s;
     const int Ho = form == 1 ? 2 * H : (H - 1) / stride + 1;
     if (form == 4) {                             // WideResNet's form: a dense 3x3 / 1x1 at stride 1 or 2, scale optional
@@ -3203,7 +3210,7 @@ int dmad_qkv_attention_f32(const float* qkv, int32_t B, int32_t T, int32_t heads
 int dmad_qkv_attention_bwd(const float* qkv, const float* go, int32_t B, int32_t T, int32_t heads, float* gqkv, dmad_stream s) {
     if (!qkv || !go || !gqkv) return fail(DMAD_ERR_INVALID, "null argument");
     if (B < 1 || heads < 1) return fail(DMAD_ERR_INVALID, "bad geometry");
-    if (int r = unvjp_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, attention backward) failed: %d", r);
+    CHK(need_kernels(KF_UNET_ATT_BWD));
     if (int rc = launch_qkv_attention_bwd(qkv, go, gqkv, B, T, heads, (hipStream_t)s))
         return fail(rc > 0 ? DMAD_ERR_HIP : DMAD_ERR_INVALID, "attention backward (T = %d): unsupported map size", T);
     LASTCHK();
@@ -3330,8 +3337,7 @@ int dmad_reserve_unet_vjp(dmad_engine* e, int32_t max_batch) {
             }
             CHK(pack_once(e, &e->un_outT, 9 * kUnMC, [&] { launch_unvjp_pack(e->un_outw, e->un_outT, kUnMC, 9, 1, 1, kUnMC, 0, 2, nullptr); }));   // [9][128] -> [128][9], flipped
             HIPCHK(hipGetLastError());
-            if (int r = unvjp_configure()) return fail(DMAD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS, attention backward) failed: %d", r);
-            return 0;
+            return need_kernels(KF_UNET_ATT_BWD);
         },
         [&](int vB) -> int {
             // tape slots and saved-map gradients, in floats per spectrogram

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 namespace dmad {
 
@@ -87,6 +88,12 @@ __device__ inline float clamp_min_nan(float t, float lo) { return t < lo ? lo : 
 __device__ inline float clamp_nan(float t, float lo, float hi) { return t < lo ? lo : (t > hi ? hi : t); }
 // AmplitudeToDB(stype='power') of one value: the function of dmad_power_to_db and of the KWS mel front-end (kws_mel.hip)
 __device__ inline float power_db(float p) { return __fmul_rn(10.f, (float)log10((double)clamp_min_nan(p, 1e-10f))); }
+
+// A development A/B switch of the library (INTEGRATION.md lists them): on unless the variable is set to something that starts with '0'.
+inline bool env_switch_on(const char* name) {
+    const char* v = getenv(name);
+    return !(v && v[0] == '0');
+}
 
 __device__ inline float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ inline float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }

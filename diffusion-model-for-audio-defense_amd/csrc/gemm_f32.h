@@ -69,7 +69,5 @@ int launch_gemm_f32(const GemmF32Args& a, hipStream_t s, float* slab = nullptr, 
 struct GemmF32Choice { int bm, narrow, two, splits; };
 GemmF32Choice gemm_f32_last_choice();
 int gemm_take_bad_shapes();   // number of launches refused on this thread since the last call (reset to 0)
-int gemm_f32_configure();     // per device, from dmad_create: dynamic-LDS attribute of the 8-slot narrow-tile kernel (0 or a hipError_t)
-int gemm_x3_configure();      // per device, from dmad_create: dynamic-LDS attribute of the split-f16 kernel (0 or a hipError_t)
 
 }  // namespace dmad

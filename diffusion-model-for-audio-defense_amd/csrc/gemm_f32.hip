@@ -19,6 +19,7 @@
 // per k-step, no register staging.
 #include "gemm_f32.h"
 #include "gemm_x3_ablate.h"
+#include "kernel_setup.h"
 
 namespace dmad {
 
@@ -818,22 +819,14 @@ GemmF32Choice gemm_f32_last_choice() { return g_choice; }
 // launches refused since the last call (and reset): the C ABI turns a non-zero count into DMAD_ERR_INVALID at the end of the entry point
 int gemm_take_bad_shapes() { const int n = g_bad_shapes; g_bad_shapes = 0; return n; }
 
-// once per device a process uses (dmad_create): the x3 tier's 144 KiB of dynamic LDS
+// KF_GEMM_X3 (kernel_setup.hip, once per device): the x3 tier's 144 KiB of dynamic LDS
 int gemm_x3_configure() {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_x3_kernel<false, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)gemm_x3_kernel<true, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)gemm_x3_kernel<false, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS);
-    if (e != hipSuccess) return (int)e;
-    return (int)hipFuncSetAttribute((const void*)gemm_x3_kernel<false, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS);
+    return set_max_lds({{(const void*)gemm_x3_kernel<false, 4, false>, X3_LDS}, {(const void*)gemm_x3_kernel<true, 4, false>, X3_LDS},
+                        {(const void*)gemm_x3_kernel<false, 4, true>, X3_LDS}, {(const void*)gemm_x3_kernel<false, 2, true>, X3_LDS}});
 }
 
-// once per device a process uses (dmad_create, like gemm_x3_configure: the attribute is per device, so a function-local static set on the
-// first device would leave every later device without it): 128 KiB of dynamic LDS for the 8-slot narrow-tile instantiation
-int gemm_f32_configure() {
-    return (int)hipFuncSetAttribute((const void*)gemm_f32_kernel<64, false, 8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * SLOT);
-}
+// KF_GEMM_F32: 128 KiB of dynamic LDS for the 8-slot narrow-tile instantiation
+int gemm_f32_configure() { return set_max_lds({{(const void*)gemm_f32_kernel<64, false, 8, 1>, 8 * SLOT}}); }
 
 int launch_gemm_f32(const GemmF32Args& a0, hipStream_t s, float* slab, long slab_floats, long n_ref) {
     GemmF32Args a = a0;
@@ -882,7 +875,7 @@ int launch_gemm_f32(const GemmF32Args& a0, hipStream_t s, float* slab, long slab
     const unsigned gx = (unsigned)gx_, gy = (unsigned)((a.M + BM - 1) / BM);
     const int nks = a.taps * (a.K / BK);
     int S = 1;
-    static const bool narrow_on = []() { const char* v = getenv("DMAD_F32_NARROW"); return !(v && v[0] == '0'); }();      // A/B switch
+    static const bool narrow_on = env_switch_on("DMAD_F32_NARROW");      // A/B switch
     auto launch = [&](dim3 grid) {
         const bool narrow = !a.X2 && BM == 64 && narrow_on && (long)grid.x * grid.y * grid.z < 256 && nks >= 8;
         g_choice = GemmF32Choice{a.X2 ? 128 : BM, narrow ? 1 : 0, a.X2 ? 1 : 0, a.splits > 1 ? a.splits : 1};

@@ -36,6 +36,5 @@ int launch_gemm_h16(const GemmH16Args& a, hipStream_t s);
 // true if launch_gemm_h16 would serve this block WITH up2 = 1 (a: the block for the upsampled geometry, X = the half-resolution map)
 bool gemm_h16_fuses_up2(const GemmH16Args& a);
 int gemm_h16_take_bad_shapes();
-int gemm_h16_configure();     // per device, from dmad_create: dynamic-LDS attribute (0 or a hipError_t)
 
 }  // namespace dmad

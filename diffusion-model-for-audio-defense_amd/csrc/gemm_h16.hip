@@ -14,6 +14,7 @@
 // channels are a multiple of 128 only), 8 waves of 64 x 64, 3-slot LDS ring of 48 KiB (144 KiB, one workgroup per CU, two waves
 // per SIMD), two k-steps in flight while one is contracted, one barrier per k-step.
 #include "gemm_h16.h"
+#include "kernel_setup.h"
 #include <stdlib.h>
 #include <stdio.h>
 #include <vector>
@@ -40,7 +41,8 @@ __device__ __attribute__((aligned(128))) unsigned short g_zero_page_h[64];     /
     } while (0)
 
 thread_local int g_bad = 0;
-int g_h16_cus = 256;                            // workgroups of a persistent launch (one per CU, a multiple of 8: the XCD-aware tile walk)
+// workgroups of a persistent launch: one per CU, a multiple of 8 (the XCD-aware tile walk)
+int h16_cus() { const int n = device_cus(); return n >= 8 ? n & ~7 : 256; }
 
 // GroupNorm statistics in the epilogue (GemmH16Args::stats): a lane adds the four channels of its pixel of a 16 x 16 accumulator tile,
 // as the f16 values the consumer will read; stats_store reduces over the 16 pixel lanes of the quad's row group (fixed order: DPP row rotations) and
@@ -1118,59 +1120,38 @@ __global__ void __launch_bounds__(512, 2) gemm_h16_sr_kernel(GemmH16Args a, int 
 }
 
 int gemm_h16_configure() {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_h16_kernel<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, H16_LDS);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)gemm_h16_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, H16_LDS);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)gemm_h16_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, H16_LDS);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)gemm_h16_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, H16_LDS);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)gemm_h16_big_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_256);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)gemm_h16_big_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_128);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 8)
-        g_h16_cus = prop.multiProcessorCount & ~7;
-    e = hipFuncSetAttribute((const void*)gemm_h16_sr_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SR_LDS);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)gemm_h16_sr_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SR_LDS);
-    if (e != hipSuccess) return (int)e;
-
-    e = hipFuncSetAttribute((const void*)gemm_h16_pp_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_256);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)gemm_h16_pp_kernel<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_256);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)gemm_h16_pp_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_128);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)gemm_h16_pp_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_128);
-    if (e != hipSuccess) return (int)e;
-    return 0;
+    return set_max_lds({{(const void*)gemm_h16_kernel<256, false>, H16_LDS}, {(const void*)gemm_h16_kernel<128, false>, H16_LDS},
+                        {(const void*)gemm_h16_kernel<256, true>, H16_LDS}, {(const void*)gemm_h16_kernel<128, true>, H16_LDS},
+                        {(const void*)gemm_h16_big_kernel<256>, BIG_LDS_256}, {(const void*)gemm_h16_big_kernel<128>, BIG_LDS_128},
+                        {(const void*)gemm_h16_sr_kernel<true>, SR_LDS}, {(const void*)gemm_h16_sr_kernel<false>, SR_LDS},
+                        {(const void*)gemm_h16_pp_kernel<256, true>, BIG_LDS_256}, {(const void*)gemm_h16_pp_kernel<256, false>, BIG_LDS_256},
+                        {(const void*)gemm_h16_pp_kernel<128, true>, BIG_LDS_128}, {(const void*)gemm_h16_pp_kernel<128, false>, BIG_LDS_128}});
 }
 
 int gemm_h16_take_bad_shapes() { const int n = g_bad; g_bad = 0; return n; }
 
 namespace {
+// A/B switches of the routing, read once: the persistent forms, the 256-row register-prefetched kernels
+bool h16_pers_on() { static const bool on = env_switch_on("DMAD_H16_PERS"); return on; }
+bool h16_big_on() { static const bool on = env_switch_on("DMAD_H16_BIG"); return on; }
+
 // does this block go to the slice-resident form?  (the routing of launch_gemm_h16, in one place)
-bool routes_to_sr(const GemmH16Args& a) {
-    static const bool pers_on = []() { const char* v = getenv("DMAD_H16_PERS"); return !(v && v[0] == '0'); }();
-    static const bool big_on = []() { const char* v = getenv("DMAD_H16_BIG"); return !(v && v[0] == '0'); }();
-    static const bool sr_on = []() { const char* v = getenv("DMAD_H16_SR"); return !(v && v[0] == '0'); }();
+bool routes_to_sr(const GemmH16Args& a, int cus) {
+    const bool pers_on = h16_pers_on(), big_on = h16_big_on();
+    static const bool sr_on = env_switch_on("DMAD_H16_SR");
     const bool two = a.X2 != nullptr, st16 = a.stats && a.stats_px == 16;
     if (!(pers_on && big_on && sr_on) || a.groups > 1 || st16 || a.K > BIG_KMAX || a.H >= 32768 || a.W >= 32768) return false;
     if (a.N * (long)a.ldx >= (1l << 31) || (two && a.N * (long)a.ldx2 >= (1l << 31)) || a.N * (long)a.ldc >= (1l << 31)) return false;
     if (a.M % 256 || a.taps != 9 || a.stride > 1 || a.W > 32 || a.W < 1) return false;
     const long nxp = (a.N + 255) / 256, tiles = nxp * (a.M / 256);
-    return tiles >= g_h16_cus && nxp < (1l << 31);
+    return tiles >= cus && nxp < (1l << 31);
 }
 }  // namespace
 
 bool gemm_h16_fuses_up2(const GemmH16Args& a) {
     const auto pow2 = [](long v) { return v > 0 && (v & (v - 1)) == 0; };
-    static const bool up2_on = []() { const char* v = getenv("DMAD_H16_UP2"); return !(v && v[0] == '0'); }();      // A/B switch
-    return up2_on && !a.X2 && a.H >= 2 && a.W >= 2 && pow2(a.W) && pow2((long)a.H * a.W) && routes_to_sr(a);
+    static const bool up2_on = env_switch_on("DMAD_H16_UP2");      // A/B switch
+    return up2_on && !a.X2 && a.H >= 2 && a.W >= 2 && pow2(a.W) && pow2((long)a.H * a.W) && routes_to_sr(a, h16_cus());
 }
 
 int launch_gemm_h16(const GemmH16Args& a, hipStream_t s) {
@@ -1187,15 +1168,15 @@ int launch_gemm_h16(const GemmH16Args& a, hipStream_t s) {
     // slice-resident for 3 x 3 / stride 1 / 256-row blocks, ping-pong otherwise (also the two-part input).  Grouped convs with >= 256
     // tiles: the 256 x 256 / 128 x 512 tile as separate workgroups.  Everything else (small maps, 16-pixel statistics blocks): the
     // 384-row kernel.  DMAD_H16_PERS=0 / DMAD_H16_SR=0 / DMAD_H16_BIG=0 switch a form off for A/B runs.
-    static const bool big_on = []() { const char* v = getenv("DMAD_H16_BIG"); return !(v && v[0] == '0'); }();
-    static const bool pers_on = []() { const char* v = getenv("DMAD_H16_PERS"); return !(v && v[0] == '0'); }();
+    const bool big_on = h16_big_on(), pers_on = h16_pers_on();
+    const int cus = h16_cus();
     const bool st16 = a.stats && a.stats_px == 16;           // 16-pixel statistics blocks: the 384-row kernel only
     if (a.stats && a.stats_px != 0 && a.stats_px != 16 && a.stats_px != 64) { ++g_bad; return -1; }
     const bool wide = a.C16 && !a.C && !a.res && !(a.ldc & 7);
-    if (routes_to_sr(a)) {                                    // (the one predicate gemm_h16_fuses_up2 asks, too)
+    if (routes_to_sr(a, cus)) {                                    // (the one predicate gemm_h16_fuses_up2 asks, too)
         const int nxp = (int)((a.N + 255) / 256);
-        if (wide) hipLaunchKernelGGL((gemm_h16_sr_kernel<true>), dim3(g_h16_cus), dim3(512), SR_LDS, s, a, nxp);
-        else hipLaunchKernelGGL((gemm_h16_sr_kernel<false>), dim3(g_h16_cus), dim3(512), SR_LDS, s, a, nxp);
+        if (wide) hipLaunchKernelGGL((gemm_h16_sr_kernel<true>), dim3(cus), dim3(512), SR_LDS, s, a, nxp);
+        else hipLaunchKernelGGL((gemm_h16_sr_kernel<false>), dim3(cus), dim3(512), SR_LDS, s, a, nxp);
         return 0;
     }
     if (pers_on && big_on && ng == 1 && (!two || a.N * (long)a.ldx2 < (1l << 31)) && !st16 && a.K <= BIG_KMAX && a.H < 32768 && a.W < 32768 &&
@@ -1203,11 +1184,11 @@ int launch_gemm_h16(const GemmH16Args& a, hipStream_t s) {
         const int bm = a.M % 256 == 0 ? 256 : (a.M == 128 ? 128 : 0);
         if (bm) {
             const long nxp = (a.N + (bm == 256 ? 255 : 511)) / (bm == 256 ? 256 : 512), tiles = nxp * (a.M / bm);
-            if (tiles >= g_h16_cus && nxp < (1l << 31) && a.N * (long)a.ldc < (1l << 31)) {
-                if (bm == 256 && wide) hipLaunchKernelGGL((gemm_h16_pp_kernel<256, true>), dim3(g_h16_cus), dim3(512), BIG_LDS_256, s, a, (int)nxp);
-                else if (bm == 256) hipLaunchKernelGGL((gemm_h16_pp_kernel<256, false>), dim3(g_h16_cus), dim3(512), BIG_LDS_256, s, a, (int)nxp);
-                else if (wide) hipLaunchKernelGGL((gemm_h16_pp_kernel<128, true>), dim3(g_h16_cus), dim3(512), BIG_LDS_128, s, a, (int)nxp);
-                else hipLaunchKernelGGL((gemm_h16_pp_kernel<128, false>), dim3(g_h16_cus), dim3(512), BIG_LDS_128, s, a, (int)nxp);
+            if (tiles >= cus && nxp < (1l << 31) && a.N * (long)a.ldc < (1l << 31)) {
+                if (bm == 256 && wide) hipLaunchKernelGGL((gemm_h16_pp_kernel<256, true>), dim3(cus), dim3(512), BIG_LDS_256, s, a, (int)nxp);
+                else if (bm == 256) hipLaunchKernelGGL((gemm_h16_pp_kernel<256, false>), dim3(cus), dim3(512), BIG_LDS_256, s, a, (int)nxp);
+                else if (wide) hipLaunchKernelGGL((gemm_h16_pp_kernel<128, true>), dim3(cus), dim3(512), BIG_LDS_128, s, a, (int)nxp);
+                else hipLaunchKernelGGL((gemm_h16_pp_kernel<128, false>), dim3(cus), dim3(512), BIG_LDS_128, s, a, (int)nxp);
                 return 0;
             }
         }

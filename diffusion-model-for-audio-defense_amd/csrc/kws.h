@@ -55,7 +55,6 @@ constexpr int kKwsSmall = 2048;
 
 // Fills g for a row of T frames; returns nullptr, or the reason the geometry is not supported (names the field)
 const char* kws_geometry(int T, KwsGeom* g);
-int kws_configure();               // hipFuncSetAttribute(max dynamic LDS); 0 or the hipError_t
 
 // One launch over B rows spec [B][32][T] (4-byte aligned rows).  logp [B][4], cls [B] (the first maximum of logp) and g_spec [B][32][T]
 // are optional; g_spec needs g_logp [B][4] and is written whole, exact zeros outside frames 16 j .. 16 j + 4 included.  tape_stage

@@ -1,5 +1,6 @@
 // Attention-CRNN keyword spotter: forward and input VJP in one launch, one workgroup per clip (kws.h).
 #include "kws.h"
+#include "kernel_setup.h"
 
 namespace dmad {
 
@@ -428,7 +429,7 @@ const char* kws_geometry(int T, KwsGeom* g) {
     return nullptr;
 }
 
-int kws_configure() { return (int)hipFuncSetAttribute((const void*)kws_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds); }
+int kws_configure() { return set_max_lds({{(const void*)kws_kernel, kMaxLds}}); }      // KF_KWS (kernel_setup.hip, once per device)
 
 void launch_kws(const KwsWeights& w, const KwsGeom& g, const float* spec, int B, float* logp, int32_t* cls, const float* g_logp,
                 float* g_spec, int tape_stage, float* tape, hipStream_t s) {

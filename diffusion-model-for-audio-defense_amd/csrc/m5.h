@@ -39,7 +39,6 @@ struct M5Geom {
 
 // Fills g for (L, K1, n_out); returns nullptr, or the reason the geometry is not supported (names the field)
 const char* m5_geometry(int L, int K1, int n_out, M5Geom* g);
-int m5_configure();                // hipFuncSetAttribute(max dynamic LDS); 0 or the hipError_t
 
 // One launch over B clips x [B][L].  logp [B][n_out], cls [B] (the first maximum of logp), g_x [B][L] are optional; g_x needs g_logp
 // [B][n_out].  tape_layer 1..4: also writes that layer's pooled post-ReLU map, pooled [B][C][T] floats, and decisions dec [B][C][T]

@@ -1,5 +1,6 @@
 // M5 forward and input VJP in one launch, one workgroup per clip (m5.h).
 #include "m5.h"
+#include "kernel_setup.h"
 #include "philox.h"
 
 namespace dmad {
@@ -352,11 +353,10 @@ const char* m5_geometry(int L, int K1, int n_out, M5Geom* g) {
     return nullptr;
 }
 
+// KF_M5 (kernel_setup.hip, once per device)
 int m5_configure() {
-    for (const void* k : {(const void*)m5_kernel<80, M5Params>, (const void*)m5_kernel<160, M5Params>, (const void*)m5_kernel<80, M5NoisyParams>,
-                          (const void*)m5_kernel<160, M5NoisyParams>})
-        if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds)) return (int)e;
-    return 0;
+    return set_max_lds({{(const void*)m5_kernel<80, M5Params>, kMaxLds}, {(const void*)m5_kernel<160, M5Params>, kMaxLds},
+                        {(const void*)m5_kernel<80, M5NoisyParams>, kMaxLds}, {(const void*)m5_kernel<160, M5NoisyParams>, kMaxLds}});
 }
 
 void launch_m5(const M5Weights& w, const M5Geom& g, const float* x, int B, float* logp, int32_t* cls, const float* g_logp, float* g_x,

@@ -1,5 +1,6 @@
 // See unet_ops.h.
 #include "unet_ops.h"
+#include "kernel_setup.h"
 #include <stdlib.h>
 
 namespace dmad {
@@ -664,7 +665,7 @@ int launch_groupnorm_nhwc(const float* x, const float* gamma, const float* beta,
     const int want = HW >= 1024 ? 8 : HW >= 256 ? 4 : 2;          // float4s per thread: small maps are latency bound and want more threads
     while (per < want && NT > 64 && (NT / 2) % R == 0 && (NT / 2) % 64 == 0) { NT /= 2; per = (int)((n4 + NT - 1) / NT); }
     const dim3 grid((unsigned)(B * (32 / G)));
-    static const bool stream_on = []() { const char* v = getenv("DMAD_GN_STREAM"); return !(v && v[0] == '0'); }();
+    static const bool stream_on = env_switch_on("DMAD_GN_STREAM");
     if (in16 && stream_on) {
         const int G2 = 2 * G;                                   // f16 input: twice the groups for the same whole 128-byte lines per pixel
         const int R2 = G2 * c4, nt = (R2 % 3 == 0) ? 192 : 256; // a multiple of R2 (16, 24 or 48) and of 64 (128 / 512 threads measured slower)
@@ -706,11 +707,17 @@ void launch_upsample2x_nhwc(const float* in, float* out, int B, int H, int W, in
     const long total4 = (long)B * 4 * H * W * (C / 4);
     hipLaunchKernelGGL(upsample2x_nhwc_kernel, dim3(nblk(total4, 256)), dim3(256), 0, s, in, out, H, W, C / 4, total4);
 }
+// dynamic LDS of the two attention kernels at T positions; above the default 64 KiB at T = 256
+constexpr size_t att_lds_bytes(int T) { return (size_t)2 * T * AROW * sizeof(float); }
+constexpr size_t att_h16_lds_bytes(int T) { return (size_t)T * 128 + (size_t)(T / 4) * VG; }
+// KF_UNET_ATT (kernel_setup.hip, once per device)
+int unet_att_configure() {
+    return set_max_lds({{(const void*)qkv_attention_kernel<16>, (int)att_lds_bytes(256)}, {(const void*)qkv_attention_h16_kernel<16>, (int)att_h16_lds_bytes(256)}});
+}
 int launch_qkv_attention(const float* qkv, float* out, int B, int T, int heads, hipStream_t s, h16_t* out16, int split) {
-    const size_t lds = (size_t)2 * T * AROW * sizeof(float);
+    const size_t lds = att_lds_bytes(T);
     if (T == 256) {
-        static const hipError_t once = hipFuncSetAttribute((const void*)qkv_attention_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (once != hipSuccess) return (int)once;
+        if (int r = kernels_ready(KF_UNET_ATT)) return r;
         hipLaunchKernelGGL(qkv_attention_kernel<16>, dim3((unsigned)heads, (unsigned)B), dim3(512), lds, s, qkv, out, heads, out16, split);
     } else if (T == 64) {
         hipLaunchKernelGGL(qkv_attention_kernel<4>, dim3((unsigned)heads, (unsigned)B), dim3(256), lds, s, qkv, out, heads, out16, split);
@@ -722,10 +729,9 @@ int launch_qkv_attention(const float* qkv, float* out, int B, int T, int heads, 
     return 0;
 }
 int launch_qkv_attention_h16(const h16_t* qkv, h16_t* out, int B, int T, int heads, hipStream_t s) {
-    const size_t lds = (size_t)T * 128 + (size_t)(T / 4) * VG;
+    const size_t lds = att_h16_lds_bytes(T);
     if (T == 256) {
-        static const hipError_t once = hipFuncSetAttribute((const void*)qkv_attention_h16_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (once != hipSuccess) return (int)once;
+        if (int r = kernels_ready(KF_UNET_ATT)) return r;
         hipLaunchKernelGGL(qkv_attention_h16_kernel<16>, dim3((unsigned)heads, (unsigned)B), dim3(512), lds, s, qkv, out, heads);
     } else if (T == 64) {
         hipLaunchKernelGGL(qkv_attention_h16_kernel<4>, dim3((unsigned)heads, (unsigned)B), dim3(256), lds, s, qkv, out, heads);

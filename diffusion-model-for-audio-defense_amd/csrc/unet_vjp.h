@@ -19,7 +19,6 @@ int launch_groupnorm_bwd(const float* x, const float* x2, int c1, const float* g
 // the gradient of its output; writes gqkv [B*T][3C] (dq, dk, dv in the positions of q, k, v).  P is recomputed from qkv.  T = 256, 64
 // or 16; returns -1 for any other T, a hipError_t > 0 if the kernel could not be configured.
 int launch_qkv_attention_bwd(const float* qkv, const float* go, float* gqkv, int B, int T, int heads, hipStream_t s);
-int unvjp_configure();        // per device: the dynamic-LDS attribute of the T = 256 attention backward (0 or a hipError_t)
 // the zero-dilated map of a stride-2 gradient: d [B][2Ho][2Ho][C], d[2y][2x] = g[y][x], zero elsewhere (C % 4 == 0)
 void launch_dilate2x_nhwc(const float* g, float* d, int B, int Ho, int C, hipStream_t s);
 // backward of nearest x2 upsampling: gin [B][H][H][C] = sum of the 2x2 block of g [B][2H][2H][C] (+ add, optional), C % 4 == 0

@@ -1,5 +1,6 @@
 // See unet_vjp.h.
 #include "unet_vjp.h"
+#include "kernel_setup.h"
 
 namespace dmad {
 
@@ -274,7 +275,7 @@ int launch_groupnorm_bwd(const float* x, const float* x2, int c1, const float* g
 static size_t att_bwd_lds(int T) { return ((size_t)2 * T * HD + 3 * T) * sizeof(float); }
 
 int unvjp_configure() {
-    return (int)hipFuncSetAttribute((const void*)qkv_attention_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)att_bwd_lds(256));
+    return set_max_lds({{(const void*)qkv_attention_bwd_kernel, (int)att_bwd_lds(256)}});
 }
 
 int launch_qkv_attention_bwd(const float* qkv, const float* go, float* gqkv, int B, int T, int heads, hipStream_t s) {

@@ -4,6 +4,7 @@
 // input row, bit-reproducible and independent of the batch.  Where include/dmad.h states a formula with fl() the products and sums are
 // rounded on their own (__fmul_rn / __fadd_rn, no contraction), as in elementwise.hip; the FIR sums run in float64 and round once.  DESIGN.md section 17.
 #include "wave_defense.h"
+#include "kernel_setup.h"
 
 namespace dmad {
 
@@ -258,10 +259,7 @@ template <int N>
 hipError_t iir_launch(const IirArgs& c, const float* x, const float* mask_src, float* y, float* y_raw, int B, int L, int T, int nseg, float lo,
                       float hi, int reverse, hipStream_t s) {
     const size_t lds = ((size_t)L + (size_t)kIirMaxOrder * kIirMaxSegs) * sizeof(float);
-    // more than the default 64 KiB of dynamic LDS needs the attribute; it is per device, so it is set at every launch (host-side, cheap)
-    const hipError_t e = hipFuncSetAttribute((const void*)wave_iir_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)(((size_t)kIirMaxLen + (size_t)kIirMaxOrder * kIirMaxSegs) * sizeof(float)));
-    if (e != hipSuccess) return e;
+    if (int r = kernels_ready(KF_WAVE_IIR)) return (hipError_t)r;      // more than the default 64 KiB of dynamic LDS needs the attribute
     hipLaunchKernelGGL(wave_iir_kernel<N>, dim3(B), dim3(kIirMaxSegs), lds, s, c, x, mask_src, y, y_raw, L, T, nseg, lo, hi, reverse);
     return hipSuccess;
 }
@@ -273,6 +271,14 @@ FirTaps fir_taps(const float* ker, int n) {
 }
 
 }  // namespace
+
+// KF_WAVE_IIR (kernel_setup.hip, once per device): every order's kernel may take the longest clip
+int wave_iir_configure() {
+    constexpr int lds = (int)(((size_t)kIirMaxLen + (size_t)kIirMaxOrder * kIirMaxSegs) * sizeof(float));
+    return set_max_lds({{(const void*)wave_iir_kernel<1>, lds}, {(const void*)wave_iir_kernel<2>, lds}, {(const void*)wave_iir_kernel<3>, lds},
+                        {(const void*)wave_iir_kernel<4>, lds}, {(const void*)wave_iir_kernel<5>, lds}, {(const void*)wave_iir_kernel<6>, lds},
+                        {(const void*)wave_iir_kernel<7>, lds}, {(const void*)wave_iir_kernel<8>, lds}});
+}
 
 void launch_wave_smooth(const float* x, int B, int L, int kind, int window, float* y, hipStream_t s) {
     const long total = (long)B * L;

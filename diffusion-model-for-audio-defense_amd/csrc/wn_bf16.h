@@ -37,8 +37,5 @@ void launch_wn_init_bf16(const float* x, const float* w, const float* bias, cons
 void launch_wn_layer_bf16_p(const WnLayerArgs& a, int B, bool f16, hipStream_t s, bool stamps = false);
 void launch_wn_final_bf16_p(const WnFinalArgs& a, bool f16, hipStream_t s);
 bool wn_final_p_supported(int num_res_layers);
-int wn_bf16_configure();
-int wn_layer_p_configure();
-int wn_final_p_configure();
 
 }  // namespace dmad

@@ -63,9 +63,4 @@ void launch_wn_init_bf16(const float* x, const float* w, const float* bias, cons
     else hipLaunchKernelGGL(wn_init_h16<__bf16>, dim3(grid), dim3(256), 0, s, x, w, bias, emb0, h, L, LP, chunks);
 }
 
-int wn_bf16_configure() {
-    if (int r = wn_layer_p_configure()) return r;
-    return wn_final_p_configure();
-}
-
 }  // namespace dmad

@@ -19,6 +19,7 @@
 
 #include "dmad_common.h"
 #include "wn_bf16.h"
+#include "kernel_setup.h"
 
 namespace dmad {
 
@@ -234,25 +235,17 @@ __global__ void __launch_bounds__(512, 2) wn_final_p(WnFinalArgs a, long npos, i
     }
 }
 
-static int g_final_cus = 256;
-
 bool wn_final_p_supported(int num_res_layers) { return num_res_layers >= 1; }   // nks = 8 * layers: a multiple of 4, >= 8
 
 void launch_wn_final_bf16_p(const WnFinalArgs& a, bool f16, hipStream_t s) {
     const long npos = (long)a.B * a.L;
     const int ntiles = (int)((npos + FT - 1) / FT);
-    const int grid = ntiles < g_final_cus ? ntiles : g_final_cus;
+    const int cus = device_cus(), grid = ntiles < cus ? ntiles : cus;
     if (f16) hipLaunchKernelGGL(wn_final_p<_Float16>, dim3(grid), dim3(512), kWnLdsBytes, s, a, npos, ntiles);
     else hipLaunchKernelGGL(wn_final_p<__bf16>, dim3(grid), dim3(512), kWnLdsBytes, s, a, npos, ntiles);
 }
 
-int wn_final_p_configure() {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-        g_final_cus = prop.multiProcessorCount;
-    if (hipError_t e = hipFuncSetAttribute((const void*)wn_final_p<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840)) return (int)e;
-    return (int)hipFuncSetAttribute((const void*)wn_final_p<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-}
+// KF_WN_FINAL (kernel_setup.hip, once per device)
+int wn_final_p_configure() { return set_max_lds({{(const void*)wn_final_p<__bf16>, 163840}, {(const void*)wn_final_p<_Float16>, 163840}}); }
 
 }  // namespace dmad

@@ -33,6 +33,7 @@
 // (too small) vmcnt wait of its own that would drain the prefetches.
 #include "dmad_common.h"
 #include "wn_bf16.h"
+#include "kernel_setup.h"
 
 namespace dmad {
 
@@ -494,8 +495,6 @@ __global__ void __launch_bounds__(512, 2) wn_layer_p(WnLayerArgs a, int ntiles) 
     }
 }
 
-static int g_num_cus = 256;
-
 template <typename T>
 static void launch_layer_t(const WnLayerArgs& a, int grid, int ntiles, hipStream_t s, bool stamps) {
     if (stamps && !a.last) {
@@ -508,29 +507,16 @@ static void launch_layer_t(const WnLayerArgs& a, int grid, int ntiles, hipStream
 
 void launch_wn_layer_bf16_p(const WnLayerArgs& a, int B, bool f16, hipStream_t s, bool stamps) {
     const int ntiles = B * (a.L / kTileT);
-    const int grid = ntiles < g_num_cus ? ntiles : g_num_cus;
+    const int cus = device_cus(), grid = ntiles < cus ? ntiles : cus;
     if (f16) launch_layer_t<_Float16>(a, grid, ntiles, s, stamps);
     else launch_layer_t<__bf16>(a, grid, ntiles, s, stamps);
 }
 
-template <typename T>
-static int configure_layer_t() {
-    hipError_t e = hipFuncSetAttribute((const void*)wn_layer_p<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kWnLdsBytes);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)wn_layer_p<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kWnLdsBytes);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute((const void*)wn_layer_p<T, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kWnLdsBytes);
-    return (int)e;
-}
-
+// KF_WN_LAYER (kernel_setup.hip, once per device)
 int wn_layer_p_configure() {
-    if (int r = configure_layer_t<__bf16>()) return r;
-    if (int r = configure_layer_t<_Float16>()) return r;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-        g_num_cus = prop.multiProcessorCount;
-    return 0;
+    return set_max_lds({{(const void*)wn_layer_p<__bf16, false>, kWnLdsBytes}, {(const void*)wn_layer_p<__bf16, true>, kWnLdsBytes},
+                        {(const void*)wn_layer_p<__bf16, false, true>, kWnLdsBytes}, {(const void*)wn_layer_p<_Float16, false>, kWnLdsBytes},
+                        {(const void*)wn_layer_p<_Float16, true>, kWnLdsBytes}, {(const void*)wn_layer_p<_Float16, false, true>, kWnLdsBytes}});
 }
 
 }  // namespace dmad

@@ -877,7 +877,8 @@ int dmad_profile_read_final(dmad_engine* e, float* total_ms, int32_t* launches);
  * map holding channels [ksplit, K) (the UNet's th.cat read in place; x then has ksplit channels per pixel); w: device f16
  * [groups][taps][M][K] (taps 9 = 3x3 with zero padding 1, or 1); bias: fp32 [groups * M] or NULL; res16: optional f16 residual
  * [N][groups * M]; out32 / out16: fp32 map and / or f16 twin [N][groups * M], N = B * Ho * Ho, Ho = (H - 1) / stride + 1.
- * M and K are per group.  Which of the family's kernels serves a shape is the launcher's choice (the product's). */
+ * M and K are per group.  Which of the family's kernels serves a shape is the launcher's choice (the product's).
+ * This and every other standalone op export below prepares its kernels for the current device on first use (no engine is needed before). */
 int dmad_conv_h16(const uint16_t* x, const uint16_t* x2, int32_t ksplit, const uint16_t* w, const float* bias, const uint16_t* res16,
                   int32_t B, int32_t H, int32_t M, int32_t K, int32_t taps, int32_t stride, int32_t groups, int32_t relu,
                   float* out32, uint16_t* out16, dmad_stream s);

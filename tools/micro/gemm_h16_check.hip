@@ -13,6 +13,19 @@
 
 using namespace dmad;
 
+// The two functions of csrc/kernel_setup.hip that gemm_h16.hip uses: the library's own file names every kernel family, this program has one.
+namespace dmad {
+int set_max_lds(std::initializer_list<std::pair<const void*, int>> kernels) {
+    for (const auto& k : kernels)
+        if (hipError_t e = hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, k.second)) return (int)e;
+    return 0;
+}
+int device_cus() {
+    int n = 0;
+    return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, 0) == hipSuccess && n > 0 ? n : 256;
+}
+}  // namespace dmad
+
 static uint16_t f2h(float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
 static float h2f(uint16_t u) { _Float16 h; memcpy(&h, &u, 2); return (float)h; }
 static float rnd() { return (float)rand() / RAND_MAX * 2.f - 1.f; }
