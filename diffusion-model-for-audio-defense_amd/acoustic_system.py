@@ -140,6 +140,8 @@ class AcousticSystem(torch.nn.Module):
                 return logits.view(repeats, B, -1), dec.view(repeats, B).long()
             if sampler == 1:
                 den = self.defender
+                from diffusion_models.diffwave_ddpm import fixed_length_only
+                fixed_length_only(den.model, x, 'the one-call query (dmad_query_logits)')
                 ts, c_a, c_b, c_eps, c_div, c_sig = den.purify_coefficients()
                 logits, dec = getattr(eng, pre + 'query_logits')(x, repeats, 1, ts, c_a, c_b, c_eps, c_div, c_sig, seed=den.seed, sample0=den._draws)
                 den._draws += repeats * B

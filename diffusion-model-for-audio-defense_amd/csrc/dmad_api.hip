@@ -233,6 +233,8 @@ struct dmad_engine {
     float *vjp_save = nullptr, *vjp_gH = nullptr, *vjp_G = nullptr, *vjp_gg = nullptr;
     float *vjp_wdilT = nullptr, *vjp_wgT = nullptr, *vjp_wf0T = nullptr;
     float* vjp_g2 = nullptr;               // [2][vjpB][L]: the ping-pong adjoint of dmad_vpsde_purify_vjp
+    // the longest clip written into each zero-padded fp32 map since it was last clean (clean_pad: the any-length exports)
+    int dirty_hA32 = 0, dirty_hB32 = 0, dirty_save = 0, dirty_G = 0, dirty_gH = 0;
     // common work buffers
     float *xt = nullptr, *eps = nullptr, *x0 = nullptr, *znoise = nullptr;
     // classifier
@@ -1716,19 +1718,30 @@ int ensure_embed(dmad_engine* e, int t, hipStream_t s) {
     return 0;
 }
 
+// The padding invariant of the zero-padded fp32 maps ([clips][LP][ld], a clip in rows [kPad, kPad + len)): a dilated tap reads up to
+// kPad rows past either end of a clip and must find zeros there.  Rows outside [kPad, kPad + clip_len) are never written; rows
+// [kPad + len, kPad + *dirty) hold what the longest call since the map was last clean left there, so a shorter call zeroes that band
+// first, in every clip of the map, on its own stream.  A run of calls at one length (every fixed-length export) clears nothing.
+void clean_pad(float* map, int* dirty, int len, size_t clips, size_t LP, size_t ld, hipStream_t s) {
+    if (len < *dirty) launch_zero_band(map, (long)(LP * ld), (long)((kPad + len) * ld), (long)((*dirty - len) * ld), (long)clips, s);
+    *dirty = len;
+}
+
 // exact32: evaluate on the exact-fp32 path (the only one of a DMAD_FP32 engine; DMAD_MODE_FP32 and the recheck pass of a
 // DMAD_EXACT engine); batches larger than the fp32 workspace are walked in chunks of maxB32 clips
 // save != nullptr (the VJP's forward pass; B <= maxB32, fp32 path): layer n reads its residual stream from slot n of `save`
 // ([NL][vjpB][LP][256]) and writes the next one to slot n + 1 instead of the A / B ping-pong — the same launches, the same bits
-int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipStream_t s, int path = PATH_DEFAULT, float* save = nullptr) {
+// len != 0 (the any-length exports, fp32 path only): clips of len <= clip_len samples, rows [kPad, kPad + len) of the same maps
+int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipStream_t s, int path = PATH_DEFAULT, float* save = nullptr,
+                int len = 0) {
     CHK(need_wavenet(e)); CHK(need_batch(e, B));
     if (t < 0) return fail(DMAD_ERR_INVALID, "diffusion step %d < 0", t);
     CHK(ensure_embed(e, t, s));
-    const int L = e->L, LP = e->LP, NL = e->NL;
+    const int L = len ? len : e->L, LP = e->LP, NL = e->NL;
     const bool use32 = !e->bf16 || (e->f32 && (path != PATH_DEFAULT || e->mode == DMAD_MODE_FP32));
     const bool x3 = use32 && path == PATH_X3 && e->wdil_x3;     // fp32 pipeline on split-f16 operands (three MFMAs per product)
     if (use32 && B > e->maxB32)
-        return for_passes(B, e->maxB32, [&](int64_t b0, int bb) { return wavenet_eps(e, x_t + b0 * L, t, bb, eps + b0 * L, s, x3 ? PATH_X3 : PATH_FP32); });
+        return for_passes(B, e->maxB32, [&](int64_t b0, int bb) { return wavenet_eps(e, x_t + b0 * L, t, bb, eps + b0 * L, s, x3 ? PATH_X3 : PATH_FP32, nullptr, len); });
     if (!use32) {
         launch_wn_init_bf16(x_t, e->init_w, e->init_b, e->emb_table, e->hA, B, L, LP, e->f16, s);
         for (int n = 0; n < NL; ++n) {
@@ -1757,8 +1770,10 @@ int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipS
     } else {
         const long N = (long)B * L;
         const size_t sslot = (size_t)e->vjpB * LP * kC;           // one saved stream (VJP)
+        if (save) clean_pad(save, &e->dirty_save, L, (size_t)NL * e->vjpB, LP, kC, s);
+        else { clean_pad(e->hA32, &e->dirty_hA32, L, e->maxB32, LP, kC, s); clean_pad(e->hB32, &e->dirty_hB32, L, e->maxB32, LP, kC, s); }
         launch_wn_init_f32(x_t, e->init_w, e->init_b, e->emb_table, save ? save : e->hA32, B, L, LP, s, x3, x3 && e->diag[4]);
-        const size_t slab = (size_t)e->maxB32 * L * 256;          // one gate-output slab per layer
+        const size_t slab = (size_t)e->maxB32 * e->L * 256;       // one gate-output slab per layer
         for (int n = 0; n < NL; ++n) {
             float* hin = save ? save + n * sslot : (n & 1) ? e->hB32 : e->hA32;
             float* hout = save ? save + (n + 1) * sslot : (n & 1) ? e->hA32 : e->hB32;
@@ -1801,11 +1816,13 @@ int wavenet_eps(dmad_engine* e, const float* x_t, int t, int B, float* eps, hipS
 //   W_skip^T, tap 1 = region r through sqrt(1/2) W_res^T — by reading region r with a tap stride of r regions.
 // affine (the reverse VP-SDE chain): g_x = alpha * g_eps - gamma * (d eps / d x_t)^T g_eps, in the init-conv backward's epilogue
 int wavenet_vjp_pass(dmad_engine* e, const float* x_t, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s,
-                     bool affine = false, float alpha = 1.f, float gamma = 0.f) {
-    const int L = e->L, LP = e->LP, NL = e->NL;
+                     bool affine = false, float alpha = 1.f, float gamma = 0.f, int len = 0) {
+    const int L = len ? len : e->L, LP = e->LP, NL = e->NL;
     const long N = (long)B * L;
     const size_t RS = (size_t)e->vjpB * LP * kC, sslot = RS;
-    CHK(wavenet_eps(e, x_t, t, B, eps, s, PATH_FP32, e->vjp_save));
+    CHK(wavenet_eps(e, x_t, t, B, eps, s, PATH_FP32, e->vjp_save, len));
+    clean_pad(e->vjp_G, &e->dirty_G, L, 3 * (size_t)e->vjpB, LP, kC, s);
+    clean_pad(e->vjp_gH, &e->dirty_gH, L, e->vjpB, LP, 512, s);
     // final block: g_y = [y > 0] wz g_eps (y = relu(f0), kept in H32), g_s = sqrt(1/NL) W_f0^T g_y (scale folded into the image)
     launch_vjp_final(e->H32, e->wz, g_eps, e->vjp_gg, N, s);
     GemmF32Args f = plain_gemm(e->vjp_wf0T, e->vjp_gg, nullptr, nullptr, nullptr, 256, 256, N, 256, 256, 0);
@@ -1837,15 +1854,15 @@ int wavenet_vjp_pass(dmad_engine* e, const float* x_t, int t, int B, const float
     return 0;
 }
 
-int wavenet_vjp(dmad_engine* e, const float* x_t, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s) {
+int wavenet_vjp(dmad_engine* e, const float* x_t, int t, int B, const float* g_eps, float* g_x, float* eps, hipStream_t s, int len = 0) {
     if (!e->f32) return fail(DMAD_ERR_STATE, "the WaveNet VJP runs on the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights");
     CHK(need_wavenet(e));
     if (!e->vjpB) return fail(DMAD_ERR_STATE, "no VJP workspace: call dmad_reserve_vjp first");
     CHK(need_batch(e, B));
     if (t < 0) return fail(DMAD_ERR_INVALID, "diffusion step %d < 0", t);
-    const size_t L = e->L;
+    const size_t L = len ? len : e->L;
     return for_passes(B, e->vjpB, [&](int64_t b0, int bb) {
-        return wavenet_vjp_pass(e, x_t + b0 * L, t, bb, g_eps + b0 * L, g_x + b0 * L, (eps ? eps : e->eps) + b0 * L, s);
+        return wavenet_vjp_pass(e, x_t + b0 * L, t, bb, g_eps + b0 * L, g_x + b0 * L, (eps ? eps : e->eps) + b0 * L, s, false, 1.f, 0.f, len);
     });
 }
 
@@ -2744,19 +2761,115 @@ int dmad_one_shot(dmad_engine* e, const float* x_t, int32_t t, float c_a, float 
     return 0;
 }
 
-int dmad_ddpm_step(dmad_engine* e, float* x, int32_t t, float c_eps, float c_div, float c_sig, const float* z, uint64_t seed,
-                   uint64_t sample0, int32_t B, dmad_stream s) {
-    if (!e || !x) return fail(DMAD_ERR_INVALID, "null argument");
-    CHK(wavenet_eps(e, x, t, B, e->eps, (hipStream_t)s, wave_path(e)));
+}  // extern "C"
+
+namespace {
+// the preconditions of the any-length exports (dmad_*_len), which run the exact-fp32 path whatever the engine's mode; checked ahead of
+// the array pointers, so that an empty array (a null pointer from most hosts) is reported as the len = 0 it is
+int need_len(const dmad_engine* e, const char* who, int len) {
+    if (!e->f32) return fail(DMAD_ERR_STATE, "%s runs on the exact-fp32 path: a DMAD_BF16 engine holds no fp32 weights", who);
+    if (len < 1 || len > e->L) return fail(DMAD_ERR_SHAPE, "%s: len %d outside [1, clip_len=%d]", who, len, e->L);
+    return 0;
+}
+
+// dmad_ddpm_step / dmad_diffuse (len == 0: clip_len, on `path`) and their any-length forms; len == clip_len makes the fixed-length launches
+int ddpm_step(dmad_engine* e, float* x, int t, float c_eps, float c_div, float c_sig, const float* z, uint64_t seed, uint64_t sample0, int B,
+              hipStream_t s, int path, int len) {
+    CHK(wavenet_eps(e, x, t, B, e->eps, s, path, nullptr, len));
+    if (len && len != e->L) {
+        launch_sched_len(2, x, e->eps, z, c_eps, c_div, c_sig, c_sig != 0.f, seed, sample0, 1u + (uint32_t)t, x, B, len, s);
+        LASTCHK();
+        return 0;
+    }
     const float* zz = nullptr;
     if (c_sig != 0.f) {
         zz = z;
         if (!zz) {
-            launch_philox_normal(seed, sample0, 1u + (uint32_t)t, e->znoise, B, e->L, (hipStream_t)s);
+            launch_philox_normal(seed, sample0, 1u + (uint32_t)t, e->znoise, B, e->L, s);
             zz = e->znoise;
         }
     }
-    launch_lincomb(2, x, e->eps, zz, c_eps, c_div, c_sig, x, (long)B * e->L, (hipStream_t)s);
+    launch_lincomb(2, x, e->eps, zz, c_eps, c_div, c_sig, x, (long)B * e->L, s);
+    LASTCHK();
+    return 0;
+}
+
+int diffuse(dmad_engine* e, const float* x0, float c_a, float c_b, const float* z, uint64_t seed, uint64_t sample0, int B, float* x_t,
+            hipStream_t s, int len) {
+    CHK(need_batch(e, B));
+    if (len && len != e->L) {
+        launch_sched_len(1, x0, nullptr, z, c_a, c_b, 0.f, true, seed, sample0, 0xD1FFu, x_t, B, len, s);
+        LASTCHK();
+        return 0;
+    }
+    const float* zz = z;
+    if (!zz) {
+        launch_philox_normal(seed, sample0, 0xD1FFu, e->znoise, B, e->L, s);
+        zz = e->znoise;
+    }
+    launch_lincomb(1, x0, nullptr, zz, c_a, c_b, 0.f, x_t, (long)B * e->L, s);
+    LASTCHK();
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int dmad_ddpm_step(dmad_engine* e, float* x, int32_t t, float c_eps, float c_div, float c_sig, const float* z, uint64_t seed,
+                   uint64_t sample0, int32_t B, dmad_stream s) {
+    if (!e || !x) return fail(DMAD_ERR_INVALID, "null argument");
+    return ddpm_step(e, x, t, c_eps, c_div, c_sig, z, seed, sample0, B, (hipStream_t)s, wave_path(e), 0);
+}
+
+int dmad_ddpm_step_len(dmad_engine* e, float* x, int32_t t, float c_eps, float c_div, float c_sig, const float* z, uint64_t seed,
+                       uint64_t sample0, int32_t B, int32_t len, dmad_stream s) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(need_len(e, "dmad_ddpm_step_len", len));
+    if (!x) return fail(DMAD_ERR_INVALID, "null argument");
+    return ddpm_step(e, x, t, c_eps, c_div, c_sig, z, seed, sample0, B, (hipStream_t)s, PATH_FP32, len);
+}
+
+int dmad_diffuse_len(dmad_engine* e, const float* x0, float c_a, float c_b, const float* z, uint64_t seed, uint64_t sample0, int32_t B,
+                     int32_t len, float* x_t, dmad_stream s) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(need_len(e, "dmad_diffuse_len", len));
+    if (!x0 || !x_t) return fail(DMAD_ERR_INVALID, "null argument");
+    return diffuse(e, x0, c_a, c_b, z, seed, sample0, B, x_t, (hipStream_t)s, len);
+}
+
+int dmad_ddpm_purify_len(dmad_engine* e, const float* x0, int32_t t_star, float c_a, float c_b, const float* c_eps, const float* c_div,
+                         const float* c_sig, uint64_t seed, uint64_t sample0, int32_t B, int32_t len, float* out, dmad_stream s) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(need_len(e, "dmad_ddpm_purify_len", len));
+    if (!x0 || !out || !c_eps || !c_div || !c_sig) return fail(DMAD_ERR_INVALID, "null argument");
+    if (t_star < 1) return fail(DMAD_ERR_INVALID, "t_star %d < 1", t_star);
+    CHK(dmad_diffuse_len(e, x0, c_a, c_b, nullptr, seed, sample0, B, len, out, s));
+    for (int t = t_star - 1; t >= 0; --t)
+        CHK(dmad_ddpm_step_len(e, out, t, c_eps[t], c_div[t], t > 0 ? c_sig[t] : 0.f, nullptr, seed, sample0, B, len, s));
+    return 0;
+}
+
+int dmad_wavenet_eps_len(dmad_engine* e, const float* x_t, int32_t t, int32_t B, int32_t len, float* eps, dmad_stream s) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(need_len(e, "dmad_wavenet_eps_len", len));
+    if (!x_t || !eps) return fail(DMAD_ERR_INVALID, "null argument");
+    return wavenet_eps(e, x_t, t, B, eps, (hipStream_t)s, PATH_FP32, nullptr, len);
+}
+
+int dmad_wavenet_eps_vjp_len(dmad_engine* e, const float* x_t, int32_t t, int32_t B, int32_t len, const float* g_eps, float* g_x, float* eps,
+                             dmad_stream s) {
+    if (!e) return fail(DMAD_ERR_INVALID, "null argument");
+    CHK(need_len(e, "dmad_wavenet_eps_vjp_len", len));
+    if (!x_t || !g_eps || !g_x) return fail(DMAD_ERR_INVALID, "null argument");
+    return wavenet_vjp(e, x_t, t, B, g_eps, g_x, eps, (hipStream_t)s, len);
+}
+
+int dmad_philox_normal_len(dmad_engine* e, uint64_t seed, uint64_t sample0, uint32_t stream, int32_t B, int32_t len, float* z, dmad_stream s) {
+    if (!e) return fail(DMAD_ERR_INVALID, "bad argument");
+    CHK(need_len(e, "dmad_philox_normal_len", len));
+    if (!z || B < 1) return fail(DMAD_ERR_INVALID, "bad argument");
+    if (len == e->L) launch_philox_normal(seed, sample0, stream, z, B, e->L, (hipStream_t)s);
+    else launch_philox_normal_len(seed, sample0, stream, z, B, len, (hipStream_t)s);
     LASTCHK();
     return 0;
 }
@@ -2764,15 +2877,7 @@ int dmad_ddpm_step(dmad_engine* e, float* x, int32_t t, float c_eps, float c_div
 int dmad_diffuse(dmad_engine* e, const float* x0, float c_a, float c_b, const float* z, uint64_t seed, uint64_t sample0,
                  int32_t B, float* x_t, dmad_stream s) {
     if (!e || !x0 || !x_t) return fail(DMAD_ERR_INVALID, "null argument");
-    CHK(need_batch(e, B));
-    const float* zz = z;
-    if (!zz) {
-        launch_philox_normal(seed, sample0, 0xD1FFu, e->znoise, B, e->L, (hipStream_t)s);
-        zz = e->znoise;
-    }
-    launch_lincomb(1, x0, nullptr, zz, c_a, c_b, 0.f, x_t, (long)B * e->L, (hipStream_t)s);
-    LASTCHK();
-    return 0;
+    return diffuse(e, x0, c_a, c_b, z, seed, sample0, B, x_t, (hipStream_t)s, 0);
 }
 
 int dmad_unet_eps(dmad_engine* e, const float* x_t, int32_t t, int32_t B, float* eps, dmad_stream s) {
@@ -3298,11 +3403,13 @@ int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch) {
         [&](int vB) -> int {
             const size_t LP = e->LP, NL = e->NL;
             // zeroed: the padding rows of the saved streams and of the gradient maps are read as the convs' zero padding and never written
+            // (rows a longer clip wrote are cleared before a shorter one reads them: clean_pad)
             CHK(e->alloc(&e->vjp_save, NL * vB * LP * kC, true));
             CHK(e->alloc(&e->vjp_gH, (size_t)vB * LP * 512, true));
             CHK(e->alloc(&e->vjp_G, 3 * (size_t)vB * LP * kC, true));
             CHK(e->alloc(&e->vjp_gg, (size_t)vB * e->L * kC));
             CHK(e->alloc(&e->vjp_g2, 2 * (size_t)vB * e->L));
+            e->dirty_save = e->dirty_G = e->dirty_gH = 0;
             return 0;
         });
 }

@@ -23,6 +23,14 @@ void launch_lincomb(int op, const float* x, const float* y, const float* z, floa
 // draw keyed (seed, sample0 + row, stream) in registers; y may alias x; traj (optional) gets a copy of y
 void launch_vpsde_step(const float* x, const float* eps, const float* z, float c0, float c1, float h, float c2, uint64_t seed,
                        uint64_t sample0, uint32_t stream, float* y, float* traj, int B, int L, hipStream_t s);
+// Any-length forms (dmad_*_len): rows of `len` floats at a pitch of `len` (any len >= 1, no alignment assumed).  philox_normal_len:
+// row b = the first len values of launch_philox_normal's row of the same key.  sched_len: op 1 out = c0 x + c1 z (lincomb op 1),
+// op 2 out = (x - c0 eps) / c1 + (draw ? c2 z : 0) (lincomb op 2); z == nullptr: the draw stays in registers; out may alias x.
+void launch_philox_normal_len(uint64_t seed, uint64_t sample0, uint32_t stream, float* z, int B, int len, hipStream_t s);
+void launch_sched_len(int op, const float* x, const float* eps, const float* z, float c0, float c1, float c2, bool draw, uint64_t seed,
+                      uint64_t sample0, uint32_t stream, float* out, int B, int len, hipStream_t s);
+// zero `width` floats at offset `off` of each of `rows` rows of `pitch` floats (all multiples of 4, buf 16-byte aligned)
+void launch_zero_band(float* buf, long pitch, long off, long width, long rows, hipStream_t s);
 // NES probes and estimate (dmad_nes_probes / dmad_nes_grad): direction j of clip b is the Philox row keyed (seed, draw0 + b * H + j, stream),
 // regenerated in registers by both kernels.  probes: query rows [row0, row0 + rows) of the clip-major layout (2H + with_origin per clip);
 // grad[b] = (accumulate ? grad[b] : 0) + scale * sum_j (w[b][j] - w[b][H + j]) u_{b,j}, w device fp32 [B][2H]

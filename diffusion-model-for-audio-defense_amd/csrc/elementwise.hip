@@ -204,6 +204,87 @@ __global__ void vpsde_step_kernel(const float* x, const float* __restrict__ eps,
     if (traj) *(float4*)(traj + o) = out;
 }
 
+// ----------------------------------------------------------------------------------------------
+// Any-length forms of the noise and scheduler kernels (the dmad_*_len exports): rows of `len` floats at a pitch of `len`, any
+// len >= 1, so a row starts on a 16-byte boundary only where (row * len) % 4 == 0 and the base pointer allows it.  blockIdx.y walks
+// the rows, one thread per Philox counter block (4 samples: block l / 4, the words of philox_normal_kernel) of its row.  A group is
+// moved as one float4 where its address really is 16-byte aligned — a property of the row, so every wave of a row takes the same
+// branch — and as scalars otherwise; the last group of a row holds len % 4 values (the leading words of its draw) and is the only
+// partial one.  out may alias x (a thread reads its elements before it writes them).
+// ----------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+__device__ __forceinline__ void load_group(const float* p, bool vec, int n, float v[4]) {
+    if (vec) {
+        const float4 t = *(const float4*)p;
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = j < n ? p[j] : 0.f;
+    }
+}
+__device__ __forceinline__ void store_group(float* p, bool vec, int n, const float v[4]) {
+    if (vec) {
+        *(float4*)p = float4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < n) p[j] = v[j];
+    }
+}
+
+__global__ void philox_normal_len_kernel(uint64_t seed, uint64_t sample0, uint32_t stream, float* __restrict__ z, int B, int len) {
+    const int blk = blockIdx.x * blockDim.x + threadIdx.x;
+    if ((long)blk * 4 >= len) return;
+    const int n = len - blk * 4 < 4 ? len - blk * 4 : 4;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        float* p = z + (long)b * len + blk * 4;
+        float v[4];
+        philox_normal4(seed, sample0 + b, stream, blk, v);
+        store_group(p, n == 4 && aligned16(p), n, v);
+    }
+}
+
+// OP 1, the diffusion:   out = c0 * x + c1 * z                         (lincomb_kernel's op 1, the same roundings)
+// OP 2, a reverse step:  out = (x - c0 * eps) / c1 [+ c2 * z if draw]  (lincomb_kernel's op 2)
+// z == nullptr: the draw stays in registers, keyed (seed, sample0 + row, stream)
+template <int OP>
+__global__ void sched_len_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ z, float c0, float c1, float c2,
+                                 int draw, uint64_t seed, uint64_t sample0, uint32_t stream, float* out, int B, int len) {
+    const int blk = blockIdx.x * blockDim.x + threadIdx.x;
+    if ((long)blk * 4 >= len) return;
+    const int n = len - blk * 4 < 4 ? len - blk * 4 : 4;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const long o = (long)b * len + blk * 4;
+        const bool vec = n == 4 && aligned16(x + o) && aligned16(out + o) && (OP == 1 || aligned16(eps + o)) && (!z || !draw || aligned16(z + o));
+        float xa[4], ea[4] = {0.f, 0.f, 0.f, 0.f}, za[4] = {0.f, 0.f, 0.f, 0.f}, r[4];
+        load_group(x + o, vec, n, xa);
+        if (OP == 2) load_group(eps + o, vec, n, ea);
+        if (draw) {
+            if (z) load_group(z + o, vec, n, za);
+            else philox_normal4(seed, sample0 + b, stream, blk, za);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (OP == 1) {
+                r[j] = __fadd_rn(__fmul_rn(c0, xa[j]), __fmul_rn(c1, za[j]));
+            } else {
+                r[j] = __fdiv_rn(__fsub_rn(xa[j], __fmul_rn(c0, ea[j])), c1);
+                if (draw) r[j] = __fadd_rn(r[j], __fmul_rn(c2, za[j]));
+            }
+        }
+        store_group(out + o, vec, n, r);
+    }
+}
+
+// zero `width4` float4 at offset `off4` of each of `rows` rows of `pitch4` float4: the band [kPad + len, kPad + dirty) of every clip of
+// a zero-padded [..][LP][256 or 512] map (the padding invariant of the any-length exact-fp32 WaveNet path, dmad_api.hip)
+__global__ void zero_band_kernel(float4* __restrict__ buf, long pitch4, long off4, long width4, long total4) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total4) return;
+    const long row = i / width4, c = i - row * width4;
+    buf[row * pitch4 + off4 + c] = float4{0.f, 0.f, 0.f, 0.f};
+}
+
 // NES probes (dmad_nes_probes; robustness_eval/_NES.py:19-25), one thread per 4 samples of a query row.  Global row g = row0 + r is slot
 // g % per_clip of clip g / per_clip (per_clip = 2H + with_origin): the optional slot 0 is x[b] itself, then H rows x[b] + sigma * u_j and
 // H rows x[b] - sigma * u_j, with u_j the Philox row keyed (seed, draw0 + b * H + j, stream) — the words of philox_normal_kernel.  The
@@ -655,6 +736,19 @@ void launch_vpsde_step(const float* x, const float* eps, const float* z, float c
                        uint64_t sample0, uint32_t stream, float* y, float* traj, int B, int L, hipStream_t s) {
     hipLaunchKernelGGL(vpsde_step_kernel, dim3(nblk((long)B * (L / 4), 256)), dim3(256), 0, s, x, eps, z, c0, c1, h, c2, seed, sample0, stream,
                        y, traj, B, L);
+}
+static inline dim3 len_grid(int B, int len) { return dim3(nblk((len + 3) / 4, 256), (unsigned)(B < 65535 ? B : 65535)); }
+void launch_philox_normal_len(uint64_t seed, uint64_t sample0, uint32_t stream, float* z, int B, int len, hipStream_t s) {
+    hipLaunchKernelGGL(philox_normal_len_kernel, len_grid(B, len), dim3(256), 0, s, seed, sample0, stream, z, B, len);
+}
+void launch_sched_len(int op, const float* x, const float* eps, const float* z, float c0, float c1, float c2, bool draw, uint64_t seed,
+                      uint64_t sample0, uint32_t stream, float* out, int B, int len, hipStream_t s) {
+    if (op == 1) hipLaunchKernelGGL(sched_len_kernel<1>, len_grid(B, len), dim3(256), 0, s, x, eps, z, c0, c1, c2, 1, seed, sample0, stream, out, B, len);
+    else hipLaunchKernelGGL(sched_len_kernel<2>, len_grid(B, len), dim3(256), 0, s, x, eps, z, c0, c1, c2, draw ? 1 : 0, seed, sample0, stream, out, B, len);
+}
+void launch_zero_band(float* buf, long pitch, long off, long width, long rows, hipStream_t s) {
+    const long total4 = rows * (width / 4);
+    if (total4 > 0) hipLaunchKernelGGL(zero_band_kernel, dim3(nblk(total4, 256)), dim3(256), 0, s, (float4*)buf, pitch / 4, off / 4, width / 4, total4);
 }
 void launch_nes_probes(const float* x, float sigma, int H, int with_origin, uint64_t seed, uint64_t draw0, uint32_t stream, long row0,
                        int rows, float* out, int L, hipStream_t s) {

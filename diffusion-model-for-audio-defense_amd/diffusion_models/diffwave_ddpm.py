@@ -16,6 +16,11 @@ purifier (the white-box attack drivers: `x.requires_grad` with gradients enabled
 names: 'torch', the torch restatement of dmad_hip/autograd.py, or 'hip', the engine's exact-fp32 forward with its
 native vector-Jacobian product (dmad_wavenet_eps_vjp); every other call is the HIP engine's.
 
+Clip length: every call runs at the engine's clip_len.  A model built with `any_length=True` (create_diffwave_model, WaveNetHIP) also
+takes clips of any length <= clip_len on `forward`, `_diffusion`, `_reverse`, `compute_eps_t`, `compute_coefficients` and
+`model((x, t))`: they run on the engine's any-length exact-fp32 exports (dmad_*_len; FP32 / EXACT engines), with the noise the first
+len values of the clip_len draws.  The other surfaces raise NotImplementedError for such a clip.
+
 Noise: the reference draws every Gaussian on the CPU default generator and copies it over
 (ref l.66,100).  `noise_source='torch_cpu'` reproduces exactly that stream (parity);
 `noise_source='device'` (default) draws counter-based Philox noise on the GPU."""
@@ -37,9 +42,12 @@ class WaveNetHIP(torch.nn.Module):
 
     GRAD_BACKENDS = ('auto', 'torch', 'hip')
 
-    def __init__(self, engine: "_eng.Engine", state_dict=None, grad_backend: str = 'auto'):
+    def __init__(self, engine: "_eng.Engine", state_dict=None, grad_backend: str = 'auto', any_length: bool = False):
         super().__init__()
         self.engine = engine
+        # any_length: clips whose last dimension differs from engine.L (and is at most engine.L) run on the engine's any-length
+        # exact-fp32 exports (wavenet_eps_len and its VJP); clips of exactly engine.L keep the fixed-length calls
+        self.any_length = bool(any_length)
         # the torch differentiation branch (dmad_hip/autograd.py) evaluates the same folded weights with torch ops
         self._folded = None
         if state_dict is not None:
@@ -66,15 +74,29 @@ class WaveNetHIP(torch.nn.Module):
         t = float(steps[0])
         if not bool((steps == t).all()) or t != int(t):
             raise NotImplementedError('per-row / fractional diffusion steps are not supported by the HIP engine')
+        by_len = self.any_length and audio.shape[-1] != self.engine.L
         if _ag.needs_grad(audio):
             if self._grad_backend == 'hip':
-                return _ag.wavenet_eps_hip(self.engine, audio, int(t))
+                return (_ag.wavenet_eps_len_hip if by_len else _ag.wavenet_eps_hip)(self.engine, audio, int(t))
             if self._folded is None:
                 raise NotImplementedError("this WaveNetHIP has no gradient branch: pass grad_backend='hip' for the engine's native VJP "
                                           '(FP32 / EXACT engines), or build the model with create_diffwave_model(...) or '
                                           'WaveNetHIP(engine, state_dict=...) to get the torch restatement')
             return _ag.wavenet_eps(self._folded, audio, int(t))
-        return self.engine.wavenet_eps(audio, int(t)).unsqueeze(1)
+        return (self.engine.wavenet_eps_len if by_len else self.engine.wavenet_eps)(audio, int(t)).unsqueeze(1)
+
+
+ANY_LENGTH_SURFACES = ('DiffWave.forward, _diffusion, _reverse, compute_eps_t, compute_coefficients and model((x, t)) of a model built '
+                       'with any_length=True')
+
+
+def fixed_length_only(model, x, what: str) -> None:
+    """The surfaces that run at the engine's clip_len only (`what`), on a WaveNetHIP with any_length=True: a clip of another length is
+    refused here, before any library call, with the list of what does accept it."""
+    eng = model.engine
+    if getattr(model, 'any_length', False) and x.shape[-1] != eng.L:
+        raise NotImplementedError('%s runs at the engine\'s clip_len (%d samples) only, not at %d: clips of any length <= clip_len are '
+                                  'accepted by %s' % (what, eng.L, x.shape[-1], ANY_LENGTH_SURFACES))
 
 
 class DiffWave(torch.nn.Module):
@@ -96,6 +118,10 @@ class DiffWave(torch.nn.Module):
     @property
     def engine(self) -> "_eng.Engine":
         return self.model.engine
+
+    def _by_len(self, x) -> bool:
+        """x goes to the engine's any-length exports: the model was built with any_length=True and x is not clip_len long"""
+        return getattr(self.model, 'any_length', False) and x.shape[-1] != self.engine.L
 
     def _tables(self):
         hp = self.diffusion_hyperparams
@@ -135,7 +161,10 @@ class DiffWave(torch.nn.Module):
 
         def draw(stream):
             z = self._noise(x_0.shape, dev)
-            return z if z is not None else self.engine.philox_normal(self.seed, base, stream, B).unsqueeze(1)
+            if z is not None:
+                return z
+            length = x_0.shape[-1] if self._by_len(x_0) else None       # the first `length` values of the clip_len rows
+            return self.engine.philox_normal(self.seed, base, stream, B, length=length).unsqueeze(1)
         ts = self.reverse_timestep
         x = torch.sqrt(Alpha_bar[ts - 1]).to(dev) * x_0 + torch.sqrt(1 - Alpha_bar[ts - 1]).to(dev) * draw(0xD1FF)
         for t in range(ts - 1, -1, -1):
@@ -154,7 +183,8 @@ class DiffWave(torch.nn.Module):
         if self.noise_source == 'device':     # the whole chain in one library call (dmad_ddpm_purify)
             assert waveforms.ndim == 3
             ts, c_a, c_b, c_eps, c_div, c_sig = self.purify_coefficients()
-            out = self.engine.ddpm_purify(waveforms, ts, c_a, c_b, c_eps, c_div, c_sig, seed=self.seed, sample0=self._draws)
+            purify = self.engine.ddpm_purify_len if self._by_len(waveforms) else self.engine.ddpm_purify
+            out = purify(waveforms, ts, c_a, c_b, c_eps, c_div, c_sig, seed=self.seed, sample0=self._draws)
             self._draws += waveforms.shape[0]
             return out.unsqueeze(1)
         base = self._draws                    # device noise: row i of this call is sample base + i in BOTH phases
@@ -172,7 +202,7 @@ class DiffWave(torch.nn.Module):
         c_a = float(torch.sqrt(Alpha_bar[t]))
         c_b = float(torch.sqrt(1 - Alpha_bar[t]))
         z = self._noise(x_0.shape, x_0.device)
-        out = self.engine.diffuse(x_0, c_a, c_b, z, seed=self.seed, sample0=self._draws)
+        out = (self.engine.diffuse_len if self._by_len(x_0) else self.engine.diffuse)(x_0, c_a, c_b, z, seed=self.seed, sample0=self._draws)
         self._draws += x_0.shape[0]
         return out.unsqueeze(1)
 
@@ -183,12 +213,13 @@ class DiffWave(torch.nn.Module):
         assert x_t.ndim == 3
         x = x_t.detach()[:, 0].contiguous().float().clone()
         base = self._draws
+        step = self.engine.ddpm_step_len if self._by_len(x_t) else self.engine.ddpm_step
         for t in range(self.reverse_timestep - 1, -1, -1):
             c_eps = float((1 - Alpha[t]) / torch.sqrt(1 - Alpha_bar[t]))
             c_div = float(torch.sqrt(Alpha[t]))
             c_sig = float(Sigma[t]) if t > 0 else 0.0
             z = self._noise(x_t.shape, x_t.device) if t > 0 else None
-            self.engine.ddpm_step(x, t, c_eps, c_div, c_sig, z, seed=self.seed, sample0=base)
+            step(x, t, c_eps, c_div, c_sig, z, seed=self.seed, sample0=base)
         self._draws += x.shape[0]
         return x.unsqueeze(1)
 
@@ -211,6 +242,7 @@ class DiffWave(torch.nn.Module):
 
     def one_shot_denoise(self, x_t):
         x_t = self._to_tensor(x_t)
+        fixed_length_only(self.model, x_t, 'DiffWave.one_shot_denoise')
         t = self.reverse_timestep - 1
         Alpha_bar = self.diffusion_hyperparams["Alpha_bar"]
         c_a = float((1 / Alpha_bar).sqrt()[t])
@@ -223,6 +255,7 @@ class DiffWave(torch.nn.Module):
     @torch.no_grad()
     def two_shot_denoise(self, x_t):
         x_t = self._to_tensor(x_t)
+        fixed_length_only(self.model, x_t, 'DiffWave.two_shot_denoise')
         t = self.reverse_timestep - 1
         hp = self.diffusion_hyperparams
         Alpha, Alpha_bar, Beta = hp["Alpha"], hp["Alpha_bar"], hp["Beta"]
@@ -270,6 +303,7 @@ class DiffWave(torch.nn.Module):
     def fast_reverse(self, x_t):
         """K = 3 strided sampler (ref l.106-141); note the reference uses Beta_tilde (not its sqrt) as sigma."""
         x_t = self._to_tensor(x_t)
+        fixed_length_only(self.model, x_t, 'DiffWave.fast_reverse')
         Alpha_bar = self.diffusion_hyperparams["Alpha_bar"]
         K = 3
         S = torch.round(torch.linspace(1, self.reverse_timestep, K)).int() - 1
@@ -314,6 +348,7 @@ class ReffWave(torch.nn.Module):
     @torch.no_grad()
     def forward(self, waveforms: Union[torch.Tensor, np.ndarray]):
         output = DiffWave._to_tensor(waveforms)
+        fixed_length_only(self.model, output, 'ReffWave.forward')
         for _ in range(self.num_re):
             output = self.diffusion(output)
             output = self.one_shot_denoise(output)
@@ -322,6 +357,7 @@ class ReffWave(torch.nn.Module):
     @torch.no_grad()
     def diffusion(self, x_0) -> torch.Tensor:
         x_0 = DiffWave._to_tensor(x_0)
+        fixed_length_only(self.model, x_0, 'ReffWave.diffusion')
         hp = self.diffusion_hyperparams
         T, Alpha, Alpha_bar, Sigma = hp["T"], hp["Alpha"], hp["Alpha_bar"], hp["Sigma"]
         assert len(Alpha) == T
@@ -338,6 +374,7 @@ class ReffWave(torch.nn.Module):
     @torch.no_grad()
     def one_shot_denoise(self, x_t):
         x_t = DiffWave._to_tensor(x_t)
+        fixed_length_only(self.model, x_t, 'ReffWave.one_shot_denoise')
         t = self.reverse_timestep - 1
         Alpha_bar = self.diffusion_hyperparams["Alpha_bar"]
         return self.model.engine.one_shot(x_t, t, float((1 / Alpha_bar).sqrt()[t]), float((1 / Alpha_bar - 1).sqrt()[t])).unsqueeze(1)
@@ -347,11 +384,12 @@ class ReffWave(torch.nn.Module):
 
 
 def create_diffwave_model(model_path, config_path, reverse_timestep=25, state_dict=None, noise_source='device',
-                          precision=None, max_batch=None, engine=None, grad_backend='auto'):
+                          precision=None, max_batch=None, engine=None, grad_backend='auto', any_length=False):
     """Reference signature (ref l.395-411) plus optional keyword-only extras.  Reads the JSON keys
     `wavenet_config` and `diffusion_config`, loads checkpoint['model_state_dict'] (weight_g/weight_v
     layout), folds and uploads the weights.  `state_dict` may be passed instead of
-    a checkpoint path (synthetic weights).  `grad_backend`: WaveNetHIP.grad_backend of the model."""
+    a checkpoint path (synthetic weights).  `grad_backend`: WaveNetHIP.grad_backend of the model.  `any_length`: clips shorter
+    than the engine's clip_len run at their own length on the exact-fp32 path (WaveNetHIP.any_length; FP32 / EXACT engines)."""
     with open(config_path) as f:
         cfg = json.loads(f.read())
     wavenet_config = cfg["wavenet_config"]
@@ -363,5 +401,5 @@ def create_diffwave_model(model_path, config_path, reverse_timestep=25, state_di
     if engine is None and eng.has_wavenet and eng.wavenet_owner != _eng.state_fingerprint(state_dict):
         eng = _eng.get_engine(wavenet_config, precision=precision, max_batch=max_batch, fresh=True)   # a second, different DiffWave
     eng.bind('wavenet', state_dict, eng.load_wavenet)
-    return DiffWave(model=WaveNetHIP(eng, state_dict=state_dict, grad_backend=grad_backend), diffusion_hyperparams=diffusion_hyperparams,
+    return DiffWave(model=WaveNetHIP(eng, state_dict=state_dict, grad_backend=grad_backend, any_length=any_length), diffusion_hyperparams=diffusion_hyperparams,
                     reverse_timestep=reverse_timestep, noise_source=noise_source)

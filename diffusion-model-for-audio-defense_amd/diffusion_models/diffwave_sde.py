@@ -34,7 +34,7 @@ from dmad_hip import autograd as _ag
 from dmad_hip import engine as _eng
 from dmad_hip._lib import DmadError
 from ._rev_vpsde import ChainPurifier, RevVPSDEBase, VPSDESchedule, _extract_into_tensor, euler_schedule  # noqa: F401  (reference export)
-from .diffwave_ddpm import DiffWave, create_diffwave_model
+from .diffwave_ddpm import DiffWave, create_diffwave_model, fixed_length_only
 
 VPSDE_STREAM_DIFFUSE = 0x5DE00000          # Philox stream of the diffusion draw (include/dmad.h dmad_vpsde_purify)
 VPSDE_STREAM_STEP0 = 0x5DE00001            # ... of Euler step n: VPSDE_STREAM_STEP0 + n
@@ -110,8 +110,9 @@ class RevVPSDE(RevVPSDEBase):
 
 class RevDiffWave(ChainPurifier, torch.nn.Module):
     """The reference's RevDiffWave (explicitly adapted for DiffWave).  Reads args.ddpm_path, ddpm_config, t, score_type, sample_step,
-    rand_t, t_delta and use_bm.  Keywords beyond the reference's: state_dict / engine / precision / max_batch (passed to
-    create_diffwave_model; synthetic weights), score_grad ('none' | 'hip' | 'torch', see the module docstring), seed (Philox key)."""
+    rand_t, t_delta and use_bm.  Keywords beyond the reference's: state_dict / engine / precision / max_batch / grad_backend / any_length
+    (passed to create_diffwave_model; synthetic weights; any_length serves `.model`, the DDPM DiffWave: the VP-SDE chain of forward() runs
+    at the engine's clip_len only), score_grad ('none' | 'hip' | 'torch', see the module docstring), seed (Philox key)."""
     SCORE_GRADS = SCORE_GRADS
 
     def __init__(self, args, device=None, score_grad='none', seed=0, **kw):
@@ -121,7 +122,7 @@ class RevDiffWave(ChainPurifier, torch.nn.Module):
             device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
         self.device = device
         audio_shape = (1, 16000)
-        extra = {key: kw.pop(key) for key in ('state_dict', 'engine', 'precision', 'max_batch') if key in kw}
+        extra = {key: kw.pop(key) for key in ('state_dict', 'engine', 'precision', 'max_batch', 'grad_backend', 'any_length') if key in kw}
         if kw:
             raise TypeError('unexpected keyword arguments %s' % sorted(kw))
         model = create_diffwave_model(model_path=args.ddpm_path, config_path=args.ddpm_config, reverse_timestep=args.t, **extra)
@@ -175,6 +176,7 @@ class RevDiffWave(ChainPurifier, torch.nn.Module):
         input, the rounds concatenated on dim 0."""
         assert isinstance(audio, torch.Tensor)
         assert audio.ndim == 3, audio.ndim
+        fixed_length_only(self.model.model, audio, 'the reverse VP-SDE chain (RevDiffWave.forward)')
         x0 = audio.to(self.device)
         if self.rev_vpsde.score_type != 'guided_diffusion':     # the reference raises when sdeint first evaluates the drift
             raise NotImplementedError(f'Unknown score type in RevVPSDE: {self.rev_vpsde.score_type}!')

@@ -101,6 +101,14 @@ _SIGNATURES = {
     'dmad_wavenet_eps_path': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_reserve_vjp': (C.c_int, [_P, C.c_int32]),
     'dmad_wavenet_eps_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    # the any-length forms of the exact-fp32 DiffWave path: their twins' arguments with `len` after B
+    'dmad_wavenet_eps_len': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_wavenet_eps_vjp_len': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    'dmad_philox_normal_len': (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_diffuse_len': (C.c_int, [_P, _P, C.c_float, C.c_float, _P, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, _P, _P]),
+    'dmad_ddpm_step_len': (C.c_int, [_P, _P, C.c_int32, C.c_float, C.c_float, C.c_float, _P, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, _P]),
+    'dmad_ddpm_purify_len': (C.c_int, [_P, _P, C.c_int32, C.c_float, C.c_float, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, _P,
+                                       _P]),
     'dmad_reserve_unet_vjp': (C.c_int, [_P, C.c_int32]),
     'dmad_unet_eps_vjp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     'dmad_reserve_classifier_vjp': (C.c_int, [_P, C.c_int32]),

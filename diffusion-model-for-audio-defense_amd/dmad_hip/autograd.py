@@ -170,6 +170,37 @@ def wavenet_eps_hip(engine, audio: torch.Tensor, t: int) -> torch.Tensor:
     return WaveNetEpsHIP.apply(audio, engine, int(t))
 
 
+class WaveNetEpsLenHIP(torch.autograd.Function):
+    """WaveNetEpsHIP for clips of any length <= engine.L (audio [B,1,len]): wavenet_eps_len forward, wavenet_eps_vjp_len backward,
+    both on the exact-fp32 path whatever the engine's mode.  First-order only: create_graph=True raises."""
+
+    @staticmethod
+    def forward(ctx, audio, engine, t):
+        from . import engine as _eng
+        _require_cuda(audio)
+        if engine.precision not in (_eng.FP32, _eng.EXACT):
+            raise DmadError('the HIP VJP runs on the exact-fp32 path: a BF16 engine holds no fp32 weights (use an FP32 or EXACT engine)')
+        eps = engine.wavenet_eps_len(audio, t)
+        ctx.engine, ctx.t = engine, int(t)
+        ctx.save_for_backward(audio)
+        return eps.view(audio.shape)
+
+    @staticmethod
+    def backward(ctx, g_eps):
+        _first_order_only('WaveNet')
+        audio, = ctx.saved_tensors
+        eng, B = ctx.engine, audio.shape[0]
+        if eng.vjp_batch < B:
+            eng.reserve_vjp(B)
+        g_x = eng.wavenet_eps_vjp_len(audio, ctx.t, g_eps.reshape(audio.shape).contiguous())
+        return g_x.view(audio.shape).to(audio.dtype), None, None
+
+
+def wavenet_eps_len_hip(engine, audio: torch.Tensor, t: int) -> torch.Tensor:
+    """eps = WaveNet((audio [B,1,len], t * ones)) for len <= engine.L on the engine, differentiable in `audio` (WaveNetEpsLenHIP)."""
+    return WaveNetEpsLenHIP.apply(audio, engine, int(t))
+
+
 def has_unet_vjp(engine) -> bool:
     """The engine holds the exact-fp32 UNet tier as a product path (FP32 and EXACT engines), the tier UNetEpsHIP runs on."""
     from . import engine as _eng

@@ -629,6 +629,55 @@ class Engine:
         want_eps: also return eps, bit-identical to wavenet_eps_path(x_t, t, 1).  Needs reserve_vjp first (DmadError otherwise)."""
         return self._eps_vjp(self.lib.dmad_wavenet_eps_vjp, self._wave, x_t, t, g_eps, want_eps)
 
+    # ------------------------------------------------------------------ clips of any length on the exact-fp32 path (dmad_*_len)
+    @staticmethod
+    def _wave_len(x: torch.Tensor, like: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[B, len] or [B, 1, len] -> contiguous fp32 [B, len]; the length is the tensor's (the library checks 1 <= len <= clip_len)"""
+        _on_gpu(x)
+        x = x.detach()
+        if x.dim() == 3:
+            assert x.shape[1] == 1, 'expected [B,1,len]'
+            x = x[:, 0]
+        assert x.dim() == 2, 'expected [B,len], got %s' % (tuple(x.shape),)
+        if like is not None and x.shape != like.shape:
+            raise DmadError('shape %s does not match the waveforms %s' % (tuple(x.shape), tuple(like.shape)))
+        return x.contiguous().float()
+
+    def wavenet_eps_len(self, x_t: torch.Tensor, t: int) -> torch.Tensor:
+        """dmad_wavenet_eps_len: eps on the exact-fp32 path for clips of x_t's own length, 1 <= len <= clip_len.  At len == clip_len
+        the bits of wavenet_eps_path(x_t, t, 1)."""
+        x = self._wave_len(x_t)
+        return self._mapped(self.lib.dmad_wavenet_eps_len, x, int(t), _N, x.shape[1])
+
+    def wavenet_eps_vjp_len(self, x_t: torch.Tensor, t: int, g_eps: torch.Tensor, want_eps: bool = False):
+        """dmad_wavenet_eps_vjp_len: wavenet_eps_vjp for clips of x_t's own length (the same reserve_vjp reservation)."""
+        x = self._wave_len(x_t)
+        g = self._wave_len(g_eps, x)
+        gx = torch.empty_like(x)
+        eps = torch.empty_like(x) if want_eps else None
+        self._passes(self.lib.dmad_wavenet_eps_vjp_len, x.shape[0], _per(x), int(t), _N, x.shape[1], _per(g), _per(gx), _per(eps))
+        return (gx, eps) if want_eps else gx
+
+    def diffuse_len(self, x0: torch.Tensor, c_a: float, c_b: float, z: Optional[torch.Tensor], seed: int = 0, sample0: int = 0):
+        x = self._wave_len(x0)
+        zz = None if z is None else self._wave_len(z, x)
+        return self._mapped(self.lib.dmad_diffuse_len, x, float(c_a), float(c_b), _per(zz), int(seed), _key(sample0), _N, x.shape[1])
+
+    def ddpm_step_len(self, x: torch.Tensor, t: int, c_eps: float, c_div: float, c_sig: float, z: Optional[torch.Tensor],
+                      seed: int = 0, sample0: int = 0):
+        """in place on x ([B, len] contiguous fp32 CUDA)."""
+        assert x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.dtype == torch.float32
+        zz = None if z is None else self._wave_len(z, x)
+        self._passes(self.lib.dmad_ddpm_step_len, x.shape[0], _per(x), int(t), float(c_eps), float(c_div), float(c_sig), _per(zz), int(seed),
+                     _key(sample0), _N, x.shape[1])
+        return x
+
+    def ddpm_purify_len(self, x0: torch.Tensor, t_star: int, c_a: float, c_b: float, c_eps, c_div, c_sig, seed: int = 0, sample0: int = 0):
+        """ddpm_purify for clips of x0's own length: the draws are the first len values of the fixed-length call's."""
+        x = self._wave_len(x0)
+        return self._mapped(self.lib.dmad_ddpm_purify_len, x, int(t_star), float(c_a), float(c_b), *_floats(t_star, c_eps, c_div, c_sig),
+                            int(seed), _key(sample0), _N, x.shape[1])
+
     def vpsde_purify(self, x0: torch.Tensor, c_a: float, c_b: float, k, h, hb, q, gs, z: Optional[torch.Tensor] = None, seed: int = 0,
                      sample0: int = 0, path: int = 0, want_traj: bool = False):
         """dmad_vpsde_purify: the reverse VP-SDE chain (diffusion to the start, then one Euler-Maruyama step per entry of k / h / hb /
@@ -1584,8 +1633,14 @@ class Engine:
         """dmad_philox_uniform: [B, L], row b the uniforms ((word >> 8) + 0.5) * 2^-24 of key (seed, sample0 + b, stream)."""
         return self._philox(self.lib.dmad_philox_uniform, seed, sample0, stream, B)
 
-    def philox_normal(self, seed: int, sample0: int, stream: int, B: int) -> torch.Tensor:
-        return self._philox(self.lib.dmad_philox_normal, seed, sample0, stream, B)
+    def philox_normal(self, seed: int, sample0: int, stream: int, B: int, length: Optional[int] = None) -> torch.Tensor:
+        """[B, L] normals of key (seed, sample0 + b, stream); length: [B, length], the first `length` values of those rows
+        (dmad_philox_normal_len, 1 <= length <= L)."""
+        if length is None:
+            return self._philox(self.lib.dmad_philox_normal, seed, sample0, stream, B)
+        out = torch.empty((B, int(length)), dtype=torch.float32, device=self.device)
+        check(self.lib.dmad_philox_normal_len(self._h, int(seed), int(sample0), int(stream), int(B), int(length), _ptr(out), _stream()))
+        return out
 
     def philox_raw(self, seed: int, sample: int, stream: int, nblocks: int) -> torch.Tensor:
         out = torch.empty(nblocks * 4, dtype=torch.int32, device=self.device)

@@ -180,6 +180,9 @@ class RobustCertificate():
 
         coeffs = None
         if self.denoiser is not None:
+            if hasattr(getattr(self.denoiser, 'model', None), 'any_length'):      # a DiffWave mirror: the vote loops run at clip_len only
+                from diffusion_models.diffwave_ddpm import fixed_length_only
+                fixed_length_only(self.denoiser.model, x, 'the vote loop (RobustCertificate.smooth_predict)')
             alpha_bar_star = 1 / (1 + sigma ** 2)
             t_star = self.compute_t_star(alpha_bar_star)
             self.denoiser.reverse_timestep = t_star

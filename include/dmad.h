@@ -277,6 +277,34 @@ int dmad_reserve_vjp(dmad_engine* e, int32_t max_batch);
 int dmad_wavenet_eps_vjp(dmad_engine* e, const float* x_t, int32_t t, int32_t B, const float* g_eps, float* g_x, float* eps,
                          dmad_stream s);
 
+/* Clips of any length on the exact-fp32 DiffWave path (the keyword-spotting driver runs every clip at its own length, at batch 1).
+ * Each export takes the arguments of its fixed-length twin with `len` after B: every waveform array is contiguous device fp32
+ * [B][len], 1 <= len <= clip_len, at a pitch of len floats — rows are NOT 16-byte aligned when len % 4 != 0 and nothing assumes they
+ * are.  Twins: dmad_wavenet_eps_len ~ dmad_wavenet_eps_path(.., path = 1, ..), dmad_wavenet_eps_vjp_len ~ dmad_wavenet_eps_vjp (the same
+ * dmad_reserve_vjp reservation), dmad_philox_normal_len ~ dmad_philox_normal, dmad_diffuse_len / dmad_ddpm_step_len /
+ * dmad_ddpm_purify_len ~ dmad_diffuse / dmad_ddpm_step / dmad_ddpm_purify.
+ *   - They always run the exact-fp32 path, whatever the engine's mode: DMAD_FP32 and DMAD_EXACT engines; DMAD_ERR_STATE on a DMAD_BF16
+ *     engine.  len < 1 or len > clip_len: DMAD_ERR_SHAPE.  B as in the twin.
+ *   - len == clip_len makes the twin's launches: bit-identical results.  Same N = B * len, same launches: a clip's eps does not depend
+ *     on the clip_len of the engine that ran it.
+ *   - Noise is a prefix: a row of dmad_philox_normal_len is the first len values of dmad_philox_normal's row of the same (seed, sample,
+ *     stream) — counter block l / 4, a last block of 1-3 values takes the leading words of its draw — and the draws the scheduler
+ *     exports make in registers are those values (streams 0xD1FF and 1 + t, as the twins).  The scheduler arithmetic keeps the twins'
+ *     operation order and roundings.
+ *   - No allocation: they use the fp32 workspace and the VJP reservation as they stand (sized by clip_len); dmad_device_bytes is
+ *     unchanged.  Before a call shorter than the longest one since, the engine zeroes rows [len, longest) of its zero-padded maps, so
+ *     that the dilated taps past the clip's end read zeros; a run of calls at one length clears nothing. */
+int dmad_wavenet_eps_len(dmad_engine* e, const float* x_t, int32_t t, int32_t B, int32_t len, float* eps, dmad_stream s);
+int dmad_wavenet_eps_vjp_len(dmad_engine* e, const float* x_t, int32_t t, int32_t B, int32_t len, const float* g_eps, float* g_x, float* eps,
+                             dmad_stream s);
+int dmad_philox_normal_len(dmad_engine* e, uint64_t seed, uint64_t sample0, uint32_t stream, int32_t B, int32_t len, float* z, dmad_stream s);
+int dmad_diffuse_len(dmad_engine* e, const float* x0, float c_a, float c_b, const float* z, uint64_t seed, uint64_t sample0, int32_t B,
+                     int32_t len, float* x_t, dmad_stream s);
+int dmad_ddpm_step_len(dmad_engine* e, float* x, int32_t t, float c_eps, float c_div, float c_sig, const float* z, uint64_t seed,
+                       uint64_t sample0, int32_t B, int32_t len, dmad_stream s);
+int dmad_ddpm_purify_len(dmad_engine* e, const float* x0, int32_t t_star, float c_a, float c_b, const float* c_eps, const float* c_div,
+                         const float* c_sig, uint64_t seed, uint64_t sample0, int32_t B, int32_t len, float* out, dmad_stream s);
+
 /* Vector-Jacobian product of the Improved-Diffusion UNet on its exact-fp32 tier — the gradient the white-box attack drivers take THROUGH
  * the spectrogram-domain purifier (AcousticSystem(.., defense_type='spec'); adaptive_attack_eval.py --defense Diffusion-Spec calls the
  * UNet outside no_grad, improved_diffusion_sde.py:90-118).
