@@ -10,7 +10,8 @@ AcousticSystem(classifier, MelSpectrogramDB, defender) with the defenses
   * Diffusion-Spec  RevImprovedDiffusion (the reverse VP-SDE on the spectrogram, diffusion_models/improved_diffusion_sde.py).
 Every other attack (Qin-I, Kenansville, FAKEBOB, SirenAttack) and defense (AS, MS, DS, LPF, BPF, FeCo, DefenseGAN) raises
 NotImplementedError naming the piece this package does not have, or the driver that runs it (Qin-I and `--max_iter_2` > 0:
-imperceptible_attack_eval.py; FAKEBOB and SirenAttack: black_box_attack_eval.py and siren_attack_eval.py; the baseline defenses AS, MS,
+imperceptible_attack_eval.py; FAKEBOB, SirenAttack and Kenansville (FFT form): black_box_attack_eval.py, siren_attack_eval.py and
+kenansville_attack_eval.py; the baseline defenses AS, MS,
 DS, LPF, BPF: baseline_defense_eval.py).
 
 Additions to the reference's flags:
@@ -36,10 +37,9 @@ REFERENCE_CLASSIFIER_PATH = ('audio_models/ConvNets_SpeechCommands/checkpoints/j
                              'reg=1e-08-best-robust-acc.pth')
 ATTACKS = ['CW', 'Qin-I', 'Kenansville', 'FAKEBOB', 'SirenAttack']
 DEFENSES = ['Diffusion', 'Diffusion-Spec', 'AS', 'MS', 'DS', 'LPF', 'BPF', 'FeCo', 'DefenseGAN', 'None']
-_MISSING_ATTACK = {
-    'Kenansville': 'the black-box attacks (robustness_eval/black_box_attack.py)',
-}
-_OTHER_DRIVER = {'FAKEBOB': 'black_box_attack_eval.py', 'SirenAttack': 'siren_attack_eval.py'}    # query-only attacks run by a driver of their own
+_MISSING_ATTACK = {}
+# query-only attacks run by a driver of their own (Kenansville: its FFT form; the SSA form is not provided)
+_OTHER_DRIVER = {'FAKEBOB': 'black_box_attack_eval.py', 'SirenAttack': 'siren_attack_eval.py', 'Kenansville': 'kenansville_attack_eval.py'}
 QIN_DRIVER = 'imperceptible_attack_eval.py'       # Qin-I (AudioAttack stage 2, max_iter_2 > 0)
 BASELINE_DEFENSES = ['AS', 'MS', 'DS', 'LPF', 'BPF']                # transforms/time_defense.py, transforms/frequency_defense.py
 _MISSING_DEFENSE = {

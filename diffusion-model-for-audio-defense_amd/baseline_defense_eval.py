@@ -43,8 +43,8 @@ def build_parser():
 def check_supported(args):
     """NotImplementedError for every attack, defense and option this driver does not run."""
     if args.attack not in ATTACKS:
-        raise NotImplementedError('--attack %s: this driver runs CW, FAKEBOB and SirenAttack (Qin-I: imperceptible_attack_eval.py, without a baseline defense; Kenansville '
-                                  'is not provided)' % args.attack)
+        raise NotImplementedError('--attack %s: this driver runs CW, FAKEBOB and SirenAttack (Qin-I: imperceptible_attack_eval.py, without a baseline defense; Kenansville, FFT form: '
+                                  'kenansville_attack_eval.py, without a baseline defense)' % args.attack)
     if args.defense in ('None', 'Diffusion', 'Diffusion-Spec'):
         raise NotImplementedError('--defense %s: %s runs it under --attack %s, this driver runs the baseline defenses %s'
                                   % (args.defense, _ATTACK_DRIVER[args.attack], args.attack, ', '.join(DEFENSES)))

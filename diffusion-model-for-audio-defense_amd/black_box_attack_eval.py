@@ -4,7 +4,8 @@
   python black_box_attack_eval.py --data_path <SC09 test folder> --attack FAKEBOB --defense Diffusion --t 1
 
 It shares its flags, `build_system`, the defense checks and the evaluation loop (`evaluate`) with adaptive_attack_eval.py (the
-white-box driver, which sends FAKEBOB here) and accepts only `--attack FAKEBOB` (SirenAttack: siren_attack_eval.py; Kenansville is not provided).
+white-box driver, which sends FAKEBOB here) and accepts only `--attack FAKEBOB` (SirenAttack: siren_attack_eval.py; Kenansville: its
+FFT form runs in kenansville_attack_eval.py, the SSA form is not provided).
 `--save_path` writes the clean / purified / adversarial waveforms as 16-bit WAV files, as in the white-box driver (refused with
 `--defense Diffusion-Spec`, whose spectrogram images need a plotting library).  The attacker is built with the
 reference driver's constants: epsilon 0.002, confidence 0.5, max_iter 200, samples_per_draw 200 in one draw batch, max_lr 5e-4,
@@ -36,7 +37,7 @@ def check_supported(args):
     """NotImplementedError for anything but FAKEBOB, and for a defense / option adaptive_attack_eval.py refuses for every attack."""
     if args.attack != 'FAKEBOB':
         raise NotImplementedError('--attack %s: this driver runs FAKEBOB only (CW: adaptive_attack_eval.py; SirenAttack: '
-                                  'siren_attack_eval.py; Qin-I: imperceptible_attack_eval.py; Kenansville is not provided)' % args.attack)
+                                  'siren_attack_eval.py; Qin-I: imperceptible_attack_eval.py; Kenansville, FFT form: kenansville_attack_eval.py)' % args.attack)
     white_box.check_defense(args)
 
 

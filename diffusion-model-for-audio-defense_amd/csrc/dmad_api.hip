@@ -19,6 +19,7 @@
 #include "unet_ops.h"
 #include "elementwise.h"
 #include "wave_defense.h"
+#include "wave_fft.h"
 #include "m5.h"
 #include "kws.h"
 #include "kws_mel.h"
@@ -366,6 +367,9 @@ struct dmad_engine {
     KwsMelConst kmel;
     float* kws_spec = nullptr;
     float* kws_gspec = nullptr;
+    // Whole-clip real FFT pair (wave_fft.h): the plan of clip_len and the twiddle table, built at first use on any engine
+    FftPlan fft_plan;
+    float* fft_tw = nullptr;
 
     template <typename T>
     int alloc(T** p, size_t n, bool zero = false) {
@@ -447,6 +451,18 @@ int need_kws_mel(dmad_engine* e) {          // the constants of kws_mel.h, float
     CHK(e->upload(&ab, h.ab)); CHK(e->upload(&fb, h.fb)); CHK(e->upload(&w0, h.w0)); CHK(e->upload(&w1, h.w1));
     CHK(e->upload(&m0, h.m0)); CHK(e->upload(&lo, h.lo)); CHK(e->upload(&hi, h.hi)); CHK(e->upload(&af, h.af));
     e->kmel = KwsMelConst{af, ab, fb, w0, w1, m0, lo, hi};       // af last: it is the guard
+    return 0;
+}
+int need_wave_fft(dmad_engine* e, const char* who) {      // the plan of clip_len and exp(-2 pi i j / L), float64 on the host rounded once
+    if (e->fft_tw) return 0;
+    FftPlan p;
+    if (const char* m = wave_fft_plan(e->L, &p)) return fail(DMAD_ERR_SHAPE, "%s: the wave FFT does not serve clip_len %d: %s", who, e->L, m);
+    std::vector<float> tw(2 * (size_t)e->L);
+    wave_fft_twiddles(e->L, tw.data());
+    float* d = nullptr;
+    CHK(e->upload(&d, tw));
+    e->fft_plan = p;
+    e->fft_tw = d;                          // last: it is the guard
     return 0;
 }
 int need_m5(const dmad_engine* e) { return e->m5_final ? 0 : fail(DMAD_ERR_STATE, "M5 weights are not finalised (dmad_load_weight + dmad_finalize_weights)"); }
@@ -4130,6 +4146,44 @@ int dmad_pso_update_best(dmad_engine* e, const float* loss, const int64_t* predi
     if (B < 1 || P < 1) return fail(DMAD_ERR_INVALID, "dmad_pso_update_best: B %d and P %d must be >= 1", B, P);
     launch_pso_update_best(loss, (const long long*)predict, loc, (const long long*)index, B, P, pbests, pbest_loc, gbests, gbest_loc,
                            (long long*)gbest_predict, e->L, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+// _KenanFFT.py:68 (torch.fft.rfft) and l.198 (the row maximum of |FFT|): one workgroup per clip
+int dmad_wave_rfft(dmad_engine* e, const float* x, int32_t B, float* spec, float* maxmag, dmad_stream s) {
+    if (!e || !x || !spec || !maxmag) return fail(DMAD_ERR_INVALID, "dmad_wave_rfft: null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "dmad_wave_rfft: B %d must be >= 1", B);
+    CHK(need_wave_fft(e, "dmad_wave_rfft"));
+    if (((uintptr_t)x | (uintptr_t)spec) & 7) return fail(DMAD_ERR_INVALID, "dmad_wave_rfft: x and spec must be 8-byte aligned");
+    CHK(need_kernels(KF_WAVE_FFT));
+    launch_wave_rfft(e->fft_plan, e->fft_tw, x, B, spec, maxmag, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+// _KenanFFT.py:72 (the masked assignment) and l.77 (torch.fft.irfft) in one launch
+int dmad_wave_irfft_threshold(dmad_engine* e, const float* spec, const float* factor, int32_t B, float* out, int32_t* kept, dmad_stream s) {
+    if (!e || !spec || !out || !kept) return fail(DMAD_ERR_INVALID, "dmad_wave_irfft_threshold: null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "dmad_wave_irfft_threshold: B %d must be >= 1", B);
+    CHK(need_wave_fft(e, "dmad_wave_irfft_threshold"));
+    if (((uintptr_t)spec | (uintptr_t)out) & 7) return fail(DMAD_ERR_INVALID, "dmad_wave_irfft_threshold: spec and out must be 8-byte aligned");
+    CHK(need_kernels(KF_WAVE_FFT));
+    launch_wave_irfft_threshold(e->fft_plan, e->fft_tw, spec, factor, B, out, kept, (hipStream_t)s);
+    LASTCHK();
+    return 0;
+}
+
+// _KenanFFT.py:233-243 (the per-clip loop of the bisection) without the host loop
+int dmad_kenan_update(dmad_engine* e, const int64_t* pred, const int64_t* label, int32_t B, int32_t targeted, const float* perturbed,
+                      float* best, float* fmin, float* fmax, float* factor, int32_t* succ, dmad_stream s) {
+    if (!e || !pred || !label || !perturbed || !best || !fmin || !fmax || !factor || !succ)
+        return fail(DMAD_ERR_INVALID, "dmad_kenan_update: null argument");
+    if (B < 1) return fail(DMAD_ERR_INVALID, "dmad_kenan_update: B %d must be >= 1", B);
+    if (targeted != 0 && targeted != 1) return fail(DMAD_ERR_INVALID, "dmad_kenan_update: targeted must be 0 or 1");
+    if (((uintptr_t)perturbed | (uintptr_t)best) & 15) return fail(DMAD_ERR_INVALID, "dmad_kenan_update: perturbed and best must be 16-byte aligned");
+    launch_kenan_update((const long long*)pred, (const long long*)label, B, e->L, targeted, perturbed, best, fmin, fmax, factor, succ,
+                        (hipStream_t)s);
     LASTCHK();
     return 0;
 }

@@ -20,7 +20,8 @@ enum : unsigned {
     KF_UNET_ATT_BWD = 1u << 7,   // unet_vjp.hip: attention backward, T = 256
     KF_UNET_ATT = 1u << 8,       // unet_ops.hip: fp32 and f16 attention, T = 256
     KF_WAVE_IIR = 1u << 9,       // wave_defense.hip: wave_iir_kernel<1..8>
-    KF_COUNT = 10
+    KF_WAVE_FFT = 1u << 10,      // wave_fft.hip: the whole-clip real FFT pair
+    KF_COUNT = 11
 };
 const char* kernel_family_name(unsigned family);        // of one family bit, for messages
 

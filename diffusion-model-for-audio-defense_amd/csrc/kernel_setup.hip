@@ -18,14 +18,16 @@ int kws_configure();
 int unvjp_configure();
 int unet_att_configure();
 int wave_iir_configure();
+int wave_fft_configure();
 
 namespace {
 // both in the order of the KF_ bits
 const SetupTable::ConfigureFn kConfigure[KF_COUNT] = {gemm_f32_configure,   gemm_x3_configure, gemm_h16_configure, wn_layer_p_configure,
                                                       wn_final_p_configure, m5_configure,      kws_configure,      unvjp_configure,
-                                                      unet_att_configure,   wave_iir_configure};
+                                                      unet_att_configure,   wave_iir_configure, wave_fft_configure};
 const char* const kNames[KF_COUNT] = {"fp32 narrow tile", "split-f16 tier", "f16 conv GEMM",      "WaveNet layer", "WaveNet tail",
-                                      "M5",               "KWS",            "attention backward", "attention",     "IIR filter"};
+                                      "M5",               "KWS",            "attention backward", "attention",     "IIR filter",
+                                      "wave FFT"};
 
 SetupTable& table() {
     static SetupTable t(kConfigure, KF_COUNT);

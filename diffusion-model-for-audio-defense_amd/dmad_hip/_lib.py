@@ -168,6 +168,9 @@ _SIGNATURES = {
     'dmad_pso_step': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_uint64,
                                 _P, _P, _P, _P]),
     'dmad_pso_update_best': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    'dmad_wave_rfft': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
+    'dmad_wave_irfft_threshold': (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P]),
+    'dmad_kenan_update': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     'dmad_wave_smooth': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_wave_smooth_vjp': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'dmad_wave_resample': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),

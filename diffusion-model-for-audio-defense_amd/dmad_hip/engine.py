@@ -1330,6 +1330,62 @@ class Engine:
                                             _ptr(gbests), _ptr(gbest_loc), _ptr(gbest_predict), _stream()))
         return pbests, pbest_loc, gbests, gbest_loc, gbest_predict
 
+    # ------------------------------------------------------------------ whole-clip real FFT pair and the Kenansville bisection
+    def _fft_check(self, rc: int):
+        """check() of the FFT pair: a clip_len the plan does not serve (DMAD_ERR_SHAPE) is refused with the way out"""
+        try:
+            check(rc)
+        except DmadError as err:
+            if 'the wave FFT does not serve clip_len' not in str(err):
+                raise
+            raise DmadError("%s; Kenansville(fft_backend='torch') (torch.fft) serves any length" % err) from None
+
+    def wave_rfft(self, x: torch.Tensor):
+        """dmad_wave_rfft: x [B,L] or [B,1,L] -> (spec [B, L/2 + 1, 2] fp32 (re, im) = torch.fft.rfft(x), maxmag [B] = max_k |spec[b][k]|).
+        One workgroup per clip, exact fp32 in a fixed order; B is not limited by max_batch."""
+        xw = self._wave(x)
+        B = xw.shape[0]
+        spec = torch.empty((B, self.L // 2 + 1, 2), device=xw.device, dtype=torch.float32)
+        maxmag = torch.empty((B,), device=xw.device, dtype=torch.float32)
+        self._fft_check(self.lib.dmad_wave_rfft(self._h, _ptr(xw), B, _ptr(spec), _ptr(maxmag), _stream()))
+        return spec, maxmag
+
+    def wave_irfft_threshold(self, spec: torch.Tensor, factor: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                             kept: Optional[torch.Tensor] = None):
+        """dmad_wave_irfft_threshold: spec [B, L/2 + 1, 2] (as wave_rfft returns it), factor fp32 [B] or None -> (out [B,L] = irfft of spec
+        with every bin |X| < factor[b] zeroed, kept int32 [B] = the surviving bins).  None: the plain inverse.  `out` / `kept` passed in
+        are written in place."""
+        _on_gpu(spec)
+        assert spec.dim() == 3 and tuple(spec.shape[1:]) == (self.L // 2 + 1, 2), \
+            'expected spec [B,%d,2], got %s' % (self.L // 2 + 1, tuple(spec.shape))
+        B = spec.shape[0]
+        spec = self._owned(_f32(spec), (B, self.L // 2 + 1, 2), name='spec')
+        if factor is not None:
+            _on_gpu(factor)
+            factor = self._owned(_f32(factor), (B,), name='factor')
+        out = self._owned(out, (B, self.L), name='out')
+        kept = self._owned(kept, (B,), torch.int32, 'kept')
+        self._fft_check(self.lib.dmad_wave_irfft_threshold(self._h, _ptr(spec), _ptr(factor), B, _ptr(out), _ptr(kept), _stream()))
+        return out, kept
+
+    def kenan_update(self, pred: torch.Tensor, label: torch.Tensor, targeted: bool, perturbed: torch.Tensor, best: torch.Tensor,
+                     fmin: torch.Tensor, fmax: torch.Tensor, factor: torch.Tensor, succ: torch.Tensor):
+        """dmad_kenan_update: pred, label int64 [B]; perturbed, best fp32 [B,L]; fmin, fmax, factor fp32 [B]; succ int32 [B].  Where the
+        clip won (pred != label, or == when targeted): best[b] <- perturbed[b], fmax[b] <- factor[b], succ[b] <- 1; else fmin[b] <-
+        factor[b]; then factor[b] <- |(fmin[b] + fmax[b]) / 2| in torch's fp32 order.  best, fmin, fmax, factor and succ are updated in
+        place and returned."""
+        _on_gpu(pred, label)
+        assert pred.dim() == 1, 'expected pred [B], got %s' % (tuple(pred.shape),)
+        B = pred.shape[0]
+        pred = self._owned(pred.contiguous(), (B,), torch.int64, 'pred')
+        label = self._owned(label.contiguous(), (B,), torch.int64, 'label')
+        perturbed, best = self._owned(perturbed, (B, self.L), name='perturbed'), self._owned(best, (B, self.L), name='best')
+        fmin, fmax, factor = (self._owned(t, (B,), name=n) for t, n in ((fmin, 'fmin'), (fmax, 'fmax'), (factor, 'factor')))
+        succ = self._owned(succ, (B,), torch.int32, 'succ')
+        check(self.lib.dmad_kenan_update(self._h, _ptr(pred), _ptr(label), B, int(bool(targeted)), _ptr(perturbed), _ptr(best), _ptr(fmin),
+                                         _ptr(fmax), _ptr(factor), _ptr(succ), _stream()))
+        return best, fmin, fmax, factor, succ
+
     # ------------------------------------------------------------------ baseline waveform defenses (dmad_wave_*)
     @staticmethod
     def _host_f32(a, n: Optional[int] = None):

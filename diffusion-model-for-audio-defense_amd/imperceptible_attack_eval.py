@@ -5,7 +5,8 @@ evaluation loop l.234-370 and the stage-2 success rate l.348-351, 371-372), with
 
 It shares its flags, `build_system`, the defense checks and the evaluation loop (`evaluate`) with adaptive_attack_eval.py (the
 white-box driver, which sends Qin-I here) and accepts only `--attack Qin-I`, its default (CW: adaptive_attack_eval.py; FAKEBOB:
-black_box_attack_eval.py; SirenAttack: siren_attack_eval.py; Kenansville is not provided), with `--defense` None, Diffusion or
+black_box_attack_eval.py; SirenAttack: siren_attack_eval.py; Kenansville: its FFT form runs in
+kenansville_attack_eval.py, the SSA form is not provided), with `--defense` None, Diffusion or
 Diffusion-Spec.  The attacker is the reference driver's: AudioAttack(model, masker=PsychoacousticMasker(), eps, norm, max_iter_1,
 max_iter_2, learning_rate_1=eps / 5), untargeted; stage 1 is the CW loop, stage 2 lowers the masking loss of the perturbation
 (robustness_eval/white_box_attack.py).  After the reference's accuracy lines it prints the stage-2 success count and rate.
@@ -38,7 +39,7 @@ def check_supported(args):
     if args.attack in _OTHER_DRIVER:
         raise NotImplementedError('--attack %s: this driver runs Qin-I only (%s runs %s)' % (args.attack, _OTHER_DRIVER[args.attack], args.attack))
     if args.attack != 'Qin-I':
-        raise NotImplementedError('--attack %s: this driver runs Qin-I only (Kenansville is not provided)' % args.attack)
+        raise NotImplementedError('--attack %s: this driver runs Qin-I only' % args.attack)
     white_box.check_defense(args)
     if args.max_iter_2 <= 0:
         raise NotImplementedError('--max_iter_2 %d: Qin-I without stage 2 is the CW attack of adaptive_attack_eval.py' % args.max_iter_2)

@@ -24,7 +24,8 @@ any_length=True on an FP32 engine of `--max_clip_len` samples that also holds th
 length on the exact-fp32 path (Engine.ddpm_purify_len), and `--grad_backend hip` differentiates through it with the engine's any-length
 vector-Jacobian product.  With `--clip_len`: the attacks CW, FAKEBOB
 and SirenAttack against the defenses None, Diffusion, AS, MS, DS, LPF and BPF.  Qin-I, Kenansville, Diffusion-Spec, FeCo and DefenseGAN
-raise NotImplementedError naming the missing piece.
+raise NotImplementedError naming the missing piece (Kenansville's FFT form runs on the 16000-sample clips of SC09, in
+kenansville_attack_eval.py).
 `run(args)` is importable so that tests can drive it without a subprocess; it returns the accuracy figures."""
 import json
 import os
@@ -43,7 +44,8 @@ DEFENSES = ['None', 'Diffusion'] + list(white_box.BASELINE_DEFENSES)
 _MISSING_ATTACK = {
     'Qin-I': 'the psychoacoustic masker at the clip lengths of this task (Engine.masking_step is built for 16000-sample clips behind the '
              'SC09 classifiers; the reference marks Qin-I "not used" here)',
-    'Kenansville': 'the black-box attacks (robustness_eval/black_box_attack.py)',
+    'Kenansville': 'the FFT attack of robustness_eval/black_box_attack.py on keyword clips (kenansville_attack_eval.py runs its FFT form on '
+                   'the 16000-sample clips of SC09; the SSA form is not provided)',
 }
 _MISSING_DEFENSE = dict(white_box._MISSING_DEFENSE)
 _MISSING_DEFENSE['Diffusion-Spec'] = ('a spectrogram purifier for [32 x T] spectrograms (the UNet of diffusion_models/improved_diffusion_sde.py is '

@@ -28,7 +28,8 @@ The reference's quirks are part of the contract (tests/golden/fakebob.npz is rec
   * the best clip is the one with the SMALLEST loss of the unperturbed probe, for an untargeted attack too;
   * `success` is set from the majority decision of the unperturbed probe, at any iteration, and is never cleared.
 `estimate_threshold` / `estimate_threshold_run` (l.221-311) serve speaker verification, a task this package has no loss for: they raise
-NotImplementedError, as does generate() for task 'SV' / 'OSI' without a threshold.  Kenansville is not provided.
+NotImplementedError, as does generate() for task 'SV' / 'OSI' without a threshold.  Of `Kenansville` (at the end of this file, and
+_KenanFFT.py) the FFT form runs; the SSA form is not provided.
 
 `SirenAttack` (l.313-580; "SirenAttack: Generating Adversarial Audio for End-to-End Acoustic Systems", AsiaCCS 2020) is a particle swarm
 on the perturbation: `n_particles` per clip, `max_epoch` epochs of `max_iter` moves, every particle scored through the EOT wrapper.
@@ -65,7 +66,7 @@ from ._EOT import EOT
 from ._NES import NES
 from ._utils import MarginLoss, resolve_loss, resolve_prediction
 
-__all__ = ['FAKEBOB', 'SirenAttack']
+__all__ = ['FAKEBOB', 'SirenAttack', 'Kenansville']
 
 
 class FAKEBOB:
@@ -466,6 +467,74 @@ class SirenAttack:
         for batch_id, s in enumerate(range(0, n_audios, batch_size)):
             e = s + batch_size
             adver_x_batch, success_batch = self.attack_batch(x[s:e], y[s:e], lower[s:e], upper[s:e], batch_id)
+            adver_x.append(adver_x_batch)
+            success += success_batch
+        return torch.cat(adver_x, 0), success
+
+
+FFT_BACKENDS = ('torch', 'device')
+
+
+class Kenansville:
+    """The reference's Kenansville (l.584-663) in its default form, atk_name='fft': see _KenanFFT.py.  `fft_backend` / `engine` are this
+    package's additions: 'torch' (default) runs the reference's torch.fft operators, 'device' the engine's whole-clip FFT pair and its
+    bisection kernel; the engine is found as SirenAttack finds it.  atk_name='ssa', the reference's float64 SVD of a Hankel matrix on the
+    CPU at batch 1, is not provided."""
+
+    def __init__(self, model, atk_name='fft', max_iter=15, raster_width=100, early_stop=False, targeted=False, verbose=1, BITS=16, batch_size=1,
+                 fft_backend='torch', engine=None):
+        if atk_name == 'ssa':
+            raise NotImplementedError("Kenansville(atk_name='ssa') is the reference's CPU SVD form (a float64 SVD of a Hankel matrix per clip, "
+                                      "at batch 1), which this package does not provide: the FFT form, atk_name='fft', runs")
+        if atk_name != 'fft':
+            raise ValueError("atk_name must be 'fft' (or 'ssa', which is not provided), not %r" % (atk_name,))
+        if fft_backend not in FFT_BACKENDS:
+            raise ValueError('fft_backend must be one of %s, not %r' % (FFT_BACKENDS, fft_backend))
+        self.model = model
+        self.atk_name = atk_name
+        self.max_iter = max_iter
+        self.raster_width = raster_width           # of the SSA form; unused by the FFT form, as in the reference
+        self.targeted = targeted
+        self.verbose = verbose
+        self.BITS = BITS
+        self.early_stop = early_stop
+        self.batch_size = batch_size
+        self.fft_backend = fft_backend
+        self.engine = self._find_engine(engine) if fft_backend == 'device' else engine
+        self.trace = None                          # a list here receives (factors, predictions) per iteration (_KenanFFT.atk_bst_fft)
+
+    def _find_engine(self, engine):
+        from dmad_hip._lib import DmadError
+        if engine is None:
+            classifier = getattr(self.model, 'classifier', None)
+            engine = getattr(classifier, '__dict__', {}).get('engine')
+        if engine is None:
+            raise DmadError("Kenansville(fft_backend='device') needs an engine: none is bound to model.classifier and no engine= was passed")
+        return engine
+
+    @torch.no_grad()
+    def _scores(self, x):
+        """The system's scores [n, C] of one evaluation per clip: the one-call query where the system has one (as _EOT.EOT asks), else
+        the forward pass."""
+        if hasattr(self.model, 'query'):
+            return self.model.query(x, 1, per_call=1)[0][0]
+        return self.model(x)
+
+    def attack_batch(self, x_batch, y_batch, batch_id, fs=16_000):
+        from ._KenanFFT import atk_bst_fft
+        return atk_bst_fft(x_batch, y_batch, self.targeted, self._scores, self.max_iter, self.verbose, backend=self.fft_backend,
+                           engine=self.engine, trace=self.trace)
+
+    def generate(self, x, y, targeted=False, fs=16_000):
+        self.targeted = targeted
+        n_audios, n_channels, _ = x.size()
+        assert n_channels == 1, 'Only Support Mono Audio'
+        assert y.shape[0] == n_audios, 'The number of x and y should be equal'
+        batch_size = min(self.batch_size, n_audios)
+        adver_x, success = [], []
+        for batch_id, s in enumerate(range(0, n_audios, batch_size)):
+            e = s + batch_size
+            adver_x_batch, success_batch = self.attack_batch(x[s:e], y[s:e], batch_id, fs=fs)
             adver_x.append(adver_x_batch)
             success += success_batch
         return torch.cat(adver_x, 0), success

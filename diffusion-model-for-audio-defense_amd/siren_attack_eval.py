@@ -4,7 +4,8 @@ evaluation loop l.234-370), with the pieces of this package in place of the CUDA
   python siren_attack_eval.py --data_path <SC09 test folder> --attack SirenAttack --defense Diffusion --t 1
 
 It shares its flags, `build_system`, the defense checks and the evaluation loop (`evaluate`) with adaptive_attack_eval.py (the
-white-box driver) and accepts only `--attack SirenAttack` (FAKEBOB: black_box_attack_eval.py; Kenansville is not provided).
+white-box driver) and accepts only `--attack SirenAttack` (FAKEBOB: black_box_attack_eval.py; Kenansville: its FFT form runs in
+kenansville_attack_eval.py, the SSA form is not provided).
 `--save_path` writes the clean / purified / adversarial waveforms as 16-bit WAV files, as in the white-box driver.  The attacker is
 built with the reference driver's constants: epsilon 0.002, max_epoch 300, max_iter 30, n_particles 25, batches of `--batch_size`
 clips, task 'SCR', untargeted.
@@ -40,7 +41,7 @@ def check_supported(args):
     """NotImplementedError for anything but SirenAttack, and for a defense / option adaptive_attack_eval.py refuses for every attack."""
     if args.attack != 'SirenAttack':
         raise NotImplementedError('--attack %s: this driver runs SirenAttack only (CW: adaptive_attack_eval.py; FAKEBOB: '
-                                  'black_box_attack_eval.py; Qin-I: imperceptible_attack_eval.py; Kenansville is not provided)' % args.attack)
+                                  'black_box_attack_eval.py; Qin-I: imperceptible_attack_eval.py; Kenansville, FFT form: kenansville_attack_eval.py)' % args.attack)
     white_box.check_defense(args)
 
 

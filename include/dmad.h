@@ -689,6 +689,36 @@ int dmad_pso_step(dmad_engine* e, const float* x, const float* lower, const floa
 int dmad_pso_update_best(dmad_engine* e, const float* loss, const int64_t* predict, const float* loc, const int64_t* index, int32_t B,
                          int32_t P, float* pbests, float* pbest_loc, float* gbests, float* gbest_loc, int64_t* gbest_predict, dmad_stream s);
 
+/* Whole-clip real FFT pair and the bisection of the Kenansville FFT attack (robustness_eval/_KenanFFT.py: fft_compression l.57-82,
+ * atk_bst_fft l.180-247).  With L = clip_len and M = L / 2, a clip is the M complex points z[n] = x[2n] + i x[2n+1]; one workgroup per
+ * clip runs their M-point Stockham FFT in LDS and the real-FFT pass around it, in fp32, in a fixed order, without atomics: a row's bits
+ * are a function of its own input row, never of B, and equal from call to call.  Twiddles are one device table of exp(-2 pi i j / L),
+ * float64 on the host rounded once, built at the first call on an engine.  M must factor into radices 4, 2 and 5 with at most one radix-2
+ * stage, and 8 M + 256 bytes must fit in a workgroup's LDS with M <= 16384; 16000 and 32000 are served.  Any other clip_len is
+ * DMAD_ERR_SHAPE with a message that names the length and the rule.  Nothing is sized by max_batch (the grid is B), and the engine's
+ * precision, mode and parts (with_wavenet, with_classifier) do not matter.  The kernels move rows as 8- and 16-byte vectors: x, spec
+ * and out must be 8-byte aligned, perturbed and best of dmad_kenan_update 16-byte aligned (clip_len is a multiple of 128, so every row
+ * then is).  B < 1, a required pointer that is null or a misaligned one: DMAD_ERR_INVALID.
+ *
+ * dmad_wave_rfft (l.68 torch.fft.rfft, and l.198 torch.fft.fft(data).abs().max(dim=2): for a real clip the maximum over the M + 1
+ * bins is the maximum over all L):  x: device fp32 [B][L];  spec: device fp32 [B][M + 1][2] (re, im), the DC and Nyquist bins with
+ * im = 0;  maxmag: device fp32 [B], max_k sqrt(re^2 + im^2), a fixed-order workgroup reduction. */
+int dmad_wave_rfft(dmad_engine* e, const float* x, int32_t B, float* spec, float* maxmag, dmad_stream s);
+
+/* l.72 (fft_image[fft_image.abs() < factor] = 0) and l.77 (torch.fft.irfft) in one launch:  spec as dmad_wave_rfft writes it;  factor:
+ * device fp32 [B], or null for the plain inverse;  out: device fp32 [B][L] = irfft of spec with every bin sqrt(re^2 + im^2) < factor[b]
+ * zeroed, scaled by 1 / L;  kept: device int32 [B], the bins that survive (M + 1 without factor).  The imaginary parts of the DC and
+ * Nyquist bins are ignored, as torch.fft.irfft ignores them.  A comparison with a NaN is false: the bin stays. */
+int dmad_wave_irfft_threshold(dmad_engine* e, const float* spec, const float* factor, int32_t B, float* out, int32_t* kept, dmad_stream s);
+
+/* l.233-243, the per-clip loop body, without the host loop.  pred, label: device int64 [B];  perturbed, best: device fp32 [B][L];
+ * fmin, fmax, factor: device fp32 [B];  succ: device int32 [B].  With won = targeted ? pred[b] == label[b] : pred[b] != label[b]:
+ *   won:   best[b] <- perturbed[b];  fmax[b] <- factor[b];  succ[b] <- 1;
+ *   else:  fmin[b] <- factor[b]   (best[b] and succ[b] stay);
+ *   then   factor[b] <- |fl(fl(fmin[b] + fmax[b]) / 2)|,  torch's fp32 statements in torch's order: bit for bit. */
+int dmad_kenan_update(dmad_engine* e, const int64_t* pred, const int64_t* label, int32_t B, int32_t targeted, const float* perturbed,
+                      float* best, float* fmin, float* fmax, float* factor, int32_t* succ, dmad_stream s);
+
 /* Baseline waveform defenses of the attack drivers (transforms/time_defense.py: AS l.102-127, MS l.130-157; transforms/
  * frequency_defense.py: DS l.37-60, LPF l.62-99, BPF l.101-141).  Everything is fp32 on rows [B][len]; an output row is a function of its
  * own input row only, never of B or of how a caller chunks the rows; there are no atomics, so results are bit-reproducible.  Unlike the
